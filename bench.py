@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec of the full ProtoPFormer train step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config deit_small|deit_tiny|cait_xxs24] [--graph]
+    python bench.py --gpus N --steps K --warmup W [--config deit_small|deit_tiny|cait_xxs24] [--graph] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment, this process only LAUNCHES: it spawns N rank processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rendezvous on 127.0.0.1) before anything here touches the GPU, relays rank 0's
@@ -14,8 +14,12 @@ Default workload = BASELINE.json configs[2]: deit_small_patch16_224, 2000x384 pr
 the host on two HIP streams each step; --graph replays one captured HIP graph per step instead (engine.GraphedTrainStep: measured
 SLOWER on ROCm 7.2 -- hipGraphLaunch re-enqueues every node, 12.5 ms of host time per replay, and spreads the two-stream step over
 four queues with half the overlap: 23.6-27.0 ms vs 18.9 ms per step, profiles/r2_graph_timeline.txt -- so it is opt-in).
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (HIP events on its launch stream, recorded inside the
-timed region) and the CPU baseline (oracle port on the host cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run only sets up, warms up, times the K steps and reports them (value, ms_per_step, ...).
+--full adds the side measurements: the roofline of the dominant kernel (HIP events on its launch stream, recorded inside the timed
+region; the same kernel alone in a child process), the named path, the host cost of one step into an empty queue, the other two
+BASELINE configurations and the CPU baseline (oracle port on the host cores, bounded sample).
+--dump-outputs DIR writes what the last timed step returned (loss, PPC terms) and a fixed, seeded sample of the parameters it
+updated, as DIR/<name>.npy (float32): two builds run with the same arguments start from identical inputs and can be compared.
 """
 import argparse
 import json
@@ -212,7 +216,7 @@ def secondary_configs(names=("deit_tiny", "cait_xxs24"), steps=20, warmup=5, tim
         key = f"{name}_bs{cfg['batch']}"
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup),
-                                "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=timeout)
+                                "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=timeout)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not line:
                 out[key] = {"error": (r.stderr or r.stdout)[-300:]}
@@ -326,6 +330,25 @@ def named_path_report(_lib, steps):
     return out
 
 
+DUMP_PARAM_SAMPLE = 1 << 22        # --dump-outputs: parameter entries written (a fixed, seeded sample: 16 MB in fp32)
+
+
+def dump_outputs(out_dir, model, loss, cov, mean):
+    """--dump-outputs: what a caller of the timed step holds after the LAST timed step -- the loss tensors it returned and the parameters
+    it updated in place.  The parameters are the model's state dict flattened in key order (a drop-in checkpoint's layout, not the flat
+    store's), sampled at DUMP_PARAM_SAMPLE indices drawn from a fixed seed: the same entries in every run of the same configuration."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("loss", loss), ("ppc_cov", cov), ("ppc_mean", mean)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    flat = torch.cat([v.detach().reshape(-1).float() for v in model.state_dict().values() if v.is_floating_point()])
+    if flat.numel() > DUMP_PARAM_SAMPLE:
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(out_dir, "params_sample.npy"), flat.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -343,6 +366,11 @@ def main():
                     help="add_on_layers_type: main.py:49 passes 'regular' (the BASELINE configurations); 'bottleneck' is the reference signature's default (not the headline metric)")
     ap.add_argument("--proto-dim", type=int, default=None, help="prototype width (with --addon bottleneck: < D/2 gives the reference's multi-stage tail)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other two BASELINE configurations after the headline one (--no-cpu-baseline skips them too)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: roofline probes (in the timed region, alone, named path), one step into an empty queue, "
+                         "the other two BASELINE configurations and the CPU baseline (--no-secondary / --no-cpu-baseline drop the last two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss tensors and a seeded sample of the updated parameters as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -423,80 +451,83 @@ def main():
             torch.cuda.synchronize()
     for _ in range(max(0, args.warmup - done)):
         step()
-    # roofline probe: HIP events around every launch of the dominant kernel (wgrad GEMM) on its launch stream.  Event-record nodes of
-    # a captured graph cannot be read back on ROCm 7.2 (hipEventElapsedTime: invalid resource handle), so in --graph mode the probe
+    probe = args.full and os.environ.get("PPF_BENCH_PROBE", "1") != "0"     # (PPF_BENCH_PROBE=0: A/B of what the probe's event records cost)
+    # --full: roofline probe, HIP events around every launch of the dominant kernel (wgrad GEMM) on its launch stream.  Event-record nodes
+    # of a captured graph cannot be read back on ROCm 7.2 (hipEventElapsedTime: invalid resource handle), so in --graph mode the probe
     # runs over 3 host-enqueued steps AFTER the timed region.
-    if graphed is None and os.environ.get("PPF_BENCH_PROBE", "1") != "0":     # (0: A/B of what the probe's event records cost)
+    if graphed is None and probe:
         _lib.call("ppf_gemm_probe", 1)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _, _ = step()
+        loss, cov, mean = step()
     t_enqueue = time.perf_counter() - t0          # host time to queue the steps: must stay well below the GPU time
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
-    # host cost of ONE step enqueued into an EMPTY queue (the figure above includes the time the host is blocked on a full queue
-    # whenever the GPU is the slower side): median of 5
-    one = []
-    for _ in range(5):
-        torch.cuda.synchronize()
-        th = time.perf_counter()
-        step()
-        one.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    one.sort()
-    t_enqueue_one = one[len(one) // 2]
-    probe_note = "HIP events around every launch inside the timed region"
-    if graphed is None:
-        _lib.call("ppf_gemm_probe", 0)
-    else:
-        _lib.call("ppf_gemm_probe", 1)
-        for _ in range(3):
-            train_one_step(model, crit, img, label, opt, epoch=20, grad_sync=sync)
-        torch.cuda.synchronize()
-        _lib.call("ppf_gemm_probe", 0)
-        probe_note = "HIP events around every launch of 3 host-enqueued steps after the timed region (graph nodes cannot be timed)"
-    # the kernels the north star names (attention forward / backward, prototype forward): in-step HIP-event time over 3 more steps of
-    # the same kind AFTER the timed region (the ~50 extra event records per step must not touch `value`)
-    # EVERY rank runs the three steps (they contain the gradient collectives); rank 0 reports its own kernels' times.
+    if args.dump_outputs and rank == 0:           # before any later step overwrites the recorded / captured step's loss tensors
+        dump_outputs(args.dump_outputs, model, loss, cov, mean)
     named = None
-    if os.environ.get("PPF_BENCH_PROBE", "1") != "0":
-        _lib.call("ppf_path_probe", 1)
-        for _ in range(3):
-            step() if graphed is None else train_one_step(model, crit, img, label, opt, epoch=20, grad_sync=sync)
+    if args.full:
+        # host cost of ONE step enqueued into an EMPTY queue (the figure above includes the time the host is blocked on a full queue
+        # whenever the GPU is the slower side): median of 5
+        one = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            step()
+            one.append(time.perf_counter() - th)
         torch.cuda.synchronize()
-        _lib.call("ppf_path_probe", 0)
-        if rank == 0:
-            try:
-                named = named_path_report(_lib, 3)
-            except Exception as e:                                      # informational leg: never takes the line down
-                named = {"error": f"{type(e).__name__}: {str(e)[:160]}"}
+        one.sort()
+        t_enqueue_one = one[len(one) // 2]
+        probe_note = "HIP events around every launch inside the timed region"
+        if graphed is None:
+            _lib.call("ppf_gemm_probe", 0)
+        else:
+            _lib.call("ppf_gemm_probe", 1)
+            for _ in range(3):
+                train_one_step(model, crit, img, label, opt, epoch=20, grad_sync=sync)
+            torch.cuda.synchronize()
+            _lib.call("ppf_gemm_probe", 0)
+            probe_note = "HIP events around every launch of 3 host-enqueued steps after the timed region (graph nodes cannot be timed)"
+        # the kernels the north star names (attention forward / backward, prototype forward): in-step HIP-event time over 3 more steps of
+        # the same kind AFTER the timed region (the ~50 extra event records per step must not touch `value`)
+        # EVERY rank runs the three steps (they contain the gradient collectives); rank 0 reports its own kernels' times.
+        if os.environ.get("PPF_BENCH_PROBE", "1") != "0":
+            _lib.call("ppf_path_probe", 1)
+            for _ in range(3):
+                step() if graphed is None else train_one_step(model, crit, img, label, opt, epoch=20, grad_sync=sync)
+            torch.cuda.synchronize()
+            _lib.call("ppf_path_probe", 0)
+            if rank == 0:
+                try:
+                    named = named_path_report(_lib, 3)
+                except Exception as e:                                      # informational leg: never takes the line down
+                    named = {"error": f"{type(e).__name__}: {str(e)[:160]}"}
     t = torch.tensor([dt], device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
-    import ctypes
-    c_ms, c_n, c_fl, c_by = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
-    try:
-        _lib.call("ppf_gemm_probe_read", ctypes.addressof(c_ms), ctypes.addressof(c_n), ctypes.addressof(c_fl), ctypes.addressof(c_by))
-    except RuntimeError as e:
-        probe_note = f"probe read failed: {e}"
-    kern_ms, n_launch, probe_flops, probe_bytes = c_ms.value, int(c_n.value), c_fl.value, c_by.value
+    if args.full:
+        import ctypes
+        c_ms, c_n, c_fl, c_by = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double(), ctypes.c_double()
+        try:
+            _lib.call("ppf_gemm_probe_read", ctypes.addressof(c_ms), ctypes.addressof(c_n), ctypes.addressof(c_fl), ctypes.addressof(c_by))
+        except RuntimeError as e:
+            probe_note = f"probe read failed: {e}"
+        kern_ms, n_launch, probe_flops, probe_bytes = c_ms.value, int(c_n.value), c_fl.value, c_by.value
     if rank == 0:
         ips = world * batch * args.steps / dt
-        achieved = (probe_flops / 1e12) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(args.config)
         ex = executed_gflop_per_img(cfg)
         out = {
             "metric": METRIC if args.config == "deit_small" and batch == 256 and args.addon == "regular" and not args.proto_dim else
                       f"images/sec train step, {cfg['arch']}+{cfg['P']} protos, bs{batch}, {world} MI355X ({cfg['label']}; not the headline metric)",
             "value": ips, "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "host_enqueue_ms_per_step": 1e3 * t_enqueue / args.steps, "host_enqueue_ms_one_step_empty_queue": 1e3 * t_enqueue_one,
+            "host_enqueue_ms_per_step": 1e3 * t_enqueue / args.steps,
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
             "config": {"workload": f"{cfg['arch']}, synthetic 224x224, {cfg['P']}x{cfg['Dp']} prototypes, {cfg['C']} classes, k={cfg['k']}, batch {batch}/GPU "
@@ -507,17 +538,22 @@ def main():
                        "global_batch": world * batch, "parallelism": f"dp{world}", "execution": graph_note},
             "rccl_world": dist.get_world_size() if dist.is_initialized() else 1,
             "rccl_backend": dist.get_backend() if dist.is_initialized() else None,
-            "roofline": {"bound": "mfma", "kernel": ops.DOMINANT_NAME, "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
-                         "traffic_unit": f"bytes/launch (PMC, see profiles/{traffic_src})" if traffic_src else None,
-                         "algorithmic_bytes": probe_bytes / max(n_launch, 1), "launches": n_launch,
-                         "avg_launch_ms": kern_ms / max(n_launch, 1),
-                         "how": probe_note + "; the kernel runs on the weight-gradient stream concurrently with the main chain (contended time)"},
             "step_mfma_frac": (ips / world) * cfg["gflop"] / 1e3 / PEAK_BF16_TFLOPS,
             "step_mfma_frac_executed": (ips / world) * ex / 1e3 / PEAK_BF16_TFLOPS,
             "gflop_per_img": {"algorithmic": cfg["gflop"], "executed": ex},
             "final_loss": float(loss),
+            "full": args.full,
         }
+    if rank == 0 and args.full:
+        achieved = (probe_flops / 1e12) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
+        traffic, traffic_src = pmc_traffic(args.config)
+        out["host_enqueue_ms_one_step_empty_queue"] = 1e3 * t_enqueue_one
+        out["roofline"] = {"bound": "mfma", "kernel": ops.DOMINANT_NAME, "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                           "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
+                           "traffic_unit": f"bytes/launch (PMC, see profiles/{traffic_src})" if traffic_src else None,
+                           "algorithmic_bytes": probe_bytes / max(n_launch, 1), "launches": n_launch,
+                           "avg_launch_ms": kern_ms / max(n_launch, 1),
+                           "how": probe_note + "; the kernel runs on the weight-gradient stream concurrently with the main chain (contended time)"}
         if named is not None:
             out["roofline"]["named_path"] = named
         if world == 1 and not args.no_cpu_baseline:
@@ -538,6 +574,7 @@ def main():
             out["secondary"] = secondary_configs()
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
+    if rank == 0:
         line = json.dumps(out)
     else:
         line = None

@@ -1,4 +1,4 @@
-"""Same-box A/B of environment-variable variants of the train step: runs `bench.py --no-cpu-baseline` for each variant in turn,
+"""Same-box A/B of environment-variable variants of the train step: runs `bench.py --full --no-cpu-baseline` for each variant in turn,
 ROUNDS times, and prints img/s per run plus the per-variant mean (box-to-box spread of the pool is +-3 %, so only numbers from one
 gpurun call are comparable).  usage: ab_step.py ROUNDS "NAME:K=V,K=V" "NAME2:" ... [-- extra bench args]"""
 import json
@@ -20,7 +20,7 @@ res = {n: [] for n, _ in variants}
 for r in range(rounds):
     for name, env in variants:
         e = dict(os.environ, **env)
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"] + extra,
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"] + extra,
                              capture_output=True, text=True, env=e, cwd=root, timeout=900)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -85,8 +85,31 @@ def test_bench_probe_switch():
     """PPF_BENCH_PROBE=0: bench.py without its event probes (what the records cost): the line has no live roofline timing and no named path."""
     env = dict(os.environ, PPF_BENCH_PROBE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "deit_tiny", "--batch", "16", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and line, (r.stdout[-1500:], r.stderr[-3000:])
     d = json.loads(line[0])
     assert d["value"] > 0 and d["roofline"].get("named_path") is None, d["roofline"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench run (no --full) times exactly --steps steps and reports nothing beyond them; --dump-outputs writes the last timed
+    step's loss tensors and a parameter sample as float32 .npy files, identical in two runs with the same arguments (same inputs)."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "deit_tiny", "--batch", "16", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and line, (r.stdout[-1500:], r.stderr[-3000:])
+        d = json.loads(line[-1])
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+        assert not {"roofline", "secondary", "cpu_baseline", "host_enqueue_ms_one_step_empty_queue"} & set(d), sorted(d)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["loss.npy", "params_sample.npy", "ppc_cov.npy", "ppc_mean.npy"], files
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 << 20
+        runs.append({f: np.load(tmp_path / name / f) for f in files})
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in runs[-1].values())
+        assert float(runs[-1]["loss.npy"]) == d["final_loss"]
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
