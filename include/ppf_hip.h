@@ -273,6 +273,15 @@ int ppf_ppc_loss_bwd(const float* gcov, const float* gmean, const float* up_cov,
 /* nn.CrossEntropyLoss (main.py:390): mean loss + d/dlogits */
 int ppf_cross_entropy(const float* logits, const void* label_i64, float* per_sample, float* dlogits, float* loss, int B, int C,
                       ppf_stream_t stream);
+/* soft-target / label-smoothing cross-entropy (main.py:384-390; timm SoftTargetCrossEntropy / LabelSmoothingCrossEntropy, and
+ * nn.CrossEntropyLoss given probability targets): loss = mean over the batch, dlogits [B][C] = d(loss)/d(logits); per_sample [B]
+ * scratch.  Exactly one of the two target forms (device pointers), the other NULL:
+ *   target [B][C] fp32 (dense):  loss_b = sum_c t_c (lse - x_c) = lse*sum(t) - sum(t*x),  dlogits = (softmax*sum(t) - t) / B
+ *                                (sum(t) == 1 is not assumed, as in torch);
+ *   label_i64 [B] + smoothing s: loss_b = (1-s)(lse - x_label) + s(lse - mean_c x),      dlogits = (softmax - (1-s) onehot - s/C) / B.
+ * Row statistics in fp64, one wave per row, fixed-order batch mean: deterministic.  A label outside [0, C) reads nothing. */
+int ppf_soft_cross_entropy(const float* logits, const float* target, const void* label_i64, float smoothing, float* per_sample,
+                           float* dlogits, float* loss, int B, int C, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);
@@ -346,6 +355,29 @@ int ppf_copy_2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch
  * rects == NULL: no erasing); mean3 / std3 are HOST pointers; state_u64 (device, optional) = step counter mixed into the noise key. */
 int ppf_image_finish_u8(const void* in_u8_hwc, float* out_nchw, int B, int H, int W, const float* mean3, const float* std3,
                         const int* rects, uint64_t seed, const void* state_u64, ppf_stream_t stream);
+/* Mixup / CutMix of the device batch (timm 0.5.4 Mixup, tools/engine_proto.py:47-48, main.py:325-335).  The per-sample parameter
+ * table is int32 [B][PPF_MIX_WORDS]: kind (0 untouched, 1 blend, 2 box paste), the box rows [yl, yh) and columns [xl, xh), and two
+ * fp32 weights stored as their bits.  Sample i is mixed with sample j = B-1-i as it was before the call:
+ *   blend: x_i = fl(fl(x_i * w_self) + fl(x_j * w_other))   (no FMA: bit-exact to timm's torch arithmetic for the same weights)
+ *   box:   x_i[:, yl:yh, xl:xh] = x_j[:, yl:yh, xl:xh]       (w_self / w_other then only serve ppf_mixup_target)
+ * ppf_mixup_apply: x fp32 [B][Cc][H][W] (device, in place).  table_host is a HOST pointer (pinned, unchanged until the copy has run
+ * on `stream`), validated (kind in range, box inside the image) and copied to table_dev (device, B*PPF_MIX_WORDS int32) on `stream`
+ * before the launch; no launch when every kind is 0. */
+#define PPF_MIX_KIND 0
+#define PPF_MIX_YL 1
+#define PPF_MIX_YH 2
+#define PPF_MIX_XL 3
+#define PPF_MIX_XH 4
+#define PPF_MIX_WSELF 5
+#define PPF_MIX_WOTHER 6
+#define PPF_MIX_WORDS 8
+int ppf_mixup_apply(float* x, const int* table_host, int* table_dev, int B, int Cc, int H, int W, ppf_stream_t stream);
+/* timm mixup_target: target [B][C] fp32 = w_self_b * onehot_s(label_b) + w_other_b * onehot_s(label_{B-1-b}) with onehot_s = off_value
+ * everywhere and on_value at the label (off = smoothing / C, on = 1 - smoothing + off, rounded to fp32 by the caller); label_i64 [B]
+ * and lam (device): w_self_b = lam[b*lam_stride], w_other_b = lam[b*lam_stride + 1] (lam_stride 0: one pair for the whole batch;
+ * the mixing table: lam = table_dev + PPF_MIX_WSELF, lam_stride = PPF_MIX_WORDS). */
+int ppf_mixup_target(const void* label_i64, const float* lam, int lam_stride, float off_value, float on_value, float* target, int B,
+                     int C, ppf_stream_t stream);
 /* out = x * (*scalar_dev): chain rule with a device-resident upstream scalar (autograd of nn.CrossEntropyLoss, main.py:390) */
 int ppf_scale_by_scalar(const float* x, const float* scalar_dev, float* out, int64_t n, ppf_stream_t stream);
 

@@ -51,6 +51,9 @@ SIGS = {
     "ppf_ppc_loss": "ppp" "iiiii" "ff" "pppp" "s",
     "ppf_ppc_loss_bwd": "pppppp" "iiii" "s",
     "ppf_cross_entropy": "ppppp" "ii" "s",
+    "ppf_soft_cross_entropy": "ppp" "f" "ppp" "ii" "s",
+    "ppf_mixup_apply": "ppp" "iiii" "s",
+    "ppf_mixup_target": "pp" "i" "ff" "p" "ii" "s",
     "ppf_sgemm": "ppp" "iii" "llll" "i" "ff" "pl" "s",
     "ppf_sgemm_pair": "ppp" "ii" "llll" "i" "f" "ppp" "ii" "llll" "i" "f" "p" "i" "ff" "i" "pl" "s",
     "ppf_axpby": "ppp" "ff" "l" "s",

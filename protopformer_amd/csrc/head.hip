@@ -1,7 +1,7 @@
 // Small fp32 kernels of the classification head and the losses:
 //   * PPC loss (protopformer.py:249-288): weighted grid mean / covariance per (sample, label prototype),
 //     one workgroup per sample, wave-shuffle reductions, analytic gradient emitted alongside the loss
-//   * cross-entropy (main.py:390) with its gradient
+//   * cross-entropy (main.py:390) with its gradient; soft-target / label-smoothing cross-entropy (main.py:384-388) with its gradient
 //   * the frozen +1/-0.5 class-connection linears (protopformer.py:126-131,314-316): a plain strided fp32 GEMM
 // All reductions run in a fixed order (per-sample partials + a single-workgroup tree), i.e. deterministic.
 #include "ppf_common.h"
@@ -137,6 +137,59 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* logits, const long
     if (lane == 0) per_sample[b] = lse - row[lab];
     const float invB = 1.0f / (float)B;
     for (int c = lane; c < C; c += 64) dlogits[(size_t)b * C + c] = (__expf(row[c] - lse) - (c == lab ? 1.0f : 0.0f)) * invB;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Soft-target (target != nullptr, [B][C]) or label-smoothing (label + smoothing) cross-entropy: one wave per row as ce_kernel.  The row
+// statistics run in fp64 and lse - x_c is formed as (mx - x_c) + log(sum exp(x - mx)), so that logits of |x| ~ 3e4 lose nothing to the
+// cancellation of lse*sum(t) - sum(t*x), and every fp32 result is rounded once, from fp64.  The fp64 exp costs 7.4 against
+// ce_kernel's 4.8 us at 256 x 200 (profiles/mixup_cost.txt): launch-bound either way.  No read depends on a label.
+__global__ __launch_bounds__(256) void soft_ce_kernel(const float* logits, const float* target, const long long* label, float smoothing,
+                                                      float* per_sample, float* dlogits, int B, int C) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const float* row = logits + (size_t)b * C;
+    float mxf = -INFINITY;
+    for (int c = lane; c < C; c += 64) mxf = fmaxf(mxf, row[c]);
+    const double mx = (double)wave_max(mxf);
+    double s = 0.0;
+    for (int c = lane; c < C; c += 64) s += exp((double)row[c] - mx);
+    const double ls = log(wave_sum_d(s));             // lse = mx + ls
+    const double invB = 1.0 / (double)B;
+    if (target) {
+        const float* t = target + (size_t)b * C;
+        double st = 0.0, acc = 0.0;
+        for (int c = lane; c < C; c += 64) {
+            const double tc = (double)t[c];
+            st += tc;
+            acc += tc * ((mx - (double)row[c]) + ls);
+        }
+        st = wave_sum_d(st);
+        acc = wave_sum_d(acc);
+        if (lane == 0) per_sample[b] = (float)acc;
+        for (int c = lane; c < C; c += 64)
+            dlogits[(size_t)b * C + c] = (float)((exp((double)row[c] - mx - ls) * st - (double)t[c]) * invB);
+    } else {
+        const long long lab = label[b];
+        double dlab = 0.0, dsum = 0.0;                 // mx - x_label, sum_c (mx - x_c)
+        for (int c = lane; c < C; c += 64) {
+            const double d = mx - (double)row[c];
+            dsum += d;
+            if (c == lab) dlab = d;
+        }
+        dlab = wave_sum_d(dlab);
+        dsum = wave_sum_d(dsum);
+        const double sm = (double)smoothing, conf = 1.0 - sm, off = sm / (double)C;
+        if (lane == 0) per_sample[b] = (float)(conf * (dlab + ls) + sm * (dsum / (double)C + ls));
+        for (int c = lane; c < C; c += 64)
+            dlogits[(size_t)b * C + c] = (float)((exp((double)row[c] - mx - ls) - (c == lab ? conf : 0.0) - off) * invB);
+    }
 }
 
 // C[m][n] = alpha * sum_k A[m*sam + k*sak] * B[n*sbn + k*sbk] + beta * C[m][n]; 32x32 tile, 2x2 outputs per thread.
@@ -365,6 +418,22 @@ int ppf_ppc_loss_bwd(const float* gcov, const float* gmean, const float* up_cov,
 int ppf_cross_entropy(const float* logits, const void* label, float* per_sample, float* dlogits, float* loss, int B, int C, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && C > 0, PPF_ERR_SHAPE, "ppf_cross_entropy: bad shape");
     hipLaunchKernelGGL(ce_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, (const long long*)label, per_sample, dlogits, B, C);
+    PPF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
+    PPF_LAUNCH_CHECK();
+    return 0;
+}
+
+// Mean soft-target (dense target [B][C]) or label-smoothing (label [B] + smoothing) cross-entropy and d(loss)/d(logits).
+int ppf_soft_cross_entropy(const float* logits, const float* target, const void* label, float smoothing, float* per_sample, float* dlogits,
+                           float* loss, int B, int C, hipStream_t stream) {
+    PPF_CHECK_ARG(B > 0 && C > 0, PPF_ERR_SHAPE, "ppf_soft_cross_entropy: bad shape B=%d C=%d", B, C);
+    PPF_CHECK_ARG(logits && per_sample && dlogits && loss, PPF_ERR_ARG, "ppf_soft_cross_entropy: null pointer");
+    PPF_CHECK_ARG((target == nullptr) != (label == nullptr), PPF_ERR_ARG, "ppf_soft_cross_entropy: pass exactly one of target / label");
+    PPF_CHECK_ARG(target || (smoothing >= 0.f && smoothing <= 1.f), PPF_ERR_ARG, "ppf_soft_cross_entropy: smoothing %g outside [0, 1]",
+                  (double)smoothing);
+    hipLaunchKernelGGL(soft_ce_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, target, (const long long*)label, smoothing, per_sample,
+                       dlogits, B, C);
     PPF_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
     PPF_LAUNCH_CHECK();

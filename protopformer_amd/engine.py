@@ -613,9 +613,11 @@ class ReplayedTrainStep(GraphedTrainStep):
 
 
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, args=None, grad_sync=None, log_every=30, logger=print,
-                    max_norm=None, step_fn=None):
+                    max_norm=None, step_fn=None, mixup_fn=None):
     """Epoch loop with the reference's signature shape (engine_proto.py:24-113); data_loader yields (samples, targets).
-    step_fn: a ReplayedTrainStep (recorded command list) or GraphedTrainStep (captured HIP graph) instead of the eager train_one_step."""
+    step_fn: a ReplayedTrainStep (recorded command list) or GraphedTrainStep (captured HIP graph) instead of the eager train_one_step.
+    mixup_fn: a mixup.Mixup applied to every device batch before the step (engine_proto.py:47-48); its kernels run outside a recorded
+    step, which copies the [B, C] soft targets into its static buffer like any other target."""
     model.train(True)
     use_ppc = True if args is None else bool(getattr(args, "use_ppc_loss", True))
     cov_coe = 0.1 if args is None else getattr(args, "ppc_cov_coe", 0.1)
@@ -628,6 +630,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, arg
     for it, (samples, targets) in enumerate(data_loader):
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
+        if mixup_fn is not None:
+            samples, targets = mixup_fn(samples, targets)
         if step_fn is not None:
             loss, _, _ = step_fn(samples, targets)
         else:

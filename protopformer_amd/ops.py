@@ -396,6 +396,33 @@ def cross_entropy(logits, label):
     return loss, dlogits
 
 
+def soft_cross_entropy(logits, target=None, label=None, smoothing=0.0):
+    """Mean cross-entropy against a dense target [B, C] fp32 or against int64 labels with label smoothing -> (loss[1], dlogits)."""
+    B, C = logits.shape
+    per = torch.empty(B, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty_like(logits)
+    loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    _lib.call("ppf_soft_cross_entropy", logits, target, label, float(smoothing), per, dlogits, loss, B, C)
+    return loss, dlogits
+
+
+MIX_WORDS, MIX_WSELF = 8, 5          # PPF_MIX_WORDS / PPF_MIX_WSELF of include/ppf_hip.h
+
+
+def mixup_apply(x, table_host, table_dev):
+    """In-place Mixup / CutMix of x [B, C, H, W] fp32 by the per-sample table (pinned host int32 [B, MIX_WORDS]; uploaded to table_dev)."""
+    B, Cc, H, W = x.shape
+    _lib.call("ppf_mixup_apply", x, table_host, table_dev, B, Cc, H, W)
+
+
+def mixup_target(label, table_dev, num_classes, off_value, on_value):
+    """timm mixup_target on the weights of the uploaded mixing table: [B, num_classes] fp32."""
+    B = label.shape[0]
+    t = torch.empty((B, num_classes), dtype=torch.float32, device=label.device)
+    _lib.call("ppf_mixup_target", label, table_dev.data_ptr() + 4 * MIX_WSELF, MIX_WORDS, float(off_value), float(on_value), t, B, num_classes)
+    return t
+
+
 def sgemm(a, b, out, M, N, K, sam, sak, sbn, sbk, alpha=1.0, beta=0.0):
     ws = _workspace(out.device, 16 * M * N * 4)
     _lib.call("ppf_sgemm", a, b, out, M, N, K, sam, sak, sbn, sbk, out.shape[-1], float(alpha), float(beta), ws, ws.numel() // 4)

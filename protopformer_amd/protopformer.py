@@ -16,6 +16,8 @@ from . import ops
 from .backbone import DEIT_FNS, TokensFn, droppath_scales, wgrad_lane
 from .deit import MyVisionTransformer
 from .flat import FlatStore
+from .mixup import (LabelSmoothingCrossEntropy, Mixup, SoftCrossEntropyFn, SoftTargetCrossEntropy, create_criterion,  # noqa: F401
+                    create_mixup, dense_target)
 
 ARCHS = {
     "deit_tiny_patch16_224": dict(kind="deit", embed_dim=192, depth=12, num_heads=3),
@@ -278,9 +280,12 @@ class WeightedLossFn(torch.autograd.Function):
 
 
 class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss() (main.py:390) on the HIP kernel."""
+    """nn.CrossEntropyLoss() (main.py:390) on the HIP kernel.  Like torch's, it also takes probability targets: a floating-point [B, C]
+    target (CutMix-only Mixup under the reference's flag defaults, main.py:384-390) runs the dense soft-target kernel."""
 
     def forward(self, logits, target):
+        if target.is_floating_point():
+            return SoftCrossEntropyFn.apply(logits, dense_target(logits, target), None, 0.0)
         return CrossEntropyFn.apply(logits, target)
 
 
@@ -443,6 +448,11 @@ class PPNet(nn.Module):
         return cls_attn, act_full.reshape(x.shape[0], self.num_prototypes, s, s)
 
     def get_PPC_loss(self, total_proto_act, cls_attn_rollout, original_fea_len, label):
+        if label.is_floating_point() or label.dim() != 1:
+            # the kernel reads int64 class labels (it picks each sample's prototypes by its label); the reference breaks on Mixup's
+            # [B, C] targets too (protopformer.py:268-270)
+            raise ValueError(f"get_PPC_loss needs integer class labels [B], got {tuple(label.shape)} {label.dtype}: the PPC loss cannot "
+                             "be used with Mixup / CutMix soft targets")
         k = total_proto_act.shape[-1] * total_proto_act.shape[-2]
         cache = self._ppc_cache
         if cache is not None and cache[0] is cls_attn_rollout:
