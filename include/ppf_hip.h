@@ -282,6 +282,18 @@ int ppf_cross_entropy(const float* logits, const void* label_i64, float* per_sam
  * Row statistics in fp64, one wave per row, fixed-order batch mean: deterministic.  A label outside [0, C) reads nothing. */
 int ppf_soft_cross_entropy(const float* logits, const float* target, const void* label_i64, float smoothing, float* per_sample,
                            float* dlogits, float* loss, int B, int C, ppf_stream_t stream);
+/* Evaluation metrics (tools/engine_proto.py:143-184) of one batch ADDED into acc, a device double[8] that persists across batches (the
+ * caller zeroes it once per epoch and reads it once at the end); logits* [B][C] fp32, logits_global / logits_local may be NULL (their
+ * slots then stay untouched):
+ *   acc[0] samples seen, acc[1] sum of per-sample cross-entropy of logits, acc[2] top-1 hits, acc[3] top-5 hits of logits,
+ *   acc[4] top-1 hits of logits_global, acc[5] top-1 hits of logits_local, acc[6] rows whose label is outside [0, C), acc[7] reserved (0).
+ * Top-1 hit: label == FIRST index of the row maximum (torch argmax).  Top-5 hit: #{j : x_j > x_t or (x_j == x_t and j < t)} < 5 (equal to
+ * "label in topk(5)" without ties; always a hit when C < 5).  A label outside [0, C) reads nothing and counts in acc[0] and acc[6] only.
+ * Row statistics in fp64 ((mx - x_t) + log(sum exp(x - mx))); one wave per row, then LDS, then a fixed-order sum over the workgroups and
+ * one adder: no floating-point atomics, two runs over the same batches give bit-identical acc.  The workgroup partials are kept in a
+ * device buffer owned by the library: calls of one process must be ordered on ONE stream. */
+int ppf_eval_metrics(const float* logits, const float* logits_global, const float* logits_local, const void* label_i64, double* acc,
+                     int B, int C, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);

@@ -52,6 +52,7 @@ SIGS = {
     "ppf_ppc_loss_bwd": "pppppp" "iiii" "s",
     "ppf_cross_entropy": "ppppp" "ii" "s",
     "ppf_soft_cross_entropy": "ppp" "f" "ppp" "ii" "s",
+    "ppf_eval_metrics": "ppppp" "ii" "s",
     "ppf_mixup_apply": "ppp" "iiii" "s",
     "ppf_mixup_target": "pp" "i" "ff" "p" "ii" "s",
     "ppf_sgemm": "ppp" "iii" "llll" "i" "ff" "pl" "s",

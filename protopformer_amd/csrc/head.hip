@@ -2,6 +2,7 @@
 //   * PPC loss (protopformer.py:249-288): weighted grid mean / covariance per (sample, label prototype),
 //     one workgroup per sample, wave-shuffle reductions, analytic gradient emitted alongside the loss
 //   * cross-entropy (main.py:390) with its gradient; soft-target / label-smoothing cross-entropy (main.py:384-388) with its gradient
+//   * evaluation metrics (engine_proto.py:143-184: loss, acc@1, acc@5, global / local acc@1) accumulated in device memory
 //   * the frozen +1/-0.5 class-connection linears (protopformer.py:126-131,314-316): a plain strided fp32 GEMM
 // All reductions run in a fixed order (per-sample partials + a single-workgroup tree), i.e. deterministic.
 #include "ppf_common.h"
@@ -190,6 +191,91 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const float* logits, const
         for (int c = lane; c < C; c += 64)
             dlogits[(size_t)b * C + c] = (float)((exp((double)row[c] - mx - ls) - (c == lab ? conf : 0.0) - off) * invB);
     }
+}
+
+// ---- evaluation metrics accumulated on the device (engine.EvalMeter) ---------------------------------------------------------------
+// One wave per row (a workgroup's 4 waves stride over the rows when B > 4 * EVAL_MAX_WG).  The per-row values are wave-uniform after the
+// shuffles; every wave adds its rows in ascending order, thread 0 adds the 4 waves through LDS, eval_metrics_finish_kernel adds the
+// workgroups in a fixed tree and ONE thread adds the result into acc: no floating-point atomics, bit-identical from run to run.  The
+// workgroup partials live in a module-scope device buffer (the entry point has no scratch argument), which is why calls must be
+// ordered on one stream.
+constexpr int EVAL_MAX_WG = 1024, EVAL_NV = 6;           // per-workgroup values: ce sum, top-1, top-5, global top-1, local top-1, bad labels
+__device__ double g_eval_partial[EVAL_MAX_WG * EVAL_NV];
+
+// first index of the row maximum (torch argmax); wave-uniform result
+__device__ __forceinline__ int wave_argmax_first(const float* row, int C, int lane, float& mx_out) {
+    float mx = -INFINITY;
+    int at = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const float x = row[c];
+        if (x > mx || at == 0x7fffffff) { mx = x; at = c; }        // strict >: a lane keeps the first index of its own maximum
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float omx = __shfl_xor(mx, o, 64);
+        const int oat = __shfl_xor(at, o, 64);
+        if (omx > mx || (omx == mx && oat < at)) { mx = omx; at = oat; }
+    }
+    mx_out = mx;
+    return at;
+}
+
+__global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restrict__ logits, const float* __restrict__ logits_global,
+                                                           const float* __restrict__ logits_local, const long long* __restrict__ label,
+                                                           int B, int C) {
+    __shared__ double red[4][EVAL_NV];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double ce = 0.0;
+    int hit1 = 0, hit5 = 0, hitg = 0, hitl = 0, bad = 0;
+    for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+        const long long lab = label[b];
+        if (lab < 0 || lab >= (long long)C) { ++bad; continue; }   // (wave-uniform) nothing is read through such a label
+        const int t = (int)lab;
+        const float* row = logits + (size_t)b * C;
+        float mxf;
+        hit1 += wave_argmax_first(row, C, lane, mxf) == t;
+        const float xt = row[t];
+        const double mx = (double)mxf;
+        double s = 0.0;
+        int ahead = 0;                                             // #{j : x_j > x_t or (x_j == x_t and j < t)}
+        for (int c = lane; c < C; c += 64) {
+            const float x = row[c];
+            s += exp((double)x - mx);
+            ahead += (x > xt || (x == xt && c < t)) ? 1 : 0;
+        }
+        ce += (mx - (double)xt) + log(wave_sum_d(s));              // lse - x_t as in soft_ce_kernel: nothing lost at |x| ~ 3e4
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ahead += __shfl_xor(ahead, o, 64);
+        hit5 += ahead < 5;
+        if (logits_global) hitg += wave_argmax_first(logits_global + (size_t)b * C, C, lane, mxf) == t;
+        if (logits_local) hitl += wave_argmax_first(logits_local + (size_t)b * C, C, lane, mxf) == t;
+    }
+    if (lane == 0) {
+        red[wave][0] = ce; red[wave][1] = (double)hit1; red[wave][2] = (double)hit5;
+        red[wave][3] = (double)hitg; red[wave][4] = (double)hitl; red[wave][5] = (double)bad;
+    }
+    __syncthreads();
+    if (threadIdx.x < EVAL_NV)
+        g_eval_partial[blockIdx.x * EVAL_NV + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// acc[0] += B, acc[1..6] += the workgroup partials added in a fixed order (strided per thread, then an LDS tree); slot 4 / 5 only when
+// that branch was given; acc[7] is never touched.
+__global__ __launch_bounds__(256) void eval_metrics_finish_kernel(double* __restrict__ acc, int nwg, int B, int has_global, int has_local) {
+    __shared__ double red[256];
+    for (int v = 0; v < EVAL_NV; ++v) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < nwg; i += 256) s += g_eval_partial[i * EVAL_NV + v];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && !(v == 3 && !has_global) && !(v == 4 && !has_local)) acc[v + 1] += red[0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) acc[0] += (double)B;
 }
 
 // C[m][n] = alpha * sum_k A[m*sam + k*sak] * B[n*sbn + k*sbk] + beta * C[m][n]; 32x32 tile, 2x2 outputs per thread.
@@ -436,6 +522,19 @@ int ppf_soft_cross_entropy(const float* logits, const float* target, const void*
                        dlogits, B, C);
     PPF_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
+    PPF_LAUNCH_CHECK();
+    return 0;
+}
+
+// Evaluation metrics of one batch added into acc (device double[8], include/ppf_hip.h); two launches, no host read.
+int ppf_eval_metrics(const float* logits, const float* logits_global, const float* logits_local, const void* label, double* acc, int B, int C,
+                     hipStream_t stream) {
+    PPF_CHECK_ARG(B > 0 && C > 0, PPF_ERR_SHAPE, "ppf_eval_metrics: bad shape B=%d C=%d", B, C);
+    PPF_CHECK_ARG(logits && label && acc, PPF_ERR_ARG, "ppf_eval_metrics: null pointer");
+    const int nwg = (B + 3) / 4 < EVAL_MAX_WG ? (B + 3) / 4 : EVAL_MAX_WG;
+    hipLaunchKernelGGL(eval_metrics_kernel, dim3(nwg), dim3(256), 0, stream, logits, logits_global, logits_local, (const long long*)label, B, C);
+    PPF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(eval_metrics_finish_kernel, dim3(1), dim3(256), 0, stream, acc, nwg, B, logits_global != nullptr, logits_local != nullptr);
     PPF_LAUNCH_CHECK();
     return 0;
 }

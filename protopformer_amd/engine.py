@@ -10,6 +10,7 @@ schedule tools/create_scheduler.py:20-32; checkpoint layout main.py:393-407, 436
                        folding 1/world into the optimizer kernel; replicas are made identical by a rank-0 broadcast.
 * train_one_step / GraphedTrainStep / train_one_epoch : the reference's step body (forward, CE + PPC, backward, clip, step,
                        EMA), eagerly or as one captured HIP graph that is replayed per step.
+* evaluate / EvalMeter / evaluate_epoch : the validation loop (engine_proto.py:143-184); evaluate_epoch keeps its metrics on the device.
 * save_checkpoint / load_checkpoint : the reference's checkpoint dict {model, optimizer, lr_scheduler, epoch, model_ema}.
 """
 import math
@@ -671,6 +672,49 @@ def evaluate(data_loader, model, device):
         correct_l += int((aux[3].argmax(1) == target).sum())
         count += images.shape[0]
     return dict(acc1=100.0 * correct / count, global_acc1=100.0 * correct_g / count, local_acc1=100.0 * correct_l / count, loss=loss_sum / count)
+
+
+class EvalMeter:
+    """The validation metrics of engine_proto.py:143-184 (loss, acc@1, acc@5, global / local acc@1) accumulated in device memory by
+    ppf_eval_metrics: update() only launches, result() is the one read-back of an epoch.  With a live process group reduce_() sums the
+    accumulators of all ranks (--dist-eval; metric_logger.synchronize_between_processes)."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros(ops.EVAL_SLOTS, dtype=torch.float64, device=device)
+
+    def reset(self):
+        self.acc.zero_()
+
+    def update(self, logits, target, logits_global=None, logits_local=None):
+        ops.eval_metrics(self.acc, logits, target, logits_global, logits_local)
+
+    def reduce_(self):
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.acc, op=dist.ReduceOp.SUM)
+
+    def result(self):
+        n, ce, top1, top5, top1_g, top1_l, bad, _ = self.acc.tolist()
+        if bad != 0:
+            raise ValueError(f"EvalMeter: {int(bad)} of {int(n)} labels lie outside [0, num_classes) of the logits")
+        if n == 0:
+            raise ValueError("EvalMeter: no sample was seen (empty data loader)")
+        return dict(acc1=100.0 * top1 / n, acc5=100.0 * top5 / n, global_acc1=100.0 * top1_g / n, local_acc1=100.0 * top1_l / n, loss=ce / n,
+                    n=int(n))
+
+
+@torch.no_grad()
+def evaluate_epoch(data_loader, model, device, distributed=False):
+    """The validation loop of engine_proto.py:143-184 without a host synchronisation inside the epoch: two launches per batch add the
+    metrics on the device (EvalMeter), read once at the end.  distributed: every rank saw its own shard (--dist-eval), sum them."""
+    model.eval()
+    meter = EvalMeter(device)
+    for images, target, *_ in data_loader:
+        images, target = images.to(device, non_blocking=True), target.to(device, non_blocking=True)
+        output, aux = model(images)
+        meter.update(output, target, aux[2], aux[3])
+    if distributed:
+        meter.reduce_()
+    return meter.result()
 
 
 # ---------------------------------------------------------------------------------------------------- checkpoint I/O

@@ -406,6 +406,26 @@ def soft_cross_entropy(logits, target=None, label=None, smoothing=0.0):
     return loss, dlogits
 
 
+EVAL_SLOTS = 8                       # acc of ppf_eval_metrics: n, ce sum, top-1, top-5, global top-1, local top-1, bad labels, reserved
+
+
+def eval_metrics(acc, logits, label, logits_global=None, logits_local=None):
+    """Add one batch's evaluation metrics into acc (device float64[8], include/ppf_hip.h); launches only, nothing is read back."""
+    if acc.dtype != torch.float64 or acc.numel() != EVAL_SLOTS or not acc.is_contiguous() or not acc.is_cuda:
+        raise ValueError("eval_metrics: acc must be a contiguous float64[8] device tensor")
+    if logits.dim() != 2 or label.dim() != 1 or label.shape[0] != logits.shape[0] or label.dtype != torch.int64:
+        raise ValueError(f"eval_metrics: logits [B, C] and int64 labels [B] expected, got {tuple(logits.shape)} and {tuple(label.shape)} {label.dtype}")
+    B, C = logits.shape
+    rows = []
+    for t in (logits, logits_global, logits_local):
+        if t is not None:
+            if t.shape != logits.shape or t.dtype != torch.float32 or t.device != acc.device:
+                raise ValueError(f"eval_metrics: fp32 [B, C] logits on {acc.device} expected, got {tuple(t.shape)} {t.dtype} on {t.device}")
+            t = t.contiguous()
+        rows.append(t)
+    _lib.call("ppf_eval_metrics", rows[0], rows[1], rows[2], label.contiguous(), acc, B, C)
+
+
 MIX_WORDS, MIX_WSELF = 8, 5          # PPF_MIX_WORDS / PPF_MIX_WSELF of include/ppf_hip.h
 
 
