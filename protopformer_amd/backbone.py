@@ -55,19 +55,69 @@ def _dp(dp, slot):
     return None if scales is None or index[slot] < 0 else scales[index[slot]]
 
 
-# ------------------------------------------------------------------------------------------------ DeiT forward
-def deit_embed(feats, store, img, saved=None):
-    """PatchEmbed (im2col + GEMM) + cls token + position embedding (deit:172-181). Returns x fp32 [B, 1+Np, D]."""
+# ------------------------------------------------------------------------------------------------ forward
+def embed_tokens(feats, store, img, saved=None, *, lead):
+    """PatchEmbed (im2col + GEMM) + cls token + position embedding.  lead = 1: x fp32 [B, 1+Np, D] with the cls token in front
+    (deit:172-181); lead = 0: the patch tokens only, the cls token gets no position and joins later (cait:307-309)."""
     pe = feats.patch_embed
     B = img.shape[0]
     D, Np = feats.embed_dim, pe.num_patches
     cols = ops.im2col_patch(img.contiguous().float(), pe.patch_size)
     w16 = store.w16(pe.proj.weight).reshape(D, -1)
     tok = ops.gemm(cols, w16, epi=EPI_F32, bias=pe.proj.bias)
-    x = ops.assemble_tokens(tok, feats.cls_token, feats.pos_embed, B, Np, D, 1)
+    x = ops.assemble_tokens(tok, feats.cls_token, feats.pos_embed, B, Np, D, lead)
     if saved is not None:
         saved["cols"] = cols
     return x
+
+
+def row_tile_fwd(M, Nc, D, hid):
+    """Tile height at which the full-row GEMMs of csrc/rowgemm.hip (residual product + the LayerNorm that follows it, one launch) take the
+    residual products of a block on M rows, Nc per sample; None where they do not cover the shape."""
+    rpt = ops.rowgemm_tile_rows(M, Nc)
+    return rpt if ops.rowgemm_ok(D, D, rpt) and ops.rowgemm_ok(D, hid, rpt) else None
+
+
+def block_fwd(blk, store, x, Nc, attn, scales, row_tile, pre, nxt, save):
+    """One pre-norm residual block on x fp32 [B*Nc, D] (Nc tokens per sample):
+        norm1 -> qkv GEMM -> attention -> proj GEMM + residual (+ norm2) -> fc1 GEMM + GELU -> fc2 GEMM + residual (+ norm1 of `nxt`).
+    attn(blk, qkv) -> (ao bf16 [B*Nc, D], what its backward needs: entries of the saved dict).  scales: the (s1, s2) DropPath factors of
+    the two branches.  With gamma_1 / gamma_2 on the block (LayerScale) each branch is scaled per column and its unscaled output kept.
+    row_tile (row_tile_fwd; None: separate launches): the residual products are full-row GEMMs that also emit the LayerNorm that follows
+    them: `pre` = (n1, mean1, rstd1) out of the previous block's fc2 launch, and the block `nxt` whose norm1 rides on this one's.
+    Returns (x_out, pre of the coming block or None, saved activations or None)."""
+    M, D = x.shape
+    g1, g2 = getattr(blk, "gamma_1", None), getattr(blk, "gamma_2", None)
+    s1, s2 = scales
+    qkv_l, proj, fc1, fc2, norm2 = blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2, blk.norm2
+    rpt, fused = row_tile, row_tile is not None
+    n1, mean1, rstd1 = pre if pre is not None else ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, LN_EPS)
+    qkv = ops.gemm(n1, store.w16(qkv_l.weight), epi=EPI_BF16, bias=qkv_l.bias)
+    ao, attn_saved = attn(blk, qkv)
+    raw1 = torch.empty((M, D), dtype=torch.bfloat16, device=x.device) if save and g1 is not None else None
+    if fused:
+        x1, n2, mean2, rstd2 = ops.rowgemm_resid_ln(ao, store.w16(proj.weight), x, rpt, bias=proj.bias, rowscale=s1, rows_per_group=Nc,
+                                                    ln_w=norm2.weight, ln_b=norm2.bias, eps=LN_EPS, colscale=g1, aux_out=raw1)
+    else:
+        x1 = ops.gemm(ao, store.w16(proj.weight), epi=EPI_RESID, bias=proj.bias, res=x, rowscale=s1, rows_per_group=Nc, colscale=g1, aux_out=raw1)
+        n2, mean2, rstd2 = ops.layernorm_fwd(x1, norm2.weight, norm2.bias, LN_EPS)
+    h = torch.empty((M, fc1.out_features), dtype=torch.uint8, device=x.device)            # gelu'(pre-activation), 8-bit codes (csrc/gemm_common.h)
+    g = ops.gemm(n2, store.w16(fc1.weight), epi=EPI_GELU, bias=fc1.bias, aux_out=h)
+    raw2 = torch.empty((M, D), dtype=torch.bfloat16, device=x.device) if save and g2 is not None else None
+    pre = None
+    if fused:
+        x2, nn1, nm1, nr1 = ops.rowgemm_resid_ln(g, store.w16(fc2.weight), x1, rpt, bias=fc2.bias, rowscale=s2, rows_per_group=Nc,
+                                                 ln_w=nxt.norm1.weight if nxt is not None else None, ln_b=nxt.norm1.bias if nxt is not None else None,
+                                                 eps=LN_EPS, colscale=g2, aux_out=raw2)
+        if nxt is not None:
+            pre = (nn1, nm1, nr1)
+    else:
+        x2 = ops.gemm(g, store.w16(fc2.weight), epi=EPI_RESID, bias=fc2.bias, res=x1, rowscale=s2, rows_per_group=Nc, colscale=g2, aux_out=raw2)
+    L = None
+    if save:
+        L = dict(x=x, n1=n1, mean1=mean1, rstd1=rstd1, qkv=qkv, ao=ao, x1=x1, n2=n2, mean2=mean2, rstd2=rstd2, h=h, g=g, raw1=raw1, raw2=raw2,
+                 s1=s1, s2=s2, N=Nc, **attn_saved)
+    return x2, pre, L
 
 
 def deit_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save, compact=None):
@@ -101,32 +151,15 @@ def deit_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save, compact
     roll_side = reserve_layer > 0
     pre = None                                    # (n1, mean1, rstd1) of the coming block when the previous block's fc2 GEMM produced them
     nblk = len(feats.blocks)
-    for i, blk in enumerate(feats.blocks):
-        if i == reserve_layer:
-            lane.join()
-            if rolled is not None:
-                cls_attn, idx, policy = rolled
-            else:
-                cls_attn, idx, policy = ops.rollout(hm, reserve_layer, B, N, reserve_k, lead=1, thr=thr if side_thr else None)
-            if compact:
-                rows = ops.reserved_rows_map(idx, N)
-                x = ops.gather_rows(x, rows)
-                Nc, eps_n, policy = 1 + reserve_k, N, None
-                pre = None
-        M = B * Nc
-        hid = blk.mlp.fc1.out_features
-        # full-row GEMMs (csrc/rowgemm.hip): the residual products also emit the LayerNorm that follows them
-        rpt = ops.rowgemm_tile_rows(B * Nc, Nc)
-        fused = ops.rowgemm_ok(D, D, rpt) and ops.rowgemm_ok(D, hid, rpt)
-        n1, mean1, rstd1 = pre if pre is not None else ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, LN_EPS)
-        pre = None
-        qkv = ops.gemm(n1, store.w16(blk.attn.qkv.weight), epi=EPI_BF16, bias=blk.attn.qkv.bias)
+
+    def attn(blk, qkv):                           # attention of block i (the loop below) + what the side stream gets behind it
+        nonlocal rolled
         # the head-mean map of a layer in front of the reservation (the rollout's input) comes out of the attention launch itself where the
         # one-launch kernel covers the shape; otherwise it is recomputed from the saved statistics on the side stream
         hm_fused = i < reserve_layer and ops.attn_fwd_hm_ok(H, Nc, D)
         ao, rowmax, zinv = ops.attn_fwd(qkv, B, H, Nc, D, policy=policy, self_keep=True, eps_n=eps_n, headmean=hm[i] if hm_fused else None)
         if i < reserve_layer:
-            def side(qkv=qkv, rowmax=rowmax, zinv=zinv, i=i, hm_fused=hm_fused):
+            def side(i=i):
                 if not hm_fused:
                     ops.attn_headmean(qkv, rowmax, zinv, B, H, N, D, policy=policy, self_keep=True, out=hm[i])
                 if side_thr:
@@ -140,37 +173,29 @@ def deit_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save, compact
                 rolled = ops.rollout_outputs(B, N, reserve_k, 1, x.device)
                 lane.submit(lambda: ops.rollout(hm, reserve_layer, B, N, reserve_k, lead=1, thr=thr if side_thr else None, out=rolled),
                             (hm, thr) + rolled)
-        s1, s2 = _dp(dp, 2 * i), _dp(dp, 2 * i + 1)
-        if fused:
-            x1, n2, mean2, rstd2 = ops.rowgemm_resid_ln(ao, store.w16(blk.attn.proj.weight), x, rpt, bias=blk.attn.proj.bias, rowscale=s1, rows_per_group=Nc,
-                                                        ln_w=blk.norm2.weight, ln_b=blk.norm2.bias, eps=LN_EPS)
-        else:
-            x1 = ops.gemm(ao, store.w16(blk.attn.proj.weight), epi=EPI_RESID, bias=blk.attn.proj.bias, res=x, rowscale=s1, rows_per_group=Nc)
-            n2, mean2, rstd2 = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, LN_EPS)
-        h = torch.empty((M, hid), dtype=torch.uint8, device=x.device)            # gelu'(pre-activation), 8-bit codes (csrc/gemm_common.h)
-        g = ops.gemm(n2, store.w16(blk.mlp.fc1.weight), epi=EPI_GELU, bias=blk.mlp.fc1.bias, aux_out=h)
-        if fused:
-            # the next block's norm1 rides on this block's fc2 product, unless the token gather of the reservation comes in between
-            nxt = feats.blocks[i + 1] if (i + 1 < nblk and not (compact and i + 1 == reserve_layer)) else None
-            x2, nn1, nm1, nr1 = ops.rowgemm_resid_ln(g, store.w16(blk.mlp.fc2.weight), x1, rpt, bias=blk.mlp.fc2.bias, rowscale=s2, rows_per_group=Nc,
-                                                     ln_w=nxt.norm1.weight if nxt is not None else None, ln_b=nxt.norm1.bias if nxt is not None else None,
-                                                     eps=LN_EPS)
-            pre = (nn1, nm1, nr1) if nxt is not None else None
-        else:
-            x2 = ops.gemm(g, store.w16(blk.mlp.fc2.weight), epi=EPI_RESID, bias=blk.mlp.fc2.bias, res=x1, rowscale=s2, rows_per_group=Nc)
+        return ao, dict(rowmax=rowmax, zinv=zinv, policy=policy, eps_n=eps_n)
+
+    for i, blk in enumerate(feats.blocks):
+        if i == reserve_layer:
+            lane.join()
+            if rolled is not None:
+                cls_attn, idx, policy = rolled
+            else:
+                cls_attn, idx, policy = ops.rollout(hm, reserve_layer, B, N, reserve_k, lead=1, thr=thr if side_thr else None)
+            if compact:
+                rows = ops.reserved_rows_map(idx, N)
+                x = ops.gather_rows(x, rows)
+                Nc, eps_n, policy = 1 + reserve_k, N, None
+                pre = None
+        # the next block's norm1 rides on this block's fc2 product, unless the token gather of the reservation comes in between
+        nxt = feats.blocks[i + 1] if (i + 1 < nblk and not (compact and i + 1 == reserve_layer)) else None
+        row_tile = row_tile_fwd(B * Nc, Nc, D, blk.mlp.fc1.out_features)
+        x, pre, L = block_fwd(blk, store, x, Nc, attn, (_dp(dp, 2 * i), _dp(dp, 2 * i + 1)), row_tile, pre, nxt, save)
         if save:
-            layers.append(dict(x=x, n1=n1, mean1=mean1, rstd1=rstd1, qkv=qkv, ao=ao, rowmax=rowmax, zinv=zinv, x1=x1, n2=n2,
-                               mean2=mean2, rstd2=rstd2, h=h, g=g, policy=policy, s1=s1, s2=s2, N=Nc, eps_n=eps_n,
-                               rows=rows if (compact and i == reserve_layer) else None))
-        x = x2
+            L["rows"] = rows if (compact and i == reserve_layer) else None
+            layers.append(L)
     lane.join()
     return x.reshape(B, Nc, D), cls_attn, idx, layers
-
-
-def gather_rows_map(idx, N):
-    """Source-row map of the reserved tokens: per sample [cls, 1+idx...] as flat rows of the [B*N] token matrix
-    (integer index plumbing of protopformer.py:156-162)."""
-    return ops.reserved_rows_map(idx, N)
 
 
 def head_tokens_fwd(ppnet, store, x, idx):
@@ -180,7 +205,7 @@ def head_tokens_fwd(ppnet, store, x, idx):
     feats = ppnet.features
     B, N, D = x.shape
     k = idx.shape[1]
-    row_map = gather_rows_map(idx, N) if N != 1 + k else None
+    row_map = ops.reserved_rows_map(idx, N) if N != 1 + k else None
     nf, meanf, rstdf = ops.layernorm_fwd(x.reshape(B * N, D), feats.norm.weight, feats.norm.bias, LN_EPS, row_map=row_map)
     f, chain = addon_fwd(ppnet, store, nf)
     return f.reshape(B, 1 + k, f.shape[-1]), dict(row_map=row_map, nf=nf, meanf=meanf, rstdf=rstdf, chain=chain)
@@ -337,62 +362,52 @@ def _wgrad(store, dy16, x16, weight, bias=None, defer=False):
 _DGRAD_ROW = 3
 
 
-def _dgrad(dy16, store, weight, wt, rows=None, which=0):
+def _dgrad(store, dy16, weight, rows, which):
     """dx = dy W as bf16.  With the transposed weight shadow (FlatStore.register_transposed) both operands are contraction-contiguous and
     the product can take the 224 x 128 direct-to-LDS kernel (csrc/gemm_bf16.hip gemm224g_kernel: one round of the chip instead of 1.54 for
     the N = 384 outputs); otherwise the [K][N] weight is read transposed by the generic kernel."""
-    if wt is not None and (_DGRAD_ROW & which) and rows is not None and ops.rowgemm_ok(wt.shape[0], wt.shape[1], rows):
+    wt = store.w16t(weight)
+    if wt is not None and (_DGRAD_ROW & which) and ops.rowgemm_ok(wt.shape[0], wt.shape[1], rows):
         return ops.rowgemm_bf16(dy16, wt, rows)
     if wt is not None:
         return ops.gemm(dy16, wt, epi=EPI_BF16)
     return ops.gemm(dy16, store.w16(weight), trans_b=True, epi=EPI_BF16)
 
 
-def deit_backward(ppnet, store, saved, df):
-    """Backward of image -> f. df: fp32 [B*(1+k), Dp] gradient w.r.t. the sigmoid outputs."""
-    feats = ppnet.features
-    layers, head = saved["layers"], saved["head"]
-    x_last = saved["x_last"]                      # [B, N, D] fp32 (pre-final-norm)
-    B, N, D = x_last.shape
-    M = B * N
-    dev = x_last.device
+def head_bwd(ppnet, store, saved, df):
+    """Add-on backward: sigmoid' (and the fp32 tail of a bottleneck head), then the two GEMMs of its first convolution.
+    -> dnf bf16: gradient w.r.t. the final norm's output on the reserved rows."""
+    head = saved["head"]
     conv = addon_convs(ppnet)[0]
-    # add-on: sigmoid' (and the fp32 tail of a bottleneck head) then the two GEMMs of its first convolution
-    lane = wgrad_lane(store)
-    lnb = functools.partial(ops.layernorm_bwd, lane=lane, defer_reduce=True)      # column-sum reductions (parameter grads): side stream
     dz = addon_bwd(ppnet, store, head, saved["f"].reshape(-1, saved["f"].shape[-1]), df)
     _wgrad(store, dz, head["nf"], conv.weight)
-    dnf = ops.gemm(dz, store.w16(conv.weight).reshape(conv.out_channels, D), trans_b=True, epi=EPI_BF16)
-    # final norm backward scatters into the (zero) residual-stream gradient; also emits the bf16 gradient of the last fc2
-    # (x_last is already the reserved rows when the last blocks ran compacted: then nothing is scattered here)
-    alloc = ops.zeros if head["row_map"] is not None else (lambda shape, dtype, device: torch.empty(shape, dtype=dtype, device=device))
-    dx = alloc((M, D), torch.float32, dev)
-    dyb = lane.track(alloc((M, D), torch.bfloat16, dev))
-    last = feats.blocks[-1]
-    lnb(dnf, x_last.reshape(M, D), feats.norm.weight, head["meanf"], head["rstdf"], store.grad_view(feats.norm.weight),
-                      store.grad_view(feats.norm.bias), dx_out=dx, row_map=head["row_map"], cast_out=dyb, rowscale=layers[-1]["s2"],
-                      rows_per_group=N, dbias_next=store.grad_view(last.mlp.fc2.bias))
-    gs = getattr(ppnet, "_grad_sync", None)           # data-parallel: all-reduce chunks as their layers complete
-    if gs is not None:
-        lane.flush()
-        _lib.run_live(lambda: gs.chunk_ready(gs.tail_chunk, also=lane.streams))
-    # The bf16 branch gradient alternates between two buffers: the LayerNorm backward that produces the next one does not have to
-    # wait for the side stream's weight-gradient GEMM that still reads the current one (the main stream would otherwise be tied to
-    # the progress of the side stream twice per block).  Round 4: four buffers in
-    # rotation instead of two (the side stream lags up to a block behind at the start of backward: +0.6 % deit_small, +0.5 % deit_tiny
-    # same-box; six = four).  Parking the prototype-gradient kernel until a few blocks' weight gradients have run was measured
-    # 1 % SLOWER: at the start of backward it overlaps the serial head section, later it lands in the saturated part.
-    dyb_alt = None
+    return ops.gemm(dz, store.w16(conv.weight).reshape(conv.out_channels, -1), trans_b=True, epi=EPI_BF16)
 
-    # buffers the branch gradient rotates through (2 = ping-pong; 4: +0.6 % same-box at D = 384).  The narrow models never reuse one
-    # (64 > two per block): their side stream lags whole blocks behind and every reuse is a main-stream wait (cait_xxs24 +4 % same-box,
-    # deit_tiny +0.2 %; 24-48 buffers of B*N*D bf16 = 0.2-0.5 GB of the 288); at D = 384 no reuse measured -0.7 % (larger footprint).
+
+def chunk_ready(gs, lane, chunk):
+    """Data-parallel (gs: engine.GradSync): the gradients of `chunk` are complete once everything enqueued so far has run; their
+    all-reduce goes out behind it."""
+    lane.flush()
+    _lib.run_live(lambda: gs.chunk_ready(chunk, also=lane.streams))
+
+
+def dyb_ring(lane, D):
+    """The bf16 branch gradient `dyb` rotates through several buffers: the kernel that produces the next one does not have to wait for the
+    side stream's weight-gradient GEMM that still reads the current one (the main stream would otherwise be tied to the progress of the
+    side stream twice per block: a 44 us stall per block on CaiT).  Round 4: four buffers in rotation instead of two (the side stream
+    lags up to a block behind at the start of backward: +0.6 % deit_small, +0.5 % deit_tiny same-box; six = four).  The narrow models
+    never reuse one (64 > two per block): their side stream lags whole blocks behind and every reuse is a main-stream wait (cait_xxs24
+    +4 % same-box, deit_tiny +0.2 %; 24-48 buffers of B*N*D bf16 = 0.2-0.5 GB of the 288); at D = 384 no reuse measured -0.7 % (larger
+    footprint).  Parking the prototype-gradient kernel until a few blocks' weight gradients have run was measured 1 % SLOWER: at the
+    start of backward it overlaps the serial head section, later it lands in the saturated part.
+    Returns next_dyb(cur) -> the buffer the next branch gradient goes to, ordered behind the side stream's last read of it.  A buffer
+    that enters the rotation from outside (the first one, one of another shape) must be registered with lane.track() by its owner."""
     nring = 4 if D > 256 else 64
-    ring = {}
+    ring = {}                                             # shape -> buffers in rotation
 
-    def next_dyb(cur, alt):
+    def next_dyb(cur):
         if nring >= 64:                                   # never reused: nothing to order against the side stream, no marks
-            return torch.empty_like(cur), cur
+            return torch.empty_like(cur)
         bufs = ring.setdefault(tuple(cur.shape), [cur])
         if not any(b.data_ptr() == cur.data_ptr() for b in bufs):
             bufs.append(cur)
@@ -403,85 +418,153 @@ def deit_backward(ppnet, store, saved, df):
             i = next(j for j, b in enumerate(bufs) if b.data_ptr() == cur.data_ptr())
             nxt = bufs[(i + 1) % len(bufs)]
         lane.before_overwrite(nxt)
-        return nxt, cur
+        return nxt
 
-    # Bias gradients of proj / fc2 are column sums of the bf16 branch gradient `dyb`: the LayerNorm-backward KERNEL adds them while it
-    # writes dyb (dbias_next); the fused GEMM + LayerNorm-backward (csrc/rowgemm.hip) does not, there the weight-gradient GEMM that
-    # reads dyb anyway sums its columns (COLSUM).  bias_done: the producer of the current dyb has already accumulated the bias gradient.
+    return next_dyb
+
+
+def branch_out(store, dyb, rowscale, rows_per_group, gamma=None, raw=None):
+    """Arguments of a LayerNorm-backward / scale-cast pass that also emits dyb, the bf16 gradient at the output of the residual branch
+    below it: dyb = bf16(rowscale * [gamma *] dx), and with LayerScale dgamma += sum_m rowscale * dx * raw (raw: the unscaled branch)."""
+    kw = dict(cast_out=dyb, rowscale=rowscale, rows_per_group=rows_per_group)
+    if gamma is not None:
+        kw.update(colscale=gamma, branch=raw, dcolscale=store.grad_view(gamma))
+    return kw
+
+
+def mlp_bwd(store, blk, L, dyb, bias_done):
+    """dyb = bf16 gradient of the fc2 output -> dh, the gradient at fc1's output; queues both weight gradients.  bias_done False: dyb's
+    producer did not accumulate fc2.bias' gradient, the weight-gradient GEMM that reads dyb anyway sums its columns."""
+    fc1, fc2 = blk.mlp.fc1, blk.mlp.fc2
+    _wgrad(store, dyb, L["g"], fc2.weight, None if bias_done else fc2.bias, defer=True)
+    w2t = store.w16t(fc2.weight)
+    if w2t is not None:      # contraction-contiguous operands: the direct-to-LDS kernel (gemm128g, four workgroups per CU) takes K = 384
+        dh = ops.gemm(dyb, w2t, epi=EPI_DGELU, aux_in=L["h"])
+    else:
+        dh = ops.gemm(dyb, store.w16(fc2.weight), trans_b=True, epi=EPI_DGELU, aux_in=L["h"])
+    _wgrad(store, dh, L["n2"], fc1.weight, fc1.bias)
+    return dh
+
+
+def row_tile_bwd(store, blk, D, rpt):
+    """rpt where the backward full-row kernels (input gradient of fc1 / qkv + LayerNorm backward in one launch, proj's on the plain one)
+    cover this block at that tile height -- they read the transposed weight shadows --, else None."""
+    covered = (all(store.w16t(w) is not None for w in (blk.mlp.fc1.weight, blk.attn.qkv.weight, blk.attn.proj.weight))
+               and ops.rowgemm_ok(D, blk.mlp.fc1.out_features, rpt) and ops.rowgemm_ok(D, 3 * D, rpt) and ops.rowgemm_ok(D, D, rpt))
+    return rpt if covered else None
+
+
+def block_bwd(blk, store, L, dx, dyb, bias_done, below, *, next_dyb, attn_bwd, lnb, dgrad, row_tile):
+    """Backward of block_fwd.  dx fp32 [B*N, D]: gradient of the residual stream at the block's output (updated in place to the one at
+    its input); dyb: bf16 gradient at the fc2 output (DropPath / LayerScale already applied); bias_done: dyb's producer has accumulated
+    fc2.bias' gradient.  below = (block, saved dict) of the block in front, or None: then no branch gradient is produced.
+    Bias gradients of proj / fc2 are column sums of dyb: the LayerNorm-backward KERNEL adds them while it writes dyb (dbias_next); the
+    fused GEMM + LayerNorm-backward (csrc/rowgemm.hip) does not, there the weight-gradient GEMM that reads dyb anyway sums its columns.
+    What each backbone measured and hands in: attn_bwd(blk, L, dao) -> dqkv; lnb = ops.layernorm_bwd bound to the lane and its way of
+    scheduling the column-sum reduction; dgrad(dy16, weight, rows, which) -> dy W as bf16, the input gradient where it is a launch of
+    its own (which: fc1 1, qkv 2, proj 4); row_tile (row_tile_bwd): tile height for the full-row kernels that fuse the input gradient
+    of fc1 / qkv with the LayerNorm backward (and take proj's), or None to keep them out of this block.
+    Returns (dyb at the fc2 output of the block in front, its bias_done)."""
+    lane = wgrad_lane(store)
+    gv = store.grad_view
+    Nl = L["N"]
+    fc1, qkv, proj = blk.mlp.fc1, blk.attn.qkv, blk.attn.proj            # (nn.Module attribute lookups are the host cost of this function)
+    fused = row_tile is not None
+
+    def norm_bwd(dy, weight, dn, x, mean, rstd, norm, out, bias_next=None):
+        """LayerNorm backward into dx of the gradient dn (= dy W where the full-row kernel computes it itself) + the branch gradient `out`
+        (bias_next: the bias of the Linear that produced that branch)."""
+        nw = norm.weight
+        if fused:
+            ops.rowgemm_lnbwd(dy, store.w16t(weight), x, mean, rstd, nw, gv(nw), gv(norm.bias), row_tile, dres_in=dx, dx_out=dx,
+                              lane=lane, defer_reduce=True, **out)
+        else:
+            lnb(dn, x, nw, mean, rstd, gv(nw), gv(norm.bias), dres_in=dx, dx_out=dx, dbias_next=gv(bias_next) if out else None, **out)
+
+    # MLP branch: x2 = x1 + s2 * (gelu(n2 W1^T + b1) W2^T + b2)
+    dh = mlp_bwd(store, blk, L, dyb, bias_done)
+    dyb = next_dyb(dyb)
+    dn2 = None if fused else dgrad(dh, fc1.weight, Nl, 1)
+    norm_bwd(dh, fc1.weight, dn2, L["x1"], L["mean2"], L["rstd2"], blk.norm2, branch_out(store, dyb, L["s1"], Nl, getattr(blk, "gamma_1", None), L["raw1"]),
+             proj.bias)
+    bias_done = not fused
+    # attention branch: x1 = x + s1 * (attn(n1) Wp^T + bp)
+    _wgrad(store, dyb, L["ao"], proj.weight, None if bias_done else proj.bias, defer=True)
+    dao = ops.rowgemm_bf16(dyb, store.w16t(proj.weight), row_tile) if fused else dgrad(dyb, proj.weight, Nl, 4)
+    dqkv = attn_bwd(blk, L, dao)
+    _wgrad(store, dqkv, L["n1"], qkv.weight, qkv.bias)
+    dn1 = None if fused else dgrad(dqkv, qkv.weight, Nl, 2)
+    if below is None:
+        norm_bwd(dqkv, qkv.weight, dn1, L["x"], L["mean1"], L["rstd1"], blk.norm1, {})
+        return None, bias_done
+    prev, Lp = below
+    dyb = next_dyb(dyb)
+    norm_bwd(dqkv, qkv.weight, dn1, L["x"], L["mean1"], L["rstd1"], blk.norm1,
+             branch_out(store, dyb, Lp["s2"], Nl, getattr(prev, "gamma_2", None), Lp["raw2"]), prev.mlp.fc2.bias)
+    return dyb, not fused
+
+
+def embed_bwd(ppnet, store, saved, dx, lead):
+    """Token assembly + patch embedding backward (dx fp32 [B*(Np+lead), D]), the last gradient chunk, and the lane joined."""
+    feats = ppnet.features
+    pe = feats.patch_embed
+    Np, D = pe.num_patches, dx.shape[1]
+    gv = store.grad_view
+    dtok = ops.assemble_tokens_bwd(dx, gv(feats.pos_embed).reshape(Np + lead, D), gv(feats.cls_token).reshape(D) if lead else None,
+                                   dx.shape[0] // (Np + lead), Np, D, lead)
+    _wgrad(store, dtok, saved["cols"], pe.proj.weight, pe.proj.bias)
+    lane = wgrad_lane(store)
+    gs = getattr(ppnet, "_grad_sync", None)
+    if gs is not None:
+        chunk_ready(gs, lane, gs.head_chunk)
+    lane.join()
+
+
+def deit_backward(ppnet, store, saved, df):
+    """Backward of image -> f. df: fp32 [B*(1+k), Dp] gradient w.r.t. the sigmoid outputs."""
+    feats = ppnet.features
+    layers, head = saved["layers"], saved["head"]
+    x_last = saved["x_last"]                      # [B, N, D] fp32 (pre-final-norm)
+    B, N, D = x_last.shape
+    M = B * N
+    dev = x_last.device
+    lane = wgrad_lane(store)
+    lnb = functools.partial(ops.layernorm_bwd, lane=lane, defer_reduce=True)      # column-sum reductions (parameter grads): side stream
+    dnf = head_bwd(ppnet, store, saved, df)
+    # final norm backward scatters into the (zero) residual-stream gradient; also emits the bf16 gradient of the last fc2
+    # (x_last is already the reserved rows when the last blocks ran compacted: then nothing is scattered here)
+    alloc = ops.zeros if head["row_map"] is not None else (lambda shape, dtype, device: torch.empty(shape, dtype=dtype, device=device))
+    dx = alloc((M, D), torch.float32, dev)
+    dyb = lane.track(alloc((M, D), torch.bfloat16, dev))
+    last = feats.blocks[-1]
+    lnb(dnf, x_last.reshape(M, D), feats.norm.weight, head["meanf"], head["rstdf"], store.grad_view(feats.norm.weight),
+        store.grad_view(feats.norm.bias), dx_out=dx, row_map=head["row_map"], cast_out=dyb, rowscale=layers[-1]["s2"],
+        rows_per_group=N, dbias_next=store.grad_view(last.mlp.fc2.bias))
+    gs = getattr(ppnet, "_grad_sync", None)           # data-parallel: all-reduce chunks as their layers complete
+    if gs is not None:
+        chunk_ready(gs, lane, gs.tail_chunk)
+    # input gradients of fc1 / qkv / proj where they are launches of their own: _dgrad with the _DGRAD_ROW routing
+    bwd = functools.partial(block_bwd, next_dyb=dyb_ring(lane, D), lnb=lnb, dgrad=functools.partial(_dgrad, store),
+                            attn_bwd=lambda blk, L, dao: ops.attn_bwd(L["qkv"], L["ao"], dao, L["rowmax"], L["zinv"], B, feats.num_heads, L["N"], D,
+                                                                      policy=L["policy"], self_keep=True, eps_n=L["eps_n"]))
     bias_done = True
     for i in range(len(layers) - 1, -1, -1):
-        L, blk = layers[i], feats.blocks[i]
+        L = layers[i]
         Nl = L["N"]                                       # tokens per sample in this block (1+k once compacted)
-        hid = blk.mlp.fc1.out_features
-        w1t, wqt, wpt = store.w16t(blk.mlp.fc1.weight), store.w16t(blk.attn.qkv.weight), store.w16t(blk.attn.proj.weight)
-        rpt = ops.rowgemm_tile_rows(B * Nl, Nl, backward=True)
-        fused = (_row_bwd(B * Nl, D) and w1t is not None and wqt is not None and wpt is not None and ops.rowgemm_ok(D, hid, rpt) and ops.rowgemm_ok(D, 3 * D, rpt)
-                 and ops.rowgemm_ok(D, D, rpt))
-        # MLP branch: x2 = x1 + s2 * (gelu(n2 W1^T + b1) W2^T + b2)
-        _wgrad(store, dyb, L["g"], blk.mlp.fc2.weight, None if bias_done else blk.mlp.fc2.bias, defer=True)
-        w2t = store.w16t(blk.mlp.fc2.weight)
-        if w2t is not None:      # contraction-contiguous operands: the direct-to-LDS kernel (gemm128g, four workgroups per CU) takes K = 384
-            dh = ops.gemm(dyb, w2t, epi=EPI_DGELU, aux_in=L["h"])
-        else:
-            dh = ops.gemm(dyb, store.w16(blk.mlp.fc2.weight), trans_b=True, epi=EPI_DGELU, aux_in=L["h"])
-        _wgrad(store, dh, L["n2"], blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-        dyb, dyb_alt = next_dyb(dyb, dyb_alt)
-        if fused:
-            ops.rowgemm_lnbwd(dh, w1t, L["x1"], L["mean2"], L["rstd2"], blk.norm2.weight, store.grad_view(blk.norm2.weight), store.grad_view(blk.norm2.bias),
-                              rpt, dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=L["s1"], rows_per_group=Nl, lane=lane, defer_reduce=True)
-        else:
-            dn2 = _dgrad(dh, store, blk.mlp.fc1.weight, w1t, Nl, 1)
-            lnb(dn2, L["x1"], blk.norm2.weight, L["mean2"], L["rstd2"], store.grad_view(blk.norm2.weight),
-                              store.grad_view(blk.norm2.bias), dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=L["s1"], rows_per_group=Nl,
-                              dbias_next=store.grad_view(blk.attn.proj.bias))
-        bias_done = not fused
-        # attention branch: x1 = x + s1 * (attn(n1) Wp^T + bp)
-        _wgrad(store, dyb, L["ao"], blk.attn.proj.weight, None if bias_done else blk.attn.proj.bias, defer=True)
-        if fused:
-            dao = ops.rowgemm_bf16(dyb, wpt, rpt)
-        else:
-            dao = _dgrad(dyb, store, blk.attn.proj.weight, wpt, Nl, 4)
-        dqkv = ops.attn_bwd(L["qkv"], L["ao"], dao, L["rowmax"], L["zinv"], B, feats.num_heads, Nl, D, policy=L["policy"], self_keep=True, eps_n=L["eps_n"])
-        _wgrad(store, dqkv, L["n1"], blk.attn.qkv.weight, blk.attn.qkv.bias)
-        dn1 = None if fused else _dgrad(dqkv, store, blk.attn.qkv.weight, wqt, Nl, 2)
-        if i > 0:
-            prev = feats.blocks[i - 1]
-            dyb, dyb_alt = next_dyb(dyb, dyb_alt)
-            if fused:
-                ops.rowgemm_lnbwd(dqkv, wqt, L["x"], L["mean1"], L["rstd1"], blk.norm1.weight, store.grad_view(blk.norm1.weight), store.grad_view(blk.norm1.bias),
-                                  rpt, dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=layers[i - 1]["s2"], rows_per_group=Nl, lane=lane, defer_reduce=True)
-            else:
-                lnb(dn1, L["x"], blk.norm1.weight, L["mean1"], L["rstd1"], store.grad_view(blk.norm1.weight),
-                                  store.grad_view(blk.norm1.bias), dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=layers[i - 1]["s2"],
-                                  rows_per_group=Nl, dbias_next=store.grad_view(prev.mlp.fc2.bias))
-            bias_done = not fused
-            if L["rows"] is not None:
-                # this block ran on the reserved rows: hand its input gradient back to the full token matrix (zeros elsewhere)
-                Mf = B * layers[i - 1]["N"]
-                dx = ops.scatter_rows(dx, L["rows"], Mf)
-                dyb = lane.track(ops.scatter_rows(dyb, L["rows"], Mf))
-                dyb_alt = None
-        else:
-            if fused:
-                ops.rowgemm_lnbwd(dqkv, wqt, L["x"], L["mean1"], L["rstd1"], blk.norm1.weight, store.grad_view(blk.norm1.weight), store.grad_view(blk.norm1.bias),
-                                  rpt, dres_in=dx, dx_out=dx, lane=lane, defer_reduce=True)
-            else:
-                lnb(dn1, L["x"], blk.norm1.weight, L["mean1"], L["rstd1"], store.grad_view(blk.norm1.weight),
-                                  store.grad_view(blk.norm1.bias), dres_in=dx, dx_out=dx)
+        # full-row kernels: small problems only (_ROW_BWD_MAX_ELEMS), with tiles that leave CUs to the side stream
+        row_tile = row_tile_bwd(store, feats.blocks[i], D, ops.rowgemm_tile_rows(B * Nl, Nl, backward=True)) if _row_bwd(B * Nl, D) else None
+        dyb, bias_done = bwd(feats.blocks[i], store, L, dx, dyb, bias_done, (feats.blocks[i - 1], layers[i - 1]) if i > 0 else None,
+                             row_tile=row_tile)
+        if i > 0 and L["rows"] is not None:
+            # this block ran on the reserved rows: hand its input gradient back to the full token matrix (zeros elsewhere)
+            Mf = B * layers[i - 1]["N"]
+            dx = ops.scatter_rows(dx, L["rows"], Mf)
+            dyb = lane.track(ops.scatter_rows(dyb, L["rows"], Mf))
         if gs is not None and i in gs.block_chunk:
-            lane.flush()
-            _lib.run_live(lambda c=gs.block_chunk[i]: gs.chunk_ready(c, also=lane.streams))
-    # token assembly + patch embedding
-    pe = feats.patch_embed
-    Np = pe.num_patches
+            chunk_ready(gs, lane, gs.block_chunk[i])
     if layers and layers[0]["rows"] is not None:          # reservation in front of block 0: the embedding sees all tokens
-        dx = ops.scatter_rows(dx, layers[0]["rows"], B * (Np + 1))
-    dtok = ops.assemble_tokens_bwd(dx, store.grad_view(feats.pos_embed).reshape(Np + 1, D), store.grad_view(feats.cls_token).reshape(D), B, Np, D, 1)
-    _wgrad(store, dtok, saved["cols"], pe.proj.weight, pe.proj.bias)
-    if gs is not None:
-        lane.flush()
-        _lib.run_live(lambda: gs.chunk_ready(gs.head_chunk, also=lane.streams))
-    lane.join()
+        dx = ops.scatter_rows(dx, layers[0]["rows"], B * (feats.patch_embed.num_patches + 1))
+    embed_bwd(ppnet, store, saved, dx, 1)
 
 
 class TokensFn(torch.autograd.Function):
@@ -526,9 +609,9 @@ class TokensFn(torch.autograd.Function):
         return (None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
-def deit_t16_params(feats):
+def t16_params(feats):
     """Weights whose input-gradient products read W^T contraction-contiguous (csrc/rowgemm.hip, gemm224g / gemm128g): fc1, qkv, proj, fc2."""
     return [w for blk in feats.blocks for w in (blk.mlp.fc1.weight, blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc2.weight)]
 
 
-DEIT_FNS = dict(embed=deit_embed, blocks=deit_blocks_fwd, backward=deit_backward, t16_params=deit_t16_params)
+DEIT_FNS = dict(embed=functools.partial(embed_tokens, lead=1), blocks=deit_blocks_fwd, backward=deit_backward, t16_params=t16_params)

@@ -12,10 +12,11 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from .backbone import LN_EPS, _dp, _wgrad, addon_bwd, addon_convs, head_tokens_fwd, wgrad_lane
+from . import ops
+from .backbone import (LN_EPS, _ROLL_BATCH, _dp, _wgrad, block_bwd, block_fwd, branch_out, chunk_ready, dyb_ring, embed_bwd, embed_tokens, head_bwd,
+                       mlp_bwd, row_tile_bwd, row_tile_fwd, t16_params, wgrad_lane)
 from .deit import _Mlp, _PatchEmbed, _init_vit
-from .ops import EPI_BF16, EPI_DGELU, EPI_F32, EPI_GELU, EPI_RESID
+from .ops import EPI_ATOMIC, EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID
 
 
 class _TalkingHeadAttn(nn.Module):
@@ -83,7 +84,7 @@ class MyCait(nn.Module):
     @torch.no_grad()
     def forward_feature_patch_embed_all(self, x):
         """cait:303-312 (inference-only compatibility wrapper): returns (cls_tokens [B,1,D], x [B,Np,D])."""
-        xe = cait_embed(self, self._store(), x)
+        xe = embed_tokens(self, self._store(), x, lead=0)
         return self.cls_token.expand(x.shape[0], -1, -1), xe
 
     @torch.no_grad()
@@ -97,17 +98,6 @@ class MyCait(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ forward
-def cait_embed(feats, store, img, saved=None):
-    pe = feats.patch_embed
-    B, D, Np = img.shape[0], feats.embed_dim, pe.num_patches
-    cols = ops.im2col_patch(img.contiguous().float(), pe.patch_size)
-    tok = ops.gemm(cols, store.w16(pe.proj.weight).reshape(D, -1), epi=EPI_F32, bias=pe.proj.bias)
-    x = ops.assemble_tokens(tok, feats.cls_token, feats.pos_embed, B, Np, D, 0)          # cls gets no position (cait:307-309)
-    if saved is not None:
-        saved["cols"] = cols
-    return x
-
-
 def _th_attention_fwd(blk, qkv, B, H, N, D, hm_slot):
     """Talking-heads attention (cait:115-130) from packed qkv; returns (out bf16 [B*N,D], P fp32, A bf16)."""
     hd = D // H
@@ -143,45 +133,19 @@ def cait_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save):
     lane = wgrad_lane(store)
     layers = []
     x = x.reshape(M, D)
-    # The projection / fc2 GEMM, the LayerScale residual and the LayerNorm that follows run as one full-row kernel (csrc/rowgemm.hip) where
-    # the shape is covered: `pre` carries the next block's norm1 output out of the previous block's fc2 launch.
-    rpt = ops.rowgemm_tile_rows(M, N)
-    rowk = (bool(feats.blocks) and ops.rowgemm_ok(D, D, rpt)
-            and ops.rowgemm_ok(D, feats.blocks[0].mlp.fc1.out_features, rpt))
-    pre = None
-    rb = 3                                                                     # backbone._ROLL_BATCH
-    for i, blk in enumerate(feats.blocks):
-        n1, mean1, rstd1 = pre if pre is not None else ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, LN_EPS)
-        qkv = ops.gemm(n1, store.w16(blk.attn.qkv.weight), epi=EPI_BF16, bias=blk.attn.qkv.bias)
+    row_tile = row_tile_fwd(M, N, D, feats.blocks[0].mlp.fc1.out_features)      # every block has the same shape
+    pre = None                                    # the coming block's norm1 out of the previous block's fc2 launch (backbone.block_fwd)
+
+    def attn(blk, qkv):                           # attention of block i (the loop below) + what the side stream gets behind it
         ao, prob, a16 = _th_attention_fwd(blk, qkv, B, H, N, D, hm[i])
-        # the rollout's order statistic, off the critical path (three layers per main-stream event record, as backbone.forward_blocks)
-        side = lambda i=i: ops.rollout_threshold(hm[i], thr[i], N)
-        lane.submit(side, (hm, thr), defer=(i % rb != rb - 1) and i != len(feats.blocks) - 1)
-        s1, s2 = _dp(dp, 2 * i), _dp(dp, 2 * i + 1)
-        raw1 = torch.empty((M, D), dtype=torch.bfloat16, device=x.device) if save else None
-        if rowk:
-            x1, n2, mean2, rstd2 = ops.rowgemm_resid_ln(ao, store.w16(blk.attn.proj.weight), x, rpt, bias=blk.attn.proj.bias, rowscale=s1, rows_per_group=N,
-                                                        ln_w=blk.norm2.weight, ln_b=blk.norm2.bias, eps=LN_EPS, colscale=blk.gamma_1, aux_out=raw1)
-        else:
-            x1 = ops.gemm(ao, store.w16(blk.attn.proj.weight), epi=EPI_RESID, bias=blk.attn.proj.bias, res=x, rowscale=s1, rows_per_group=N,
-                          colscale=blk.gamma_1, aux_out=raw1)
-            n2, mean2, rstd2 = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, LN_EPS)
-        h = torch.empty((M, blk.mlp.fc1.out_features), dtype=torch.uint8, device=x.device)     # gelu'(pre-activation), 8-bit codes
-        g = ops.gemm(n2, store.w16(blk.mlp.fc1.weight), epi=EPI_GELU, bias=blk.mlp.fc1.bias, aux_out=h)
-        raw2 = torch.empty((M, D), dtype=torch.bfloat16, device=x.device) if save else None
-        nxt = feats.blocks[i + 1] if i + 1 < depth else None
-        if rowk:
-            x2, nn1, nm1, nr1 = ops.rowgemm_resid_ln(g, store.w16(blk.mlp.fc2.weight), x1, rpt, bias=blk.mlp.fc2.bias, rowscale=s2, rows_per_group=N,
-                                                     ln_w=nxt.norm1.weight if nxt is not None else None, ln_b=nxt.norm1.bias if nxt is not None else None,
-                                                     eps=LN_EPS, colscale=blk.gamma_2, aux_out=raw2)
-            pre = (nn1, nm1, nr1) if nxt is not None else None
-        else:
-            x2 = ops.gemm(g, store.w16(blk.mlp.fc2.weight), epi=EPI_RESID, bias=blk.mlp.fc2.bias, res=x1, rowscale=s2, rows_per_group=N,
-                          colscale=blk.gamma_2, aux_out=raw2)
+        # the rollout's order statistic of every layer, off the critical path (_ROLL_BATCH layers per main-stream event record)
+        lane.submit(lambda i=i: ops.rollout_threshold(hm[i], thr[i], N), (hm, thr), defer=(i % _ROLL_BATCH != _ROLL_BATCH - 1) and i != depth - 1)
+        return ao, dict(prob=prob, a16=a16)
+
+    for i, blk in enumerate(feats.blocks):
+        x, pre, L = block_fwd(blk, store, x, N, attn, (_dp(dp, 2 * i), _dp(dp, 2 * i + 1)), row_tile, pre, feats.blocks[i + 1] if i + 1 < depth else None, save)
         if save:
-            layers.append(dict(x=x, n1=n1, mean1=mean1, rstd1=rstd1, qkv=qkv, prob=prob, a16=a16, ao=ao, x1=x1, n2=n2, mean2=mean2,
-                               rstd2=rstd2, h=h, g=g, raw1=raw1, raw2=raw2, s1=s1, s2=s2))
-        x = x2
+            layers.append(L)
     # ---- class-attention stage: only the cls token changes
     N1 = N + 1
     # (every sub-matrix copy of this stage goes through the library -- ops.gather_rows / copy_2d / cat_rows -- not through ATen: a
@@ -200,10 +164,7 @@ def cait_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save):
         n, mean1, rstd1 = ops.layernorm_fwd(u, blk.norm1.weight, blk.norm1.bias, LN_EPS)
         kk = ops.gemm(n, store.w16(blk.attn.k.weight), epi=EPI_BF16, bias=blk.attn.k.bias)
         vv = ops.gemm(n, store.w16(blk.attn.v.weight), epi=EPI_BF16, bias=blk.attn.v.bias)
-        ncls = n.reshape(B, N1 * D)[:, :D]                                       # cls rows of n: row stride N1*D
-        qq = torch.empty((B, D), dtype=torch.bfloat16, device=x.device)
-        ops._lib.call("ppf_gemm_bf16", n, store.w16(blk.attn.q.weight), qq, B, D, D, N1 * D, D, D, 0, 0, EPI_BF16, blk.attn.q.bias, None, 0,
-                      None, 1, None, None, None, 0, None, 1.0, None, 0)
+        qq = ops.gemm(n, store.w16(blk.attn.q.weight), epi=EPI_BF16, bias=blk.attn.q.bias, lda=N1 * D)      # the cls rows of n: row stride N1*D
         out, attn, zinv, _ = ops.class_attn_fwd(qq, kk, vv, policy, B, H, N1, D, rowmean=rowmeans[j])
         raw1 = torch.empty((B, D), dtype=torch.bfloat16, device=x.device) if save else None
         cls1 = ops.gemm(out, store.w16(blk.attn.proj.weight), epi=EPI_RESID, bias=blk.attn.proj.bias, res=cls, colscale=blk.gamma_1, aux_out=raw1)
@@ -274,22 +235,6 @@ def _th_attention_bwd(store, blk, L, dao, B, H, N, D):
     return dqkv
 
 
-def _mlp_bwd(store, blk, L, dyb, fc2_bias=False, want_dn=True):
-    """Shared MLP backward: consumes dyb = bf16 gradient of the fc2 output; returns dn2 bf16 (want_dn) or dh, the gradient at fc1's
-    output (the caller then fuses fc1's input gradient with the LayerNorm backward).  fc2_bias: dyb's producer did not accumulate
-    fc2.bias' gradient, the weight-gradient GEMM that reads dyb anyway sums its columns."""
-    _wgrad(store, dyb, L["g"], blk.mlp.fc2.weight, blk.mlp.fc2.bias if fc2_bias else None, defer=True)
-    w2t = store.w16t(blk.mlp.fc2.weight)
-    if w2t is not None:          # contraction-contiguous operands: the direct-to-LDS kernels (csrc/gemm_bf16.hip gemm224g / gemm128g)
-        dh = ops.gemm(dyb, w2t, epi=EPI_DGELU, aux_in=L["h"])
-    else:
-        dh = ops.gemm(dyb, store.w16(blk.mlp.fc2.weight), trans_b=True, epi=EPI_DGELU, aux_in=L["h"])
-    _wgrad(store, dh, L["n2"], blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-    if not want_dn:
-        return dh
-    return ops.gemm(dh, store.w16(blk.mlp.fc1.weight), trans_b=True, epi=EPI_BF16)
-
-
 def cait_backward(ppnet, store, saved, df):
     feats = ppnet.features
     sa, ca = saved["layers"]["sa"], saved["layers"]["ca"]
@@ -299,13 +244,12 @@ def cait_backward(ppnet, store, saved, df):
     N, H = N1 - 1, feats.num_heads
     M = B * N
     dev = u_last.device
-    conv = addon_convs(ppnet)[0]
     gv = store.grad_view
     lane = wgrad_lane(store)
-    lnb = functools.partial(ops.layernorm_bwd, lane=lane)      # column-sum reductions (parameter grads) go to the side stream
-    dz = addon_bwd(ppnet, store, head, saved["f"].reshape(-1, saved["f"].shape[-1]), df)
-    _wgrad(store, dz, head["nf"], conv.weight)
-    dnf = ops.gemm(dz, store.w16(conv.weight).reshape(conv.out_channels, D), trans_b=True, epi=EPI_BF16)
+    # column-sum reductions (parameter grads) go to the side stream, each launched at once: parked until the lane's next submit measured
+    # -6 % on this backbone, whose scale / cast passes are followed by main-stream work first (ops.layernorm_bwd)
+    lnb = functools.partial(ops.layernorm_bwd, lane=lane)
+    dnf = head_bwd(ppnet, store, saved, df)
     du = ops.zeros((B * N1, D), torch.float32, dev)
     lnb(dnf, u_last.reshape(B * N1, D), feats.norm.weight, head["meanf"], head["rstdf"], gv(feats.norm.weight),
                       gv(feats.norm.bias), dx_out=du, row_map=head["row_map"])
@@ -314,15 +258,14 @@ def cait_backward(ppnet, store, saved, df):
     dcls = ops.copy_2d(torch.empty((B, D), dtype=torch.float32, device=dev), du2[:, :D])
     gs = getattr(ppnet, "_grad_sync", None)            # data-parallel: the final norm + add-on + prototype gradients are complete (round 6: this
     if gs is not None:                                 # chunk was launched LAST, 45 us of exchange behind the last backward kernel)
-        lane.flush()
-        _lib.run_live(lambda: gs.chunk_ready(gs.tail_chunk, also=lane.streams))
+        chunk_ready(gs, lane, gs.tail_chunk)
     # ---- class-attention blocks (reverse)
     for j in range(len(ca) - 1, -1, -1):
         L, blk = ca[j], feats.blocks_token_only[j]
         dyb = lane.track(torch.empty((B, D), dtype=torch.bfloat16, device=dev))
         lnb(None, None, None, None, None, None, None, dres_in=dcls, cast_out=dyb, colscale=blk.gamma_2,
                           dbias_next=gv(blk.mlp.fc2.bias), branch=L["raw2"], dcolscale=gv(blk.gamma_2))
-        dn2 = _mlp_bwd(store, blk, L, dyb)
+        dn2 = ops.gemm(mlp_bwd(store, blk, L, dyb, True), store.w16(blk.mlp.fc1.weight), trans_b=True, epi=EPI_BF16)
         lane.before_overwrite(dyb)
         lnb(dn2, L["cls1"], blk.norm2.weight, L["mean2"], L["rstd2"], gv(blk.norm2.weight), gv(blk.norm2.bias), dres_in=dcls,
                           dx_out=dcls, cast_out=dyb, colscale=blk.gamma_1, dbias_next=gv(blk.attn.proj.bias), branch=L["raw1"],
@@ -331,9 +274,9 @@ def cait_backward(ppnet, store, saved, df):
         dout = ops.gemm(dyb, store.w16(blk.attn.proj.weight), trans_b=True, epi=EPI_BF16)
         dq, dk, dv = ops.class_attn_bwd(L["q"], L["k"], L["v"], L["attn"], L["zinv"], dout, B, H, N1, D)
         # projections q (cls rows only), k, v
-        ncls = L["n"].reshape(B, N1 * D)[:, :D]
-        ops._lib.call("ppf_gemm_bf16", dq, L["n"], gv(blk.attn.q.weight), D, D, B, D, N1 * D, D, 1, 1, ops.EPI_ATOMIC, None, None, 0, None, 1,
-                      None, None, None, 0, gv(blk.attn.q.bias), 1.0, None, 0)
+        # (q saw the cls rows of n only: row stride N1*D; the contraction is the batch, on the main stream and without split-K scratch)
+        ops.gemm(dq, L["n"], trans_a=True, trans_b=True, epi=EPI_ATOMIC, out=gv(blk.attn.q.weight), colsum=gv(blk.attn.q.bias), ldb=N1 * D,
+                 workspace=False)
         _wgrad(store, dk, L["n"], blk.attn.k.weight, blk.attn.k.bias)
         _wgrad(store, dv, L["n"], blk.attn.v.weight, blk.attn.v.bias)
         dnk = ops.gemm(dk, store.w16(blk.attn.k.weight), trans_b=True, epi=EPI_F32)
@@ -350,90 +293,21 @@ def cait_backward(ppnet, store, saved, df):
     dx = ops.copy_2d(torch.empty((B, N * D), dtype=torch.float32, device=dev), du2[:, D:]).reshape(M, D)
     dyb = lane.track(torch.empty((M, D), dtype=torch.bfloat16, device=dev))
     last = feats.blocks[-1]
-    lnb(None, None, None, None, None, None, None, dres_in=dx, cast_out=dyb, rowscale=sa[-1]["s2"], rows_per_group=N,
-                      colscale=last.gamma_2, dbias_next=gv(last.mlp.fc2.bias), branch=sa[-1]["raw2"], dcolscale=gv(last.gamma_2))
+    lnb(None, None, None, None, None, None, None, dres_in=dx, dbias_next=gv(last.mlp.fc2.bias),
+        **branch_out(store, dyb, sa[-1]["s2"], N, last.gamma_2, sa[-1]["raw2"]))
     # Input gradient of fc1 / qkv + LayerNorm backward + LayerScale terms of the branch below as one full-row kernel (csrc/rowgemm.hip,
-    # RG_LNBWD_LS) where the shape is covered.  Half-sample tiles as in the forward pass (measured on this backbone, same box: 8 885 vs
+    # RG_LNBWD_LS) wherever the shape is covered.  Half-sample tiles as in the forward pass (measured on this backbone, same box: 8 885 vs
     # 8 300 img/s with whole samples -- the opposite of deit_tiny, whose side stream carries relatively more weight-gradient work).
-    rptb = ops.rowgemm_tile_rows(M, N)
-    hid = feats.blocks[0].mlp.fc1.out_features if len(feats.blocks) else 0
-    rowb = (len(sa) > 0 and store.w16t(feats.blocks[0].mlp.fc1.weight) is not None
-            and ops.rowgemm_ok(D, hid, rptb) and ops.rowgemm_ok(D, 3 * D, rptb) and ops.rowgemm_ok(D, D, rptb))
+    # Where the input gradients are launches of their own, they read W transposed through the generic kernel.
+    bwd = functools.partial(block_bwd, next_dyb=dyb_ring(lane, D), lnb=lnb, row_tile=row_tile_bwd(store, last, D, ops.rowgemm_tile_rows(M, N)),
+                            dgrad=lambda dy16, weight, rows, which: ops.gemm(dy16, store.w16(weight), trans_b=True, epi=EPI_BF16),
+                            attn_bwd=lambda blk, L, dao: _th_attention_bwd(store, blk, L, dao, B, H, N, D))
     bias_done = True                       # the producer of the current dyb has already accumulated the bias gradient of the Linear above it
-    # The bf16 branch gradient alternates between two buffers (as backbone.deit_backward): the kernel that produces the next one does not
-    # wait for the side stream's weight-gradient GEMM that still reads the current one (measured: a 44 us stall per block otherwise).
-    dyb_alt = None
-    nring = 4 if D > 256 else 64       # buffers in rotation, as backbone.deit_backward (narrow: no reuse)
-    ring = []
-
-    def next_dyb(cur, alt):
-        if nring >= 64:                                    # never reused: nothing to order against the side stream, no marks
-            return torch.empty_like(cur), cur
-        if not any(b.data_ptr() == cur.data_ptr() for b in ring):
-            ring.append(cur)
-        if len(ring) < nring:
-            nxt = lane.track(torch.empty_like(cur))
-            ring.append(nxt)
-        else:
-            i = next(j for j, b in enumerate(ring) if b.data_ptr() == cur.data_ptr())
-            nxt = ring[(i + 1) % len(ring)]
-        lane.before_overwrite(nxt)
-        return nxt, cur
-
     for i in range(len(sa) - 1, -1, -1):
-        L, blk = sa[i], feats.blocks[i]
-        if rowb:
-            dh = _mlp_bwd(store, blk, L, dyb, fc2_bias=not bias_done, want_dn=False)
-            dyb, dyb_alt = next_dyb(dyb, dyb_alt)
-            ops.rowgemm_lnbwd(dh, store.w16t(blk.mlp.fc1.weight), L["x1"], L["mean2"], L["rstd2"], blk.norm2.weight, gv(blk.norm2.weight), gv(blk.norm2.bias),
-                              rptb, dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=L["s1"], rows_per_group=N, lane=lane, defer_reduce=True,
-                              colscale=blk.gamma_1, branch=L["raw1"], dcolscale=gv(blk.gamma_1))
-            _wgrad(store, dyb, L["ao"], blk.attn.proj.weight, blk.attn.proj.bias, defer=True)
-            dao = ops.rowgemm_bf16(dyb, store.w16t(blk.attn.proj.weight), rptb)
-        else:
-            dn2 = _mlp_bwd(store, blk, L, dyb, fc2_bias=not bias_done)
-            dyb, dyb_alt = next_dyb(dyb, dyb_alt)
-            lnb(dn2, L["x1"], blk.norm2.weight, L["mean2"], L["rstd2"], gv(blk.norm2.weight), gv(blk.norm2.bias), dres_in=dx, dx_out=dx,
-                              cast_out=dyb, rowscale=L["s1"], rows_per_group=N, colscale=blk.gamma_1, dbias_next=gv(blk.attn.proj.bias),
-                              branch=L["raw1"], dcolscale=gv(blk.gamma_1))
-            _wgrad(store, dyb, L["ao"], blk.attn.proj.weight, defer=True)
-            dao = ops.gemm(dyb, store.w16(blk.attn.proj.weight), trans_b=True, epi=EPI_BF16)
-        dqkv = _th_attention_bwd(store, blk, L, dao, B, H, N, D)
-        _wgrad(store, dqkv, L["n1"], blk.attn.qkv.weight, blk.attn.qkv.bias)
-        dn1 = None if rowb else ops.gemm(dqkv, store.w16(blk.attn.qkv.weight), trans_b=True, epi=EPI_BF16)
-        if i > 0:
-            prev, Lp = feats.blocks[i - 1], sa[i - 1]
-            dyb, dyb_alt = next_dyb(dyb, dyb_alt)
-            if rowb:
-                ops.rowgemm_lnbwd(dqkv, store.w16t(blk.attn.qkv.weight), L["x"], L["mean1"], L["rstd1"], blk.norm1.weight, gv(blk.norm1.weight), gv(blk.norm1.bias),
-                                  rptb, dres_in=dx, dx_out=dx, cast_out=dyb, rowscale=Lp["s2"], rows_per_group=N, lane=lane, defer_reduce=True,
-                                  colscale=prev.gamma_2, branch=Lp["raw2"], dcolscale=gv(prev.gamma_2))
-            else:
-                lnb(dn1, L["x"], blk.norm1.weight, L["mean1"], L["rstd1"], gv(blk.norm1.weight), gv(blk.norm1.bias), dres_in=dx,
-                                  dx_out=dx, cast_out=dyb, rowscale=Lp["s2"], rows_per_group=N, colscale=prev.gamma_2,
-                                  dbias_next=gv(prev.mlp.fc2.bias), branch=Lp["raw2"], dcolscale=gv(prev.gamma_2))
-            bias_done = not rowb
-        else:
-            if rowb:
-                ops.rowgemm_lnbwd(dqkv, store.w16t(blk.attn.qkv.weight), L["x"], L["mean1"], L["rstd1"], blk.norm1.weight, gv(blk.norm1.weight), gv(blk.norm1.bias),
-                                  rptb, dres_in=dx, dx_out=dx, lane=lane, defer_reduce=True)
-            else:
-                lnb(dn1, L["x"], blk.norm1.weight, L["mean1"], L["rstd1"], gv(blk.norm1.weight), gv(blk.norm1.bias), dres_in=dx, dx_out=dx)
+        dyb, bias_done = bwd(feats.blocks[i], store, sa[i], dx, dyb, bias_done, (feats.blocks[i - 1], sa[i - 1]) if i > 0 else None)
         if gs is not None and i in gs.block_chunk:
-            lane.flush()
-            _lib.run_live(lambda c=gs.block_chunk[i]: gs.chunk_ready(c, also=lane.streams))
-    pe = feats.patch_embed
-    dtok = ops.assemble_tokens_bwd(dx, gv(feats.pos_embed).reshape(N, D), None, B, N, D, 0)
-    _wgrad(store, dtok, saved["cols"], pe.proj.weight, pe.proj.bias)
-    if gs is not None:
-        lane.flush()
-        _lib.run_live(lambda: gs.chunk_ready(gs.head_chunk, also=lane.streams))
-    lane.join()
+            chunk_ready(gs, lane, gs.block_chunk[i])
+    embed_bwd(ppnet, store, saved, dx, 0)
 
 
-def cait_t16_params(feats):
-    """Weights whose input-gradient products read W^T contraction-contiguous (csrc/rowgemm.hip): fc1, qkv, proj of the talking-heads blocks."""
-    return [w for blk in feats.blocks for w in (blk.mlp.fc1.weight, blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc2.weight)]
-
-
-CAIT_FNS = dict(embed=cait_embed, blocks=cait_blocks_fwd, backward=cait_backward, t16_params=cait_t16_params)
+CAIT_FNS = dict(embed=functools.partial(embed_tokens, lead=0), blocks=cait_blocks_fwd, backward=cait_backward, t16_params=t16_params)

@@ -85,9 +85,9 @@ class MyVisionTransformer(nn.Module):
     # ---- the reference's two entry points (deit:172-181, 209-240), inference-only compatibility wrappers
     @torch.no_grad()
     def forward_feature_patch_embed_all(self, x):
-        from .backbone import deit_embed
+        from .backbone import embed_tokens
         store = self._store()
-        xe = deit_embed(self, store, x)
+        xe = embed_tokens(self, store, x, lead=1)
         return xe[:, :1], xe[:, 1:]
 
     @torch.no_grad()

@@ -56,13 +56,16 @@ def _chk(t, dtype=None):
 
 
 def gemm(a, b, *, trans_a=False, trans_b=False, epi=EPI_BF16, out=None, bias=None, res=None, rowscale=None,
-         rows_per_group=1, colscale=None, aux_in=None, aux_out=None, colsum=None, alpha=1.0):
+         rows_per_group=1, colscale=None, aux_in=None, aux_out=None, colsum=None, alpha=1.0, lda=None, ldb=None, workspace=True):
     """C[M,N] (+)= epi(sum_kc A(m,kc) B(n,kc)); a/b are 2-D bf16. Storage: a is [M,K] ([K,M] if trans_a),
-    b is [N,K] ([K,N] if trans_b)."""
+    b is [N,K] ([K,N] if trans_b).  lda / ldb: a row stride larger than the row length -- the operand's rows are the first shape[1]
+    entries of every lda (ldb) elements of the tensor (the cls rows of a [B*N1, D] token matrix: lda = N1*D).
+    workspace=False: EPI_ATOMIC without the split-K scratch (fp32 atomics where the contraction is split at all)."""
     _chk(a, torch.bfloat16), _chk(b, torch.bfloat16)
-    M, K = (a.shape[1], a.shape[0]) if trans_a else a.shape
-    N = b.shape[1] if trans_b else b.shape[0]
-    Kb = b.shape[0] if trans_b else b.shape[1]
+    lda = a.shape[1] if lda is None else lda
+    ldb = b.shape[1] if ldb is None else ldb
+    M, K = (a.shape[1], a.numel() // lda) if trans_a else (a.numel() // lda, a.shape[1])
+    N, Kb = (b.shape[1], b.numel() // ldb) if trans_b else (b.numel() // ldb, b.shape[1])
     assert K == Kb, f"contraction mismatch {K} vs {Kb}"
     if out is None:
         odt = torch.float32 if epi in (EPI_F32, EPI_SIGMOID_F32, EPI_RESID, EPI_ATOMIC) else torch.bfloat16
@@ -76,9 +79,9 @@ def gemm(a, b, *, trans_a=False, trans_b=False, epi=EPI_BF16, out=None, bias=Non
             _chk(t, torch.uint8 if epi in (EPI_GELU, EPI_DGELU) else torch.bfloat16)
             ldaux = t.shape[-1]
     ws = None
-    if epi == EPI_ATOMIC:
+    if epi == EPI_ATOMIC and workspace:
         ws = _gemm_workspace(a.device, _lib.lib().ppf_gemm_workspace_bytes(M, N, K))
-    _lib.call("ppf_gemm_bf16", a, b, out, M, N, K, a.shape[1], b.shape[1], out.shape[-1], int(trans_a), int(trans_b), epi,
+    _lib.call("ppf_gemm_bf16", a, b, out, M, N, K, lda, ldb, out.shape[-1], int(trans_a), int(trans_b), epi,
               bias, res, res.shape[-1] if res is not None else 0, rowscale, rows_per_group, colscale, aux_in, aux_out, ldaux,
               colsum, float(alpha), ws, ws.numel() if ws is not None else 0)
     return out
