@@ -294,6 +294,23 @@ int ppf_soft_cross_entropy(const float* logits, const float* target, const void*
  * device buffer owned by the library: calls of one process must be ordered on ONE stream. */
 int ppf_eval_metrics(const float* logits, const float* logits_global, const float* logits_local, const void* label_i64, double* acc,
                      int B, int C, ppf_stream_t stream);
+/* Prototype bank: dataset-wide nearest patches per prototype (the ranking ProtoPNet-family tools show and project onto; the reference
+ * has no such pass).  One launch merges a batch's candidates into persistent per-prototype lists of K entries, sorted best-first, all in
+ * device memory and updated in place: val [P][K] fp32 activations, img [P][K] int32 image ids, pos [P][K] int32 index in the side x side
+ * patch grid (idx[b][argmax[b][p]]; -1 on the global branch), best_feat [P][Dp] fp32 = the latent token of the rank-0 entry, rewritten
+ * only when the launch changes rank 0.  ppf_proto_topk_init fills val with -inf and img / pos with -1 (an unfilled slot; sorts last).
+ *   act_max [B][P], argmax [B][P]: as ppf_proto_fwd writes them; argmax == NULL (global / cls branch): the token is tok row t0 itself.
+ *   idx [B][k] int32: the reserved-token indices (NULL exactly when argmax is NULL).  tok / stride_b / t0 / Dp: the addressing of
+ *   ppf_proto_fwd (sample b's token i at tok + b*stride_b + (t0+i)*Dp; tok and best_feat 16-byte aligned, stride_b % 4 == 0).
+ *   label_i64 [B], image_id [B] int32 (>= 0).  ppc > 0: class-specific, sample b is offered to prototype p only if label[b] == p / ppc;
+ *   ppc == 0: every sample is offered to every prototype (label_i64 may be NULL).
+ * Order (total): larger activation first, equal activations by smaller image id; NaN and -inf candidates are never admitted.  The final
+ * state is therefore independent of the batch size and of the order the batches arrive in.  Image ids must be unique across all the
+ * launches that feed one list: the caller's contract, not checked.  1 <= K <= 64, 1 <= B <= 1024, P >= 1, Dp % 4 == 0. */
+int ppf_proto_topk_init(float* val, int* img, int* pos, int P, int K, ppf_stream_t stream);
+int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx, int k, const float* tok, int64_t stride_b, int t0, int Dp,
+                         const void* label_i64, const int* image_id, int ppc, int B, int P, int K, float* val, int* img, int* pos,
+                         float* best_feat, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);

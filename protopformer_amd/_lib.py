@@ -53,6 +53,8 @@ SIGS = {
     "ppf_cross_entropy": "ppppp" "ii" "s",
     "ppf_soft_cross_entropy": "ppp" "f" "ppp" "ii" "s",
     "ppf_eval_metrics": "ppppp" "ii" "s",
+    "ppf_proto_topk_init": "ppp" "ii" "s",
+    "ppf_proto_topk_merge": "ppp" "i" "p" "l" "ii" "pp" "i" "iii" "pppp" "s",
     "ppf_mixup_apply": "ppp" "iiii" "s",
     "ppf_mixup_target": "pp" "i" "ff" "p" "ii" "s",
     "ppf_sgemm": "ppp" "iii" "llll" "i" "ff" "pl" "s",

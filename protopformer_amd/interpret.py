@@ -289,3 +289,28 @@ def consistency_from_outputs(attn, acts, targets, ids, parts, image_sizes, k, im
         e, m = consistency_from_tables(tables, masks, part_thresh)
         effects.extend(e); max_parts.extend(m)
     return (float(np.mean(effects)) if effects else 0.0), effects, max_parts, grid
+
+
+# ------------------------------------------------------------------------------------------------ dataset-wide nearest patches
+def patch_box(grid_pos, side, patch_size):
+    """Pixel rectangle (x0, y0, x1, y1), end-exclusive, of cell `grid_pos` (row-major) of the side x side patch grid."""
+    if not 0 <= int(grid_pos) < side * side:
+        raise ValueError(f"patch_box: grid position {grid_pos} outside the {side} x {side} grid")
+    row, col = int(grid_pos) // side, int(grid_pos) % side
+    return col * patch_size, row * patch_size, (col + 1) * patch_size, (row + 1) * patch_size
+
+
+def nearest_patches(ppnet, loader, topk=10, class_specific=True):
+    """Rank the whole of `loader` per prototype: returns the filled bank.PrototypeBank (its result() holds, per prototype, the topk
+    activations, image ids and grid cells; project_() pushes the prototypes onto their best patches).  loader yields (x, labels) or
+    (x, labels, ids) (Cub2011(return_id=True)); without ids an image's id is its running index in loader order, so the loader must
+    not shuffle.  Ids must be unique over the loader."""
+    from .bank import PrototypeBank
+    bank = PrototypeBank(ppnet, topk=topk, class_specific=class_specific)
+    seen = 0
+    for x, y, *rest in loader:
+        B = x.shape[0]
+        ids = rest[0] if rest else torch.arange(seen, seen + B, dtype=torch.int32)
+        bank.update(x.cuda() if not x.is_cuda else x, y, ids)
+        seen += B
+    return bank

@@ -429,6 +429,46 @@ def eval_metrics(acc, logits, label, logits_global=None, logits_local=None):
     _lib.call("ppf_eval_metrics", rows[0], rows[1], rows[2], label.contiguous(), acc, B, C)
 
 
+def proto_topk_init(val, img, pos):
+    """Empty per-prototype lists: val [P, K] fp32 = -inf, img / pos [P, K] int32 = -1."""
+    _chk(val, torch.float32), _chk(img, torch.int32), _chk(pos, torch.int32)
+    P, K = val.shape
+    if img.shape != val.shape or pos.shape != val.shape:
+        raise ValueError("proto_topk_init: val, img and pos must share the shape [P, K]")
+    _lib.call("ppf_proto_topk_init", val, img, pos, P, K)
+
+
+def proto_topk_merge(act_max, argmax, idx, tokens, t0, label, image_id, ppc, val, img, pos, best_feat):
+    """Merge one batch into the running per-prototype top-K lists (ppf_proto_topk_merge, include/ppf_hip.h); launches only.
+    act_max [B, P] fp32 and argmax [B, P] int32 as proto_fwd returns them (argmax None: global branch, then idx None too);
+    idx [B, k] int32; tokens fp32 [B, Ttot, Dp], the candidate's token is tokens[b, t0 + argmax[b, p]]; label int64 [B] (None with
+    ppc == 0), image_id int32 [B]; val / img / pos [P, K] and best_feat [P, Dp] are updated in place."""
+    _chk(act_max, torch.float32), _chk(tokens, torch.float32), _chk(image_id, torch.int32)
+    _chk(val, torch.float32), _chk(img, torch.int32), _chk(pos, torch.int32), _chk(best_feat, torch.float32)
+    B, P = act_max.shape
+    K = val.shape[1]
+    _, Ttot, Dp = tokens.shape
+    if (argmax is None) != (idx is None):
+        raise ValueError("proto_topk_merge: argmax and idx come together (both None on the global branch)")
+    k = 0
+    if argmax is not None:
+        _chk(argmax, torch.int32), _chk(idx, torch.int32)
+        k = idx.shape[1]
+        if argmax.shape != act_max.shape or idx.shape[0] != B or t0 + k > Ttot:
+            raise ValueError(f"proto_topk_merge: argmax {tuple(argmax.shape)} / idx {tuple(idx.shape)} do not fit act_max {tuple(act_max.shape)} "
+                             f"and {Ttot} tokens from t0={t0}")
+    if tokens.shape[0] != B or image_id.shape != (B,) or t0 >= Ttot:
+        raise ValueError(f"proto_topk_merge: tokens {tuple(tokens.shape)} / image_id {tuple(image_id.shape)} do not fit a batch of {B}")
+    if val.shape != (P, K) or img.shape != (P, K) or pos.shape != (P, K) or best_feat.shape != (P, Dp):
+        raise ValueError(f"proto_topk_merge: the state must be val / img / pos [{P}, K] and best_feat [{P}, {Dp}]")
+    if ppc > 0:
+        if label is None or label.dtype != torch.int64 or label.shape != (B,):
+            raise ValueError("proto_topk_merge: class-specific mode needs int64 labels [B]")
+        _chk(label)
+    _lib.call("ppf_proto_topk_merge", act_max, argmax, idx, k, tokens, Ttot * Dp, t0, Dp, label if ppc > 0 else None, image_id, int(ppc), B, P, K,
+              val, img, pos, best_feat)
+
+
 MIX_WORDS, MIX_WSELF = 8, 5          # PPF_MIX_WORDS / PPF_MIX_WSELF of include/ppf_hip.h
 
 

@@ -141,6 +141,7 @@ class ProtoLayerFn(torch.autograd.Function):
         act_g, _, dist_g, _ = ops.proto_fwd(f, 0, 1, pg, act_kind, ppnet.epsilon, want_dist=need_bwd, want_act=False)
         ctx.set_materialize_grads(False)
         ppnet._last_argmax = argmax              # (B, P) int32: the token each local prototype's max-pool selected (tests, visualisation)
+        ppnet._last_act_max = (act_l, act_g)     # (B, P) / (B, P_global) pooled activations of this call (bank.PrototypeBank.update)
         if need_bwd:
             ctx.save_for_backward(f, protos_local, protos_global, dist if keep_dist else act_full)
             ctx.aux = (argmax, not keep_dist, dist_g, act_kind, ppnet)
