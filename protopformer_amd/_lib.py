@@ -3,102 +3,54 @@
 There is NO CPU or eager fallback: if the shared library is missing or a call fails, this raises."""
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PPF_LIB_PATH") or os.path.join(_HERE, "lib", "libppf_hip.so")      # PPF_LIB_PATH: an alternative build (same-box A/B of two builds)
 
-# signature spec per entry point: p = device/host pointer, i = int32, l = int64, L = uint64, f = float, z = size_t, s = hipStream_t
-SIGS = {
-    "ppf_gemm_bf16": "pppiiiiiiiiippipipppipf" "pz" "s",
-    "ppf_device_info": "pppi",
-    "ppf_rowgemm_bf16": "pp" "iiiiii" "pp" "s",
-    "ppf_rowgemm_resid_ln": "pp" "iiiiii" "p" "pp" "pi" "pp" "pp" "ppp" "f" "s",
-    "ppf_rowgemm_lnbwd": "pp" "iiiiii" "pppp" "ppp" "pi" "pp" "pz" "s",
-    "ppf_rowgemm_colsum": "p" "iii" "ppp" "s",
-    "ppf_layernorm_bwd_f32": "pppppppp" "ii" "f" "s",
-    "ppf_ew_bwd_f32": "i" "ppp" "p" "i" "ii" "s",
-    "ppf_colsum_f32": "pp" "ii" "s",
-    "ppf_attn_bwd_f32": "ppppp" "iiiiii" "s",
-    "ppf_th_attn_bwd_f32": "ppppppp" "pppp" "iiii" "s",
-    "ppf_class_attn_bwd_f32": "pppppppp" "iiii" "s",
-    "ppf_transpose_bf16_batched": "ppp" "ii" "s",
-    "ppf_gemm_probe": "i",
-    "ppf_gemm_test_force_g224": "i",
-    "ppf_gemm_probe_read": "pppp",
-    "ppf_path_probe": "i",
-    "ppf_path_probe_read": "ipppp",
-    "ppf_layernorm_fwd": "ppppppp" "iif" "s",
-    "ppf_layernorm_bwd": "pppppp" "pppp" "pp" "i" "pppp" "ii" "pz" "s",
-    "ppf_layernorm_bwd_reduce": "p" "ii" "pppp" "s",
-    "ppf_cast_f32_bf16": "ppls",
-    "ppf_cast_bf16_f32": "ppls",
-    "ppf_im2col_patch": "ppiiiiis",
-    "ppf_assemble_tokens": "ppppiiiis",
-    "ppf_assemble_tokens_bwd": "ppppiiiis",
-    "ppf_adamw_step": "pppppp" "li" "ppp" "fff" "i" "ff" "s",
-    "ppf_attn_fwd": "ppppp" "iiiii" "i" "s",
-    "ppf_attn_fwd_hm": "pppppp" "i" "iiiii" "i" "s",
-    "ppf_attn_headmean": "ppppp" "i" "iiiii" "i" "s",
-    "ppf_attn_bwd": "pppppppp" "iiiii" "i" "s",
-    "ppf_rollout": "pl" "iiii" "p" "iiii" "f" "i" "pppp" "s",
-    "ppf_rollout_threshold": "p" "iiii" "p" "s",
-    "ppf_proto_fwd": "pliip" "iiii" "f" "pppp" "pz" "s",
-    "ppf_proto_bwd": "pliip" "iiii" "f" "pi" "pppp" "l" "p" "pz" "s",
-    "ppf_proto_bwd_rows": "pliip" "iiii" "f" "pi" "pp" "i" "ppp" "l" "p" "pz" "s",
-    "ppf_proto_bwd_single": "plip" "iiii" "f" "ppp" "l" "p" "pz" "s",
-    "ppf_ppc_loss": "ppp" "iiiii" "ff" "pppp" "s",
-    "ppf_ppc_loss_bwd": "pppppp" "iiii" "s",
-    "ppf_cross_entropy": "ppppp" "ii" "s",
-    "ppf_soft_cross_entropy": "ppp" "f" "ppp" "ii" "s",
-    "ppf_eval_metrics": "ppppp" "ii" "s",
-    "ppf_proto_topk_init": "ppp" "ii" "s",
-    "ppf_proto_topk_merge": "ppp" "i" "p" "l" "ii" "pp" "i" "iii" "pppp" "s",
-    "ppf_mixup_apply": "ppp" "iiii" "s",
-    "ppf_mixup_target": "pp" "i" "ff" "p" "ii" "s",
-    "ppf_sgemm": "ppp" "iii" "llll" "i" "ff" "pl" "s",
-    "ppf_sgemm_pair": "ppp" "ii" "llll" "i" "f" "ppp" "ii" "llll" "i" "f" "p" "i" "ff" "i" "pl" "s",
-    "ppf_axpby": "ppp" "ff" "l" "s",
-    "ppf_axpbypcz": "pppp" "fff" "l" "s",
-    "ppf_topk_sorted": "piiips",
-    "ppf_gemm_bf16_batched": "ppp" "iiiiii" "iii" "f" "ii" "llllll" "i" "s",
-    "ppf_th_scores": "pppp" "iiiii" "s",
-    "ppf_th_dwl": "ppp" "iiiii" "s",
-    "ppf_th_softmax_mix": "ppppp" "iiiii" "s",
-    "ppf_th_softmax_bwd": "pppppppp" "iiiii" "s",
-    "ppf_th_fwd": "pppppppppp" "iiiiii" "s",
-    "ppf_th_bwd": "ppppppppp" "iiiii" "s",
-    "ppf_th_param_reduce": "p" "iii" "pppp" "s",
-    "ppf_th_grads": "ppppp" "iiiii" "s",
-    "ppf_class_attn_fwd": "pppppppp" "iiii" "s",
-    "ppf_class_attn_bwd": "ppppppppp" "iiii" "s",
-    "ppf_merge3_cast": "pppp" "iii" "s",
-    "ppf_sigmoid_bwd": "ppppii" "pz" "s",
-    "ppf_im2col_patch_f32": "pp" "iiiii" "s",
-    "ppf_layernorm_fwd_f32": "ppppp" "iif" "s",
-    "ppf_epilogue_f32": "pp" "i" "pp" "i" "p" "ii" "s",
-    "ppf_attn_fwd_f32": "pppp" "i" "iiii" "ii" "s",
-    "ppf_th_attn_fwd_f32": "ppppp" "pp" "i" "iiii" "s",
-    "ppf_class_attn_fwd_f32": "pppppp" "iiii" "s",
-    "ppf_adamw_step_dev": "pppppp" "li" "pp" "ffff" "s",
-    "ppf_adamw_step_guarded": "pppppp" "li" "pp" "ffff" "pp" "s",
-    "ppf_hyper_set": "ppi" "s",
-    "ppf_clip_grad_scale": "pl" "ff" "ppp" "s",
-    "ppf_droppath_scales": "pp" "ii" "Lp" "s",
-    "ppf_reserved_rows_map": "pp" "iii" "s",
-    "ppf_gather_rows": "ppp" "ii" "s",
-    "ppf_scatter_rows": "ppp" "iii" "s",
-    "ppf_memset_zero": "pz" "s",
-    "ppf_copy_2d": "pl" "pl" "ll" "s",
-    "ppf_image_finish_u8": "pp" "iii" "ppp" "Lp" "s",
-    "ppf_scale_by_scalar": "ppp" "l" "s",
-    "ppf_stream_wait_stream": "pp",
-    "ppf_stream_arm": "pi",
-    "ppf_stream_wait_mark": "pl",
-}
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "ppf_hip.h")
 
-EXPECTED_ABI = 10              # == PPF_ABI_VERSION of include/ppf_hip.h this table was written against (tests/test_abi_cpu.py)
+# include/ppf_hip.h is the one place an entry point is declared: the kernels are compiled against it and this binding is parsed from it.
+# signature spec per entry point: p = device/host pointer, i = int32, l = int64, L = uint64, f = float, z = size_t, s = hipStream_t
+_LETTER = {"int": "i", "int64_t": "l", "uint64_t": "L", "float": "f", "size_t": "z"}
+_RET = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+
+
+def _ctype(text):
+    return re.sub(r"\s*\*", "*", " ".join(text.split()))              # one spelling: 'const char*'
+
+
+def parse_header(text):
+    """({entry point: spec}, {entry point: ctypes return type}, {PPF_X: value of an integer #define}) of the text of a ppf_hip.h.
+    A ppf_stream_t in the LAST position is the stream call() appends ('s'), except in the ppf_stream_* functions, whose streams are
+    explicit arguments ('p').  A type without an entry in _LETTER / _RET raises, naming the function: it never defaults."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {k: int(v) for k, v in re.findall(r"^#define\s+(PPF_\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M)}
+    sigs, rets = {}, {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(ppf_\w+)\s*\(([^()]*)\)\s*;", re.sub(r"^\s*#.*$", "", text, flags=re.M)):
+        if _ctype(ret) not in _RET:
+            raise ValueError(f"{name}: return type '{_ctype(ret)}' has no ctypes mapping")
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        spec = ""
+        for i, prm in enumerate(params):
+            t = _ctype(re.sub(r"\bconst\b|\w+\s*$", "", prm))          # the type without qualifier and parameter name
+            if t == "ppf_stream_t":
+                spec += "s" if i == len(params) - 1 and not name.startswith("ppf_stream_") else "p"
+            elif t.endswith("*"):
+                spec += "p"
+            elif t in _LETTER:
+                spec += _LETTER[t]
+            else:
+                raise ValueError(f"{name}: parameter '{prm.strip()}' has no ctypes mapping")
+        sigs[name], rets[name] = spec, _RET[_ctype(ret)]
+    return sigs, rets, defines
+
+
+with open(HEADER) as _f:
+    SIGS, _RESTYPE, DEFINES = parse_header(_f.read())
+EXPECTED_ABI = DEFINES["PPF_ABI_VERSION"]              # lib() refuses a library built from a header of another version
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "L": ctypes.c_uint64, "f": ctypes.c_float, "s": ctypes.c_void_p, "z": ctypes.c_size_t}
 _lib = None
@@ -113,55 +65,18 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} not found: build it with `python -m protopformer_amd.build` "
                                "(there is no fallback path)")
         _lib = ctypes.CDLL(LIB_PATH)
-        _lib.ppf_last_error.restype = ctypes.c_char_p
-        _lib.ppf_abi_version.restype = ctypes.c_int
         got = _lib.ppf_abi_version()
         if got != EXPECTED_ABI:
             _lib = None
             raise RuntimeError(f"{LIB_PATH} was built for ABI version {got}, this binding expects {EXPECTED_ABI}: rebuild it with "
                                "`python -m protopformer_amd.build --force` (a stale library would receive shifted arguments)")
-        _lib.ppf_gemm_workspace_bytes.restype = ctypes.c_size_t
-        _lib.ppf_gemm_workspace_bytes.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_sgemm_pair_workspace.restype = ctypes.c_int64
-        _lib.ppf_sgemm_pair_workspace.argtypes = [ctypes.c_int] * 5
-        _lib.ppf_proto_bwd_single_workspace.restype = ctypes.c_size_t
-        _lib.ppf_proto_bwd_single_workspace.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_proto_bwd_workspace.restype = ctypes.c_size_t
-        _lib.ppf_proto_fwd_workspace.restype = ctypes.c_size_t
-        _lib.ppf_proto_fwd_workspace.argtypes = [ctypes.c_int] * 2
-        _lib.ppf_proto_bwd_workspace.argtypes = [ctypes.c_int] * 6
-        _lib.ppf_layernorm_bwd_blocks.restype = ctypes.c_int
-        _lib.ppf_layernorm_bwd_blocks.argtypes = [ctypes.c_int]
-        _lib.ppf_sigmoid_bwd_blocks.restype = ctypes.c_int
-        _lib.ppf_sigmoid_bwd_blocks.argtypes = [ctypes.c_int]
-        _lib.ppf_clip_grad_blocks.restype = ctypes.c_int
-        _lib.ppf_clip_grad_blocks.argtypes = []
-        _lib.ppf_rowgemm_supported.restype = ctypes.c_int
-        _lib.ppf_rowgemm_supported.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_attn_fwd_hm_supported.restype = ctypes.c_int
-        _lib.ppf_attn_fwd_hm_supported.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_th_fused_supported.restype = ctypes.c_int
-        _lib.ppf_th_fused_supported.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_th_grads_supported.restype = ctypes.c_int
-        _lib.ppf_th_grads_supported.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_th_bwd_partial_floats.restype = ctypes.c_size_t
-        _lib.ppf_th_bwd_partial_floats.argtypes = [ctypes.c_int] * 3
-        _lib.ppf_stream_mark.restype = ctypes.c_int64
-        _lib.ppf_stream_mark.argtypes = [ctypes.c_void_p]
         for name, spec in SIGS.items():
             fn = getattr(_lib, name)
-            fn.restype = ctypes.c_int
+            fn.restype = _RESTYPE[name]
             fn.argtypes = [_CT[c] for c in spec]
-            _FAST[name] = (fn, tuple(i for i, c in enumerate(spec) if c == "p"), spec.endswith("s"), len(spec))
+            if fn.restype is ctypes.c_int:             # call() reads the return value as a status
+                _FAST[name] = (fn, tuple(i for i, c in enumerate(spec) if c == "p"), spec.endswith("s"), len(spec))
     return _lib
-
-
-def _ptr(x):
-    if x is None:
-        return None
-    if isinstance(x, torch.Tensor) or hasattr(x, "data_ptr"):
-        return x.data_ptr()
-    return x
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)     # C entry: ~0.2 us (torch.cuda.current_stream() costs ~8 us)

@@ -14,6 +14,7 @@
 //                 the saved statistics (no B*H*N*N tensor ever exists)
 //   attn_bwd_stream / attn_bwd_onepass   dQ, dK, dV in one launch, every (query tile, key tile) pair visited once
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include <type_traits>
 #include <cstdlib>
 

@@ -11,6 +11,7 @@
 //   th_softmax_bwd  dP, dWw, dbw, dS', dbl, dS_h = sum_g Wl[g,h] dS'_g
 //   class_attn_fwd / _bwd   one query (the cls token) per (sample, head) with the policy softmax without identity term
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include <type_traits>
 
 namespace {

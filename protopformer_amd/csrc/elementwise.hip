@@ -1,6 +1,7 @@
 // HBM-bound streaming kernels: fp32->bf16 parameter cast, patch im2col, token assembly (cls/pos) and its
 // backward, fused AdamW(+EMA+bf16 recast).  All vectorised 16 B per lane, grid-stride.
 #include "ppf_common.h"
+#include "ppf_hip.h"
 
 namespace {
 

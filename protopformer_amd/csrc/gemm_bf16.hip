@@ -20,6 +20,7 @@
 // output row m: 8/16-byte row-major stores and vector bias/residual accesses.
 // blockIdx is remapped XCD-aware (n-tiles of one m-panel share an XCD's L2).
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include "gemm_common.h"
 #include <cstdlib>
 #include <utility>

@@ -6,6 +6,7 @@
 //   * the frozen +1/-0.5 class-connection linears (protopformer.py:126-131,314-316): a plain strided fp32 GEMM
 // All reductions run in a fixed order (per-sample partials + a single-workgroup tree), i.e. deterministic.
 #include "ppf_common.h"
+#include "ppf_hip.h"
 
 namespace {
 

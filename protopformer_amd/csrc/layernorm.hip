@@ -2,6 +2,7 @@
 // One wavefront per row: lane l owns the column pairs c = 2*l + 128*j (coalesced 512-B segments),
 // row statistics by wave shuffles, two-pass variance in registers.  HBM-bound streaming kernels.
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include <cstdlib>
 #include <type_traits>
 

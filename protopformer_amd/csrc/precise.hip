@@ -3,6 +3,7 @@
 // north-star tolerance (1e-3 rel) against the reference-generated fixtures, separating "bf16 operand rounding" from "kernel bug".
 // Written for clarity, not speed: it is never on the measured path.
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include <math.h>
 
 namespace {

@@ -14,6 +14,7 @@
 //   proto_bwd_tokens : one workgroup per sample, waves own tokens, scan the prototype axis
 //   proto_bwd_protos : one workgroup per prototype, waves own samples, scan the token axis
 #include "ppf_common.h"
+#include "ppf_hip.h"
 #include <type_traits>
 #include <cstdlib>
 

@@ -10,6 +10,7 @@
 // Finally the k largest entries of the resulting cls attention are emitted as ascending indices (top-k +
 // sort of the reference), together with the 0/1 key policy for the next block.
 #include "ppf_common.h"
+#include "ppf_hip.h"
 
 namespace {
 

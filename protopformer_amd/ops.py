@@ -469,7 +469,7 @@ def proto_topk_merge(act_max, argmax, idx, tokens, t0, label, image_id, ppc, val
               val, img, pos, best_feat)
 
 
-MIX_WORDS, MIX_WSELF = 8, 5          # PPF_MIX_WORDS / PPF_MIX_WSELF of include/ppf_hip.h
+MIX_WORDS, MIX_WSELF = _lib.DEFINES["PPF_MIX_WORDS"], _lib.DEFINES["PPF_MIX_WSELF"]          # read from include/ppf_hip.h
 
 
 def mixup_apply(x, table_host, table_dev):

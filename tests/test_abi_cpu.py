@@ -31,15 +31,51 @@ def test_header_symbols_exported(lib):
 
 
 def test_binding_table_matches_header(lib):
+    """_lib.SIGS is parsed from the header: an independent count of the parameters of EVERY declaration must agree with it."""
     from protopformer_amd import _lib
-    declared = set(_declared())
-    assert set(_lib.SIGS) <= declared
+    assert set(_lib.SIGS) == set(_declared())
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     for name, spec in _lib.SIGS.items():
         m = re.search(r"\b" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
         assert m, name
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        nargs = len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"])
         assert nargs == len(spec), f"{name}: header has {nargs} parameters, binding spec {len(spec)}"
+
+
+def test_derived_signatures_known_answers(lib):
+    """Full signatures as the hand-written table had them; together they use every letter and every return type."""
+    from protopformer_amd import _lib
+    want = {"ppf_gemm_bf16": "pppiiiiiiiiippipipppipfpzs", "ppf_droppath_scales": "ppiiLps", "ppf_sgemm": "pppiiilllliffpls",
+            "ppf_stream_wait_stream": "pp", "ppf_stream_wait_mark": "pl", "ppf_device_info": "pppi", "ppf_stream_mark": "p",
+            "ppf_gemm_workspace_bytes": "iii", "ppf_last_error": "", "ppf_clip_grad_blocks": ""}
+    assert {n: _lib.SIGS[n] for n in want} == want
+    assert set("".join(want.values())) == set(_lib._CT)
+    ret = {"ppf_stream_mark": ctypes.c_int64, "ppf_gemm_workspace_bytes": ctypes.c_size_t, "ppf_last_error": ctypes.c_char_p,
+           "ppf_clip_grad_blocks": ctypes.c_int, "ppf_gemm_bf16": ctypes.c_int}
+    bound = _lib.lib()
+    for n, r in ret.items():
+        fn = getattr(bound, n)
+        assert fn.restype is r and list(fn.argtypes) == [_lib._CT[c] for c in want[n]], n
+    for n in want:                              # call() serves the status-returning entry points only
+        assert (n in _lib._FAST) == (getattr(bound, n).restype is ctypes.c_int), n
+    fn, ptr_pos, has_stream, arity = _lib._FAST["ppf_droppath_scales"]
+    assert ptr_pos == (0, 1, 5) and has_stream and arity == 7
+    assert _lib._FAST["ppf_stream_wait_stream"][1:] == ((0, 1), False, 2)
+
+
+@pytest.mark.parametrize("decl,word", [("int ppf_bad_one(const float* x, double scale, ppf_stream_t stream);", "ppf_bad_one"),
+                                       ("unsigned ppf_bad_two(int n);", "ppf_bad_two"),
+                                       ("int ppf_bad_three(const float* x, long n, ppf_stream_t stream);", "ppf_bad_three")])
+def test_unmapped_type_raises_with_the_name(decl, word):
+    from protopformer_amd import _lib
+    with pytest.raises(ValueError, match=word):
+        _lib.parse_header("int ppf_fine(int n);\n" + decl)
+
+
+def test_header_defines_reach_python():
+    from protopformer_amd import _lib, ops
+    assert (_lib.DEFINES["PPF_ERR_SHAPE"], _lib.DEFINES["PPF_MIX_WOTHER"]) == (-1, 6)
+    assert (ops.MIX_WORDS, ops.MIX_WSELF) == (8, 5)
 
 
 def test_error_channel_without_gpu(lib):
