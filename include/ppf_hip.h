@@ -326,6 +326,36 @@ int ppf_axpby(const float* x, const float* y, float* out, float a, float b, int6
 /* out = a x + b y + c z: loss = CE + ppc_cov_coe * cov + ppc_mean_coe * mean in one launch (tools/engine_proto.py:61-64) */
 int ppf_axpbypcz(const float* x, const float* y, const float* z, float* out, float a, float b, float c, int64_t n, ppf_stream_t stream);
 
+/* ---- interpretability post-processing (csrc/interp.hip; protopformer_amd/interpret.py resize_cubic, prototype_part_table,
+ * find_high_activation_crop; reference eval_interpretability.py:206-226, main_visualize.py:44-66,381-398) ------------------------------
+ * grids [M][g][g] fp32 (contiguous): the activation maps of M (image, prototype) pairs on the patch grid.  Every entry point below
+ * up-samples them to S x S exactly as interpret.resize_cubic does (cv2.INTER_CUBIC: Keys kernel a = -0.75, half-pixel centres,
+ * replicated border; fp64 without contraction, axis 0 then axis 1, taps added in index order, one cast to fp32): the values are
+ * bit-identical to the host function's, so ties resolve as they do there.  1 <= g <= 64, 1 <= S <= 1024, and the LDS image
+ * (g*g + 4*S + 32*g)*8 + 4*S bytes must fit 48 KiB; M >= 1.  Additions of ABI 10: no existing entry point changed.
+ *   ppf_act_upsample     out [M][S][S] fp32 = the maps themselves (16-byte stores when S % 4 == 0 and out is 16-byte aligned).
+ *   ppf_act_peak         the same arithmetic without writing the map: peak_val [M] = the map's maximum, peak_yx [M][2] int32 = (y, x) of
+ *                        its FIRST occurrence in row-major order (np.where(up == up.max())[..][0]).  The part table is FUSED into this
+ *                        launch: with parts != NULL it also writes table_u8 as ppf_act_part_table would (parts == NULL: table_u8 NULL
+ *                        and maps_per_img / n_parts / half_size ignored).
+ *   ppf_act_part_table   table_u8 [M][n_parts] uint8 (0/1) from given peaks = interpret.prototype_part_table: map m belongs to image
+ *                        m / maps_per_img, parts [M / maps_per_img][n_parts][3] int32 = (valid, x, y) per part id, entry 1 iff valid and
+ *                        y0 <= y <= y1 and x0 <= x <= x1 (inclusive on both ends, as in_bbox) for the box y0 = max(0, peak_y - half_size),
+ *                        y1 = min(S, peak_y + half_size), likewise in x.
+ *   ppf_act_order_stats  stats [M][2] fp32 = the values of ascending 0-based ranks k_lo and k_hi (k_lo <= k_hi <= k_lo + 1, k_hi < S*S)
+ *                        among the S*S fp32 values of each map: an exact radix selection on the bit patterns, not a sort (-0 orders
+ *                        below +0).  The caller interpolates the percentile threshold between the two on the host (numpy's own lerp).
+ *   ppf_act_box          box [M][4] int32 = (y0, y1, x0, x1), end-exclusive, of the entries with (double)up >= thr[m] (thr: fp64 [M]);
+ *                        (0, 1, 0, 1) when nothing passes (interpret.find_high_activation_crop).
+ * NaN never wins a comparison (a map of NaNs: peak (0, 0), value -inf).  Deterministic: integer atomics only. */
+int ppf_act_upsample(const float* grids, float* out, int M, int g, int S, ppf_stream_t stream);
+int ppf_act_peak(const float* grids, int M, int g, int S, float* peak_val, int* peak_yx, const int* parts, int maps_per_img, int n_parts,
+                 int half_size, void* table_u8, ppf_stream_t stream);
+int ppf_act_part_table(const int* peak_yx, int M, int S, const int* parts, int maps_per_img, int n_parts, int half_size, void* table_u8,
+                       ppf_stream_t stream);
+int ppf_act_order_stats(const float* grids, int M, int g, int S, int k_lo, int k_hi, float* stats, ppf_stream_t stream);
+int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int* box, ppf_stream_t stream);
+
 /* ---- streaming kernels -------------------------------------------------------------------------------------------- */
 int ppf_cast_f32_bf16(const float* in, void* out, int64_t n, ppf_stream_t stream);
 /* bf16 -> fp32 (exact; n % 8 == 0): the optional bf16 wire format of the gradient all-reduce (engine.GradSync payload='bf16';

@@ -248,28 +248,48 @@ def consistency_from_tables(tables, masks, part_thresh=0.8):
 
 
 @torch.no_grad()
-def consistency_score(ppnet, loader, parts, image_sizes, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15):
+def consistency_score(ppnet, loader, parts, image_sizes, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15, device=False):
     """eval_interpretability.py:136-290: push_forward over the test set, the class's own prototypes expanded to the patch grid, the
     part table per image, and the fraction of prototypes that are part-consistent.  loader yields (x, targets, img_ids);
-    image_sizes: {img_id: (width, height)} of the original files (the reference reads them with cv2.imread)."""
+    image_sizes: {img_id: (width, height)} of the original files (the reference reads them with cv2.imread).
+    device=True: the part tables are made on the GPU, one peak + table launch per batch (see consistency_from_outputs); only the
+    (B, ppc, n_parts) uint8 tables come back.  Same score; the default (host) path is the referee."""
     ppnet.eval()
     ppc, k, img_size = ppnet.num_prototypes_per_class, ppnet.reserve_token_nums[0], ppnet.img_size
-    attn, acts, targets, ids = [], [], [], []
+    attn, acts, targets, ids, tables, masks = [], [], [], [], [], []
     for x, t, i in loader:
         ta, pa = ppnet.push_forward(x.cuda() if not x.is_cuda else x)
         t = torch.as_tensor(t)
         cols = (t.to(pa.device) * ppc)[:, None] + torch.arange(ppc, device=pa.device)[None, :]
-        acts.append(torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1])).cpu())
-        attn.append(ta.cpu()); targets.append(t.cpu()); ids.append(torch.as_tensor(i).cpu())
+        own = torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1]))
+        targets.append(t.cpu()); ids.append(torch.as_tensor(i).cpu())
+        if device:
+            tb, mk = _device_tables(_grid_on_device(ta, own, k), ids[-1].numpy(), parts, image_sizes, img_size, half_size, n_parts)
+            tables.append(tb); masks.append(mk)
+        else:
+            acts.append(own.cpu()); attn.append(ta.cpu())
+    if device:
+        tables = torch.cat(tables).cpu().numpy() if tables else np.zeros((0, ppc, n_parts), dtype=np.uint8)
+        return _score_from_tables(tables, np.concatenate(masks) if masks else np.zeros((0, n_parts)), torch.cat(targets).numpy(), num_classes,
+                                  part_thresh)[0]
     return consistency_from_outputs(torch.cat(attn), torch.cat(acts), torch.cat(targets).numpy(), torch.cat(ids).numpy(), parts, image_sizes, k,
                                     img_size, num_classes, part_thresh, half_size, n_parts)[0]
 
 
-def consistency_from_outputs(attn, acts, targets, ids, parts, image_sizes, k, img_size, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15):
+def consistency_from_outputs(attn, acts, targets, ids, parts, image_sizes, k, img_size, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15,
+                             device=False):
     """eval_interpretability.py:152-290 on collected push_forward outputs: attn (B, Np) rollout scores, acts (B, ppc, s, s) the class's
     own prototype activations on the k = s*s reserved tokens, targets / ids (B,).  Returns (score, effect per (class, prototype),
     best part fraction per (class, prototype), activations on the patch grid).  Classes without a test image are skipped (the
-    reference's loop assumes every class has one)."""
+    reference's loop assumes every class has one).
+    device=True: attn / acts go to (or stay on) the GPU, expand_to_grid runs there, one ppf_act_peak launch makes every part table, and
+    only the (B, ppc, n_parts) uint8 tables are read back; the grid is returned as a CUDA tensor.  Same score, effects and fractions."""
+    if device:
+        attn, acts = torch.as_tensor(attn).cuda(), torch.as_tensor(acts).cuda()
+        targets, ids = np.asarray(targets), np.asarray(ids)
+        grid = _grid_on_device(attn, acts, k)
+        tables, masks = _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts)
+        return _score_from_tables(tables.cpu().numpy(), masks, targets, num_classes, part_thresh) + (grid,)
     attn, acts = torch.as_tensor(attn), torch.as_tensor(acts)
     targets, ids = np.asarray(targets), np.asarray(ids)
     grid = expand_to_grid(acts.float(), attn.float(), k).numpy() if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts.numpy()
@@ -289,6 +309,96 @@ def consistency_from_outputs(attn, acts, targets, ids, parts, image_sizes, k, im
         e, m = consistency_from_tables(tables, masks, part_thresh)
         effects.extend(e); max_parts.extend(m)
     return (float(np.mean(effects)) if effects else 0.0), effects, max_parts, grid
+
+
+# ------------------------------------------------------------------------------------------------ the same post-processing on the device
+def _maps3(grids):
+    """(..., g, g) CUDA maps as the (M, g, g) view the kernels take, and the leading shape; layout and dtype are the kernels' to refuse."""
+    if not isinstance(grids, torch.Tensor) or grids.dim() < 2:
+        return grids, ()
+    lead = tuple(grids.shape[:-2])
+    if grids.dim() == 3 or not grids.is_contiguous():
+        return grids, lead
+    return grids.reshape((int(np.prod(lead, dtype=np.int64)),) + tuple(grids.shape[-2:])), lead
+
+
+def upsample_cubic_device(grids, size):
+    """resize_cubic of every map of a contiguous fp32 CUDA tensor (..., g, g) -> (..., size, size), bit-identical to the host function
+    (ppf_act_upsample)."""
+    from . import ops
+    maps, lead = _maps3(grids)
+    return ops.act_upsample(maps, size).reshape(lead + (size, size))
+
+
+def activation_peaks(grids, size):
+    """Maximum and first arg-max in row-major order of every up-sampled map, without materialising it (ppf_act_peak): (values (...)
+    fp32, yx (..., 2) int32 as (y, x)) = up.max() and np.where(up == up.max())[..][0] of up = resize_cubic(map, size)."""
+    from . import ops
+    maps, lead = _maps3(grids)
+    val, yx, _ = ops.act_peak(maps, size)
+    return val.reshape(lead), yx.reshape(lead + (2,))
+
+
+def percentile_ranks(n, percentile):
+    """The two 0-based ascending ranks np.percentile(a, percentile) (linear) of n values interpolates between, and the fraction of the
+    way from the first to the second: numpy's virtual index (n - 1) * q, in the form its implementation evaluates it."""
+    if not 0 <= percentile <= 100:
+        raise ValueError(f"percentile {percentile} outside [0, 100]")
+    q = percentile / 100.0
+    v = n * q + (1.0 + q * (1.0 - 1.0 - 1.0)) - 1.0
+    lo = min(max(int(np.floor(v)), 0), n - 1)
+    return lo, min(lo + 1, n - 1), min(max(v - lo, 0.0), 1.0)
+
+
+def high_activation_boxes(grids, size, percentile=95):
+    """find_high_activation_crop(resize_cubic(map, size), percentile) of every map: (..., 4) int32 (y0, y1, x0, x1) on the device.
+    ppf_act_order_stats selects the two order statistics around the percentile exactly; the threshold between them is numpy's own
+    interpolation (np.percentile of the pair at the matching fraction, on the host: one (M, 2) read-back); ppf_act_box takes it."""
+    from . import ops
+    maps, lead = _maps3(grids)
+    lo, hi, frac = percentile_ranks(int(size) * int(size), percentile) if int(size) >= 1 else (0, 0, 0.0)
+    stats = ops.act_order_stats(maps, size, lo, hi).cpu().numpy()
+    thr = np.percentile(stats, frac * 100.0, axis=1) if stats.shape[0] else np.zeros(0)
+    thr = torch.from_numpy(np.ascontiguousarray(thr, dtype=np.float64)).to(maps.device)
+    return ops.act_box(maps, size, thr).reshape(lead + (4,))
+
+
+def _grid_on_device(attn, acts, k):
+    """The (B, ppc, g, g) fp32 maps on the patch grid from device tensors (expand_to_grid is torch: it runs where its inputs are)."""
+    attn, acts = attn.float(), acts.float()
+    return (expand_to_grid(acts, attn, k) if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts).contiguous()
+
+
+def _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
+    """Part tables of a batch: grid (B, ppc, g, g) CUDA -> (tables (B, ppc, n_parts) uint8 CUDA, masks (B, n_parts) numpy).  The part
+    list goes up as (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image pixels as consistency_from_outputs scales them."""
+    from . import ops
+    B, ppc = grid.shape[:2]
+    plist, masks = np.zeros((B, n_parts, 3), dtype=np.int32), np.zeros((B, n_parts))
+    for j in range(B):
+        w, h = image_sizes[int(ids[j])]
+        for pid, x, y in parts.id_to_part_loc.get(int(ids[j]), []):
+            if plist[j, pid - 1, 0]:
+                raise ValueError(f"image {int(ids[j])} lists part {pid} twice: the device path takes one location per part")
+            masks[j, pid - 1] = 1
+            plist[j, pid - 1] = (1, int(img_size * (x / w)), int(img_size * (y / h)))
+    if B == 0:
+        return torch.zeros((0, ppc, n_parts), dtype=torch.uint8, device=grid.device), masks
+    _, _, table = ops.act_peak(grid.reshape(B * ppc, grid.shape[-2], grid.shape[-1]), img_size, torch.from_numpy(plist).to(grid.device), half_size)
+    return table.reshape(B, ppc, n_parts), masks
+
+
+def _score_from_tables(tables, masks, targets, num_classes, part_thresh):
+    """(score, effects, best fractions) from per-image tables (B, ppc, n_parts) and masks (B, n_parts), class by class in the host
+    path's order."""
+    effects, max_parts = [], []
+    for c in range(num_classes):
+        sel = np.nonzero(targets == c)[0]
+        if sel.size == 0:
+            continue
+        e, m = consistency_from_tables(tables[sel].astype(np.float64), masks[sel], part_thresh)
+        effects.extend(e); max_parts.extend(m)
+    return (float(np.mean(effects)) if effects else 0.0), effects, max_parts
 
 
 # ------------------------------------------------------------------------------------------------ dataset-wide nearest patches

@@ -469,6 +469,88 @@ def proto_topk_merge(act_max, argmax, idx, tokens, t0, label, image_id, ppc, val
               val, img, pos, best_feat)
 
 
+# ---- interpretability post-processing (csrc/interp.hip): activation maps [M, g, g] fp32 -> S x S, bit-identical to interpret.resize_cubic
+def _act_maps(name, grids, size):
+    """(M, g, S) of the maps handed to a ppf_act_* entry point.  What the C side cannot see -- layout and dtype -- is refused here with
+    the library's own shape error (the message form of _lib.call for PPF_ERR_SHAPE), before anything is launched."""
+    def bad(why):
+        return RuntimeError(f"{name} failed (rc={_lib.DEFINES['PPF_ERR_SHAPE']}): {name}: {why}")
+    if not isinstance(grids, torch.Tensor) or not grids.is_cuda:
+        raise bad("the maps must be a CUDA tensor (there is no host path here: interpret.resize_cubic is the host function)")
+    if grids.dtype != torch.float32:
+        raise bad(f"the maps must be fp32, got {grids.dtype}")
+    if grids.dim() != 3 or grids.shape[1] != grids.shape[2]:
+        raise bad(f"the maps must be [M, g, g], got {tuple(grids.shape)}")
+    if not grids.is_contiguous():
+        raise bad(f"the maps must be contiguous, got strides {tuple(grids.stride())}")
+    if int(size) != size:
+        raise bad(f"the output size must be an integer, got {size!r}")
+    return grids.shape[0], grids.shape[1], int(size)
+
+
+def act_upsample(grids, size):
+    """[M, g, g] fp32 -> [M, size, size] fp32 (ppf_act_upsample)."""
+    M, g, S = _act_maps("ppf_act_upsample", grids, size)
+    out = torch.empty((M, max(S, 0), max(S, 0)), dtype=torch.float32, device=grids.device)
+    if M > 0:
+        _lib.call("ppf_act_upsample", grids, out, M, g, S)
+    return out
+
+
+def act_peak(grids, size, parts=None, half_size=0):
+    """Peak of every up-sampled map without writing it (ppf_act_peak): (values [M] fp32, yx [M, 2] int32, table).  parts [M_img, n_parts, 3]
+    int32 (valid, x, y) with M a multiple of M_img: the same launch also fills table [M, n_parts] uint8 (else None)."""
+    M, g, S = _act_maps("ppf_act_peak", grids, size)
+    val = torch.empty(M, dtype=torch.float32, device=grids.device)
+    yx = torch.empty((M, 2), dtype=torch.int32, device=grids.device)
+    table, per, n_parts = None, 0, 0
+    if parts is not None:
+        n_parts, per = _act_parts("ppf_act_peak", parts, M)
+        table = torch.empty((M, n_parts), dtype=torch.uint8, device=grids.device)
+    if M > 0:
+        _lib.call("ppf_act_peak", grids, M, g, S, val, yx, parts, per, n_parts, int(half_size), table)
+    return val, yx, table
+
+
+def _act_parts(name, parts, M):
+    if parts.dtype != torch.int32 or parts.dim() != 3 or parts.shape[2] != 3 or not parts.is_contiguous() or not parts.is_cuda:
+        raise ValueError(f"{name}: parts must be a contiguous int32 CUDA tensor [M_img, n_parts, 3] of (valid, x, y)")
+    if parts.shape[0] == 0 or M % parts.shape[0] != 0:
+        raise ValueError(f"{name}: {M} maps do not divide over {parts.shape[0]} images")
+    return parts.shape[1], M // parts.shape[0]
+
+
+def act_part_table(yx, size, parts, half_size):
+    """[M, n_parts] uint8 table of prototype_part_table from given peaks yx [M, 2] int32 (ppf_act_part_table)."""
+    _chk(yx, torch.int32)
+    M = yx.shape[0]
+    n_parts, per = _act_parts("ppf_act_part_table", parts, M)
+    table = torch.empty((M, n_parts), dtype=torch.uint8, device=yx.device)
+    _lib.call("ppf_act_part_table", yx, M, int(size), parts, per, n_parts, int(half_size), table)
+    return table
+
+
+def act_order_stats(grids, size, k_lo, k_hi):
+    """[M, 2] fp32: the values of ascending 0-based ranks k_lo, k_hi (k_hi - k_lo in {0, 1}) of every up-sampled map (ppf_act_order_stats)."""
+    M, g, S = _act_maps("ppf_act_order_stats", grids, size)
+    stats = torch.empty((M, 2), dtype=torch.float32, device=grids.device)
+    if M > 0:
+        _lib.call("ppf_act_order_stats", grids, M, g, S, int(k_lo), int(k_hi), stats)
+    return stats
+
+
+def act_box(grids, size, thr):
+    """[M, 4] int32 (y0, y1, x0, x1) of up >= thr[m]; thr fp64 [M] on the device (ppf_act_box)."""
+    M, g, S = _act_maps("ppf_act_box", grids, size)
+    _chk(thr, torch.float64)
+    if thr.shape != (M,):
+        raise ValueError(f"act_box: one fp64 threshold per map expected, got {tuple(thr.shape)} for {M} maps")
+    box = torch.empty((M, 4), dtype=torch.int32, device=grids.device)
+    if M > 0:
+        _lib.call("ppf_act_box", grids, thr, M, g, S, box)
+    return box
+
+
 MIX_WORDS, MIX_WSELF = _lib.DEFINES["PPF_MIX_WORDS"], _lib.DEFINES["PPF_MIX_WSELF"]          # read from include/ppf_hip.h
 
 
