@@ -231,6 +231,8 @@ def replay(rec):
                 arm(arm_at[i], 1)           # this call's launches carry their completion event: the wait that follows records nothing
             rc = c[1](*c[2])
             if rc != 0:
+                if i in arm_at:
+                    arm(arm_at[i], 0)       # a failed call leaves no armed stream behind for later eager launches
                 raise RuntimeError(f"{c[3]} failed in replay (rc={rc}): {_lib.ppf_last_error().decode()}")
         elif k == 1:
             t = mark(c[1])

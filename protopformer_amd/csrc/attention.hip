@@ -42,12 +42,6 @@ struct AttnParams {
     float eps_c;           // eps / N_ref: the +eps/N term of the policy softmax; N_ref = tokens BEFORE reservation (compacted blocks pass it)
 };
 
-__device__ __forceinline__ int kswz(int row) {
-    const int u = row >> 1;
-    return ((u & 1) << 2) | (((u >> 2) & 1) << 1) | ((u >> 1) & 1);
-}
-__device__ __forceinline__ int row_off(int row, int c16) { return row * 128 + ((c16 ^ kswz(row)) << 4); }
-
 // MFMA A/B fragment, contraction-contiguous rows: lane -> row base+(lane&31), 8 values at d = ks*16 + (lane>>5)*8
 __device__ __forceinline__ bf16x8 frag_rows(const unsigned char* tile, int base, int ks, int lane) {
     return *reinterpret_cast<const bf16x8*>(tile + row_off(base + (lane & 31), ks * 2 + (lane >> 5)));
@@ -1059,26 +1053,17 @@ int ppf_attn_fwd_hm(const void* qkv, void* out, const float* policy, float* rowm
     const int nb = (N + 15) / 16;
     const dim3 grid((nb + F16_WAVES - 1) / F16_WAVES, B);
     constexpr int lds6 = Fwd16<64, 6>::LDS, lds13 = Fwd16<64, 13>::LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<64, 13, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds13);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<64, 13, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds13);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<64, 13, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds13);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(attn_fwd16): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
+    const dim3 block(F16_NTHR);
+    const char* who = "ppf_attn_fwd_hm";
     // round 6 (profiles/r6_attn_fwd_packed.txt): the packed softmax where only the last key tile is padded -- 65.8 -> 58.1 us stand-alone, +0.6 % of the step
-    if (N <= 96) {
-        if (policy) hipLaunchKernelGGL((attn_fwd16_kernel<64, 6, true, false>), grid, dim3(F16_NTHR), lds6, stream, p);
-        else if (N > 80) hipLaunchKernelGGL((attn_fwd16_kernel<64, 6, false, true>), grid, dim3(F16_NTHR), lds6, stream, p);
-        else hipLaunchKernelGGL((attn_fwd16_kernel<64, 6, false, false>), grid, dim3(F16_NTHR), lds6, stream, p);
-    } else {
-        if (policy) hipLaunchKernelGGL((attn_fwd16_kernel<64, 13, true, false>), grid, dim3(F16_NTHR), lds13, stream, p);
-        else if (N > 192) hipLaunchKernelGGL((attn_fwd16_kernel<64, 13, false, true>), grid, dim3(F16_NTHR), lds13, stream, p);
-        else hipLaunchKernelGGL((attn_fwd16_kernel<64, 13, false, false>), grid, dim3(F16_NTHR), lds13, stream, p);
+    if (N > 96) {
+        if (policy) return ppf_launch<attn_fwd16_kernel<64, 13, true, false>>(grid, block, lds13, stream, who, p);
+        if (N <= 192) return ppf_launch<attn_fwd16_kernel<64, 13, false, false>>(grid, block, lds13, stream, who, p);
+        return ppf_launch<attn_fwd16_kernel<64, 13, false, true>>(grid, block, lds13, stream, who, p);
     }
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (policy) return ppf_launch<attn_fwd16_kernel<64, 6, true, false>>(grid, block, lds6, stream, who, p);
+    if (N > 80) return ppf_launch<attn_fwd16_kernel<64, 6, false, true>>(grid, block, lds6, stream, who, p);
+    return ppf_launch<attn_fwd16_kernel<64, 6, false, false>>(grid, block, lds6, stream, who, p);
 }
 
 // headmean[B][N][NP] = mean_h probabilities (NP = N rounded up to a multiple of 4; pad columns are written as 0).
@@ -1114,42 +1099,18 @@ int ppf_attn_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
         using G = Geo<decltype(nt)::value>;
         constexpr int HDv = decltype(hd)::value, NTv = decltype(nt)::value;
         if constexpr (HDv == 64) {
-            {                   // head_dim 64: the streaming form of the one-pass kernel (round 4: 163 -> 134 us, profiles/r4_attn_bwd.txt)
-                constexpr int lds_bytes = StreamLds<HDv, NTv>::BYTES;
-                auto kern = attn_bwd_stream_kernel<HDv, NTv>;
-                static bool attr_set = false;
-                static int slots = 0;                          // workgroups the chip holds at once: CUs x (LDS- and wave-limited) per CU
-                if (!attr_set) {
-                    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                    if (e != hipSuccess) { ppf_set_error("ppf_attn_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-                    int dev = 0, cus = 256;
-                    (void)hipGetDevice(&dev);
-                    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                    int per = (160 * 1024) / lds_bytes;
-                    if (per > 8 / NTv) per = 8 / NTv;           // <= 256 VGPRs: two waves per SIMD
-                    if (per < 1) per = 1;
-                    slots = cus * per;
-                    attr_set = true;
-                }
-                // every workgroup walks the same number of items (the launch lasts as long as its longest walk): 384 items on 256 slots
-                // take two rounds either way, 192 workgroups leave the other CUs to the side stream
-                const int nitems = B * H, rounds = (nitems + slots - 1) / slots, grid = (nitems + rounds - 1) / rounds;
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(NTv * 64), lds_bytes, stream, p, nitems);
-                PPF_LAUNCH_CHECK();
-                return 0;
-            }
+            // head_dim 64: the streaming form of the one-pass kernel (round 4: 163 -> 134 us, profiles/r4_attn_bwd.txt)
+            constexpr int lds_bytes = StreamLds<HDv, NTv>::BYTES;
+            int per = (160 * 1024) / lds_bytes;
+            if (per > 8 / NTv) per = 8 / NTv;               // <= 256 VGPRs: two waves per SIMD
+            if (per < 1) per = 1;
+            const int slots = ppf_cu_count() * per;         // workgroups the chip holds at once: CUs x (LDS- and wave-limited) per CU
+            // every workgroup walks the same number of items (the launch lasts as long as its longest walk): 384 items on 256 slots
+            // take two rounds either way, 192 workgroups leave the other CUs to the side stream
+            const int nitems = B * H, rounds = (nitems + slots - 1) / slots, grid = (nitems + rounds - 1) / rounds;
+            return ppf_launch<attn_bwd_stream_kernel<HDv, NTv>>(dim3(grid), dim3(NTv * 64), lds_bytes, stream, "ppf_attn_bwd", p, nitems);
         } else {                // other head widths: the non-persistent one-pass kernel
-            constexpr int lds_bytes = OnePassLds<HDv, NTv>::BYTES;
-            auto kern = attn_bwd_onepass_kernel<HDv, NTv>;
-            static bool attr_set = false;                  // one flag per instantiation (the lambda is instantiated per (hd, nt))
-            if (!attr_set) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-                if (e != hipSuccess) { ppf_set_error("ppf_attn_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(kern, dim3(1, H, B), dim3(G::NTHR), lds_bytes, stream, p);
-            PPF_LAUNCH_CHECK();
-            return 0;
+            return ppf_launch<attn_bwd_onepass_kernel<HDv, NTv>>(dim3(1, H, B), dim3(G::NTHR), OnePassLds<HDv, NTv>::BYTES, stream, "ppf_attn_bwd", p);
         }
     });
 }

@@ -18,12 +18,6 @@ namespace {
 
 constexpr float SOFTMAX_EPS = 1e-6f;
 
-__device__ __forceinline__ int kswz(int row) {
-    const int u = row >> 1;
-    return ((u & 1) << 2) | (((u >> 2) & 1) << 1) | ((u >> 1) & 1);
-}
-__device__ __forceinline__ int row_off(int row, int c16) { return row * 128 + ((c16 ^ kswz(row)) << 4); }
-
 struct ThParams {
     const bf16_t* qkv;      // [B*N][3D]
     int B, H, N, D, NP;
@@ -1075,16 +1069,7 @@ int ppf_th_fwd(const void* qkv, const float* wl, const float* bl, const float* w
     return dispatch_th(D / H, H, "ppf_th_fwd", [&](auto hd, auto hv) {
         constexpr int HD = decltype(hd)::value, HV = decltype(hv)::value;
         const size_t lds = (size_t)(out ? 2 : 1) * HV * N * HD * 2;
-        auto k = th_fwd_kernel<HD, HV>;
-        static bool attr_set = false;               // one per (HD, HV) instantiation of this generic lambda
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(talking heads): %s", hipGetErrorString(e)); return (int)e; }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(k, dim3(th_groups(N), B), dim3(TH_NTHR), lds, stream, p);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<th_fwd_kernel<HD, HV>>(dim3(th_groups(N), B), dim3(TH_NTHR), lds, stream, "ppf_th_fwd", p);
     });
 }
 // Backward of the same: dout = dO bf16 [B*N][D]; writes ds16 = bf16 dS [B][H][N][NPK] (operand of the dQ / dK products) and one row of
@@ -1101,16 +1086,7 @@ int ppf_th_bwd(const void* qkv, const void* dout, const float* wl, const float* 
     return dispatch_th(D / H, H, "ppf_th_bwd", [&](auto hd, auto hv) {
         constexpr int HD = decltype(hd)::value, HV = decltype(hv)::value;
         const size_t lds = (size_t)2 * HV * N * HD * 2 + TH_WAVES * (2 * HV * HV + 2 * HV) * sizeof(float);
-        auto k = th_bwd_kernel<HD, HV>;
-        static bool attr_set = false;               // one per (HD, HV) instantiation of this generic lambda
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(talking heads): %s", hipGetErrorString(e)); return (int)e; }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(k, dim3(th_groups(N), B), dim3(TH_NTHR), lds, stream, p);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<th_bwd_kernel<HD, HV>>(dim3(th_groups(N), B), dim3(TH_NTHR), lds, stream, "ppf_th_bwd", p);
     });
 }
 // dqkv [B*N][3D] (bf16, every column written) from ds16 / a16 [B][H][N][NPK] (th_bwd's dS, th_fwd's A), packed qkv and dout = dO [B*N][D]:
@@ -1128,22 +1104,13 @@ int ppf_th_grads(const void* qkv, const void* dout, const void* ds16, const void
     const int hd = D / H;
     const size_t lds = (size_t)3 * 224 * hd * 2 + (size_t)4 * 32 * NPK * 2 + 64;      // + slack: the last transposed read of a tile overhangs its row by 16 bytes
     const float scale = 1.0f / sqrtf((float)hd);
-#define PPF_TH_GRADS(HDV)                                                                                                                     \
-    {                                                                                                                                         \
-        auto k = th_grads_kernel<HDV>;                                                                                                        \
-        static bool attr_set = false;                                                                                                         \
-        if (!attr_set) {                                                                                                                      \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-            if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(th_grads): %s", hipGetErrorString(e)); return (int)e; }                 \
-            attr_set = true;                                                                                                                  \
-        }                                                                                                                                     \
-        hipLaunchKernelGGL(k, dim3(H, B), dim3(TG_NTHR), lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, (const bf16_t*)ds16,               \
-                           (const bf16_t*)a16, (bf16_t*)dqkv, B, H, N, D, NPK, scale);                                                        \
-    }
-    if (hd == 48) PPF_TH_GRADS(48) else if (hd == 64) PPF_TH_GRADS(64) else PPF_TH_GRADS(32)
-#undef PPF_TH_GRADS
-    PPF_LAUNCH_CHECK();
-    return 0;
+    auto run = [&](auto hdv) {
+        return ppf_launch<th_grads_kernel<decltype(hdv)::value>>(dim3(H, B), dim3(TG_NTHR), lds, stream, "ppf_th_grads", (const bf16_t*)qkv, (const bf16_t*)dout,
+                                                                 (const bf16_t*)ds16, (const bf16_t*)a16, (bf16_t*)dqkv, B, H, N, D, NPK, scale);
+    };
+    if (hd == 48) return run(std::integral_constant<int, 48>());
+    if (hd == 64) return run(std::integral_constant<int, 64>());
+    return run(std::integral_constant<int, 32>());
 }
 
 int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, float* dbw, float* dbl, float* dwl, hipStream_t stream) {

@@ -526,7 +526,7 @@ int ppf_gather_rows(const void* src, const int* rows, void* dst, int nrows, int 
 // dst (nrows_dst rows) = 0 everywhere except dst[rows[r]] = src[r]
 int ppf_scatter_rows(const void* src, const int* rows, void* dst, int nrows_src, int nrows_dst, int row_bytes, hipStream_t stream) {
     PPF_CHECK_ARG(nrows_src > 0 && nrows_dst >= nrows_src && row_bytes > 0 && row_bytes % 16 == 0, PPF_ERR_ALIGN, "ppf_scatter_rows: bad arguments");
-    hipError_t e = hipMemsetAsync(dst, 0, (size_t)nrows_dst * row_bytes, stream);
+    hipError_t e = ppf_memset_async(dst, 0, (size_t)nrows_dst * row_bytes, stream);
     if (e != hipSuccess) { ppf_set_error("ppf_scatter_rows: memset failed: %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(move_rows_kernel, dim3(grid_for((int64_t)nrows_src * (row_bytes / 16))), dim3(256), 0, stream, (const uint4*)src, rows, (uint4*)dst,
                        nrows_src, row_bytes / 16, 1);
@@ -549,7 +549,7 @@ int ppf_image_finish_u8(const void* in_u8_hwc, float* out_nchw, int B, int H, in
 
 int ppf_memset_zero(void* ptr, size_t bytes, hipStream_t stream) {
     if (bytes == 0) return 0;
-    hipError_t e = hipMemsetAsync(ptr, 0, bytes, stream);
+    hipError_t e = ppf_memset_async(ptr, 0, bytes, stream);
     if (e != hipSuccess) { ppf_set_error("ppf_memset_zero: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }
@@ -582,7 +582,7 @@ int ppf_copy_2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch
         PPF_LAUNCH_CHECK();
         return 0;
     }
-    hipError_t e = hipMemcpy2DAsync(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)width, (size_t)rows, hipMemcpyDeviceToDevice, stream);
+    hipError_t e = ppf_memcpy2d_async(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)width, (size_t)rows, hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) { ppf_set_error("ppf_copy_2d: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }

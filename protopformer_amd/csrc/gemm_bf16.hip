@@ -35,7 +35,7 @@ constexpr int STAGE_LD = 68;                     // fp32 pitch of the per-wave e
 constexpr int STAGE_BYTES = 4 * 32 * STAGE_LD * 4;   // 4 waves x 32 rows
 
 
-__device__ __forceinline__ int lds_off_mode0(int r, int c16) { return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4); }
+__device__ __forceinline__ int lds_off_mode0(int r, int c16) { return lds_row_off(r, c16); }      // row-major tile: the shared 128-byte-row swizzle
 // transposed tile [64 kc][ROWS r]: row pitch ROWS*2 bytes, 64-byte units XOR-swizzled by kc&3 inside each 256-byte group
 template <int ROWS>
 __device__ __forceinline__ int lds_off_mode1(int kc, int col) {
@@ -459,20 +459,11 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
 
 template <int WMW, int WNW>
 int launch_wgrad8(const GemmParams& p, int splitk, hipStream_t stream) {
-    auto kern = wgrad8_kernel<WMW, WNW, true>;
     constexpr int NTHR = 64 * WMW * WNW, TBM = 64 * WMW, TBN = 64 * WNW;
     constexpr int opnd = (TBM + TBN) * BK * 2, strips = (NTHR / 64) * 32 * STAGE_LD * 4;
     constexpr int lds = opnd > strips ? opnd : strips;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(wgrad8): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN);
-    hipLaunchKernelGGL(kern, dim3(tiles * splitk), dim3(NTHR), lds, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<wgrad8_kernel<WMW, WNW, true>>(dim3(tiles * splitk), dim3(NTHR), lds, stream, "wgrad8", p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -501,7 +492,7 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm128g_kernel(const GemmParam
     unsigned char* tB = smem + TBM * BK * 2;
     unsigned offA[NLA], offB[4];
     {
-        const int rb = tid >> 3, ch = (tid & 7) ^ ((rb >> 1) & 7);       // rows rb + 32 i share the swizzle
+        const int rb = tid >> 3, ch = (tid & 7) ^ lds_swz(rb);       // rows rb + 32 i share the swizzle
 #pragma unroll
         for (int i = 0; i < NLA; ++i) offA[i] = ((unsigned)min(m0 + rb + 32 * i, p.M - 1) * (unsigned)p.lda + ch * 8) * 2u;
 #pragma unroll
@@ -564,20 +555,11 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm128g_kernel(const GemmParam
 
 template <int EPI, int MT, int OCC>
 int launch_g4_mt(const GemmParams& p, hipStream_t stream) {
-    auto kern = gemm128g_kernel<EPI, MT, OCC>;
     constexpr int TBM = 64 * MT;
     constexpr int opnd = TBM * BK * 2 + TILE_BYTES;
     constexpr int lds = opnd > STAGE_BYTES ? opnd : STAGE_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(gemm128g): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NTHREADS), lds, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<gemm128g_kernel<EPI, MT, OCC>>(dim3(tiles), dim3(NTHREADS), lds, stream, "gemm128g", p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -603,7 +585,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm224g_kernel(const GemmParams 
     unsigned char* tB = smem + G224_ROWS * BK * 2;
     unsigned offA[G224_MT], offB[4];
     {
-        const int rb = tid >> 3, ch = (tid & 7) ^ ((rb >> 1) & 7);       // rows rb + 32 i share the swizzle
+        const int rb = tid >> 3, ch = (tid & 7) ^ lds_swz(rb);       // rows rb + 32 i share the swizzle
 #pragma unroll
         for (int i = 0; i < G224_MT; ++i) offA[i] = ((unsigned)min(m0 + rb + 32 * i, p.M - 1) * (unsigned)p.lda + ch * 8) * 2u;
 #pragma unroll
@@ -678,7 +660,7 @@ bool g224_eligible(const GemmParams& p, int epi) {
     if ((long long)p.M * p.lda >= (1ll << 30) || (long long)p.N * p.ldb >= (1ll << 30)) return false;
     if (g_force_g224) return true;
     if (p.K < 768) return false;                 // round 5: the K = 384 input gradient of proj is +0.8 % of the deit_small step on 128 x 128 tiles (six K tiles do not pay for the larger tile's prologue / epilogue)
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    const int cus = ppf_cu_count();
     const long long tn = (p.N + BN - 1) / BN;
     const long long t128 = (long long)((p.M + BM - 1) / BM) * tn, t224 = (long long)((p.M + G224_ROWS - 1) / G224_ROWS) * tn;
     const int per128 = g4_eligible(p) ? 4 : 3;
@@ -692,16 +674,8 @@ bool g224_eligible(const GemmParams& p, int epi) {
 }
 int launch_g224(const GemmParams& p, hipStream_t stream) {
     constexpr int lds = G224_ROWS * BK * 2 + TILE_BYTES;           // 28 + 16 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm224g_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(gemm224g): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     const int tiles = ((p.M + G224_ROWS - 1) / G224_ROWS) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL(gemm224g_kernel, dim3(tiles), dim3(NTHREADS), lds, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<gemm224g_kernel>(dim3(tiles), dim3(NTHREADS), lds, stream, "gemm224g", p);
 }
 
 // MT = 4 (256x128 workgroup tiles, 128x64 per wave: 25 % fewer LDS fragment bytes per MFMA) was measured SLOWER at three and at two
@@ -721,20 +695,11 @@ template <bool TA, bool TB, int EPI, bool COLSUM, int MT>
 int launch_impl(const GemmParams& p, int splitk, hipStream_t stream, int nbatch) {
     constexpr int TBM = 64 * MT;
     const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + BN - 1) / BN);
-    auto kern = gemm_kernel<TA, TB, EPI, COLSUM, MT>;
     constexpr int opnd = TBM * BK * 2 + TILE_BYTES;
     constexpr int lds = opnd > STAGE_BYTES ? opnd : STAGE_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(gemm): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     GemmParams q = p;
     q.nsplit = splitk;
-    hipLaunchKernelGGL(kern, dim3(tiles * splitk, nbatch, 1), dim3(NTHREADS), lds, stream, q);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<gemm_kernel<TA, TB, EPI, COLSUM, MT>>(dim3(tiles * splitk, nbatch, 1), dim3(NTHREADS), lds, stream, "gemm", q);
 }
 
 // Tile choice: 256x128 when the m extent is tall enough to fill the chip with 256-row tiles (activation GEMMs), else 128x128.

@@ -110,7 +110,7 @@ int ppf_mixup_apply(float* x, const int* table_host, int* table_dev, int B, int 
                           r[PPF_MIX_YH], r[PPF_MIX_XL], r[PPF_MIX_XH], H, W);
         any = any || kind != 0;
     }
-    const hipError_t e = hipMemcpyAsync(table_dev, table_host, (size_t)B * PPF_MIX_WORDS * sizeof(int), hipMemcpyHostToDevice, stream);
+    const hipError_t e = ppf_memcpy_async(table_dev, table_host, (size_t)B * PPF_MIX_WORDS * sizeof(int), hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) {
         ppf_set_error("ppf_mixup_apply: parameter upload failed: %s", hipGetErrorString(e));
         return (int)e;

@@ -135,6 +135,19 @@ __device__ __forceinline__ void lds_dma16_hidden(const void* gptr, uint32_t lds_
 }
 __device__ __forceinline__ uint32_t lds_offset_of(const void* p) { return (uint32_t)(uintptr_t)p; }      // flat LDS address: aperture | offset
 
+// ---- LDS tiles of 128-byte rows (64 bf16: eight 16-byte chunks): byte offset of chunk c16 of a row, chunk index XORed with a function of the row.
+// lds_swz: three bits of row >> 1.  Conflict-free for ds_read_b128 fragments of consecutive rows (contraction-contiguous MFMA operands:
+//          the GEMMs, the full-row GEMM, the prototype distances).  Pick this one when the tile is only ever read by rows.
+// kswz:    the same three bits permuted.  Conflict-free for those row reads AND for ds_read_b64_tr_b16, which reads the tile "transposed"
+//          (attention, talking heads).  Pick this one when a tile is read both ways.
+__device__ __forceinline__ int lds_swz(int row) { return (row >> 1) & 7; }
+__device__ __forceinline__ int lds_row_off(int row, int c16) { return row * 128 + ((c16 ^ lds_swz(row)) << 4); }
+__device__ __forceinline__ int kswz(int row) {
+    const int u = row >> 1;
+    return ((u & 1) << 2) | (((u >> 2) & 1) << 1) | ((u >> 1) & 1);
+}
+__device__ __forceinline__ int row_off(int row, int c16) { return row * 128 + ((c16 ^ kswz(row)) << 4); }
+
 // ---- kernel launches that carry their own completion event (round 6) -----------------------------------------------------------------
 // Cross-stream ordering used to cost the MAIN queue one event-record packet per dependency (ppf_stream_wait_stream: hipEventRecord on the
 // producer's stream): ~70 packets per deit_small step, each a 4-8 us bubble between two dependent kernels (profiles/r6_queue_gaps.txt: 0.74 us
@@ -143,6 +156,9 @@ __device__ __forceinline__ uint32_t lds_offset_of(const void* p) { return (uint3
 // "armed" for the duration of one library call by the replay loop (ppf_stream_arm, when the recorded list shows that the call is followed by
 // a wait on its stream); every launch of that call then takes an event from the library's ring, and ppf_stream_wait_stream uses the last
 // one instead of recording.  Unarmed launches (everything outside a replayed step) are plain <<< >>> launches.
+// RULE: the wait uses the stop event of the LAST macro launch on the stream, so whatever else the library enqueues on a stream (memset,
+// copy) goes through the wrappers of ppf_launch.h, which tell the runtime that the last operation is no longer such a launch; raw
+// hipMemsetAsync / hipMemcpy*Async / <<< >>> appear nowhere else in csrc (tests/test_launch_cpu.py).
 #ifdef __cplusplus
 #include <hip/hip_ext.h>
 hipEvent_t ppf_take_stop_event(hipStream_t s);          // csrc/ppf_runtime.hip; nullptr unless `s` is armed
@@ -153,6 +169,7 @@ hipEvent_t ppf_take_stop_event(hipStream_t s);          // csrc/ppf_runtime.hip;
         if (ppf_ev_) hipExtLaunchKernelGGL(kernelName, dim3(numBlocks), dim3(numThreads), memPerBlock, streamId, nullptr, ppf_ev_, 0, __VA_ARGS__); \
         else kernelName<<<(numBlocks), (numThreads), (memPerBlock), (streamId)>>>(__VA_ARGS__);                                          \
     } while (0)
+#include "ppf_launch.h"
 #endif
 
 // Bijective XCD-aware remap of a 1-D block id: consecutive virtual ids land on the same XCD (private L2).

@@ -416,11 +416,7 @@ int ppf_attn_fwd_f32(const float* qkv, float* out, const float* policy, float* h
     PPF_CHECK_ARG(B > 0 && H > 0 && N > 0 && N <= 256 && D % H == 0 && D / H <= 64 && (!headmean || NP >= N), PPF_ERR_SHAPE,
                   "ppf_attn_fwd_f32: bad shape B=%d H=%d N=%d D=%d", B, H, N, D);
     const size_t lds = (size_t)2 * N * (D / H) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)attn_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { ppf_set_error("ppf_attn_fwd_f32: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(attn_f32_kernel, dim3(B), dim3(256), lds, stream, qkv, out, policy, headmean, NP, H, N, D, self_keep, eps_n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<attn_f32_kernel>(dim3(B), dim3(256), lds, stream, "ppf_attn_fwd_f32", qkv, out, policy, headmean, NP, H, N, D, self_keep, eps_n);
 }
 
 int ppf_th_attn_fwd_f32(const float* qkv, const float* wl, const float* bl, const float* ww, const float* bw, float* out, float* headmean, int NP,
@@ -631,11 +627,7 @@ int ppf_attn_bwd_f32(const float* qkv, const float* dout, const float* policy, f
     PPF_CHECK_ARG(qkv && dout && dqkv && scratch && B > 0 && H > 0 && N > 0 && N <= 256 && D % H == 0 && D / H <= 64, PPF_ERR_SHAPE,
                   "ppf_attn_bwd_f32: bad shape B=%d H=%d N=%d D=%d", B, H, N, D);
     const size_t lds = (size_t)2 * N * (D / H) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { ppf_set_error("ppf_attn_bwd_f32: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(B * H), dim3(256), lds, stream, qkv, dout, policy, dqkv, scratch, H, N, D, self_keep, eps_n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<attn_bwd_f32_kernel>(dim3(B * H), dim3(256), lds, stream, "ppf_attn_bwd_f32", qkv, dout, policy, dqkv, scratch, H, N, D, self_keep, eps_n);
 }
 
 
@@ -645,11 +637,7 @@ int ppf_th_attn_bwd_f32(const float* qkv, const float* dout, const float* wl, co
     PPF_CHECK_ARG(qkv && dout && wl && bl && ww && bw && dqkv && dwl && dbl && dww && dbw && B > 0 && H > 0 && H <= 16 && N > 0 && N <= 256 && D % H == 0,
                   PPF_ERR_SHAPE, "ppf_th_attn_bwd_f32: bad shape B=%d H=%d N=%d D=%d", B, H, N, D);
     const size_t lds = ((size_t)D + 3 * (size_t)H * N + 256 + 2 * H * H + 2 * H) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)th_attn_bwd_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { ppf_set_error("ppf_th_attn_bwd_f32: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(th_attn_bwd_f32_kernel, dim3(B * N), dim3(256), lds, stream, qkv, dout, wl, bl, ww, bw, dqkv, dwl, dbl, dww, dbw, H, N, D);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<th_attn_bwd_f32_kernel>(dim3(B * N), dim3(256), lds, stream, "ppf_th_attn_bwd_f32", qkv, dout, wl, bl, ww, bw, dqkv, dwl, dbl, dww, dbw, H, N, D);
 }
 
 int ppf_class_attn_bwd_f32(const float* q, const float* k, const float* v, const float* policy, const float* dout, float* dq, float* dk, float* dv,

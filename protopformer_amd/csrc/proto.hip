@@ -154,7 +154,6 @@ __device__ __forceinline__ Split3 split3(float lo, float hi) {
     r.c = pack_bf16x2(l2, h2);
     return r;
 }
-__device__ __forceinline__ int p6_off(int r, int c16) { return r * 128 + ((c16 ^ ((r >> 1) & 7)) << 4); }   // 128-byte rows, chunk swizzle
 
 // Prototype operand of proto_fwd6_kernel<.., PRE>: one wave per 16-step of a 32-prototype block splits that lane's 8 contraction values
 // (prototype = block * 32 + (lane & 31), k = step * 16 + 8 (lane >> 5) ..) into the three bf16 pieces and stores them where the main kernel's
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? 3 : 2) void proto_fwd6_kernel(const 
             const float4 v = stg[j];
             x2p[j] += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
             const Split3 s0 = split3(v.x, v.y), s1 = split3(v.z, v.w);
-            const int off = p6_off(row, c4 >> 1) + 8 * (c4 & 1);
+            const int off = lds_row_off(row, c4 >> 1) + 8 * (c4 & 1);
             *reinterpret_cast<uint2*>(planes + off) = make_uint2(s0.a, s1.a);
             *reinterpret_cast<uint2*>(planes + PLANE + off) = make_uint2(s0.b, s1.b);
             *reinterpret_cast<uint2*>(planes + 2 * PLANE + off) = make_uint2(s0.c, s1.c);
@@ -280,7 +279,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? 3 : 2) void proto_fwd6_kernel(const 
                 }
 #pragma unroll
                 for (int t = 0; t < TT; ++t) {
-                    const int off = p6_off(t * 32 + l31, ks * 2 + hh);
+                    const int off = lds_row_off(t * 32 + l31, ks * 2 + hh);
                     const bf16x8 xa = *reinterpret_cast<const bf16x8*>(planes + off);
                     const bf16x8 xb = *reinterpret_cast<const bf16x8*>(planes + PLANE + off);
                     const bf16x8 xc = *reinterpret_cast<const bf16x8*>(planes + 2 * PLANE + off);
@@ -1067,52 +1066,46 @@ static int proto_bwd_launch(ProtoBwdParams p, void* workspace, size_t workspace_
     if (tg.ok && p.g_rows && p.ppc > PT_NW) tg.ok = false;
     if (tg.ok && !(workspace && workspace_bytes >= need + tg.ws_bytes && ((uintptr_t)p.tok & 15) == 0)) tg.ok = false;
     const int nj = (Dp + 63) / 64;
-    auto run = [&](auto njc) {
+    const char* who = "ppf_proto_bwd";
+    auto run = [&](auto njc) -> int {                 // every launch is checked on its own: the first failure is the one reported
         constexpr int NJ = decltype(njc)::value;
+        int rc = 0;
         if (p.dtok) {
-            if (p.g_full) hipLaunchKernelGGL(proto_bwd_mark_kernel, dim3(W, B), dim3(256), 0, stream, p, (uint32_t*)workspace, W);
-            else hipLaunchKernelGGL(proto_bwd_mark_sparse_kernel, dim3(B), dim3(256), 0, stream, p, (uint32_t*)workspace, W);
-            if (W <= 64) hipLaunchKernelGGL((proto_bwd_tokens_kernel<NJ, 1>), dim3(B * T), dim3(64), 0, stream, p, (const uint32_t*)workspace, W);
-            else hipLaunchKernelGGL((proto_bwd_tokens_kernel<NJ, 8>), dim3(B * T), dim3(512), 0, stream, p, (const uint32_t*)workspace, W);
+            uint32_t* marks = (uint32_t*)workspace;
+            if (p.g_full) rc = ppf_launch<proto_bwd_mark_kernel>(dim3(W, B), dim3(256), 0, stream, who, p, marks, W);
+            else rc = ppf_launch<proto_bwd_mark_sparse_kernel>(dim3(B), dim3(256), 0, stream, who, p, marks, W);
+            if (rc) return rc;
+            if (W <= 64) rc = ppf_launch<proto_bwd_tokens_kernel<NJ, 1>>(dim3(B * T), dim3(64), 0, stream, who, p, (const uint32_t*)marks, W);
+            else rc = ppf_launch<proto_bwd_tokens_kernel<NJ, 8>>(dim3(B * T), dim3(512), 0, stream, who, p, (const uint32_t*)marks, W);
+            if (rc) return rc;
         }
         if (p.dprotos && tg.ok) {
             if constexpr (NJ <= 6) {
                 const int lds = 2 * tg.chunk_pad;
-                static int attr_lds = 0;
-                if (lds > attr_lds) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proto_bwd_protos_tiled_kernel<NJ, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proto_bwd_protos_rows_kernel<NJ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    attr_lds = lds;
-                }
                 float* part = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + need);
                 float* psum = part + (size_t)tg.sg * P * Dp;
                 float* rpart = psum + (size_t)tg.sg * P;
                 if (p.g_max)
-                    hipLaunchKernelGGL((proto_bwd_protos_tiled_kernel<NJ, 16>), dim3(tg.pt * tg.sg), dim3(1024), lds, stream, p, part, psum, tg.pt, tg.sg,
-                                       tg.spg, tg.R, tg.nchunks, tg.chunk_pad);
-                if (p.g_rows)
-                    hipLaunchKernelGGL((proto_bwd_protos_rows_kernel<NJ>), dim3(B), dim3(1024), lds, stream, p, rpart, tg.R, tg.nchunks, tg.chunk_pad);
-                hipLaunchKernelGGL(proto_bwd_protos_finish_kernel, dim3(P), dim3(128), 0, stream, p.g_max ? part : nullptr, psum, p.g_rows ? rpart : nullptr,
-                                   p.row_label, p.ppc, p.protos, p.dprotos, B, P, Dp, tg.sg);
+                    rc = ppf_launch<proto_bwd_protos_tiled_kernel<NJ, 16>>(dim3(tg.pt * tg.sg), dim3(1024), lds, stream, who, p, part, psum, tg.pt, tg.sg,
+                                                                           tg.spg, tg.R, tg.nchunks, tg.chunk_pad);
+                if (rc) return rc;
+                if (p.g_rows) rc = ppf_launch<proto_bwd_protos_rows_kernel<NJ>>(dim3(B), dim3(1024), lds, stream, who, p, rpart, tg.R, tg.nchunks, tg.chunk_pad);
+                if (rc) return rc;
+                rc = ppf_launch<proto_bwd_protos_finish_kernel>(dim3(P), dim3(128), 0, stream, who, p.g_max ? part : nullptr, psum, p.g_rows ? rpart : nullptr, p.row_label,
+                                                                p.ppc, p.protos, p.dprotos, B, P, Dp, tg.sg);
             }
         } else if (p.dprotos) {
             constexpr int lds = PB_NW * PB_CHUNK * 6 + PB_NW * NJ * 64 * 4 + (PB_NW + 1) * 4;
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proto_bwd_protos_kernel<NJ>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                attr_set = true;
-            }
-            hipLaunchKernelGGL((proto_bwd_protos_kernel<NJ>), dim3(P), dim3(1024), lds, stream, p);
+            rc = ppf_launch<proto_bwd_protos_kernel<NJ>>(dim3(P), dim3(1024), lds, stream, who, p);
         }
+        return rc;
     };
-    if (nj <= 1) run(std::integral_constant<int, 1>());
-    else if (nj <= 2) run(std::integral_constant<int, 2>());
-    else if (nj <= 3) run(std::integral_constant<int, 3>());
-    else if (nj <= 4) run(std::integral_constant<int, 4>());
-    else if (nj <= 6) run(std::integral_constant<int, 6>());
-    else run(std::integral_constant<int, 8>());
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (nj <= 1) return run(std::integral_constant<int, 1>());
+    if (nj <= 2) return run(std::integral_constant<int, 2>());
+    if (nj <= 3) return run(std::integral_constant<int, 3>());
+    if (nj <= 4) return run(std::integral_constant<int, 4>());
+    if (nj <= 6) return run(std::integral_constant<int, 6>());
+    return run(std::integral_constant<int, 8>());
 }
 
 int ppf_proto_bwd(const float* tok, int64_t stride_b, int t0, int T, const float* protos, int B, int P, int Dp, int act_kind, float eps,

@@ -63,7 +63,6 @@ struct RowGemmParams {
 
 // 16-byte chunk c of a 128-byte row r is stored at chunk c ^ swz(r): the four 16-lane groups of a ds_read_b128 (lanes {0-3,12-15,20-27},
 // {4-11,16-19,28-31}, +32) that read 16 rows x 4 chunks then touch 16 different 16-byte slots each (conflict-free)
-__device__ __forceinline__ int rg_swz(int row) { return (row >> 1) & 7; }
 
 // VW (2 or 4) consecutive floats <-> registers; bf16 store of VW values
 template <int VW> __device__ __forceinline__ void rg_ld(float (&d)[VW], const float* src) {
@@ -110,7 +109,7 @@ __global__ __launch_bounds__(RG_NTHR, 2) void rowgemm_kernel(const RowGemmParams
         if (b < NPA) { prow = b * 8; dst[i] = b * 1024; }
         else { int bb = b - NPA + rot; bb -= bb >= NPB ? NPB : 0; prow = bb * 8; dst[i] = A_BYTES + bb * 1024; }
         const int r = prow + (lane >> 3);
-        const int cs = (lane & 7) ^ rg_swz(r);                             // SOURCE chunk of this lane's LDS slot
+        const int cs = (lane & 7) ^ lds_swz(r);                             // SOURCE chunk of this lane's LDS slot
         if (b < NPA) src[i] = gA + (size_t)min(r, rows - 1) * p.lda * 2 + cs * 16;       // rows past the tile repeat its last row (masked later)
         else src[i] = gB + (size_t)r * p.ldb * 2 + cs * 16;
     }
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(RG_NTHR, 2) void rowgemm_kernel(const RowGemmParams
     // ---- fragment read addresses: lane l of a 16-row tile reads row (l & 15), chunk 4 ks + (l >> 4), stored at chunk ^ swz(row) ----
     int frag[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) frag[ks] = (lane & 15) * 128 + (((ks * 4 + (lane >> 4)) ^ rg_swz(lane & 15)) << 4);
+    for (int ks = 0; ks < 2; ++ks) frag[ks] = (lane & 15) * 128 + (((ks * 4 + (lane >> 4)) ^ lds_swz(lane & 15)) << 4);
     const int a_base = wm * MTW * 2048, b_base = A_BYTES + wn * 48 * 128;
 
     f32x4 acc[MTW][3];
@@ -449,16 +448,7 @@ constexpr int rg_lds_bytes() {
 template <int D, int MT, int EPI>
 int rg_launch(const RowGemmParams& p, int tiles, hipStream_t stream) {
     constexpr int lds = rg_lds_bytes<D, MT>();
-    auto kern = rowgemm_kernel<D, MT, EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(rowgemm): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(RG_NTHR), lds, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<rowgemm_kernel<D, MT, EPI>>(dim3(tiles), dim3(RG_NTHR), lds, stream, "rowgemm", p);
 }
 
 template <int D, int MT>
