@@ -23,8 +23,7 @@
 #include "ppf_hip.h"
 #include "gemm_common.h"
 #include <cstdlib>
-#include <utility>
-#include <vector>
+#include <type_traits>
 
 namespace {
 using namespace ppfg;
@@ -44,10 +43,13 @@ __device__ __forceinline__ int lds_off_mode1(int kc, int col) {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));       // a native 128-bit register tuple
 
-// Operand tile of ROWS rows (m or n) x 64 contraction values, staged global -> registers -> LDS by 256 threads.
-template <bool T, int ROWS>
+// Operand tile of ROWS rows (m or n) x 64 contraction values, staged global -> registers -> LDS by NTHR threads.
+template <bool T, int ROWS, int NTHR = NTHREADS>
 struct TileIO {
-    static constexpr int NLD = ROWS / 32;            // 16-byte loads per thread
+    static constexpr int NLD = ROWS * 8 / NTHR;      // 16-byte loads per thread
+    static constexpr int RPP = NTHR / 8;             // mode 0: rows per pass (eight 16-byte chunks per row)
+    static constexpr int CPR = ROWS / 8;             // mode 1: 16-byte chunks per kc row
+    static constexpr int KPP = NTHR / CPR;           // mode 1: kc rows per pass
     // Branch-free: every load is issued unconditionally from a clamped (always valid) address and the "outside the matrix"
     // predicate travels as a bit mask that sstore applies.  Loads under per-lane branches made the compiler wait vmcnt(0) at
     // every K step (it cannot count loads across exec-masked branches), which serialised the register pipeline.
@@ -60,20 +62,19 @@ struct TileIO {
             const int kk = kok ? k0 + c16 * 8 : 0;
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
-                const int r = row0 + rb + 32 * i;
+                const int r = row0 + rb + RPP * i;
                 const bf16_t* src = X + (size_t)min(r, R - 1) * ld + kk;
                 reg[i] = *reinterpret_cast<const u32x4*>(src);
                 mask |= (kok && r < R) ? (1u << i) : 0u;
             }
         } else {
-            constexpr int CPR = ROWS / 8;            // 16-byte chunks per kc row
             const int c16 = tid % CPR, kb = tid / CPR;
             const int col = row0 + c16 * 8;
             const bool cok = kpad ? col < R : (col + 8) <= R;
             const int cc = cok ? col : 0;
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
-                const int kc = k0 + kb + (256 / CPR) * i;
+                const int kc = k0 + kb + KPP * i;
                 const bf16_t* src = X + (size_t)min(kc, kend - 1) * ld + cc;
                 reg[i] = *reinterpret_cast<const u32x4*>(src);
                 mask |= (cok && kc < kend) ? (1u << i) : 0u;
@@ -87,13 +88,12 @@ struct TileIO {
             const int c16 = tid & 7, rb = tid >> 3;
 #pragma unroll
             for (int i = 0; i < NLD; ++i)
-                *reinterpret_cast<u32x4*>(tile + lds_off_mode0(rb + 32 * i, c16)) = ((mask >> i) & 1u) ? reg[i] : zero;
+                *reinterpret_cast<u32x4*>(tile + lds_off_mode0(rb + RPP * i, c16)) = ((mask >> i) & 1u) ? reg[i] : zero;
         } else {
-            constexpr int CPR = ROWS / 8;
             const int c16 = tid % CPR, kb = tid / CPR;
 #pragma unroll
             for (int i = 0; i < NLD; ++i)
-                *reinterpret_cast<u32x4*>(tile + lds_off_mode1<ROWS>(kb + (256 / CPR) * i, c16 * 8)) = ((mask >> i) & 1u) ? reg[i] : zero;
+                *reinterpret_cast<u32x4*>(tile + lds_off_mode1<ROWS>(kb + KPP * i, c16 * 8)) = ((mask >> i) & 1u) ? reg[i] : zero;
         }
     }
     // Fragment of the 32-row sub-tile starting at rbase for k-substep ks (16 contraction values):
@@ -171,14 +171,52 @@ __device__ __forceinline__ void epilogue_rows(const GemmParams& p, const float* 
     }
 }
 
-// MT = 32-row MFMA tiles per wave along m: MT = 2 -> 128x128 workgroup tile (3 workgroups/CU), MT = 4 -> 256x128 (wave tile
-// 128x64, 2 workgroups/CU): fewer LDS bytes and barriers per flop for the tall activation GEMMs (M = B*N tokens).
-// The next K tile is prefetched into registers while the current one is multiplied (three workgroups per CU).  (A three-deep register
-// pipeline with hand-counted waits was measured equal stand-alone and 1.8 % slower in the step -- the kernel is not latency-bound,
-// profiles/r2_wgrad_pmc.txt -- and removed in round 4.)
-template <bool TA, bool TB, int EPI, bool COLSUM, int MT>
-__global__ __launch_bounds__(NTHREADS, MT == 2 ? 3 : 2) void gemm_kernel(const GemmParams p_) {
-    constexpr int PD = 1;
+// Contraction range [kbeg, kend) of K slice `zslice` of `nsplit`: multiples of BK except the tail; kbeg >= kend: an empty slice.  The K-tile
+// count is left to the caller, after its empty-slice return: computed in front of that return the kernels come out 5 % longer.
+struct KSlice { int kbeg, kend; };
+__device__ __forceinline__ KSlice k_slice(int K, int nsplit, int zslice) {
+    const int kchunk = (((K + nsplit - 1) / nsplit) + BK - 1) / BK * BK;
+    const int kbeg = zslice * kchunk;
+    return {kbeg, min(K, kbeg + kchunk)};
+}
+
+// Epilogue of the 32-row block mi of a wave's 64-column tile (acc[ni][mi]: 2 x MT MFMA tiles; the block's top-left corner is (mbase, nbase)).
+// After the MFMAs a lane holds, for each ni: row m = lane&31 and, for g = 0..3, the four consecutive columns n = 32*ni+8*g+4*(lane>>5)..
+// (acc regs 4g..4g+3): row-strided 8/16-byte pieces.  Each wave therefore transposes its accumulators through a private LDS strip (32 rows
+// x 64 fp32 at a time) so that 16 consecutive lanes cover one 64-column row segment: bias / residual reads and the output stores become
+// full 128/256-byte runs.  (The caller's last barrier has already retired every read of the operand tiles.)
+template <int EPI, int MT>
+__device__ __forceinline__ void strip_epilogue(const GemmParams& p, const f32x16 (&acc)[2][MT], int mi, unsigned char* smem, int wave, int lane,
+                                               int mbase, int nbase) {
+    const int h = lane >> 5;
+    float* stage = reinterpret_cast<float*>(smem) + wave * (32 * STAGE_LD);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<float4*>(stage + (lane & 31) * STAGE_LD + 32 * ni + 8 * g + 4 * h) =
+                make_float4(acc[ni][mi][4 * g], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
+    __builtin_amdgcn_wave_barrier();                           // keep the compiler from moving reads above the writes
+    epilogue_rows<EPI>(p, stage, mbase, nbase, lane);
+    __builtin_amdgcn_wave_barrier();                           // the next 32-row block overwrites the strip
+}
+
+// Row m's partial column sum of this K slice: behind the slice's M*N partial tile in the split-K workspace.
+__device__ __forceinline__ void store_partial_colsum(const GemmParams& p, int m, float v) {
+    p.ws[p.zslice * ((size_t)p.M * p.N + (size_t)p.cs_parts * p.M) + (size_t)p.M * p.N + m] = v;
+}
+
+// 128x128x64 per 256-thread workgroup (2 x 2 waves of 64 x 64), three workgroups per CU; batched problems along gridDim.y.  The next K tile is
+// prefetched into registers while the current one is multiplied.  (A three-deep register pipeline with hand-counted waits was measured equal
+// stand-alone and 1.8 % slower in the step -- the kernel is not latency-bound, profiles/r2_wgrad_pmc.txt -- and removed in round 4.  256-row
+// tiles, four MFMA tiles per wave along m, lost at every shape: see launch() below.)
+// PD (register stages, 1) and the kt0 / u loop nest are what is left of that pipeline, and they stay: written as one plain loop over kt with
+// ra[NLD] -- the form wgrad8_kernel has -- this kernel compiles to 140-142 VGPRs instead of 128-130 and 8 % more instructions, and the three
+// trans_b instantiations lose their fourth workgroup per CU (MEASUREMENTS.md 5j).  So the two kernels share the loaders and the steps around
+// the loop, not the loop.
+template <bool TA, bool TB, int EPI, bool COLSUM>
+__global__ __launch_bounds__(NTHREADS, 3) void gemm_kernel(const GemmParams p_) {
+    constexpr int PD = 1, MT = 2;                   // register stages; 32-row MFMA tiles per wave along m
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int TBM = 64 * MT;                    // workgroup tile rows
     constexpr int A_BYTES = TBM * BK * 2;
@@ -204,11 +242,7 @@ __global__ __launch_bounds__(NTHREADS, MT == 2 ? 3 : 2) void gemm_kernel(const G
         p.C = (EPI == EPI_BF16) ? (void*)(reinterpret_cast<bf16_t*>(p.C) + co) : (void*)(reinterpret_cast<float*>(p.C) + co);
     }
 
-    // contraction range of this K slice: multiples of BK except the tail
-    const int nsplit = p.nsplit;
-    const int kchunk = (((p.K + nsplit - 1) / nsplit) + BK - 1) / BK * BK;
-    const int kbeg = zslice * kchunk;
-    const int kend = min(p.K, kbeg + kchunk);
+    const auto [kbeg, kend] = k_slice(p.K, p.nsplit, zslice);
     if (kbeg >= kend) return;
     const int nk = (kend - kbeg + BK - 1) / BK;
 
@@ -286,31 +320,14 @@ __global__ __launch_bounds__(NTHREADS, MT == 2 ? 3 : 2) void gemm_kernel(const G
         }
     }
 
-    // epilogue.  After the MFMAs a lane holds, for each (ni, mi): row m = wm+32*mi+(lane&31) and, for g = 0..3, the four
-    // consecutive columns n = wn+32*ni+8*g+4*(lane>>5).. (acc regs 4g..4g+3): row-strided 8/16-byte pieces.  Each wave
-    // therefore transposes its accumulators through a private LDS strip (32 rows x 64 fp32 at a time) so that 16
-    // consecutive lanes cover one 64-column row segment: bias / residual reads and the output stores become full
-    // 128/256-byte runs.  (The main loop's last barrier has already retired every read of the operand tiles.)
-    const int h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * (32 * STAGE_LD);
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(stage + (lane & 31) * STAGE_LD + 32 * ni + 8 * g + 4 * h) =
-                    make_float4(acc[ni][mi][4 * g], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
-        __builtin_amdgcn_wave_barrier();                           // keep the compiler from moving reads above the writes
-        epilogue_rows<EPI>(p, stage, m0 + wm + 32 * mi, n0 + wn, lane);
-        __builtin_amdgcn_wave_barrier();                           // the next 32-row block overwrites the strip
+        strip_epilogue<EPI>(p, acc, mi, smem, wave, lane, m0 + wm + 32 * mi, n0 + wn);
         if constexpr (COLSUM) {
             const int m = m0 + wm + 32 * mi + (lane & 31);
-            if (do_colsum && h == 0 && m < p.M) {
-                if constexpr (EPI == EPI_PARTIAL) {
-                    float* dst = p.ws + p.zslice * ((size_t)p.M * p.N + (size_t)p.cs_parts * p.M) + (size_t)p.M * p.N + m;
-                    *dst = accs[mi][0];
-                } else unsafeAtomicAdd(p.colsum + m, accs[mi][0]);
+            if (do_colsum && (lane >> 5) == 0 && m < p.M) {
+                if constexpr (EPI == EPI_PARTIAL) store_partial_colsum(p, m, accs[mi][0]);
+                else unsafeAtomicAdd(p.colsum + m, accs[mi][0]);
             }
         }
     }
@@ -322,42 +339,14 @@ __global__ __launch_bounds__(NTHREADS, MT == 2 ? 3 : 2) void gemm_kernel(const G
 // (profiles/r4_wgrad_l2_knockout.txt: half the loads = +3.3 % of the step).  Two 128 x 128 sub-tiles that share one operand tile in LDS
 // read 25 % less; every wave keeps the 64 x 64 accumulator tile (64 VGPRs) of the four-wave kernel, so the footprint per wave is
 // unchanged and the launch has half as many, twice as large workgroups (48 KiB of operand tiles each).  Both operands transposed
-// (contraction = rows in memory), register-staged with one tile of prefetch, ordered split-K partial tiles (EPI_PARTIAL) only.
-template <int ROWS, int NTHR>
-struct TileT {
-    static constexpr int CPR = ROWS / 8;             // 16-byte chunks per contraction row
-    static constexpr int KPP = NTHR / CPR;           // contraction rows per pass
-    static constexpr int NLD = BK / KPP;             // passes = 16-byte loads per thread
-    static __device__ __forceinline__ unsigned gload(u32x4 (&reg)[NLD], const bf16_t* __restrict__ X, int ld, int R, int row0, int k0, int kend, int tid) {
-        const int c16 = tid % CPR, kb = tid / CPR;
-        const int col = row0 + c16 * 8;
-        const bool cok = (col + 8) <= R;
-        const int cc = cok ? col : 0;
-        unsigned mask = 0;
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int kc = k0 + kb + KPP * i;
-            reg[i] = *reinterpret_cast<const u32x4*>(X + (size_t)min(kc, kend - 1) * ld + cc);
-            mask |= (cok && kc < kend) ? (1u << i) : 0u;
-        }
-        return mask;
-    }
-    static __device__ __forceinline__ void sstore(const u32x4 (&reg)[NLD], unsigned mask, unsigned char* tile, int tid) {
-        const u32x4 zero = {0u, 0u, 0u, 0u};
-        const int c16 = tid % CPR, kb = tid / CPR;
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            *reinterpret_cast<u32x4*>(tile + lds_off_mode1<ROWS>(kb + KPP * i, c16 * 8)) = ((mask >> i) & 1u) ? reg[i] : zero;
-    }
-    static __device__ __forceinline__ bf16x8 frag(const unsigned char* tile, int rbase, int ks, int lane) { return TileIO<true, ROWS>::frag(tile, rbase, ks, lane); }
-};
-
+// (contraction = rows in memory), register-staged with one tile of prefetch, ordered split-K partial tiles (EPI_PARTIAL) only, never batched,
+// never kpad.
 template <int WMW, int WNW, bool COLSUM>
 __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmParams p_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NTHR = 64 * WMW * WNW, TBM = 64 * WMW, TBN = 64 * WNW;
-    using IOA = TileT<TBM, NTHR>;
-    using IOB = TileT<TBN, NTHR>;
+    using IOA = TileIO<true, TBM, NTHR>;
+    using IOB = TileIO<true, TBN, NTHR>;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = (wave % WMW) * 64, wn = (wave / WMW) * 64;
@@ -368,10 +357,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
     const int m0 = (vid / tiles_n) * TBM, n0 = (vid % tiles_n) * TBN;
     GemmParams p = p_;
     p.zslice = zslice;
-    const int nsplit = p.nsplit;
-    const int kchunk = (((p.K + nsplit - 1) / nsplit) + BK - 1) / BK * BK;
-    const int kbeg = zslice * kchunk;
-    const int kend = min(p.K, kbeg + kchunk);
+    const auto [kbeg, kend] = k_slice(p.K, p.nsplit, zslice);
     if (kbeg >= kend) return;
     const int nk = (kend - kbeg + BK - 1) / BK;
 
@@ -394,16 +380,16 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
     const bool do_colsum = COLSUM && p.colsum != nullptr && n0 == 0 && wn == 0;
     unsigned char* tA = smem;
     unsigned char* tB = smem + TBM * BK * 2;
-    ma = IOA::gload(ra, p.A, p.lda, p.M, m0, kbeg, kend, tid);
-    mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, kbeg, kend, tid);
+    ma = IOA::gload(ra, p.A, p.lda, p.M, m0, kbeg, kend, tid, 0);
+    mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, kbeg, kend, tid, 0);
     IOA::sstore(ra, ma, tA, tid);
     IOB::sstore(rb, mb, tB, tid);
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         {                                                    // next tile into registers while this one is multiplied (past the end: a
             const int k0 = kbeg + min(kt + 1, nk - 1) * BK;  // harmless re-read of the last tile, never stored)
-            ma = IOA::gload(ra, p.A, p.lda, p.M, m0, k0, kend, tid);
-            mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, k0, kend, tid);
+            ma = IOA::gload(ra, p.A, p.lda, p.M, m0, k0, kend, tid, 0);
+            mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, k0, kend, tid, 0);
         }
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
@@ -434,25 +420,12 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
         __syncthreads();
     }
     // epilogue: as gemm_kernel (a private 32 x 64 fp32 strip per wave, row-contiguous partial-tile stores)
-    const int h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * (32 * STAGE_LD);
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(stage + (lane & 31) * STAGE_LD + 32 * ni + 8 * g + 4 * h) =
-                    make_float4(acc[ni][mi][4 * g], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
-        __builtin_amdgcn_wave_barrier();
-        epilogue_rows<EPI_PARTIAL>(p, stage, m0 + wm + 32 * mi, n0 + wn, lane);
-        __builtin_amdgcn_wave_barrier();
+        strip_epilogue<EPI_PARTIAL>(p, acc, mi, smem, wave, lane, m0 + wm + 32 * mi, n0 + wn);
         if constexpr (COLSUM) {
             const int m = m0 + wm + 32 * mi + (lane & 31);
-            if (do_colsum && h == 0 && m < p.M) {
-                float* dst = p.ws + p.zslice * ((size_t)p.M * p.N + (size_t)p.cs_parts * p.M) + (size_t)p.M * p.N + m;
-                *dst = accs[mi][0];
-            }
+            if (do_colsum && (lane >> 5) == 0 && m < p.M) store_partial_colsum(p, m, accs[mi][0]);
         }
     }
 }
@@ -477,40 +450,21 @@ int launch_wgrad8(const GemmParams& p, int splitk, hipStream_t stream) {
 typedef __attribute__((address_space(3))) void g4_lds_t;
 typedef const __attribute__((address_space(1))) void g4_gbl_t;
 
-template <int EPI, int MT, int OCC>
-__global__ __launch_bounds__(NTHREADS, OCC) void gemm128g_kernel(const GemmParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    using IO = TileIO<false, 128>;
-    constexpr int TBM = 64 * MT, NLA = 2 * MT;                 // A rows per workgroup, 32-row load instructions per K tile
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = (wave & 1) * (32 * MT), wn = (wave >> 1) * 64;
-    const int tiles_n = (p.N + BN - 1) / BN;
-    const int vid = xcd_remap(blockIdx.x, gridDim.x);
-    const int m0 = (vid / tiles_n) * TBM, n0 = (vid % tiles_n) * BN;
-    unsigned char* tA = smem;
-    unsigned char* tB = smem + TBM * BK * 2;
+// The direct-to-LDS K step of a 256-thread workgroup: NLA 32-row groups of A (rows m0 ..) and four of B (rows n0 ..), one 16-byte
+// global_load_lds per thread and row group; load(kt) returns once K tile kt is in tA / tB for every wave.
+template <int NLA>
+struct DirectLds {
     unsigned offA[NLA], offB[4];
-    {
+    const unsigned char *gA, *gB;
+    __device__ __forceinline__ DirectLds(const GemmParams& p, int m0, int n0, int tid)
+        : gA(reinterpret_cast<const unsigned char*>(p.A)), gB(reinterpret_cast<const unsigned char*>(p.B)) {
         const int rb = tid >> 3, ch = (tid & 7) ^ lds_swz(rb);       // rows rb + 32 i share the swizzle
 #pragma unroll
         for (int i = 0; i < NLA; ++i) offA[i] = ((unsigned)min(m0 + rb + 32 * i, p.M - 1) * (unsigned)p.lda + ch * 8) * 2u;
 #pragma unroll
         for (int i = 0; i < 4; ++i) offB[i] = ((unsigned)min(n0 + rb + 32 * i, p.N - 1) * (unsigned)p.ldb + ch * 8) * 2u;
     }
-    const unsigned char* gA = reinterpret_cast<const unsigned char*>(p.A);
-    const unsigned char* gB = reinterpret_cast<const unsigned char*>(p.B);
-    f32x16 acc[2][MT];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nk = p.K / BK;
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt > 0) __syncthreads();                          // everyone finished reading the previous K tile
+    __device__ __forceinline__ void load(int kt, unsigned char* tA, unsigned char* tB, int wave) const {
         const unsigned char* ka = gA + (size_t)kt * (BK * 2);
         const unsigned char* kb = gB + (size_t)kt * (BK * 2);
 #pragma unroll
@@ -521,45 +475,61 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm128g_kernel(const GemmParam
             __builtin_amdgcn_global_load_lds((g4_gbl_t*)(kb + offB[i]), (g4_lds_t*)(tB + i * 4096 + wave * 1024), 16, 0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+    }
+};
+
+template <int EPI>
+__global__ __launch_bounds__(NTHREADS, 4) void gemm128g_kernel(const GemmParams p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using IO = TileIO<false, 128>;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = (wave & 1) * 64, wn = (wave >> 1) * 64;
+    const int tiles_n = (p.N + BN - 1) / BN;
+    const int vid = xcd_remap(blockIdx.x, gridDim.x);
+    const int m0 = (vid / tiles_n) * BM, n0 = (vid % tiles_n) * BN;
+    unsigned char* tA = smem;
+    unsigned char* tB = smem + TILE_BYTES;
+    const DirectLds<BM / 32> dl(p, m0, n0, tid);
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int nk = p.K / BK;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt > 0) __syncthreads();                          // everyone finished reading the previous K tile
+        dl.load(kt, tA, tB, wave);
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
-            bf16x8 fa[MT], fb[2];
+            bf16x8 fa[2], fb[2];
 #pragma unroll
-            for (int i = 0; i < MT; ++i) fa[i] = IO::frag(tA, wm + 32 * i, ks, lane);
+            for (int i = 0; i < 2; ++i) fa[i] = IO::frag(tA, wm + 32 * i, ks, lane);
 #pragma unroll
             for (int i = 0; i < 2; ++i) fb[i] = IO::frag(tB, wn + 32 * i, ks, lane);
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                for (int mi = 0; mi < MT; ++mi)
+                for (int mi = 0; mi < 2; ++mi)
                     acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
         }
     }
     __syncthreads();
-
-    const int h = lane >> 5;
-    float* stage = reinterpret_cast<float*>(smem) + wave * (32 * STAGE_LD);
 #pragma unroll
-    for (int mi = 0; mi < MT; ++mi) {
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(stage + (lane & 31) * STAGE_LD + 32 * ni + 8 * g + 4 * h) =
-                    make_float4(acc[ni][mi][4 * g], acc[ni][mi][4 * g + 1], acc[ni][mi][4 * g + 2], acc[ni][mi][4 * g + 3]);
-        __builtin_amdgcn_wave_barrier();
-        epilogue_rows<EPI>(p, stage, m0 + wm + 32 * mi, n0 + wn, lane);
-        __builtin_amdgcn_wave_barrier();
-    }
+    for (int mi = 0; mi < 2; ++mi) strip_epilogue<EPI>(p, acc, mi, smem, wave, lane, m0 + wm + 32 * mi, n0 + wn);
 }
 
-template <int EPI, int MT, int OCC>
-int launch_g4_mt(const GemmParams& p, hipStream_t stream) {
-    constexpr int TBM = 64 * MT;
-    constexpr int opnd = TBM * BK * 2 + TILE_BYTES;
-    constexpr int lds = opnd > STAGE_BYTES ? opnd : STAGE_BYTES;
-    const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + BN - 1) / BN);
-    return ppf_launch<gemm128g_kernel<EPI, MT, OCC>>(dim3(tiles), dim3(NTHREADS), lds, stream, "gemm128g", p);
+// 256x128 workgroup tiles (128x64 per wave: 25 % fewer LDS fragment bytes per MFMA) were measured SLOWER at three and at two
+// workgroups per CU (qkv 60.6 -> 83.6 / 69.0 us, fc1+GELU 132 -> 155 / 146 us, train step -5.4 % / -1.9 %; profiles/r2_gemm_knockout.txt):
+// what these K = 384 GEMMs want is more independent workgroups per CU, not fewer LDS bytes.
+template <int EPI>
+int launch_g4(const GemmParams& p, hipStream_t stream) {
+    constexpr int lds = 2 * TILE_BYTES > STAGE_BYTES ? 2 * TILE_BYTES : STAGE_BYTES;
+    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    return ppf_launch<gemm128g_kernel<EPI>>(dim3(tiles), dim3(NTHREADS), lds, stream, "gemm128g", p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -583,16 +553,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm224g_kernel(const GemmParams 
     const int m0 = (vid / tiles_n) * G224_ROWS, n0 = (vid % tiles_n) * BN;
     unsigned char* tA = smem;
     unsigned char* tB = smem + G224_ROWS * BK * 2;
-    unsigned offA[G224_MT], offB[4];
-    {
-        const int rb = tid >> 3, ch = (tid & 7) ^ lds_swz(rb);       // rows rb + 32 i share the swizzle
-#pragma unroll
-        for (int i = 0; i < G224_MT; ++i) offA[i] = ((unsigned)min(m0 + rb + 32 * i, p.M - 1) * (unsigned)p.lda + ch * 8) * 2u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) offB[i] = ((unsigned)min(n0 + rb + 32 * i, p.N - 1) * (unsigned)p.ldb + ch * 8) * 2u;
-    }
-    const unsigned char* gA = reinterpret_cast<const unsigned char*>(p.A);
-    const unsigned char* gB = reinterpret_cast<const unsigned char*>(p.B);
+    const DirectLds<G224_MT> dl(p, m0, n0, tid);
     f32x16 acc[G224_MT];
 #pragma unroll
     for (int j = 0; j < G224_MT; ++j)
@@ -601,16 +562,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm224g_kernel(const GemmParams 
     const int nk = p.K / BK;
     for (int kt = 0; kt < nk; ++kt) {
         if (kt > 0) __syncthreads();                          // everyone finished reading the previous K tile
-        const unsigned char* ka = gA + (size_t)kt * (BK * 2);
-        const unsigned char* kb = gB + (size_t)kt * (BK * 2);
-#pragma unroll
-        for (int i = 0; i < G224_MT; ++i)
-            __builtin_amdgcn_global_load_lds((g4_gbl_t*)(ka + offA[i]), (g4_lds_t*)(tA + i * 4096 + wave * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((g4_gbl_t*)(kb + offB[i]), (g4_lds_t*)(tB + i * 4096 + wave * 1024), 16, 0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        dl.load(kt, tA, tB, wave);
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
             const bf16x8 fb = IO::frag(tB, wn, ks, lane);
@@ -678,12 +630,6 @@ int launch_g224(const GemmParams& p, hipStream_t stream) {
     return ppf_launch<gemm224g_kernel>(dim3(tiles), dim3(NTHREADS), lds, stream, "gemm224g", p);
 }
 
-// MT = 4 (256x128 workgroup tiles, 128x64 per wave: 25 % fewer LDS fragment bytes per MFMA) was measured SLOWER at three and at two
-// workgroups per CU (qkv 60.6 -> 83.6 / 69.0 us, fc1+GELU 132 -> 155 / 146 us, train step -5.4 % / -1.9 %; profiles/r2_gemm_knockout.txt):
-// what these K = 384 GEMMs want is more independent workgroups per CU, not fewer LDS bytes.  Only MT = 2 is instantiated.
-template <int EPI>
-int launch_g4(const GemmParams& p, hipStream_t stream) { return launch_g4_mt<EPI, 2, 4>(p, stream); }
-
 bool g4_eligible(const GemmParams& p) {
     // measured (profiles/r1_gemm_ab.txt): -12 % at K = 384 with N >= 1152 (qkv 74 -> 65 us, fc1+GELU 151 -> 133), neutral at N = 384,
     // +5 % at K = 1536 where the register-prefetched kernel overlaps better inside a workgroup -> short contractions only
@@ -691,23 +637,15 @@ bool g4_eligible(const GemmParams& p) {
            (long long)p.N * p.ldb < (1ll << 30) && (long long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) >= 512;
 }
 
-template <bool TA, bool TB, int EPI, bool COLSUM, int MT>
-int launch_impl(const GemmParams& p, int splitk, hipStream_t stream, int nbatch) {
-    constexpr int TBM = 64 * MT;
-    const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + BN - 1) / BN);
-    constexpr int opnd = TBM * BK * 2 + TILE_BYTES;
-    constexpr int lds = opnd > STAGE_BYTES ? opnd : STAGE_BYTES;
-    GemmParams q = p;
-    q.nsplit = splitk;
-    return ppf_launch<gemm_kernel<TA, TB, EPI, COLSUM, MT>>(dim3(tiles * splitk, nbatch, 1), dim3(NTHREADS), lds, stream, "gemm", q);
-}
-
-// Tile choice: 256x128 when the m extent is tall enough to fill the chip with 256-row tiles (activation GEMMs), else 128x128.
-// (The 256x128 form of this kernel was 5-30 % slower at every shape of these models -- profiles/r1_gemm_tile_ab.txt, r4_wgrad_tiles.txt -- and
-// is no longer instantiated.)
+// 128x128 tiles at every shape.  (The 256x128 form of this kernel, for m extents tall enough to fill the chip with 256-row tiles, was
+// 5-30 % slower at every shape of these models -- profiles/r1_gemm_tile_ab.txt, r4_wgrad_tiles.txt -- and is no longer instantiated.)
 template <bool TA, bool TB, int EPI, bool COLSUM>
 int launch(const GemmParams& p, int splitk, hipStream_t stream, int nbatch = 1) {
-    return launch_impl<TA, TB, EPI, COLSUM, 2>(p, splitk, stream, nbatch);
+    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    constexpr int lds = 2 * TILE_BYTES > STAGE_BYTES ? 2 * TILE_BYTES : STAGE_BYTES;
+    GemmParams q = p;
+    q.nsplit = splitk;
+    return ppf_launch<gemm_kernel<TA, TB, EPI, COLSUM>>(dim3(tiles * splitk, nbatch, 1), dim3(NTHREADS), lds, stream, "gemm", q);
 }
 
 // out[i] += sum_z ws[z][i] for the M*N tile elements (row stride ldc) and, when colsum != null, the cs_parts * M partial column sums.
@@ -754,23 +692,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // Events come from a pool that is reused from one probe session to the next (nothing is created or destroyed per launch once
 // the pool has grown); when the step is captured with the probe on, the records become event-record nodes that every replay
 // re-records, so a read after the timed region returns the last replay's launch durations.
-struct Probe {
-    bool on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    size_t used = 0;
-    double flops = 0.0, bytes = 0.0;
-    std::pair<hipEvent_t, hipEvent_t> acquire() {
-        if (used == pool.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            // timing events that the host only reads after a device synchronise: no system-scope fence at each record
-            const unsigned fl = hipEventDisableSystemFence;
-            (void)hipEventCreateWithFlags(&a, fl); (void)hipEventCreateWithFlags(&b, fl);
-            pool.emplace_back(a, b);
-        }
-        return pool[used++];
-    }
-};
-Probe g_probe;
+PpfEventPool g_probe;
+bool g_probe_on = false;
 
 // The first PPF_GEMM_COUNTER_BYTES of a split-K workspace are reserved (they held the arrival counters of the in-kernel reduce of round
 // 3; the layout of the ABI is kept): the CALLER hands over a workspace used by ppf_gemm_bf16 calls of ONE stream only.
@@ -792,6 +715,13 @@ int pick_splitk(int M, int N, int K) {
     // slices are BK-aligned chunks: drop the ones that would be empty (a partial-tile slice must always be written)
     const int kchunk = (((K + s - 1) / s) + BK - 1) / BK * BK;
     return (K + kchunk - 1) / kchunk;
+}
+
+// Maps the runtime epilogue number to a compile-time constant: when epi is one of EPIS, rc = f(std::integral_constant<int, epi>()) and true;
+// false (f not called) for an epilogue the call site does not list -- the lists ARE the set of instantiated kernels.
+template <int... EPIS, class F>
+bool dispatch_epi(int epi, int& rc, F&& f) {
+    return ((epi == EPIS && (rc = f(std::integral_constant<int, EPIS>()), true)) || ...);
 }
 
 }  // namespace
@@ -834,72 +764,54 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
     if (epi == EPI_RESID) PPF_CHECK_ARG(res != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=4 needs a residual");
     if (epi == EPI_GELU) PPF_CHECK_ARG(aux_out != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=2 needs aux_out");
     if (epi == EPI_DGELU) PPF_CHECK_ARG(aux_in != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=5 needs aux_in");
+    int rc;
     if (!trans_a && !trans_b) {
         if (g224_eligible(p, epi)) return launch_g224(p, stream);
-        if (g4_eligible(p)) {
-            switch (epi) {
-                case EPI_BF16: return launch_g4<EPI_BF16>(p, stream);
-                case EPI_GELU: return launch_g4<EPI_GELU>(p, stream);
-                case EPI_RESID: return launch_g4<EPI_RESID>(p, stream);
-                case EPI_DGELU: return launch_g4<EPI_DGELU>(p, stream);
-                default: break;
-            }
-        }
-        switch (epi) {
-            case EPI_BF16: return launch<false, false, EPI_BF16, false>(p, 1, stream);
-            case EPI_F32: return launch<false, false, EPI_F32, false>(p, 1, stream);
-            case EPI_GELU: return launch<false, false, EPI_GELU, false>(p, 1, stream);
-            case EPI_SIGMOID_F32: return launch<false, false, EPI_SIGMOID_F32, false>(p, 1, stream);
-            case EPI_RESID: return launch<false, false, EPI_RESID, false>(p, 1, stream);
-            case EPI_DGELU: return launch<false, false, EPI_DGELU, false>(p, 1, stream);
-            default: break;
-        }
+        const auto g4 = [&](auto e) { return launch_g4<decltype(e)::value>(p, stream); };
+        const auto nt = [&](auto e) { return launch<false, false, decltype(e)::value, false>(p, 1, stream); };
+        if (g4_eligible(p) && dispatch_epi<EPI_BF16, EPI_GELU, EPI_RESID, EPI_DGELU>(epi, rc, g4)) return rc;
+        if (dispatch_epi<EPI_BF16, EPI_F32, EPI_GELU, EPI_SIGMOID_F32, EPI_RESID, EPI_DGELU>(epi, rc, nt)) return rc;
     } else if (!trans_a && trans_b) {
-        switch (epi) {
-            case EPI_BF16: return launch<false, true, EPI_BF16, false>(p, 1, stream);
-            case EPI_F32: return launch<false, true, EPI_F32, false>(p, 1, stream);
-            case EPI_DGELU: return launch<false, true, EPI_DGELU, false>(p, 1, stream);
-            default: break;
+        const auto nn = [&](auto e) { return launch<false, true, decltype(e)::value, false>(p, 1, stream); };
+        if (dispatch_epi<EPI_BF16, EPI_F32, EPI_DGELU>(epi, rc, nn)) return rc;
+    } else if (epi == EPI_ATOMIC) {
+        // split over the contraction: with a workspace the K slices leave fp32 partial tiles that splitk_reduce_kernel adds to C in
+        // slice order (the 28 MB of slabs are recycled by every weight gradient and stay in the L2 / memory-side cache:
+        // profiles/r4_reduce_batch.txt); without one: fp32 atomics.  (The 256x256 weight-gradient kernels of rounds 1-3 and the
+        // in-kernel last-arriver reduce were measured slower IN THE STEP once more in round 4 and deleted: profiles/r4_wgrad_tiles.txt.)
+        const int ns = pick_splitk(M, N, K);
+        const size_t need = PPF_GEMM_COUNTER_BYTES + (size_t)ns * ((size_t)M * N + M) * sizeof(float);
+        if (workspace == nullptr || workspace_bytes < need || ns == 1) return launch<true, true, EPI_ATOMIC, true>(p, ns, stream);
+        p.ws = (float*)((unsigned char*)workspace + PPF_GEMM_COUNTER_BYTES);
+        p.cs_parts = 1;
+        p.nsplit = ns;
+        hipEvent_t e1 = nullptr;
+        if (g_probe_on) {
+            const auto ev = g_probe.acquire();
+            (void)hipEventRecord(ev.first, stream);
+            e1 = ev.second;
         }
-    } else {
-        switch (epi) {
-            case EPI_ATOMIC: {
-                // split over the contraction: with a workspace the K slices leave fp32 partial tiles that splitk_reduce_kernel adds to C in
-                // slice order (the 28 MB of slabs are recycled by every weight gradient and stay in the L2 / memory-side cache:
-                // profiles/r4_reduce_batch.txt); without one: fp32 atomics.  (The 256x256 weight-gradient kernels of rounds 1-3 and the
-                // in-kernel last-arriver reduce were measured slower IN THE STEP once more in round 4 and deleted: profiles/r4_wgrad_tiles.txt.)
-                const int ns = pick_splitk(M, N, K);
-                const size_t need = PPF_GEMM_COUNTER_BYTES + (size_t)ns * ((size_t)M * N + M) * sizeof(float);
-                if (workspace == nullptr || workspace_bytes < need || ns == 1) return launch<true, true, EPI_ATOMIC, true>(p, ns, stream);
-                p.ws = (float*)((unsigned char*)workspace + PPF_GEMM_COUNTER_BYTES);
-                p.cs_parts = 1;
-                p.nsplit = ns;
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (g_probe.on) { auto ev = g_probe.acquire(); e0 = ev.first; e1 = ev.second; (void)hipEventRecord(e0, stream); }
-                // eight-wave tiles where one output side is long and the other at least 384: 256 x 128 (rows) or 128 x 256 (columns).
-                // Same-box: deit_small +0.1 .. +0.4 % in four A/Bs with 19.5 % fewer L2 requests from the weight gradients
-                // (profiles/r4_wgrad_l2_knockout.txt); the D = 192 models lose (deit_tiny -2.8 %, cait_xxs24 -0.8 %: a third of their
-                // 128-column tiles is padding).
-                const bool wide = (M < N ? M : N) >= 320;
-                int rc;
-                if (wide && M >= 512 && M >= N && (M % 256 == 0 || M >= 1024)) rc = launch_wgrad8<4, 2>(p, ns, stream);
-                else if (wide && N >= 512 && (N % 256 == 0 || N >= 1024)) rc = launch_wgrad8<2, 4>(p, ns, stream);
-                else rc = launch<true, true, EPI_PARTIAL, true>(p, ns, stream);
-                if (rc) return rc;
-                if (g_probe.on) {
-                    (void)hipEventRecord(e1, stream);
-                    g_probe.flops += 2.0 * M * N * (double)K;
-                    g_probe.bytes += 2.0 * ((double)M * K + (double)N * K) + 4.0 * M * N;
-                }
-                const size_t work = (size_t)M * N / 4 + (colsum ? M : 0);
-                const int grid = (int)((work + 255) / 256);
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, p.ws, (float*)C, colsum, M, N, ldc, ns, p.cs_parts);
-                PPF_LAUNCH_CHECK();
-                return 0;
-            }
-            case EPI_F32: return launch<true, true, EPI_F32, false>(p, 1, stream);
-            default: break;
+        // eight-wave tiles where one output side is long and the other at least 384: 256 x 128 (rows) or 128 x 256 (columns).
+        // Same-box: deit_small +0.1 .. +0.4 % in four A/Bs with 19.5 % fewer L2 requests from the weight gradients
+        // (profiles/r4_wgrad_l2_knockout.txt); the D = 192 models lose (deit_tiny -2.8 %, cait_xxs24 -0.8 %: a third of their
+        // 128-column tiles is padding).
+        const bool wide = (M < N ? M : N) >= 320;
+        if (wide && M >= 512 && M >= N && (M % 256 == 0 || M >= 1024)) rc = launch_wgrad8<4, 2>(p, ns, stream);
+        else if (wide && N >= 512 && (N % 256 == 0 || N >= 1024)) rc = launch_wgrad8<2, 4>(p, ns, stream);
+        else rc = launch<true, true, EPI_PARTIAL, true>(p, ns, stream);
+        if (rc) return rc;
+        if (e1) {
+            (void)hipEventRecord(e1, stream);
+            g_probe.flops += 2.0 * M * N * (double)K;
+            g_probe.bytes += 2.0 * ((double)M * K + (double)N * K) + 4.0 * M * N;
         }
+        const size_t work = (size_t)M * N / 4 + (colsum ? M : 0);
+        const int grid = (int)((work + 255) / 256);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, p.ws, (float*)C, colsum, M, N, ldc, ns, p.cs_parts);
+        PPF_LAUNCH_CHECK();
+        return 0;
+    } else if (epi == EPI_F32) {
+        return launch<true, true, EPI_F32, false>(p, 1, stream);
     }
     ppf_set_error("ppf_gemm_bf16: combination trans_a=%d trans_b=%d epi=%d not instantiated", trans_a, trans_b, epi);
     return PPF_ERR_ARG;
@@ -908,30 +820,14 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
 // Roofline probe of the weight-gradient kernel (epi 6 with a workspace).  enable = 1 clears the counters and starts recording
 // (pooled events are reused), 0 stops, 2 stops and destroys the event pool (only when no captured graph references it any more).
 int ppf_gemm_probe(int enable) {
-    if (enable == 1) { g_probe.used = 0; g_probe.flops = 0.0; g_probe.bytes = 0.0; }
-    if (enable == 2) {
-        for (auto& e : g_probe.pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        g_probe.pool.clear(); g_probe.used = 0;
-    }
-    g_probe.on = enable == 1;
+    if (enable == 1) g_probe.reset();
+    if (enable == 2) g_probe.destroy();
+    g_probe_on = enable == 1;
     return 0;
 }
 // Synchronises the recorded events: total kernel milliseconds, launches, algorithmic flops and bytes since ppf_gemm_probe(1).
 int ppf_gemm_probe_read(double* ms_total, int64_t* launches, double* flops, double* bytes) {
-    double ms = 0.0;
-    for (size_t i = 0; i < g_probe.used; ++i) {
-        auto& e = g_probe.pool[i];
-        float t = 0.f;
-        hipError_t rc = hipEventSynchronize(e.second);
-        if (rc == hipSuccess) rc = hipEventElapsedTime(&t, e.first, e.second);
-        if (rc != hipSuccess) { ppf_set_error("ppf_gemm_probe_read: %s", hipGetErrorString(rc)); return (int)rc; }
-        ms += t;
-    }
-    if (ms_total) *ms_total = ms;
-    if (launches) *launches = (int64_t)g_probe.used;
-    if (flops) *flops = g_probe.flops;
-    if (bytes) *bytes = g_probe.bytes;
-    return 0;
+    return g_probe.sum_ms("ppf_gemm_probe_read", ms_total, launches, flops, bytes);
 }
 
 // Batched plain GEMMs (no bias / fused epilogue): nbatch = batch_outer * batch_inner problems, problem (o, i) uses
@@ -957,16 +853,16 @@ int ppf_gemm_bf16_batched(const void* A, const void* B, void* C, int M, int N, i
     p.aux_out = nullptr; p.ldaux = 0; p.colsum = nullptr; p.ws = nullptr; p.alpha = alpha;
     p.batch_inner = batch_inner; p.sa_o = sa_o; p.sa_i = sa_i; p.sb_o = sb_o; p.sb_i = sb_i; p.sc_o = sc_o; p.sc_i = sc_i; p.kpad = kpad;
     const int nb = batch_outer * batch_inner;
-    const int key = (trans_a ? 4 : 0) | (trans_b ? 2 : 0) | (out_f32 ? 1 : 0);
-    switch (key) {
-        case 0: return launch<false, false, EPI_BF16, false>(p, 1, stream, nb);
-        case 1: return launch<false, false, EPI_F32, false>(p, 1, stream, nb);
-        case 2: return launch<false, true, EPI_BF16, false>(p, 1, stream, nb);
-        case 3: return launch<false, true, EPI_F32, false>(p, 1, stream, nb);
-        case 6: return launch<true, true, EPI_BF16, false>(p, 1, stream, nb);
-        case 7: return launch<true, true, EPI_F32, false>(p, 1, stream, nb);
-        default: break;
-    }
+    const auto go = [&](auto ta, auto tb) {
+        int rc = PPF_ERR_ARG;
+        dispatch_epi<EPI_BF16, EPI_F32>(out_f32 ? EPI_F32 : EPI_BF16, rc, [&](auto e) {
+            return launch<decltype(ta)::value, decltype(tb)::value, decltype(e)::value, false>(p, 1, stream, nb);
+        });
+        return rc;
+    };
+    if (!trans_a && !trans_b) return go(std::false_type(), std::false_type());
+    if (!trans_a && trans_b) return go(std::false_type(), std::true_type());
+    if (trans_a && trans_b) return go(std::true_type(), std::true_type());
     ppf_set_error("ppf_gemm_bf16_batched: (trans_a=1, trans_b=0) is not instantiated");
     return PPF_ERR_ARG;
 }

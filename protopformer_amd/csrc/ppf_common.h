@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifdef __cplusplus
+#include <utility>
+#include <vector>
+#endif
 
 typedef uint16_t bf16_t;                                              // raw bf16 storage
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -38,6 +42,18 @@ extern "C" void ppf_set_error(const char* fmt, ...);
 // the north star names, on the launch stream; off (two loads and a branch) unless ppf_path_probe(1) switched it on.
 enum { PPF_PROBE_ATTN_FWD = 0, PPF_PROBE_ATTN_BWD = 1, PPF_PROBE_PROTO_FWD = 2, PPF_PROBE_NTAGS = 3 };
 #ifdef __cplusplus
+// Pooled (start, stop) timing-event pairs with the flops / bytes of what they bracket (ppf_runtime.hip): the path probe's tags and the
+// weight-gradient probe of gemm_bf16.hip.  Pairs are reused from one probe session to the next: nothing is created per launch once the pool has grown.
+struct PpfEventPool {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    size_t used = 0;
+    double flops = 0.0, bytes = 0.0;
+    std::pair<hipEvent_t, hipEvent_t> acquire();                                // the next pair (created when the pool is used up); the caller adds to the totals
+    void reset();                                                               // starts a session: no pair in use, totals zero
+    void destroy();                                                             // destroys the events (no captured graph may reference them any more)
+    // synchronises the pairs in use: summed milliseconds, pairs in use and the totals since reset(); a HIP error is returned under the name `who`
+    int sum_ms(const char* who, double* ms_total, int64_t* launches, double* flops, double* bytes);
+};
 struct PpfProbeScope {
     hipEvent_t stop = nullptr;
     hipStream_t stream;

@@ -4,8 +4,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <utility>
-#include <vector>
 
 static thread_local char g_err[512] = "";
 
@@ -107,12 +105,7 @@ int ppf_stream_wait_mark(hipStream_t stream, int64_t ticket) {
 
 // ---- path probe: in-step HIP-event time of the kernels the north star names (attention forward / backward, prototype forward) ----
 namespace {
-struct PathProbe {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-    size_t used = 0;
-    double flops = 0.0, bytes = 0.0;
-};
-PathProbe g_path[PPF_PROBE_NTAGS];
+PpfEventPool g_path[PPF_PROBE_NTAGS];
 constexpr size_t PATH_PROBE_CAP = 4096;          // event pairs per tag (one step of the largest configuration launches < 64 per tag)
 bool g_path_on = false;
 }  // namespace
@@ -141,19 +134,43 @@ int ppf_cu_count() {
     return cus;
 }
 
+std::pair<hipEvent_t, hipEvent_t> PpfEventPool::acquire() {
+    if (used == pool.size()) {
+        hipEvent_t a = nullptr, b = nullptr;           // timing events the host reads after a device synchronise: agent scope only, no system fence at each record
+        (void)hipEventCreateWithFlags(&a, hipEventDisableSystemFence); (void)hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
+        pool.emplace_back(a, b);
+    }
+    return pool[used++];
+}
+void PpfEventPool::reset() { used = 0; flops = 0.0; bytes = 0.0; }
+void PpfEventPool::destroy() {
+    for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    pool.clear(); used = 0;
+}
+int PpfEventPool::sum_ms(const char* who, double* ms_total, int64_t* launches, double* fl, double* by) {
+    double ms = 0.0;
+    for (size_t i = 0; i < used; ++i) {
+        hipError_t rc = hipEventSynchronize(pool[i].second);
+        float t = 0.f;
+        if (rc == hipSuccess) rc = hipEventElapsedTime(&t, pool[i].first, pool[i].second);
+        if (rc != hipSuccess) { ppf_set_error("%s: %s", who, hipGetErrorString(rc)); return (int)rc; }
+        ms += t;
+    }
+    if (ms_total) *ms_total = ms;
+    if (launches) *launches = (int64_t)used;
+    if (fl) *fl = flops;
+    if (by) *by = bytes;
+    return 0;
+}
+
 PpfProbeScope::PpfProbeScope(int tag, hipStream_t s, double flops, double bytes) : stream(s) {
     if (!g_path_on || tag < 0 || tag >= PPF_PROBE_NTAGS) return;
     // eager launches only: an event recorded into a capturing stream becomes a graph node that hipEventElapsedTime cannot read
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return;
-    PathProbe& pr = g_path[tag];
+    PpfEventPool& pr = g_path[tag];
     if (pr.used >= PATH_PROBE_CAP) return;             // a probe left on for a long run stops counting instead of growing without bound
-    if (pr.used == pr.pool.size()) {
-        hipEvent_t a = nullptr, b = nullptr;           // timing events the host reads after a device synchronise: agent scope only
-        (void)hipEventCreateWithFlags(&a, hipEventDisableSystemFence); (void)hipEventCreateWithFlags(&b, hipEventDisableSystemFence);
-        pr.pool.emplace_back(a, b);
-    }
-    auto& ev = pr.pool[pr.used++];
+    const auto ev = pr.acquire();
     pr.flops += flops; pr.bytes += bytes;
     (void)hipEventRecord(ev.first, stream);
     stop = ev.second;
@@ -165,11 +182,8 @@ extern "C" {
 // enable = 1 clears the counters and starts recording, 0 stops, 2 stops and destroys the event pools.
 int ppf_path_probe(int enable) {
     for (auto& pr : g_path) {
-        if (enable == 1) { pr.used = 0; pr.flops = 0.0; pr.bytes = 0.0; }
-        if (enable == 2) {
-            for (auto& e : pr.pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-            pr.pool.clear(); pr.used = 0;
-        }
+        if (enable == 1) pr.reset();
+        if (enable == 2) pr.destroy();
     }
     g_path_on = enable == 1;
     return 0;
@@ -178,20 +192,7 @@ int ppf_path_probe(int enable) {
 // Synchronises tag's events: summed kernel milliseconds, launches, algorithmic flops and bytes since ppf_path_probe(1).
 int ppf_path_probe_read(int tag, double* ms_total, int64_t* launches, double* flops, double* bytes) {
     PPF_CHECK_ARG(tag >= 0 && tag < PPF_PROBE_NTAGS, PPF_ERR_ARG, "ppf_path_probe_read: tag %d", tag);
-    PathProbe& pr = g_path[tag];
-    double ms = 0.0;
-    for (size_t i = 0; i < pr.used; ++i) {
-        hipError_t rc = hipEventSynchronize(pr.pool[i].second);
-        float t = 0.f;
-        if (rc == hipSuccess) rc = hipEventElapsedTime(&t, pr.pool[i].first, pr.pool[i].second);
-        if (rc != hipSuccess) { ppf_set_error("ppf_path_probe_read: %s", hipGetErrorString(rc)); return (int)rc; }
-        ms += t;
-    }
-    if (ms_total) *ms_total = ms;
-    if (launches) *launches = (int64_t)pr.used;
-    if (flops) *flops = pr.flops;
-    if (bytes) *bytes = pr.bytes;
-    return 0;
+    return g_path[tag].sum_ms("ppf_path_probe_read", ms_total, launches, flops, bytes);
 }
 
 }  // extern "C"

@@ -13,38 +13,25 @@ DOMINANT_NAME = ("weight-gradient bf16 MFMA GEMM, split over the contraction, or
                  "and gemm_kernel<TA=1,TB=1,EPI_PARTIAL,COLSUM> (128x128)")
 
 
-_WORKSPACE = {}
-
-
-def _workspace(device, nbytes):
-    """Reusable split-K scratch, grown on demand: one per (device, stream) -- the weight-gradient lane (backbone.WgradLane)
-    runs its GEMMs on a second stream, concurrently with main-stream kernels that also use a workspace."""
-    key = (device, _lib.stream_ptr())
-    buf = _WORKSPACE.get(key)
-    if buf is None or buf.numel() < nbytes:
-        if buf is not None:
-            _RETIRED_WS.append(buf)           # a side stream may still be using it (see _gemm_workspace)
-        buf = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
-        _WORKSPACE[key] = buf
-    return buf
-
-
-_GEMM_WS = {}
+_WORKSPACE = {}        # general scratch, by (device, stream)
+_GEMM_WS = {}          # split-K scratch of the weight-gradient GEMMs, by (device, stream)
 _RETIRED_WS = []
 
 
-def _gemm_workspace(device, nbytes):
-    """Split-K scratch of the weight-gradient GEMMs, one per (device, stream), used by nothing else: every weight gradient writes its
-    partial tiles into the same 28 MB and the ordered reduce reads them straight back (they stay in the L2 / memory-side cache;
-    giving every GEMM its own range and summing later was measured slower: profiles/r4_reduce_batch.txt)."""
+def _workspace(device, nbytes, pool=_WORKSPACE):
+    """Reusable scratch from `pool`, grown on demand: one buffer per (device, stream) -- the weight-gradient lane (backbone.WgradLane)
+    runs its GEMMs on a second stream, concurrently with main-stream kernels that also use a workspace.
+    pool=_GEMM_WS is used by the weight-gradient GEMMs and nothing else: every weight gradient writes its partial tiles into the same
+    28 MB and the ordered reduce reads them straight back (they stay in the L2 / memory-side cache; giving every GEMM its own range
+    and summing later was measured slower: profiles/r4_reduce_batch.txt)."""
     key = (device, _lib.stream_ptr())
-    buf = _GEMM_WS.get(key)
+    buf = pool.get(key)
     if buf is None or buf.numel() < nbytes:
-        # a buffer that is outgrown stays allocated: the lane may still be using it and torch's allocator knows nothing of that stream
+        # a buffer that is outgrown stays allocated: a side stream may still be using it and torch's allocator knows nothing of that stream
         if buf is not None:
             _RETIRED_WS.append(buf)
         buf = torch.empty(max(nbytes, 64 << 20), dtype=torch.uint8, device=device)
-        _GEMM_WS[key] = buf
+        pool[key] = buf
     return buf
 
 
@@ -80,7 +67,7 @@ def gemm(a, b, *, trans_a=False, trans_b=False, epi=EPI_BF16, out=None, bias=Non
             ldaux = t.shape[-1]
     ws = None
     if epi == EPI_ATOMIC and workspace:
-        ws = _gemm_workspace(a.device, _lib.lib().ppf_gemm_workspace_bytes(M, N, K))
+        ws = _workspace(a.device, _lib.lib().ppf_gemm_workspace_bytes(M, N, K), _GEMM_WS)
     _lib.call("ppf_gemm_bf16", a, b, out, M, N, K, lda, ldb, out.shape[-1], int(trans_a), int(trans_b), epi,
               bias, res, res.shape[-1] if res is not None else 0, rowscale, rows_per_group, colscale, aux_in, aux_out, ldaux,
               colsum, float(alpha), ws, ws.numel() if ws is not None else 0)
