@@ -355,6 +355,26 @@ int ppf_act_part_table(const int* peak_yx, int M, int S, const int* parts, int m
                        ppf_stream_t stream);
 int ppf_act_order_stats(const float* grids, int M, int g, int S, int k_lo, int k_hi, float* stats, ppf_stream_t stream);
 int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int* box, ppf_stream_t stream);
+/* Stability score (Huang et al., ICCV 2023: does a prototype point at the same parts when the input is perturbed?) next to the
+ * consistency score, both accumulated on the device.  Additions of ABI 10: no existing entry point changed.
+ *   ppf_add_gauss_noise    out[b][e] = fmaf(sigma, n(seed, image_id[b], e), x[b][e]) on fp32 [B][n_per_img]; out may be x.  n is a standard
+ *                          normal from Philox4x32-10 with key = seed and counter = (e/4 low, e/4 high, image id low, image id high): one
+ *                          call yields the normals of elements 4q .. 4q+3 by two Box-Muller pairs, u0 = ((r.x >> 8) + 0.5) / 2^24,
+ *                          u1 = (r.y >> 8) / 2^24, n0 = sqrt(-2 ln u0) cos(2 pi u1), n1 = sqrt(-2 ln u0) sin(2 pi u1), n2 / n3 likewise from
+ *                          (r.z, r.w); accurate logf / sincospif.  The noise of an image depends on (seed, image id, element) only, not
+ *                          on the batch size, the position in the batch or the number of calls.  image_id_i64 [B] int64.  16-byte loads and
+ *                          stores when n_per_img % 4 == 0 and both pointers are 16-byte aligned, scalar otherwise.  B >= 1,
+ *                          1 <= n_per_img <= 2^31, sigma finite and >= 0 (else PPF_ERR_SHAPE).
+ *   ppf_part_meter_update  adds a batch into int32 accumulators hits [C][ppc][n_parts], visible [C][n_parts], stable [C][ppc], images [C],
+ *                          bad [1]: for image b of class c = label[b]: images[c] += 1, visible[c][q] += (parts[b][q].valid != 0),
+ *                          hits[c][p][q] += table[b][p][q], and with table_noisy_u8 != NULL stable[c][p] += 1 when rows p of the two tables
+ *                          agree in all n_parts entries.  table_u8 / table_noisy_u8 [B][ppc][n_parts] uint8 as ppf_act_peak writes them,
+ *                          parts [B][n_parts][3] int32 (valid, x, y).  A label outside [0, C) adds one to bad[0] and nothing else.
+ *                          Integer atomics only: any split of the same images into batches, in any order, gives the same accumulators. */
+int ppf_add_gauss_noise(const float* x, float* out, int B, int64_t n_per_img, const void* image_id_i64, float sigma, uint64_t seed,
+                        ppf_stream_t stream);
+int ppf_part_meter_update(const void* table_u8, const void* table_noisy_u8, const int* parts, const void* label_i64, int B, int ppc, int n_parts,
+                          int C, int* hits, int* visible, int* stable, int* images, int* bad, ppf_stream_t stream);
 
 /* ---- streaming kernels -------------------------------------------------------------------------------------------- */
 int ppf_cast_f32_bf16(const float* in, void* out, int64_t n, ppf_stream_t stream);

@@ -223,17 +223,8 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restric
 }
 
 // ---- DropPath factors floor(keep + U) / keep (timm DropPath, deit:71,79-80) for every (slot, sample) of a step.
-// U comes from Philox4x32-10 keyed by `seed`, counter = (state[0] = step number, element index): one single-workgroup launch
+// U comes from Philox4x32-10 (ppf_common.h) keyed by `seed`, counter = (state[0] = step number, element index): one single-workgroup launch
 // per step that also advances the step number in device memory, so a captured graph replays fresh draws.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
-        c = make_uint4((uint32_t)(p1 >> 32) ^ c.y ^ k.x, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k.y, (uint32_t)p0);
-        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-    }
-    return c;
-}
 __global__ __launch_bounds__(256) void droppath_kernel(float* __restrict__ out, const float* __restrict__ keep, int nslot, int B,
                                                        uint64_t seed, unsigned long long* __restrict__ state) {
     const unsigned long long step = state[0];

@@ -19,6 +19,9 @@
 //     act_box_kernel reduces the row / column extent of up >= thr; act_order_stats_kernel selects order statistics of the S*S fp32
 //     values exactly -- the 4-pass 8-bit radix select over order-preserving keys of rollout.hip, the map recomputed in every pass
 //     instead of being held (S*S values do not fit the registers), integer LDS atomics only.
+//   * The stability score's two kernels live here too: gauss_noise_kernel adds N(0, sigma^2) noise that is a function of (seed, image id,
+//     element) alone (Philox4x32-10 + Box-Muller, accurate logf / sincospif), and part_meter_kernel adds a batch's part tables, and the
+//     row equality of a clean and a noisy table, into per-class int32 accumulators (interpret.PartMeter).
 // Everything is deterministic: no floating-point atomics, fixed summation order.  A NaN never wins a comparison (a map of NaNs reports
 // the peak (0, 0) with value -inf).
 #include <limits.h>
@@ -368,6 +371,98 @@ __global__ __launch_bounds__(NT) void act_order_stats_kernel(const float* __rest
     }
 }
 
+// ---- stability score: Gaussian input noise per image, and the per-class accumulators of both scores
+// Four standard normals of elements 4q .. 4q+3 of image `id`: one Philox4x32-10 call, counter (q, image id), key = seed, two Box-Muller
+// pairs.  Uniforms on the 24-bit grid as the input finisher builds them (u0, u2 in (0, 1): the logarithm is finite; u1, u3 in [0, 1)).
+// logf / sincospif are the accurate library functions: 2 * u is exact in fp32, so the argument of sincospif carries no rounding error.
+// PPF_NOISE_KO: measurement builds only (scripts/bench_stability.py --knockouts; the noise they make is wrong on purpose): 1 = a counter hash
+// in place of Philox, 2 = the fast logarithm, 3 = the fast sine / cosine.
+#ifndef PPF_NOISE_KO
+#define PPF_NOISE_KO 0
+#endif
+__device__ __forceinline__ void gauss4(uint64_t seed, uint64_t id, uint64_t q, float (&n)[4]) {
+#if PPF_NOISE_KO == 1
+    const uint32_t h = ((uint32_t)q * 0x9E3779B9u) ^ (uint32_t)id ^ (uint32_t)seed;
+    const uint4 r = make_uint4(h, h * 0x85EBCA6Bu, h ^ 0xC2B2AE35u, h * 0x27D4EB2Fu);
+#else
+    const uint4 r = philox4x32_10(make_uint4((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)id, (uint32_t)(id >> 32)),
+                                  make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+#endif
+    const float u0 = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
+    const float u2 = ((float)(r.z >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = (float)(r.w >> 8) * (1.0f / 16777216.0f);
+#if PPF_NOISE_KO == 2
+    const float m0 = sqrtf(-2.0f * __logf(u0)), m1 = sqrtf(-2.0f * __logf(u2));
+#else
+    const float m0 = sqrtf(-2.0f * logf(u0)), m1 = sqrtf(-2.0f * logf(u2));
+#endif
+    float s0, c0, s1, c1;
+#if PPF_NOISE_KO == 3
+    s0 = __sinf(6.283185307f * u1); c0 = __cosf(6.283185307f * u1); s1 = __sinf(6.283185307f * u3); c1 = __cosf(6.283185307f * u3);
+#else
+    sincospif(2.0f * u1, &s0, &c0);
+    sincospif(2.0f * u3, &s1, &c1);
+#endif
+    n[0] = m0 * c0; n[1] = m0 * s0; n[2] = m1 * c1; n[3] = m1 * s1;
+}
+
+// out[b][e] = fmaf(sigma, n(seed, id[b], e), x[b][e]); a lane owns one group of four elements of one image per iteration.  x and out may
+// be the same buffer (no __restrict__): a lane reads its group before it writes it and no other lane touches it.  blockIdx.y strides over
+// the images and blockIdx.x over an image's groups, so no index is divided.
+// VEC: n_per_img % 4 == 0 and both pointers 16-byte aligned, every group is one 16-byte load and one 16-byte store (a template
+// parameter for the reason given at act_upsample_kernel).
+template <bool VEC>
+__global__ __launch_bounds__(NT) void gauss_noise_kernel(const float* x, float* out, const long long* __restrict__ image_id, int B, int groups_per_img,
+                                                         long long n_per_img, float sigma, uint64_t seed) {
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const uint64_t id = (uint64_t)image_id[b];
+        const float* xb = x + (long long)b * n_per_img;
+        float* ob = out + (long long)b * n_per_img;
+        for (int q = blockIdx.x * NT + threadIdx.x; q < groups_per_img; q += gridDim.x * NT) {      // groups_per_img <= 2^29, the stride <= 2^19
+            float n[4];
+            gauss4(seed, id, (uint64_t)q, n);
+            const long long e0 = 4ll * q;
+            if (VEC) {
+                const float4 v = *reinterpret_cast<const float4*>(xb + e0);
+                *reinterpret_cast<float4*>(ob + e0) = make_float4(fmaf(sigma, n[0], v.x), fmaf(sigma, n[1], v.y), fmaf(sigma, n[2], v.z), fmaf(sigma, n[3], v.w));
+            } else {
+                const int cnt = (int)min(4ll, n_per_img - e0);             // the surplus draws of an image's last group are dropped
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < cnt) ob[e0 + j] = fmaf(sigma, n[j], xb[e0 + j]);
+            }
+        }
+    }
+}
+
+// One workgroup per image: the image's tables into the accumulators of its class.  Integer atomics only, zeros are not added: any split
+// of the same images into batches, in any order, leaves the same integers.
+__global__ __launch_bounds__(NT) void part_meter_kernel(const unsigned char* __restrict__ table, const unsigned char* __restrict__ noisy,
+                                                        const int* __restrict__ parts, const long long* __restrict__ label, int ppc, int n_parts, int C,
+                                                        int* __restrict__ hits, int* __restrict__ visible, int* __restrict__ stable,
+                                                        int* __restrict__ images, int* __restrict__ bad) {
+    const int b = blockIdx.x;
+    const long long c = label[b];
+    if (c < 0 || c >= C) {                                            // uniform
+        if (threadIdx.x == 0) atomicAdd(bad, 1);
+        return;
+    }
+    if (threadIdx.x == 0) atomicAdd(images + c, 1);
+    const int* pl = parts + (size_t)b * n_parts * 3;
+    for (int q = threadIdx.x; q < n_parts; q += NT)
+        if (pl[3 * q] != 0) atomicAdd(visible + c * n_parts + q, 1);
+    const int per = ppc * n_parts;
+    const unsigned char* t = table + (size_t)b * per;
+    for (int e = threadIdx.x; e < per; e += NT)
+        if (t[e] != 0) atomicAdd(hits + c * per + e, (int)t[e]);
+    if (noisy == nullptr) return;                                     // uniform
+    const unsigned char* tn = noisy + (size_t)b * per;
+    for (int p = threadIdx.x; p < ppc; p += NT) {
+        bool same = true;
+        for (int q = 0; q < n_parts; ++q) same = same && t[p * n_parts + q] == tn[p * n_parts + q];
+        if (same) atomicAdd(stable + c * ppc + p, 1);
+    }
+}
+
 int act_check(const char* fn, const void* grids, int M, int g, int S) {
     PPF_CHECK_ARG(M >= 1 && g >= 1 && g <= MAX_G && S >= 1 && S <= MAX_S, PPF_ERR_SHAPE,
                   "%s: bad shape M=%d g=%d S=%d (M >= 1, 1 <= g <= %d, 1 <= S <= %d)", fn, M, g, S, MAX_G, MAX_S);
@@ -447,6 +542,33 @@ int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int*
     hipLaunchKernelGGL(act_box_kernel, dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, grids, thr, g, S, (double)g / (double)S, box);
     PPF_LAUNCH_CHECK();
     return 0;
+}
+
+int ppf_add_gauss_noise(const float* x, float* out, int B, int64_t n_per_img, const void* image_id_i64, float sigma, uint64_t seed, hipStream_t stream) {
+    PPF_CHECK_ARG(B >= 1 && n_per_img >= 1 && n_per_img <= (1ll << 31), PPF_ERR_SHAPE,
+                  "ppf_add_gauss_noise: bad shape B=%d n_per_img=%lld (B >= 1, 1 <= n_per_img <= 2^31)", B, (long long)n_per_img);
+    PPF_CHECK_ARG(isfinite(sigma) && sigma >= 0.0f, PPF_ERR_SHAPE, "ppf_add_gauss_noise: sigma=%g must be finite and >= 0", (double)sigma);
+    PPF_CHECK_ARG(x != nullptr && out != nullptr && image_id_i64 != nullptr, PPF_ERR_ARG, "ppf_add_gauss_noise: null pointer");
+    // at most 2048 workgroups, as the element-wise kernels: y over the images, x over an image's groups of four
+    const int gpi = (int)((n_per_img + 3) / 4), gy = B < 2048 ? B : 2048, per_img = (gpi + NT - 1) / NT, gx = per_img < 2048 / gy ? per_img : 2048 / gy;
+    const dim3 grid((unsigned)(gx < 1 ? 1 : gx), (unsigned)gy);
+    if (n_per_img % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0)
+        return ppf_launch<gauss_noise_kernel<true>>(grid, dim3(NT), 0, stream, "ppf_add_gauss_noise", x, out, (const long long*)image_id_i64, B, gpi,
+                                                    (long long)n_per_img, sigma, seed);
+    return ppf_launch<gauss_noise_kernel<false>>(grid, dim3(NT), 0, stream, "ppf_add_gauss_noise", x, out, (const long long*)image_id_i64, B, gpi,
+                                                 (long long)n_per_img, sigma, seed);
+}
+
+int ppf_part_meter_update(const void* table_u8, const void* table_noisy_u8, const int* parts, const void* label_i64, int B, int ppc, int n_parts, int C,
+                          int* hits, int* visible, int* stable, int* images, int* bad, hipStream_t stream) {
+    PPF_CHECK_ARG(B >= 1 && ppc >= 1 && n_parts >= 1 && n_parts <= 65536 && C >= 1 && (long long)C * ppc * n_parts <= INT_MAX, PPF_ERR_SHAPE,
+                  "ppf_part_meter_update: bad shape B=%d ppc=%d n_parts=%d C=%d (all >= 1, n_parts <= 65536, C * ppc * n_parts < 2^31)", B, ppc, n_parts, C);
+    PPF_CHECK_ARG(table_u8 != nullptr && parts != nullptr && label_i64 != nullptr && hits != nullptr && visible != nullptr && stable != nullptr &&
+                      images != nullptr && bad != nullptr,
+                  PPF_ERR_ARG, "ppf_part_meter_update: null pointer (only table_noisy_u8 may be NULL)");
+    return ppf_launch<part_meter_kernel>(dim3((unsigned)B), dim3(NT), 0, stream, "ppf_part_meter_update", (const unsigned char*)table_u8,
+                                         (const unsigned char*)table_noisy_u8, parts, (const long long*)label_i64, ppc, n_parts, C, hits, visible, stable,
+                                         images, bad);
 }
 
 }  // extern "C"

@@ -188,6 +188,18 @@ hipEvent_t ppf_take_stop_event(hipStream_t s);          // csrc/ppf_runtime.hip;
 #include "ppf_launch.h"
 #endif
 
+// Philox4x32-10 (Salmon et al., SC'11): counter c, key k -> four 32-bit words.  The one generator of the library: DropPath factors and
+// the erase noise of the input finisher (elementwise.hip), the input noise of the stability score (interp.hip).
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x, p1 = (uint64_t)0xCD9E8D57u * c.z;
+        c = make_uint4((uint32_t)(p1 >> 32) ^ c.y ^ k.x, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k.y, (uint32_t)p0);
+        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
 // Bijective XCD-aware remap of a 1-D block id: consecutive virtual ids land on the same XCD (private L2).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;

@@ -369,11 +369,10 @@ def _grid_on_device(attn, acts, k):
     return (expand_to_grid(acts, attn, k) if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts).contiguous()
 
 
-def _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
-    """Part tables of a batch: grid (B, ppc, g, g) CUDA -> (tables (B, ppc, n_parts) uint8 CUDA, masks (B, n_parts) numpy).  The part
-    list goes up as (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image pixels as consistency_from_outputs scales them."""
-    from . import ops
-    B, ppc = grid.shape[:2]
+def _part_list(ids, parts, image_sizes, img_size, n_parts):
+    """The part annotations of a batch as the kernels take them: (plist (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image
+    pixels as consistency_from_outputs scales them; masks (B, n_parts) of annotated parts).  Host arrays, built once per batch."""
+    B = len(ids)
     plist, masks = np.zeros((B, n_parts, 3), dtype=np.int32), np.zeros((B, n_parts))
     for j in range(B):
         w, h = image_sizes[int(ids[j])]
@@ -382,10 +381,24 @@ def _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
                 raise ValueError(f"image {int(ids[j])} lists part {pid} twice: the device path takes one location per part")
             masks[j, pid - 1] = 1
             plist[j, pid - 1] = (1, int(img_size * (x / w)), int(img_size * (y / h)))
+    return plist, masks
+
+
+def _tables_for_parts(grid, plist_dev, img_size, half_size):
+    """grid (B, ppc, g, g) CUDA and the uploaded part list (B, n_parts, 3) -> tables (B, ppc, n_parts) uint8 CUDA: one ppf_act_peak launch."""
+    from . import ops
+    B, ppc = grid.shape[:2]
     if B == 0:
-        return torch.zeros((0, ppc, n_parts), dtype=torch.uint8, device=grid.device), masks
-    _, _, table = ops.act_peak(grid.reshape(B * ppc, grid.shape[-2], grid.shape[-1]), img_size, torch.from_numpy(plist).to(grid.device), half_size)
-    return table.reshape(B, ppc, n_parts), masks
+        return torch.zeros((0, ppc, plist_dev.shape[1]), dtype=torch.uint8, device=grid.device)
+    _, _, table = ops.act_peak(grid.reshape(B * ppc, grid.shape[-2], grid.shape[-1]), img_size, plist_dev, half_size)
+    return table.reshape(B, ppc, plist_dev.shape[1])
+
+
+def _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
+    """Part tables of a batch: grid (B, ppc, g, g) CUDA -> (tables (B, ppc, n_parts) uint8 CUDA, masks (B, n_parts) numpy).  The part
+    list goes up as (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image pixels as consistency_from_outputs scales them."""
+    plist, masks = _part_list(ids, parts, image_sizes, img_size, n_parts)
+    return _tables_for_parts(grid, torch.from_numpy(plist).to(grid.device), img_size, half_size), masks
 
 
 def _score_from_tables(tables, masks, targets, num_classes, part_thresh):
@@ -399,6 +412,192 @@ def _score_from_tables(tables, masks, targets, num_classes, part_thresh):
         e, m = consistency_from_tables(tables[sel].astype(np.float64), masks[sel], part_thresh)
         effects.extend(e); max_parts.extend(m)
     return (float(np.mean(effects)) if effects else 0.0), effects, max_parts
+
+
+# ------------------------------------------------------------------------------------------------ stability score
+# Huang et al., ICCV 2023 ("Evaluation and Improvement of Interpretability for Self-Explainable Part-Prototype Networks") report the
+# consistency score next to a stability score: prototype j of class c is stable on a test image x of class c when its row of the part
+# table is the same for x and for x + N(0, sigma^2) noise on the normalised input; stable_j is the fraction of the class's images where
+# it is, the score the mean of stable_j over the (class, prototype) pairs of the classes that have an image.  The reference has no
+# such pass.
+def add_input_noise(x, image_ids, std=0.2, seed=0):
+    """Noisy copy of an fp32 CUDA batch [B, ...]: x + std * N(0, 1) (ppf_add_gauss_noise).  The noise of an image depends on (seed, its
+    id, element) only, so a data set gets the same perturbation at every batch size and in every order."""
+    from . import ops
+    ids = torch.as_tensor(image_ids).to(device=x.device, dtype=torch.int64).contiguous()
+    return ops.add_gauss_noise(x, ids, std, seed)
+
+
+def part_meter_scores(hits, visible, stable, images, part_thresh=0.8, with_stability=True):
+    """The scores from per-class counts (numpy integers): hits (C, ppc, n_parts) = images where the part lies in the prototype's box,
+    visible (C, n_parts) = images where the part is annotated, stable (C, ppc) = images where the prototype's row survived the noise,
+    images (C,).  consistency / effects / max_parts as consistency_from_tables computes them (fp64 hits / max(visible, 1),
+    >= part_thresh), classes without an image skipped, in class order; stable_fraction = stable / images per (class, prototype) and
+    stability its mean (both None without with_stability)."""
+    hits, visible, stable, images = (np.asarray(a) for a in (hits, visible, stable, images))
+    effects, max_parts, fraction = [], [], []
+    for c in np.nonzero(images > 0)[0]:
+        denom = visible[c].astype(np.float64)
+        denom = np.where(denom == 0, 1, denom)
+        for p in range(hits.shape[1]):
+            frac = hits[c, p].astype(np.float64) / denom
+            effects.append(int((frac >= part_thresh).any()))
+            max_parts.append(float(frac.max()))
+            fraction.append(float(stable[c, p] / images[c]))
+    out = dict(consistency=float(np.mean(effects)) if effects else 0.0, effects=effects, max_parts=max_parts, stability=None, stable_fraction=None,
+               images=[int(v) for v in images])
+    if with_stability:
+        out.update(stability=float(np.mean(fraction)) if fraction else 0.0, stable_fraction=fraction)
+    return out
+
+
+class PartMeter:
+    """Per-class accumulators of the consistency and the stability score in device memory (ppf_part_meter_update): update() only
+    launches, result() is the one read-back.  Integer counts: the result does not depend on how the images were batched or ordered.
+    `device` may be 'cpu' to hold counts made elsewhere (result() works there, update() needs the GPU)."""
+
+    def __init__(self, num_classes, ppc, n_parts, device):
+        C, self.ppc, self.n_parts = int(num_classes), int(ppc), int(n_parts)
+        self.sizes = (C * self.ppc * self.n_parts, C * self.n_parts, C * self.ppc, C, 1)
+        self.buf = torch.zeros(sum(self.sizes), dtype=torch.int32, device=device)          # one buffer: one read-back
+        hits, visible, stable, images, self.bad = torch.split(self.buf, self.sizes)
+        self.hits, self.visible, self.stable, self.images = hits.view(C, self.ppc, self.n_parts), visible.view(C, self.n_parts), stable.view(C, self.ppc), images
+        self.noisy = None                  # whether the updates carry a noisy table; None before the first one
+
+    def reset(self):
+        self.buf.zero_()
+        self.noisy = None
+
+    def update(self, tables, parts_dev, labels, tables_noisy=None):
+        """tables / tables_noisy (B, ppc, n_parts) uint8 as ppf_act_peak writes them, parts_dev (B, n_parts, 3) int32, labels (B,) int64,
+        all on the meter's device.  Either every update carries a noisy table or none does."""
+        from . import ops
+        if self.noisy is not None and self.noisy != (tables_noisy is not None):
+            raise ValueError("PartMeter.update: a noisy table must come with every update or with none (stable and images would not match)")
+        ops.part_meter_update(tables, tables_noisy, parts_dev, labels, self.hits, self.visible, self.stable, self.images, self.bad)
+        self.noisy = tables_noisy is not None
+
+    def result(self, part_thresh=0.8):
+        """dict(consistency, effects, max_parts, stability, stable_fraction, images) of part_meter_scores; stability is None if no noisy
+        table was ever passed.  Raises if a label lay outside [0, num_classes)."""
+        host = self.buf.cpu().numpy()
+        hits, visible, stable, images, bad = np.split(host, np.cumsum(self.sizes)[:-1])
+        C = self.sizes[3]
+        if int(bad[0]) != 0:
+            raise ValueError(f"PartMeter: {int(bad[0])} labels lie outside [0, {C}) (of {int(images.sum()) + int(bad[0])} images)")
+        return part_meter_scores(hits.reshape(C, self.ppc, self.n_parts), visible.reshape(C, self.n_parts), stable.reshape(C, self.ppc), images,
+                                 part_thresh, bool(self.noisy))
+
+
+def _host_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
+    """prototype_part_table of every image of a host grid (B, P, g, g): (tables (B, P, n_parts) of 0 / 1, masks (B, n_parts)), the part
+    locations scaled as consistency_from_outputs scales them."""
+    B = grid.shape[0]
+    tables, masks = np.zeros((B, grid.shape[1], n_parts)), np.zeros((B, n_parts))
+    for j in range(B):
+        w, h = image_sizes[int(ids[j])]
+        labels = []
+        for pid, x, y in parts.id_to_part_loc.get(int(ids[j]), []):
+            masks[j, pid - 1] = 1
+            labels.append((pid - 1, int(img_size * (x / w)), int(img_size * (y / h))))
+        tables[j] = prototype_part_table(grid[j], labels, img_size, half_size, n_parts)
+    return tables, masks
+
+
+def _host_grid(attn, acts, k):
+    attn, acts = torch.as_tensor(attn).cpu(), torch.as_tensor(acts).cpu()
+    return expand_to_grid(acts.float(), attn.float(), k).numpy() if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts.float().numpy()
+
+
+def stability_from_tables(tables, tables_noisy, targets, num_classes):
+    """(score, stable fraction per (class, prototype)) from per-image part tables (B, ppc, n_parts) of the clean and the noisy pass:
+    rows compared over all parts, averaged over the images of a class; classes without an image are skipped, in class order."""
+    same = (np.asarray(tables) == np.asarray(tables_noisy)).all(axis=2)                      # (B, ppc)
+    fraction = []
+    for c in range(num_classes):
+        sel = np.nonzero(np.asarray(targets) == c)[0]
+        if sel.size == 0:
+            continue
+        fraction.extend(float(n / sel.size) for n in same[sel].sum(axis=0))
+    return (float(np.mean(fraction)) if fraction else 0.0), fraction
+
+
+def stability_from_outputs(attn, acts, attn_noisy, acts_noisy, targets, ids, parts, image_sizes, k, img_size, num_classes=200, half_size=36, n_parts=15,
+                           device=False):
+    """The stability score on collected push_forward outputs of a clean and a noisy pass over the same images: attn / attn_noisy
+    (B, Np) rollout scores (each pass is expanded to the patch grid by its own), acts / acts_noisy (B, ppc, s, s) the class's own
+    prototype activations, targets / ids (B,).  Returns (score, stable fraction per (class, prototype)).  The host path
+    (prototype_part_table and row equality in numpy) is the referee; device=True makes both sets of tables with ppf_act_peak from one
+    uploaded part list and reduces them in a PartMeter.  Same values."""
+    targets, ids = np.asarray(targets), np.asarray(ids)
+    if device:
+        attn, acts, attn_noisy, acts_noisy = (torch.as_tensor(a).cuda() for a in (attn, acts, attn_noisy, acts_noisy))
+        plist = torch.from_numpy(_part_list(ids, parts, image_sizes, img_size, n_parts)[0]).to(acts.device)
+        meter = PartMeter(num_classes, acts.shape[1], n_parts, acts.device)
+        meter.update(_tables_for_parts(_grid_on_device(attn, acts, k), plist, img_size, half_size), plist,
+                     torch.from_numpy(targets.astype(np.int64)).to(acts.device),
+                     _tables_for_parts(_grid_on_device(attn_noisy, acts_noisy, k), plist, img_size, half_size))
+        r = meter.result()
+        return r["stability"], r["stable_fraction"]
+    clean = _host_tables(_host_grid(attn, acts, k), ids, parts, image_sizes, img_size, half_size, n_parts)[0]
+    noisy = _host_tables(_host_grid(attn_noisy, acts_noisy, k), ids, parts, image_sizes, img_size, half_size, n_parts)[0]
+    return stability_from_tables(clean, noisy, targets, num_classes)
+
+
+@torch.no_grad()
+def interpretability_scores(ppnet, loader, parts, image_sizes, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15, noise_std=0.2, seed=0,
+                            stability=True, device=True):
+    """Consistency and stability score of a model over a test set in one pass: dict(consistency, stability, effects, max_parts,
+    stable_fraction); stability / stable_fraction are None with stability=False.  loader yields (x, targets, img_ids) (img_ids on the
+    host); image_sizes: {img_id: (width, height)} of the original files.
+    device=True: per batch push_forward(x), push_forward(add_input_noise(x, ids, noise_std, seed)), the gather of the class's own
+    prototypes, two ppf_act_peak launches that share one uploaded part list and one PartMeter update; nothing is read back before the
+    single read of the meter at the end.  device=False: the outputs of both passes are collected and scored by the host referees
+    (consistency_from_tables, stability_from_tables on prototype_part_table's tables); the noise still comes from the kernel, the one
+    source there is."""
+    ppnet.eval()
+    ppc, k, img_size = ppnet.num_prototypes_per_class, ppnet.reserve_token_nums[0], ppnet.img_size
+    meter, kept = None, []
+
+    def own_maps(xb, t):
+        ta, pa = ppnet.push_forward(xb)
+        cols = (t * ppc)[:, None] + torch.arange(ppc, device=pa.device)[None, :]
+        return ta, torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1]))
+
+    for x, t, i in loader:
+        x = x.cuda() if not x.is_cuda else x
+        ids = torch.as_tensor(i).cpu()
+        t = torch.as_tensor(t).to(device=x.device, dtype=torch.int64)
+        passes = [own_maps(x, t)]
+        if stability:
+            passes.append(own_maps(add_input_noise(x, ids, noise_std, seed), t))
+        if device:
+            if meter is None:
+                meter = PartMeter(num_classes, ppc, n_parts, x.device)
+            plist = torch.from_numpy(_part_list(ids.numpy(), parts, image_sizes, img_size, n_parts)[0]).to(x.device, non_blocking=True)
+            tables = [_tables_for_parts(_grid_on_device(ta, own, k), plist, img_size, half_size) for ta, own in passes]
+            meter.update(tables[0], plist, t.contiguous(), tables[1] if stability else None)
+        else:
+            kept.append((ids, t.cpu(), [(ta.float().cpu(), own.float().cpu()) for ta, own in passes]))
+    if device:
+        r = meter.result(part_thresh) if meter is not None else part_meter_scores(np.zeros((0, ppc, n_parts)), np.zeros((0, n_parts)), np.zeros((0, ppc)),
+                                                                                   np.zeros(0), part_thresh, stability)
+        r.pop("images")
+        return r
+    ids = torch.cat([c[0] for c in kept]).numpy() if kept else np.zeros(0, dtype=np.int64)
+    targets = torch.cat([c[1] for c in kept]).numpy() if kept else np.zeros(0, dtype=np.int64)
+    tables = []
+    for j in range(2 if stability else 1):
+        if not kept:
+            tables.append(np.zeros((0, ppc, n_parts)))
+            continue
+        grid = _host_grid(torch.cat([c[2][j][0] for c in kept]), torch.cat([c[2][j][1] for c in kept]), k)
+        tables.append(_host_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts))
+    score, effects, max_parts = _score_from_tables(tables[0][0], tables[0][1], targets, num_classes, part_thresh)
+    out = dict(consistency=score, effects=effects, max_parts=max_parts, stability=None, stable_fraction=None)
+    if stability:
+        out["stability"], out["stable_fraction"] = stability_from_tables(tables[0][0], tables[1][0], targets, num_classes)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ dataset-wide nearest patches

@@ -538,6 +538,51 @@ def act_box(grids, size, thr):
     return box
 
 
+# ---- stability score (csrc/interp.hip): per-image Gaussian input noise and the per-class accumulators of interpret.PartMeter
+def add_gauss_noise(x, image_ids, sigma, seed=0, out=None):
+    """x + sigma * N(0, 1) on an fp32 CUDA batch [B, ...] (ppf_add_gauss_noise): the noise of an image is a function of (seed, its id in
+    image_ids int64 [B], element) alone.  out: None (a new tensor), x itself (in place) or another tensor like x."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() < 1 or not x.is_contiguous():
+        raise ValueError("add_gauss_noise: x must be a contiguous fp32 CUDA tensor [B, ...]")
+    if (not isinstance(image_ids, torch.Tensor) or image_ids.dtype != torch.int64 or image_ids.shape != (x.shape[0],) or not image_ids.is_contiguous()
+            or image_ids.device != x.device):
+        raise ValueError(f"add_gauss_noise: image_ids must be a contiguous int64 tensor [{x.shape[0]}] on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError("add_gauss_noise: out must be a contiguous tensor of x's shape, dtype and device")
+    B = x.shape[0]
+    n_per_img = 1
+    for d in x.shape[1:]:
+        n_per_img *= int(d)
+    _lib.call("ppf_add_gauss_noise", x, out, B, n_per_img, image_ids, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF)
+    return out
+
+
+def part_meter_update(tables, tables_noisy, parts, labels, hits, visible, stable, images, bad):
+    """Add one batch into the int32 accumulators hits [C, ppc, n_parts], visible [C, n_parts], stable [C, ppc], images [C], bad [1]
+    (ppf_part_meter_update, include/ppf_hip.h); launches only.  tables / tables_noisy (or None) uint8 [B, ppc, n_parts], parts int32
+    [B, n_parts, 3], labels int64 [B]."""
+    if not isinstance(tables, torch.Tensor) or tables.dtype != torch.uint8 or tables.dim() != 3 or not tables.is_contiguous() or not tables.is_cuda:
+        raise ValueError("part_meter_update: tables must be a contiguous uint8 CUDA tensor [B, ppc, n_parts]")
+    B, ppc, n_parts = tables.shape
+    dev = tables.device
+    if tables_noisy is not None and (tables_noisy.dtype != torch.uint8 or tables_noisy.shape != tables.shape or not tables_noisy.is_contiguous()
+                                     or tables_noisy.device != dev):
+        raise ValueError(f"part_meter_update: tables_noisy must be None or a contiguous uint8 tensor {tuple(tables.shape)} on {dev}")
+    if parts.dtype != torch.int32 or parts.shape != (B, n_parts, 3) or not parts.is_contiguous() or parts.device != dev:
+        raise ValueError(f"part_meter_update: parts must be a contiguous int32 tensor [{B}, {n_parts}, 3] on {dev}")
+    if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous() or labels.device != dev:
+        raise ValueError(f"part_meter_update: labels must be a contiguous int64 tensor [{B}] on {dev}")
+    C = images.shape[0] if images.dim() == 1 else -1
+    for name, t, shape in (("hits", hits, (C, ppc, n_parts)), ("visible", visible, (C, n_parts)), ("stable", stable, (C, ppc)), ("images", images, (C,)),
+                           ("bad", bad, (1,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"part_meter_update: {name} must be a contiguous int32 tensor {shape} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if B > 0:
+        _lib.call("ppf_part_meter_update", tables, tables_noisy, parts, labels, B, ppc, n_parts, C, hits, visible, stable, images, bad)
+
+
 MIX_WORDS, MIX_WSELF = _lib.DEFINES["PPF_MIX_WORDS"], _lib.DEFINES["PPF_MIX_WSELF"]          # read from include/ppf_hip.h
 
 
