@@ -311,6 +311,31 @@ int ppf_proto_topk_init(float* val, int* img, int* pos, int P, int K, ppf_stream
 int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx, int k, const float* tok, int64_t stride_b, int t0, int Dp,
                          const void* label_i64, const int* image_id, int ppc, int B, int P, int K, float* val, int* img, int* pos,
                          float* best_feat, ppf_stream_t stream);
+/* Local analysis (csrc/explain.hip): why did sample b get class c?  The counterpart of the bank's global analysis, from what an eval
+ * forward leaves on the device (ProtoPNet's "local analysis"; the reference's main_visualize.py draws every prototype of a chosen class
+ * and never ranks evidence).  One launch per branch explains M classes of each of B samples: for list (b, m) of class c = cls_out[b][m]
+ * the contribution of prototype p is fl(act_max[b][p] * fl(scale * weight[c][p])) -- two separate fp32 roundings, nothing fused or
+ * reassociated -- and proto / contrib / act / cell [B][M][K] hold the K best under a TOTAL order: sign * contrib descending, equal keys
+ * by smaller prototype id.  sign = +1: evidence for the class, sign = -1: the strongest evidence against it.  NaN and +-inf
+ * contributions are never admitted.  Unfilled slots (K > P, or too few admissible candidates): proto = -1, cell = -1, contrib = act = -inf.
+ *   act_max [B][P], argmax [B][P]: as ppf_proto_fwd writes them.  argmax == NULL: the global / cls branch; idx, act_full and maps are
+ *   NULL too and cell is filled with -1.  idx [B][T] int32: the grid positions of the reserved tokens (distinct within a sample);
+ *   cell = idx[b][argmax[b][p]], -1 when that argmax lies outside [0, T).  weight [C][P]: the branch's last layer; scale: the branch's
+ *   share of the logit (1 - global_coe local, global_coe global), rounded once to fp32 by the caller; ppc: prototypes per class.
+ *   logits [B][C]; cls_in [B][M] int32: the classes to explain, or NULL: the kernel picks the top-M classes of logits itself (larger
+ *   logit first, equal logits by smaller class id, NaN never picked).  cls_out [B][M] and cls_logit [B][M] (= logits[b][c]) are always
+ *   written.  A class outside [0, C), or a slot with no pickable class, gives cls_out = -1, cls_logit = -inf, an all-unfilled list, zero
+ *   evidence and zero maps, and reads nothing out of range.
+ *   evidence [B][M][2]: [0] = the sum of the contributions of the class's own prototypes (p / ppc == c), [1] = the sum over all others;
+ *   their sum is this branch's share of logits[b][c].  Non-finite terms are included: the sums agree with the logits, they do not hide a
+ *   NaN.  Summed in fp64, rounded once to fp32.
+ *   maps [B][M][K][G] (optional; G = cells of the full patch grid, G <= 8192): map (b, m, k) is zero everywhere except
+ *   act_full[b][p][t] at cell idx[b][t] for the selected p (act_full [B][P][T] as ppf_proto_fwd writes it; an idx entry outside [0, G)
+ *   is skipped) -- interpret.expand_to_grid for the K selected prototypes only; all zero for an unfilled slot.
+ * 1 <= K <= 64, 1 <= M <= 8, M <= C, P % ppc == 0, sign = +-1.  One wave per list, no atomics: deterministic. */
+int ppf_explain_topk(const float* act_max, const int* argmax, const int* idx, int T, const float* act_full, const float* weight, float scale,
+                     int ppc, const float* logits, const int* cls_in, int sign, int B, int P, int C, int M, int K, int G, int* cls_out,
+                     float* cls_logit, int* proto, float* contrib, float* act, int* cell, float* evidence, float* maps, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);

@@ -1,0 +1,205 @@
+// Local analysis: why did this image get this class?  For every (sample, class) pair the K prototypes with the largest class evidence
+// act_max[b][p] * (scale * weight[c][p]), the evidence totals, and the activation maps of the selected prototypes on the full patch grid,
+// all from what an eval forward leaves on the device (ProtoPNet's "local analysis"; the reference has no such pass -- its
+// main_visualize.py draws every prototype of a chosen class and never ranks evidence).
+//   * explain_topk_kernel: one wave owns one (b, m) list (no atomics), lane j holds list entry j (K <= 64), as in proto_bank.hip.  The
+//     form kept is ONE WAVE PER WORKGROUP: at B = 256, M = 1 the 256 lists then spread over 256 compute units instead of 64, and nothing
+//     is shared between the lists of a workgroup that the caches do not already share (the act_max row of a sample).  P is not split over
+//     waves: the list and the sums are those of a single in-order pass.
+//   * Classes: given (cls_in) or picked by the wave itself as the top-M of its logits row with the same list mechanism (larger logit
+//     first, equal logits by smaller class id, NaN never picked); the wave of slot m takes entry m.
+//   * P is streamed in chunks of 64 with coalesced reads of the act_max and weight rows, the loads of four chunks issued together (a
+//     launch is a few hundred waves that each walk P alone: it is bound by the chain of memory round trips, not by bandwidth); the
+//     chunks are then offered one after the other in ascending order, so nothing depends on the grouping.  A chunk is tested by ballot
+//     against the current K-th entry; a survivor's rank is the popcount of the ballot of the entries that come before it (the list is
+//     sorted, so these are a prefix); the entries from that rank on move one lane up.  The order is total: sign * contribution
+//     descending, equal keys by smaller prototype id.  Both products are separate fp32 multiplications (__fmul_rn: no contraction with
+//     the sums).  NaN and +-inf contributions are never admitted, but they are part of the evidence sums.
+//   * Evidence: per-lane fp64 partial sums over the chunks, one shuffle reduction at the end, one rounding to fp32.
+//   * Maps: written by the wave after the list is final.  The inverse of idx[b] (grid cell -> reserved token, -1 elsewhere) is built once
+//     in LDS, so every cell of every map is written exactly once, coalesced: zero, or act_full[b][p][t] at cell idx[b][t].
+#include <limits.h>
+#include <math.h>
+
+#include "ppf_common.h"
+#include "ppf_hip.h"
+
+namespace {
+
+constexpr int NO_ID = INT_MAX;          // id of an unfilled list entry (sorts last among equal keys; a finite key always beats -inf)
+constexpr int UNR = 4;                  // chunks whose loads are issued together (the wave's walk over P is a chain of memory round trips)
+constexpr int MAX_G = 8192;             // grid cells whose inverse index fits the static 48 KiB of LDS with room to spare
+
+// does (v, id) come before (w, jd) in the list order?
+__device__ __forceinline__ bool beats(float v, int id, float w, int jd) { return v > w || (v == w && id < jd); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Offers the candidate (v, id, pay) of every lane with `offered` set to the sorted list (sk, sid, sp) held one entry per lane (K entries).
+__device__ __forceinline__ void offer_chunk(bool offered, float v, int id, float pay, int K, int lane, float& sk, int& sid, float& sp) {
+    const float kv = __shfl(sk, K - 1, 64);
+    const int ki = __shfl(sid, K - 1, 64);
+    unsigned long long surv = __ballot(offered && beats(v, id, kv, ki));
+    while (surv) {                                                            // wave-uniform loop over the survivors of the prefilter
+        const int src = __ffsll((long long)surv) - 1;
+        surv &= surv - 1;
+        const float cv = __shfl(v, src, 64), cp = __shfl(pay, src, 64);
+        const int cid = __shfl(id, src, 64);
+        // entries that come before the candidate: a prefix of the sorted list, so their count is the candidate's rank
+        const int rank = __popcll(__ballot(lane < K && beats(sk, sid, cv, cid)));
+        if (rank >= K) continue;                                              // the list moved on since the prefilter
+        const float uk = __shfl_up(sk, 1, 64), up = __shfl_up(sp, 1, 64);
+        const int ui = __shfl_up(sid, 1, 64);
+        if (lane < K) {
+            if (lane > rank) { sk = uk; sid = ui; sp = up; }
+            else if (lane == rank) { sk = cv; sid = cid; sp = cp; }
+        }
+    }
+}
+
+// grid: B * M workgroups of one wave; dynamic LDS: G ints when maps != NULL
+__global__ __launch_bounds__(64) void explain_topk_kernel(const float* __restrict__ act_max, const int* __restrict__ argmax, const int* __restrict__ idx,
+                                                          int T, const float* __restrict__ act_full, const float* __restrict__ weight, float scale,
+                                                          int ppc, const float* __restrict__ logits, const int* __restrict__ cls_in, int sign, int P,
+                                                          int C, int M, int K, int G, int* __restrict__ cls_out, float* __restrict__ cls_logit,
+                                                          int* __restrict__ proto, float* __restrict__ contrib, float* __restrict__ act,
+                                                          int* __restrict__ cell, float* __restrict__ evidence, float* __restrict__ maps) {
+    extern __shared__ int inv[];                                              // inv[g] = the reserved token that sits at grid cell g, or -1
+    const int lane = threadIdx.x;
+    const int list = blockIdx.x, b = list / M, m = list - b * M;
+
+    // ---- the class of this list
+    int c = -1;
+    float c_logit = -INFINITY;
+    if (cls_in) {
+        c = cls_in[list];
+        if (c >= 0 && c < C) c_logit = logits[(size_t)b * C + c];
+        else c = -1;
+    } else {
+        float ck = -INFINITY, cpay = 0.0f;
+        int cid = NO_ID;
+        for (int c0 = 0; c0 < C; c0 += 64 * UNR) {
+            float v[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int cc = c0 + u * 64 + lane;
+                v[u] = cc < C ? logits[(size_t)b * C + cc] : NAN;
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int cc = c0 + u * 64 + lane;
+                if (c0 + u * 64 < C) offer_chunk(cc < C && v[u] == v[u], v[u], cc, 0.0f, M, lane, ck, cid, cpay);   // -inf is a logit like any other; NaN is not offered
+            }
+        }
+        const int pick = __shfl(cid, m, 64);
+        if (pick != NO_ID) { c = pick; c_logit = __shfl(ck, m, 64); }
+    }
+    c = __builtin_amdgcn_readfirstlane(c);                                    // wave-uniform: the weight row below is addressed by scalars
+    if (lane == 0) { cls_out[list] = c; cls_logit[list] = c_logit; }
+
+    // ---- the list and the evidence sums
+    float sk = -INFINITY, sa = -INFINITY;                                     // key = sign * contribution, activation
+    int sid = NO_ID;
+    double ev_own = 0.0, ev_other = 0.0;
+    if (c >= 0) {
+        const float* __restrict__ arow = act_max + (size_t)b * P;
+        const float* __restrict__ wrow = weight + (size_t)c * P;
+        const int own_lo = c * ppc, own_hi = own_lo + ppc;                    // p / ppc == c
+        for (int p0 = 0; p0 < P; p0 += 64 * UNR) {
+            float av[UNR], wv[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {                                   // the loads of UNR chunks in flight together ...
+                const int p = p0 + u * 64 + lane;
+                av[u] = p < P ? arow[p] : 0.0f;
+                wv[u] = p < P ? wrow[p] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {                                   // ... the chunks themselves one after the other, in order
+                const int p = p0 + u * 64 + lane;
+                if (p0 + u * 64 >= P) break;                                  // wave-uniform
+                const bool in = p < P;
+                const float a = av[u];
+                const float w = __fmul_rn(scale, wv[u]);
+                const float ctr = __fmul_rn(a, w);
+                if (in) {
+                    if (p >= own_lo && p < own_hi) ev_own += (double)ctr;
+                    else ev_other += (double)ctr;
+                }
+                offer_chunk(in && isfinite(ctr), sign > 0 ? ctr : -ctr, p, a, K, lane, sk, sid, sa);
+            }
+        }
+    }
+    ev_own = wave_sum_f64(ev_own);
+    ev_other = wave_sum_f64(ev_other);
+    if (lane == 0) {
+        evidence[(size_t)list * 2] = (float)ev_own;
+        evidence[(size_t)list * 2 + 1] = (float)ev_other;
+    }
+
+    const bool filled = sid != NO_ID;
+    if (lane < K) {
+        int at = -1;
+        if (filled && argmax) {
+            const int t = argmax[(size_t)b * P + sid];
+            if (t >= 0 && t < T) at = idx[(size_t)b * T + t];
+        }
+        const size_t o = (size_t)list * K + lane;
+        proto[o] = filled ? sid : -1;
+        contrib[o] = filled ? (sign > 0 ? sk : -sk) : -INFINITY;              // exact: the key is the contribution or its negation
+        act[o] = filled ? sa : -INFINITY;
+        cell[o] = at;
+    }
+
+    // ---- the maps of the selected prototypes on the full grid
+    if (!maps) return;                                                        // kernel-uniform
+    for (int g = lane; g < G; g += 64) inv[g] = -1;
+    __syncthreads();
+    for (int t = lane; t < T; t += 64) {
+        const int g = idx[(size_t)b * T + t];
+        if (g >= 0 && g < G) inv[g] = t;                                      // the cells of a sample are distinct (caller's contract)
+    }
+    __syncthreads();
+    for (int k = 0; k < K; ++k) {
+        const int pk = __shfl(sid, k, 64);                                    // wave-uniform
+        float* __restrict__ out = maps + ((size_t)list * K + k) * G;
+        const float* __restrict__ src = pk != NO_ID ? act_full + ((size_t)b * P + pk) * T : nullptr;
+        for (int g = lane; g < G; g += 64) {
+            const int t = inv[g];
+            out[g] = (src && t >= 0) ? src[t] : 0.0f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int ppf_explain_topk(const float* act_max, const int* argmax, const int* idx, int T, const float* act_full, const float* weight, float scale,
+                     int ppc, const float* logits, const int* cls_in, int sign, int B, int P, int C, int M, int K, int G, int* cls_out,
+                     float* cls_logit, int* proto, float* contrib, float* act, int* cell, float* evidence, float* maps, hipStream_t stream) {
+    PPF_CHECK_ARG(K >= 1 && K <= 64, PPF_ERR_SHAPE, "ppf_explain_topk: K=%d outside [1, 64] (one list entry per lane)", K);
+    PPF_CHECK_ARG(M >= 1 && M <= 8, PPF_ERR_SHAPE, "ppf_explain_topk: M=%d outside [1, 8] (classes explained per sample)", M);
+    PPF_CHECK_ARG(C >= 1 && M <= C, PPF_ERR_SHAPE, "ppf_explain_topk: M=%d classes per sample of C=%d (1 <= M <= C)", M, C);
+    PPF_CHECK_ARG(B >= 1 && P >= 1, PPF_ERR_SHAPE, "ppf_explain_topk: bad shape B=%d P=%d (both >= 1)", B, P);
+    PPF_CHECK_ARG((long long)B * M <= INT_MAX, PPF_ERR_SHAPE, "ppf_explain_topk: B=%d x M=%d lists exceed the grid", B, M);
+    PPF_CHECK_ARG(ppc >= 1 && P % ppc == 0, PPF_ERR_SHAPE, "ppf_explain_topk: ppc=%d must be >= 1 and divide P=%d", ppc, P);
+    PPF_CHECK_ARG((long long)C * ppc <= INT_MAX, PPF_ERR_SHAPE, "ppf_explain_topk: C=%d x ppc=%d overflows", C, ppc);
+    PPF_CHECK_ARG(sign == 1 || sign == -1, PPF_ERR_ARG, "ppf_explain_topk: sign=%d must be +1 (evidence for) or -1 (evidence against)", sign);
+    PPF_CHECK_ARG((argmax == nullptr) == (idx == nullptr), PPF_ERR_ARG, "ppf_explain_topk: argmax and idx must both be given or both be NULL");
+    PPF_CHECK_ARG(argmax != nullptr || (act_full == nullptr && maps == nullptr), PPF_ERR_ARG,
+                  "ppf_explain_topk: the global branch (argmax NULL) has no act_full and no maps");
+    PPF_CHECK_ARG(argmax == nullptr || T >= 1, PPF_ERR_SHAPE, "ppf_explain_topk: T=%d reserved tokens with an argmax", T);
+    PPF_CHECK_ARG(maps == nullptr || act_full != nullptr, PPF_ERR_ARG, "ppf_explain_topk: maps need act_full");
+    PPF_CHECK_ARG(maps == nullptr || (G >= 1 && G <= MAX_G), PPF_ERR_SHAPE, "ppf_explain_topk: G=%d grid cells outside [1, %d]", G, MAX_G);
+    PPF_CHECK_ARG(act_max && weight && logits && cls_out && cls_logit && proto && contrib && act && cell && evidence, PPF_ERR_ARG,
+                  "ppf_explain_topk: null pointer");
+    return ppf_launch<explain_topk_kernel>(dim3((unsigned)(B * M)), dim3(64), maps ? (size_t)G * sizeof(int) : 0, stream, "ppf_explain_topk", act_max,
+                                           argmax, idx, T, act_full, weight, scale, ppc, logits, cls_in, sign, P, C, M, K, G, cls_out, cls_logit, proto,
+                                           contrib, act, cell, evidence, maps);
+}
+
+}  // extern "C"

@@ -623,3 +623,236 @@ def nearest_patches(ppnet, loader, topk=10, class_specific=True):
         bank.update(x.cuda() if not x.is_cuda else x, y, ids)
         seen += B
     return bank
+
+
+# ------------------------------------------------------------------------------------------------ local analysis: explain a prediction
+# ProtoPNet's "local analysis", the counterpart of the bank's global one: for one image and one class, which prototypes carry the
+# logit, where on the image each of them fired, and (with a bank) which training patches each of them stands for.  Everything comes from
+# what an eval forward leaves on the device (ppf_explain_topk, one launch per branch); the reference has no such pass.
+EXPLAIN_BRANCHES = ("local", "global")
+EXPLAIN_FIELDS = ("classes", "class_logits", "prototypes", "contributions", "activations", "cells", "evidence", "weights", "maps", "boxes")
+
+
+def _host(t, dtype):
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor):
+        t = t.detach().cpu().numpy()
+    return np.ascontiguousarray(t, dtype=dtype)
+
+
+def explain_from_outputs(act_max, weight, scale, ppc, logits, topk, classes=None, top_classes=1, sign=1, argmax=None, idx=None, act_full=None,
+                         grid_cells=0, maps=False, device=True):
+    """The K = topk strongest class evidences per (sample, class) of ONE branch from collected outputs: act_max [B, P] pooled
+    activations, weight [C, P] the branch's last layer, scale its share of the logit, logits [B, C]; the local branch adds argmax [B, P],
+    idx [B, T] and act_full [B, P, T] (with maps: maps on a grid of `grid_cells` cells).  classes int32 [B, M], or None: the top
+    `top_classes` of logits.  Returns dict(classes, class_logits [B, M], prototypes, contributions, activations, cells [B, M, K], evidence
+    [B, M, 2], maps [B, M, K, grid_cells] or None); the contract is ppf_explain_topk's (include/ppf_hip.h).
+    device=True: one ppf_explain_topk launch on CUDA tensors (device tensors out).  device=False: the numpy referee (host arrays out) --
+    the same two fp32 products, np.lexsort on (prototype id, -sign * contribution) over the finite contributions, an fp64 evidence sum."""
+    if device:
+        from . import ops
+        return ops.explain_topk(act_max, weight, scale, ppc, logits, topk, classes=classes, top_classes=top_classes, sign=sign, argmax=argmax, idx=idx,
+                                act_full=act_full, grid_cells=grid_cells, want_maps=maps)
+    act_max, weight, logits = _host(act_max, np.float32), _host(weight, np.float32), _host(logits, np.float32)
+    argmax, idx, act_full = _host(argmax, np.int64), _host(idx, np.int64), _host(act_full, np.float32)
+    (B, P), C, K, G = act_max.shape, weight.shape[0], int(topk), int(grid_cells)
+    if sign not in (1, -1) or not 1 <= K <= 64 or ppc < 1 or P % ppc:
+        raise ValueError(f"explain_from_outputs: sign={sign} topk={K} ppc={ppc} P={P} outside ppf_explain_topk's limits")
+    if classes is None:
+        M = int(top_classes)
+        cls = np.full((B, M), -1, dtype=np.int32)
+        for b in range(B):
+            ids = np.nonzero(~np.isnan(logits[b]))[0]
+            order = ids[np.lexsort((ids, -logits[b, ids]))][:M]
+            cls[b, :order.size] = order
+    else:
+        cls = _host(classes, np.int32).reshape(B, -1).copy()
+        cls[(cls < 0) | (cls >= C)] = -1
+        M = cls.shape[1]
+    if not 1 <= M <= min(8, C):
+        raise ValueError(f"explain_from_outputs: M={M} classes per sample outside [1, min(8, C={C})]")
+    T = idx.shape[1] if idx is not None else 0
+    if act_full is not None:
+        act_full = act_full.reshape(B, P, T)
+    out = dict(classes=cls, class_logits=np.full((B, M), -np.inf, dtype=np.float32), prototypes=np.full((B, M, K), -1, dtype=np.int32),
+               contributions=np.full((B, M, K), -np.inf, dtype=np.float32), activations=np.full((B, M, K), -np.inf, dtype=np.float32),
+               cells=np.full((B, M, K), -1, dtype=np.int32), evidence=np.zeros((B, M, 2), dtype=np.float32),
+               maps=np.zeros((B, M, K, G), dtype=np.float32) if maps else None)
+    with np.errstate(all="ignore"):
+        w = np.float32(scale) * weight                                               # fp32: the first rounding
+        proto_class = np.arange(P) // ppc
+        for b in range(B):
+            for m in range(M):
+                c = int(cls[b, m])
+                if c < 0:
+                    continue
+                out["class_logits"][b, m] = logits[b, c]
+                ctr = act_max[b] * w[c]                                              # fp32: the second rounding
+                own = proto_class == c
+                out["evidence"][b, m] = (ctr[own].astype(np.float64).sum(), ctr[~own].astype(np.float64).sum())
+                ids = np.nonzero(np.isfinite(ctr))[0]
+                order = ids[np.lexsort((ids, -(np.float32(sign) * ctr[ids])))][:K]
+                n = order.size
+                out["prototypes"][b, m, :n], out["contributions"][b, m, :n], out["activations"][b, m, :n] = order, ctr[order], act_max[b, order]
+                if argmax is None:
+                    continue
+                t = argmax[b, order]
+                ok = (t >= 0) & (t < T)
+                out["cells"][b, m, :n] = np.where(ok, idx[b, np.clip(t, 0, T - 1)], -1)
+                if maps:
+                    on_grid = (idx[b] >= 0) & (idx[b] < G)
+                    for k in range(n):
+                        out["maps"][b, m, k, idx[b][on_grid]] = act_full[b, order[k]][on_grid]
+    return out
+
+
+class Explanation:
+    """What explain() returns: per branch ('local' / 'global') the fields of EXPLAIN_FIELDS, as device tensors (or numpy arrays after
+    cpu()).  classes / class_logits [B, M]: the explained classes and the model's logits for them; prototypes / contributions /
+    activations / cells / weights [B, M, K]: the ranked prototypes (-1 / -inf in unfilled slots), their share of the logit, pooled
+    activation, grid cell (local branch; -1 on the global one) and raw last-layer weight; evidence [B, M, 2]: the branch's share of the
+    logit from the class's own prototypes and from all others; maps [B, M, K, side, side] and boxes [B, M, K, 4] (y0, y1, x0, x1): local
+    branch with maps=True, else None.  ex.local / ex.global_ are the two field sets; a field name on the object itself is the local one.
+    meta: ppc and scale per branch, side (cells per grid side), patch_size, img_size, against."""
+
+    def __init__(self, local, global_, ppc, scale, side, patch_size, img_size, against=False):
+        for br in (local, global_):
+            for k in EXPLAIN_FIELDS:
+                br.setdefault(k, None)
+        self.branches = {"local": local, "global": global_}
+        self.ppc, self.scale = dict(ppc), {k: float(v) for k, v in scale.items()}
+        self.side, self.patch_size, self.img_size, self.against = int(side), int(patch_size), int(img_size), bool(against)
+
+    local = property(lambda self: self.branches["local"])
+    global_ = property(lambda self: self.branches["global"])
+
+    def __getattr__(self, name):
+        if name in EXPLAIN_FIELDS:
+            return self.__dict__["branches"]["local"][name]
+        raise AttributeError(name)
+
+    @property
+    def on_host(self):
+        return not isinstance(self.branches["local"]["classes"], torch.Tensor)
+
+    def cpu(self):
+        """The same explanation with numpy arrays: every field of both branches in ONE host read."""
+        if self.on_host:
+            return self
+        items = [(br, k, v) for br in EXPLAIN_BRANCHES for k, v in self.branches[br].items() if v is not None]
+        flat = [(v if v.dtype == torch.int32 else v.float().contiguous().view(torch.int32)).reshape(-1) for _, _, v in items]
+        host = torch.cat(flat).cpu().numpy()
+        out, o = {br: dict.fromkeys(EXPLAIN_FIELDS) for br in EXPLAIN_BRANCHES}, 0
+        for br, k, v in items:
+            a = host[o:o + v.numel()]
+            o += v.numel()
+            out[br][k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
+        return Explanation(out["local"], out["global"], self.ppc, self.scale, self.side, self.patch_size, self.img_size, self.against)
+
+    def report(self, index=None, bank=None):
+        """JSON-able records, one per image (index: None = every image of the batch, or one batch position, or a sequence of them):
+        {'image': b, 'against', 'classes': [{'class', 'logit', 'local': branch, 'global': branch}]} with branch = {'scale', 'evidence_own',
+        'evidence_other', 'prototypes': [{'rank', 'prototype', 'prototype_class', 'weight', 'activation', 'contribution'; on the local
+        branch also 'cell', 'patch_box' [x0, y0, x1, y1] and (with maps) 'activation_box' [y0, y1, x0, x1]; with `bank` (the arrays of
+        prototype_bank.npz) 'nearest': that prototype's ranked training patches [{'rank', 'image_id', 'activation', 'grid_pos'}]}]}.
+        Unfilled slots and classes that could not be explained (class -1) are dropped."""
+        h = self.cpu()
+        B = h.branches["local"]["classes"].shape[0]
+        rows = range(B) if index is None else ([int(index)] if np.ndim(index) == 0 else [int(i) for i in index])
+        records = []
+        for b in rows:
+            if not 0 <= b < B:
+                raise IndexError(f"Explanation.report: image {b} outside the batch of {B}")
+            classes = []
+            for m in range(h.branches["local"]["classes"].shape[1]):
+                c = int(h.branches["local"]["classes"][b, m])
+                if c < 0:
+                    continue
+                entry = {"class": c, "logit": float(h.branches["local"]["class_logits"][b, m])}
+                for br in EXPLAIN_BRANCHES:
+                    entry[br] = h._branch_record(br, b, m, bank)
+                classes.append(entry)
+            records.append({"image": b, "against": h.against, "classes": classes})
+        return records
+
+    def _branch_record(self, br, b, m, bank):
+        f = self.branches[br]
+        protos = []
+        for k in range(f["prototypes"].shape[2]):
+            p = int(f["prototypes"][b, m, k])
+            if p < 0:
+                continue
+            e = dict(rank=len(protos), prototype=p, prototype_class=p // self.ppc[br], weight=float(f["weights"][b, m, k]) if f["weights"] is not None else None,
+                     activation=float(f["activations"][b, m, k]), contribution=float(f["contributions"][b, m, k]))
+            if br == "local":
+                cell = int(f["cells"][b, m, k])
+                e["cell"] = cell if cell >= 0 else None
+                e["patch_box"] = list(patch_box(cell, self.side, self.patch_size)) if cell >= 0 else None
+                if f["boxes"] is not None:
+                    e["activation_box"] = [int(v) for v in f["boxes"][b, m, k]]
+            if bank is not None:
+                n = int(bank[f"{br}_filled"][p])
+                e["nearest"] = [dict(rank=r, image_id=int(bank[f"{br}_image_ids"][p, r]), activation=float(bank[f"{br}_values"][p, r]),
+                                     grid_pos=int(bank[f"{br}_grid_pos"][p, r])) for r in range(n)]
+            protos.append(e)
+        return dict(scale=self.scale[br], evidence_own=float(f["evidence"][b, m, 0]), evidence_other=float(f["evidence"][b, m, 1]), prototypes=protos)
+
+
+def _explain_classes(classes, B, C, device):
+    """classes of explain() as the int32 [B, M] device tensor the kernel takes.  Host lists / arrays are range-checked here; a device
+    tensor is not read back (the kernel answers a class outside [0, C) with an unfilled row)."""
+    if isinstance(classes, torch.Tensor) and classes.is_cuda:
+        if classes.is_floating_point():
+            raise ValueError(f"explain: classes must be integers, got {classes.dtype}")
+        t = classes
+    else:
+        a = np.asarray(classes.cpu() if isinstance(classes, torch.Tensor) else classes)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"explain: classes must be integers, got {a.dtype}")
+        if a.size and (a.min() < 0 or a.max() >= C):
+            raise ValueError(f"explain: classes must lie in [0, {C}), got {int(a.min())} .. {int(a.max())}")
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+    if t.dim() == 1:
+        t = t[:, None]
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError(f"explain: classes must be [B] or [B, M] for a batch of {B}, got {tuple(t.shape)}")
+    return t.to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def explain(ppnet, x, classes=None, top_classes=1, topk=10, against=False, maps=True):
+    """Why did these images get these classes?  One eval pass of `ppnet` over the batch x, then one ppf_explain_topk launch per branch:
+    the local branch picks the classes (classes=None: the top `top_classes` of the logits; else a [B] or [B, M] integer tensor or list)
+    and the global branch explains the same ones.  topk prototypes per (image, class), by their share of the logit
+    act * (branch share * last-layer weight); against=True ranks the strongest evidence AGAINST the class instead.  maps=True also
+    returns the selected prototypes' activation maps on the patch grid and their high-activation pixel boxes (high_activation_boxes).
+    Returns an Explanation (device tensors; nothing is read back here except the two order statistics per map the boxes need)."""
+    from . import ops
+    if not x.is_cuda:
+        raise RuntimeError("explain needs a CUDA/HIP batch (no CPU fallback path; explain_from_outputs(device=False) is the host referee)")
+    B, C = x.shape[0], ppnet.last_layer.weight.shape[0]
+    cls = None if classes is None else _explain_classes(classes, B, C, x.device)
+    was_training = ppnet.training
+    ppnet.eval()
+    try:
+        _, _, idx, act_full, _, logits, _, _ = ppnet._branches(x, want_dist=False)
+        act_l, act_g = ppnet._last_act_max
+        argmax = ppnet._last_argmax
+    finally:
+        ppnet.train(was_training)
+    coe, sign = float(ppnet.global_coe), -1 if against else 1
+    G = int(ppnet.num_patches)
+    side = int(round(G ** 0.5))
+    w_l, w_g = ppnet.last_layer.weight.detach().contiguous(), ppnet.last_layer_global.weight.detach().contiguous()
+    logits = logits.contiguous()
+    local = ops.explain_topk(act_l, w_l, 1.0 - coe, ppnet.num_prototypes_per_class, logits, topk, classes=cls, top_classes=top_classes, sign=sign,
+                             argmax=argmax, idx=idx.contiguous(), act_full=act_full.contiguous(), grid_cells=G, want_maps=maps)
+    glob = ops.explain_topk(act_g, w_g, coe, ppnet.global_proto_per_class, logits, topk, classes=local["classes"], sign=sign)
+    for f, w in ((local, w_l), (glob, w_g)):
+        f["weights"] = w[f["classes"].clamp(min=0).long()[:, :, None], f["prototypes"].clamp(min=0).long()]       # raw weights of the listed pairs
+    if maps:
+        local["maps"] = local["maps"].reshape(local["maps"].shape[:3] + (side, side))
+        local["boxes"] = high_activation_boxes(local["maps"], ppnet.img_size)
+    return Explanation(local, glob, {"local": ppnet.num_prototypes_per_class, "global": ppnet.global_proto_per_class},
+                       {"local": 1.0 - coe, "global": coe}, side, ppnet.img_size // side, ppnet.img_size, against)

@@ -456,6 +456,52 @@ def proto_topk_merge(act_max, argmax, idx, tokens, t0, label, image_id, ppc, val
               val, img, pos, best_feat)
 
 
+def explain_topk(act_max, weight, scale, ppc, logits, K, *, classes=None, top_classes=1, sign=1, argmax=None, idx=None, act_full=None,
+                 grid_cells=0, want_maps=False):
+    """The K strongest class evidences per (sample, class) of one branch (ppf_explain_topk, include/ppf_hip.h); one launch.
+    act_max [B, P] fp32 and argmax [B, P] int32 as proto_fwd returns them (argmax None: global branch, then idx / act_full None and no
+    maps); idx [B, T] int32; act_full fp32 with B * P * T elements; weight [C, P] fp32; logits [B, C] fp32; classes int32 [B, M] on the
+    device, or None: the kernel picks the top `top_classes` of logits.  Returns dict(classes, class_logits [B, M], prototypes,
+    contributions, activations, cells [B, M, K], evidence [B, M, 2], maps [B, M, K, grid_cells] or None)."""
+    _chk(act_max, torch.float32), _chk(weight, torch.float32), _chk(logits, torch.float32)
+    B, P = act_max.shape
+    C = weight.shape[0]
+    if weight.shape != (C, P) or logits.shape != (B, C):
+        raise ValueError(f"explain_topk: weight {tuple(weight.shape)} / logits {tuple(logits.shape)} do not fit act_max {tuple(act_max.shape)}")
+    if (argmax is None) != (idx is None):
+        raise ValueError("explain_topk: argmax and idx come together (both None on the global branch)")
+    if want_maps and (argmax is None or act_full is None):
+        raise ValueError("explain_topk: maps need the local branch's argmax, idx and act_full")
+    T = 0
+    if argmax is not None:
+        _chk(argmax, torch.int32), _chk(idx, torch.int32)
+        T = idx.shape[1] if idx.dim() == 2 else -1
+        if argmax.shape != act_max.shape or idx.shape != (B, T):
+            raise ValueError(f"explain_topk: argmax {tuple(argmax.shape)} / idx {tuple(idx.shape)} do not fit act_max {tuple(act_max.shape)}")
+    if act_full is not None:
+        _chk(act_full, torch.float32)
+        if argmax is None or act_full.numel() != B * P * T:
+            raise ValueError(f"explain_topk: act_full {tuple(act_full.shape)} is not [{B}, {P}, {T}] of the local branch")
+    if classes is not None:
+        _chk(classes, torch.int32)
+        if classes.dim() != 2 or classes.shape[0] != B:
+            raise ValueError(f"explain_topk: classes must be int32 [{B}, M], got {tuple(classes.shape)}")
+        M = classes.shape[1]
+    else:
+        M = int(top_classes)
+    K, G, dev = int(K), int(grid_cells), act_max.device
+    shape = (B, max(M, 0), max(K, 0))
+    out = dict(classes=torch.empty(shape[:2], dtype=torch.int32, device=dev), class_logits=torch.empty(shape[:2], dtype=torch.float32, device=dev),
+               prototypes=torch.empty(shape, dtype=torch.int32, device=dev), contributions=torch.empty(shape, dtype=torch.float32, device=dev),
+               activations=torch.empty(shape, dtype=torch.float32, device=dev), cells=torch.empty(shape, dtype=torch.int32, device=dev),
+               evidence=torch.empty(shape[:2] + (2,), dtype=torch.float32, device=dev),
+               maps=torch.empty(shape + (max(G, 0),), dtype=torch.float32, device=dev) if want_maps else None)
+    _lib.call("ppf_explain_topk", act_max, argmax, idx, T, act_full, weight, float(scale), int(ppc), logits, classes, int(sign), B, P, C, M, K, G,
+              out["classes"], out["class_logits"], out["prototypes"], out["contributions"], out["activations"], out["cells"], out["evidence"],
+              out["maps"])
+    return out
+
+
 # ---- interpretability post-processing (csrc/interp.hip): activation maps [M, g, g] fp32 -> S x S, bit-identical to interpret.resize_cubic
 def _act_maps(name, grids, size):
     """(M, g, S) of the maps handed to a ppf_act_* entry point.  What the C side cannot see -- layout and dtype -- is refused here with
