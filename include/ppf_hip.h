@@ -336,6 +336,40 @@ int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx
 int ppf_explain_topk(const float* act_max, const int* argmax, const int* idx, int T, const float* act_full, const float* weight, float scale,
                      int ppc, const float* logits, const int* cls_in, int sign, int B, int P, int C, int M, int K, int G, int* cls_out,
                      float* cls_logit, int* proto, float* contrib, float* act, int* cell, float* evidence, float* maps, ppf_stream_t stream);
+/* Faithfulness of an explanation (csrc/faithful.hip): deletion / insertion curves (Petsiuk et al., RISE, 2018).  Rank the G cells of the
+ * patch grid by their evidence for a class, remove (or show only) the first counts[s] of them, and read the class probability off the
+ * model's logits for the perturbed images; the forwards in between are the caller's.  The reference has no such pass.  Additions of
+ * ABI 10: no existing entry point changed.
+ *   ppf_cell_order     order, rank int32 [B][M][G] and score fp32 [B][M][G]: a TOTAL order of the cells per (sample, class) row, tier
+ *                      ascending, then score descending, then smaller cell; NaN sorts below -inf within its tier, -0 == +0;
+ *                      rank[b][m][order[b][m][r]] == r.  The ranking uses the returned fp32 score, so it can be verified from the scores.
+ *                      mode 0 (evidence): a reserved cell g = idx[b][t] is tier 0 with score = fp32( sum over p in fp64 of
+ *                        double(fl(scale * weight[c][p])) * double(act_full[b][p][t]) ) -- the fp32 product of ppf_explain_topk, every fp64
+ *                        term exact, one rounding at the end, summation order unspecified; an unreserved cell is tier 1 with score
+ *                        token_attn[b][g].  idx entries outside [0, G) are ignored, a cell listed twice takes its smallest t.
+ *                      mode 1 (attention): every cell tier 0, score token_attn[b][g] (what the token reservation looks at).
+ *                      mode 2 (random): every cell tier 0, score (word >> 8) * 2^-24 with word = the first word of Philox4x32-10, key =
+ *                        seed, counter = (cell, 0, image id low, image id high): a function of (seed, image id, cell) alone, not of the
+ *                        batch size or order (as ppf_add_gauss_noise).
+ *                      act_full [B][P][T], idx [B][T] int32, token_attn [B][G], weight [C][P], classes [B][M] int32, image_id_i64 [B]
+ *                      int64; pointers a mode does not read may be NULL.  A class outside [0, C): order = rank = -1, score = 0 for that
+ *                      row.  1 <= G <= 1024, 1 <= T <= G (mode 0), 1 <= M <= 8.  One workgroup per row, no float atomics: deterministic.
+ *   ppf_patch_perturb  out fp32 [S][B][M][Cc][H][W] from x [B][Cc][H][W], rank [B][M][G] as above and counts int32 [S] on the DEVICE:
+ *                      insertion = 0 (deletion): a pixel of cell g is the baseline when rank[b][m][g] < counts[s], else x;
+ *                      insertion = 1: a pixel is x when rank[b][m][g] < counts[s], else the baseline.  A row of ranks -1 copies x.
+ *                      baseline fp32 [B][Cc][H][W], or NULL: the constant baseline_const.  The grid is side x side, side = sqrt(G),
+ *                      row-major; H == W, side divides H, and the patch width H / side is a multiple of 4 (a 16-byte vector never
+ *                      straddles a cell); x, baseline, out 16-byte aligned.  x and the baseline are read once, all S * M copies written
+ *                      from registers.
+ *   ppf_class_prob     prob [R] = softmax(logits[r])[cls[r]] = expf(l[c] - max) / sum expf(l - max) of logits fp32 [R][C], cls int32 [R]:
+ *                      accurate expf, the sum in fp64, one wave per row; the softmax rows are never written.  A class outside [0, C) or
+ *                      a NaN in the row gives NaN. */
+int ppf_cell_order(const float* act_full, const int* idx, const float* token_attn, const float* weight, float scale, const int* classes,
+                   const void* image_id_i64, uint64_t seed, int mode, int B, int P, int C, int T, int G, int M, int* order, int* rank, float* score,
+                   ppf_stream_t stream);
+int ppf_patch_perturb(const float* x, const int* rank, const int* counts, int S, int insertion, const float* baseline, float baseline_const, int B,
+                      int M, int Cc, int H, int W, int G, float* out, ppf_stream_t stream);
+int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* prob, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);

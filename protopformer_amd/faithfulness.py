@@ -1,0 +1,101 @@
+"""Are the explanations true?  Deletion / insertion curves (Petsiuk et al., RISE, 2018) over a split: the cells of the patch grid an
+explanation names are removed most important first (deletion: the class probability should fall) or shown alone (insertion: it should
+come back), under three orders of the cells -- the class evidence of the prototypes ('evidence'), the rollout attention the token
+reservation looks at ('attention') and a random order, the control.  The reference has no such pass.
+
+Per batch one eval forward, one `ppf_cell_order` launch per order, and per curve `ppf_patch_perturb`, the model's forwards and
+`ppf_class_prob` (interpret.faithfulness); the curves stay on the device until the split is done.
+
+    python -m protopformer_amd.faithfulness --resume CKPT --data_set CUB2011U --data_path ... --output_dir OUT [--split test] [--steps 14]
+                                            [--orders evidence attention random] [--modes deletion insertion] [--against_label]
+                                            [--max_images N] [--seed 0] [--per-image]
+                                            + the model flags of train.py
+
+writes OUT/faithfulness.json: the image count, the cell counts, per order and mode the mean curve and its area, and per order the
+difference of both areas to the random order's (an explanation is informative when its deletion area lies below and its insertion area
+above); with --per-image also OUT/faithfulness.npz (the curves, classes and ids of every image)."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+
+def get_args_parser():
+    from .interpret import CURVE_MODES, ORDER_MODES
+    from .train import get_args_parser as train_parser
+    p = argparse.ArgumentParser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", parents=[train_parser()])
+    a = p.add_argument
+    a("--split", type=str, default="test", choices=["train", "test"], help="which split is evaluated (no augmentation either way)")
+    a("--steps", type=int, default=14, help="the curves have steps + 1 points: 0, G/steps, ... G cells removed / shown")
+    a("--orders", type=str, nargs="+", default=list(ORDER_MODES), choices=list(ORDER_MODES), help="cell orders to evaluate (random is the control)")
+    a("--modes", type=str, nargs="+", default=list(CURVE_MODES), choices=list(CURVE_MODES))
+    a("--against_label", action="store_true", default=False, help="follow the probability of the image's label instead of its top class")
+    a("--max_images", type=int, default=0, metavar="N", help="stop after N images (0: the whole split)")
+    a("--per-image", dest="per_image", action="store_true", default=False, help="also write faithfulness.npz with every image's curves")
+    p.set_defaults(seed=0)                                 # keys the random order (train.py's --seed, with this tool's default)
+    return p
+
+
+def summarize(result):
+    """The JSON record of interpret.faithfulness's result: images, counts, grid_cells, orders (mean curve and area per order and mode) and
+    vs_random: per other order the two area differences to the random order and whether both have the informative sign."""
+    out = dict(images=int(result["images"]), counts=[int(c) for c in result["counts"]], grid_cells=int(result["grid_cells"]), orders=result["orders"],
+               vs_random={})
+    rnd = result["orders"].get("random")
+    for order, modes in result["orders"].items():
+        if rnd is None or order == "random":
+            continue
+        d = {f"{m}_auc_minus_random": modes[m]["auc"] - rnd[m]["auc"] for m in modes if m in rnd}
+        if len(d) == 2:
+            d["informative"] = bool(d["deletion_auc_minus_random"] < 0 < d["insertion_auc_minus_random"])
+        out["vs_random"][order] = d
+    return out
+
+
+def main(args, model=None, loader=None):
+    """loader: a ready iterable of (x, labels[, ids]) CUDA batches with its model (tests, notebooks); by default both are built from the
+    data flags as the explain tool builds them."""
+    from . import data as D
+    from . import engine as E
+    from .interpret import default_counts, faithfulness
+    from .protopformer import construct_PPNet
+    from .train import set_seed
+    set_seed(args.seed)
+    device = torch.device(args.device)
+    if loader is not None and model is None:
+        raise ValueError("faithfulness.main: a ready loader comes with a ready model (the class count is the data set's)")
+    if loader is None:
+        view = D.build_view_transform(args)                # the eval geometry: Resize(256/224 * size) + CenterCrop
+        ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
+        if hasattr(ds, "return_id"):
+            ds.return_id = True
+        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
+    if model is None:
+        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
+                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
+                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
+                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
+                                global_proto_per_class=args.global_proto_per_class,
+                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
+    model.to(device)
+    if args.resume:
+        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+    res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes), counts=default_counts(model.num_patches, args.steps),
+                       against_label=args.against_label, seed=args.seed, max_images=args.max_images)
+    os.makedirs(args.output_dir, exist_ok=True)
+    path = os.path.join(args.output_dir, "faithfulness.json")
+    with open(path, "w") as f:
+        json.dump(summarize(res), f, indent=1)
+    if args.per_image:
+        arrays = {f"{order}_{mode}": c for order, modes in res["per_image"].items() for mode, c in modes.items()}
+        np.savez(os.path.join(args.output_dir, "faithfulness.npz"), counts=np.asarray(res["counts"]), classes=res["classes"], image_ids=res["image_ids"],
+                 **arrays)
+    print(f"faithfulness of {res['images']} {args.split} images: {path}", flush=True)
+    return path
+
+
+if __name__ == "__main__":
+    cli_args = get_args_parser().parse_args()
+    main(cli_args)

@@ -856,3 +856,291 @@ def explain(ppnet, x, classes=None, top_classes=1, topk=10, against=False, maps=
         local["boxes"] = high_activation_boxes(local["maps"], ppnet.img_size)
     return Explanation(local, glob, {"local": ppnet.num_prototypes_per_class, "global": ppnet.global_proto_per_class},
                        {"local": 1.0 - coe, "global": coe}, side, ppnet.img_size // side, ppnet.img_size, against)
+
+
+# ------------------------------------------------------------------------------------------------ faithfulness: is the explanation true?
+# The deletion / insertion test (Petsiuk et al., RISE, 2018) on the patch grid: rank the cells of an image by their evidence for a class,
+# remove them most important first (deletion) or show only them (insertion), and follow the class probability.  An explanation is
+# informative when its deletion curve falls faster, and its insertion curve rises faster, than under a random order of the cells.
+# Everything stays on the device: ppf_cell_order ranks, ppf_patch_perturb builds the images, the model's own forward scores them and
+# ppf_class_prob reads the one probability per image (csrc/faithful.hip).  The reference has no such pass; the numpy forms below
+# (device=False) are the referees.
+ORDER_MODES = ("evidence", "attention", "random")
+CURVE_MODES = ("deletion", "insertion")
+
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) in numpy: counter (..., 4) and key (..., 2) of 32-bit words -> (..., 4) uint32, the
+    generator csrc/ppf_common.h implements."""
+    c = [np.asarray(counter)[..., i].astype(np.uint64) for i in range(4)]
+    k = [np.asarray(key)[..., i].astype(np.uint64) for i in range(2)]
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & mask, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & mask]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & mask, (k[1] + np.uint64(_PHILOX_W1)) & mask]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def default_counts(grid_cells, steps=14):
+    """The cell counts of a curve: 0, G/steps, 2G/steps, ... G rounded half up, duplicates dropped: strictly increasing, from 0 to G."""
+    G, steps = int(grid_cells), int(steps)
+    if G < 1 or steps < 1:
+        raise ValueError(f"default_counts: grid_cells={G} and steps={steps} must be >= 1")
+    return np.unique((np.arange(steps + 1, dtype=np.int64) * 2 * G + steps) // (2 * steps)).astype(np.int32)
+
+
+def cell_order_from_outputs(act_full, idx, token_attn, weight, scale, classes, grid_cells, mode="evidence", seed=0, image_ids=None, device=True):
+    """A total order of the grid cells per (sample, class): (order, rank int32 [B, M, G], score fp32 [B, M, G]) with
+    rank[b, m, order[b, m, r]] == r; the contract is ppf_cell_order's (include/ppf_hip.h).  act_full [B, P, T], idx [B, T] the grid cells of
+    the reserved tokens, token_attn [B, G] the rollout attention, weight [C, P] the local last layer and scale its share of the logit,
+    classes int32 [B, M].  mode 'evidence': reserved cells first, by their summed class evidence, then the others by attention;
+    'attention': by the rollout attention; 'random': by Philox draws keyed by (seed, image id, cell) (image_ids [B]; None: 0 .. B-1).
+    device=True: one ppf_cell_order launch on CUDA tensors.  device=False: the numpy referee -- the same fp32 product, an fp64 sum
+    rounded once, np.lexsort, and the numpy Philox."""
+    if mode not in ORDER_MODES:
+        raise ValueError(f"cell_order_from_outputs: mode must be one of {ORDER_MODES}, got {mode!r}")
+    G = int(grid_cells)
+    if device:
+        from . import ops
+        B = classes.shape[0]
+        ids = None
+        if mode == "random":
+            ids = (torch.arange(B, dtype=torch.int64, device=classes.device) if image_ids is None
+                   else torch.as_tensor(image_ids).to(device=classes.device, dtype=torch.int64).contiguous())
+        return ops.cell_order(classes, G, mode, act_full=act_full, idx=idx, token_attn=token_attn, weight=weight, scale=scale, image_ids=ids, seed=seed)
+    weight, cls = _host(weight, np.float32), _host(classes, np.int32)
+    (B, M), (C, P) = cls.shape, weight.shape
+    if not 1 <= G <= 1024 or not 1 <= M <= 8:
+        raise ValueError(f"cell_order_from_outputs: G={G} or M={M} outside ppf_cell_order's limits (G <= 1024, 1 <= M <= 8)")
+    order, rank = np.full((B, M, G), -1, dtype=np.int32), np.full((B, M, G), -1, dtype=np.int32)
+    score = np.zeros((B, M, G), dtype=np.float32)
+    if mode == "evidence":
+        idx = _host(idx, np.int64)
+        T = idx.shape[1]
+        act_full = _host(act_full, np.float32).reshape(B, P, T)
+        if not 1 <= T <= G:
+            raise ValueError(f"cell_order_from_outputs: T={T} reserved tokens outside [1, G={G}]")
+    if mode != "random":
+        attn = _host(token_attn, np.float32).reshape(B, G)
+    else:
+        ids = np.arange(B, dtype=np.int64) if image_ids is None else _host(image_ids, np.int64).reshape(B)
+        ids, sd = ids.astype(np.uint64), int(seed) & 0xFFFFFFFFFFFFFFFF
+    cells = np.arange(G)
+    with np.errstate(all="ignore"):
+        w = (np.float32(scale) * weight).astype(np.float32)                          # fp32: the product of explain_from_outputs
+        for b in range(B):
+            for m in range(M):
+                c = int(cls[b, m])
+                if not 0 <= c < C:
+                    continue
+                tier = np.zeros(G, dtype=np.int64)
+                if mode == "evidence":
+                    tot = (w[c].astype(np.float64)[:, None] * act_full[b].astype(np.float64)).sum(axis=0).astype(np.float32)
+                    tier[:], s = 1, attn[b].copy()
+                    for t in range(T - 1, -1, -1):                                   # descending: a cell listed twice keeps its smallest t
+                        if 0 <= idx[b, t] < G:
+                            tier[idx[b, t]], s[idx[b, t]] = 0, tot[t]
+                elif mode == "attention":
+                    s = attn[b].copy()
+                else:
+                    ctr = np.stack([cells.astype(np.uint64), np.zeros(G, dtype=np.uint64), np.full(G, ids[b] & np.uint64(0xFFFFFFFF)),
+                                    np.full(G, ids[b] >> np.uint64(32))], axis=-1)
+                    word = philox4x32_10(ctr, np.array([sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint64))[:, 0]
+                    s = (word >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+                nan = np.isnan(s)
+                o = np.lexsort((cells, np.where(nan, np.float32(0), -s), nan, tier))   # tier, NaN last, score descending, smaller cell
+                order[b, m], score[b, m] = o, s
+                rank[b, m, o] = cells
+    return order, rank, score
+
+
+def perturb_patches(x, rank, counts, insertion=False, baseline=0.0, device=True):
+    """The perturbed images [S, B, M, Cc, H, W] of x [B, Cc, H, W]: with rank [B, M, G] from cell_order_from_outputs and counts [S],
+    deletion replaces the pixels of the cells with rank < counts[s] by the baseline, insertion keeps x in those cells only; a row of ranks
+    -1 copies x.  baseline: a number (0 = the data-set mean colour in normalised space) or a tensor like x.  device=True: one
+    ppf_patch_perturb launch (counts may be a host list); device=False: numpy."""
+    if device:
+        from . import ops
+        counts = counts if isinstance(counts, torch.Tensor) else torch.from_numpy(np.asarray(counts, dtype=np.int32))
+        return ops.patch_perturb(x, rank, counts.to(device=x.device, dtype=torch.int32).contiguous(), insertion, baseline)
+    x, rank, counts = _host(x, np.float32), _host(rank, np.int64), _host(counts, np.int64).reshape(-1)
+    (B, Cc, H, W), (M, G) = x.shape, rank.shape[1:]
+    side = int(round(G ** 0.5))
+    if H != W or side * side != G or H % side or (H // side) % 4:
+        raise ValueError(f"perturb_patches: H={H} W={W} G={G}: square images, a square grid whose side divides H, patch width a multiple of 4")
+    patch = H // side
+    pix = rank.reshape(B, M, side, side).repeat(patch, axis=2).repeat(patch, axis=3)                # [B, M, H, W]: the rank of each pixel's cell
+    keep = (pix[None] < 0) | ((pix[None] < counts[:, None, None, None, None]) == bool(insertion))   # [S, B, M, H, W]
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    return np.where(keep[:, :, :, None], x[None, :, None], base[None, :, None]).astype(np.float32)
+
+
+class Faithfulness:
+    """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
+    class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
+    order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G."""
+    FIELDS = ("counts", "classes", "order", "rank", "score")
+
+    def __init__(self, curves, counts, classes, order, rank, score, grid_cells):
+        self.curves, self.counts, self.classes, self.order, self.rank, self.score = dict(curves), counts, classes, order, rank, score
+        self.grid_cells = int(grid_cells)
+
+    @property
+    def on_host(self):
+        return not isinstance(self.counts, torch.Tensor)
+
+    def cpu(self):
+        """The same object with numpy arrays: every field in ONE host read."""
+        if self.on_host:
+            return self
+        items = [(k, getattr(self, k)) for k in self.FIELDS] + [("curve:" + k, v) for k, v in self.curves.items()]
+        flat = [(v if v.dtype == torch.int32 else v.float().contiguous().view(torch.int32)).reshape(-1) for _, v in items]
+        host = torch.cat(flat).cpu().numpy()
+        out, o = {}, 0
+        for k, v in items:
+            a = host[o:o + v.numel()]
+            o += v.numel()
+            out[k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
+        return Faithfulness({k[6:]: v for k, v in out.items() if k.startswith("curve:")}, *(out[k] for k in self.FIELDS), self.grid_cells)
+
+    def auc(self):
+        """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
+        h = self.cpu()
+        return {k: curve_auc(v, h.counts, h.grid_cells) for k, v in h.curves.items()}
+
+
+def curve_auc(curves, counts, grid_cells):
+    """Trapezoid of curves [..., S] over counts / grid_cells, in fp64."""
+    f = np.asarray(counts, dtype=np.float64) / float(grid_cells)
+    c = np.asarray(curves, dtype=np.float64)
+    return ((c[..., 1:] + c[..., :-1]) * 0.5 * np.diff(f)).sum(-1)
+
+
+def _eval_outputs(ppnet, x):
+    """One eval forward: what the cell orders and the class pick need, all on the device."""
+    was_training = ppnet.training
+    ppnet.eval()
+    try:
+        _, token_attn, idx, act_full, _, logits, _, _ = ppnet._branches(x, want_dist=False)
+        act_l = ppnet._last_act_max[0]
+    finally:
+        ppnet.train(was_training)
+    B = x.shape[0]
+    return dict(token_attn=token_attn.reshape(B, -1).float().contiguous(), idx=idx.contiguous(), act_full=act_full.contiguous(), logits=logits.contiguous(),
+                act_max=act_l)
+
+
+def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes):
+    from . import ops
+    B, G = x.shape[0], int(ppnet.num_patches)
+    M, S = cls.shape[1], counts.shape[0]
+    w_l = ppnet.last_layer.weight.detach().contiguous()
+    ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G, mode=order,
+                                                seed=seed, image_ids=image_ids)
+    # scratch: the perturbed images of one chunk of steps, steps_per_chunk * B * M images, never more than scratch_bytes (one step at least)
+    per_step = B * M * x[0].numel() * 4
+    chunk = max(1, min(S, int(scratch_bytes) // per_step))
+    bs = int(batch_size) if batch_size else B
+    cls_flat = cls.reshape(1, B * M).expand(chunk, B * M).reshape(-1).contiguous()
+    buf = torch.empty((chunk, B, M) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    curves = {}
+    was_training = ppnet.training
+    ppnet.eval()
+    try:
+        for mode in modes:
+            if mode not in CURVE_MODES:
+                raise ValueError(f"faithfulness_curves: modes must come from {CURVE_MODES}, got {mode!r}")
+            prob = torch.empty((S, B, M), dtype=torch.float32, device=x.device)
+            for s0 in range(0, S, chunk):
+                n = min(chunk, S - s0)
+                imgs = ops.patch_perturb(x, rank, counts[s0:s0 + n].contiguous(), mode == "insertion", baseline, out=buf[:n])
+                imgs = imgs.reshape((n * B * M,) + tuple(x.shape[1:]))
+                logits = torch.cat([ppnet._branches(imgs[i:i + bs], want_dist=False)[5] for i in range(0, imgs.shape[0], bs)])
+                prob[s0:s0 + n] = ops.class_prob(logits.contiguous(), cls_flat[:n * B * M]).reshape(n, B, M)
+            curves[mode] = prob.permute(1, 2, 0).contiguous()
+    finally:
+        ppnet.train(was_training)
+    return Faithfulness(curves, counts, cls, ordr, rank, score, G)
+
+
+def _pick_classes(ppnet, outs, classes, top_classes, B):
+    """classes as explain takes them; None: the top `top_classes` of the logits, picked as ppf_explain_topk picks them."""
+    from . import ops
+    C = ppnet.last_layer.weight.shape[0]
+    if classes is not None:
+        return _explain_classes(classes, B, C, outs["logits"].device)
+    return ops.explain_topk(outs["act_max"], ppnet.last_layer.weight.detach().contiguous(), 1.0 - float(ppnet.global_coe), ppnet.num_prototypes_per_class,
+                            outs["logits"], 1, top_classes=top_classes)["classes"]
+
+
+@torch.no_grad()
+def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, modes=CURVE_MODES, order="evidence", baseline=0.0, seed=0, image_ids=None,
+                        batch_size=None, scratch_bytes=1 << 30):
+    """Deletion / insertion curves of a batch x [B, 3, H, W] (CUDA): one eval forward, one ppf_cell_order launch, then per mode
+    ppf_patch_perturb in chunks of steps, the model's forward over each chunk in sub-batches of `batch_size` images (default B; the
+    images of a chunk are ordered step, sample, class) and one ppf_class_prob per chunk.  The chunk's images are the one large scratch
+    buffer: steps-per-chunk = scratch_bytes // (B * M * image bytes), at least one step, so at most max(scratch_bytes, one step) bytes.
+    classes: as in explain (None: the top `top_classes` of the logits).  counts: the numbers of cells removed / shown (default
+    default_counts(G)).  order: 'evidence', 'attention' or 'random' (seed, image_ids: the random order's key).  baseline: what a removed
+    pixel becomes, a number in normalised space (0 = the data-set mean colour) or a tensor like x.  Returns a Faithfulness (device
+    tensors; nothing is read back here)."""
+    if not x.is_cuda:
+        raise RuntimeError("faithfulness_curves needs a CUDA/HIP batch (no CPU fallback path; cell_order_from_outputs / perturb_patches with "
+                           "device=False are the host referees)")
+    x = x.float().contiguous()
+    G = int(ppnet.num_patches)
+    outs = _eval_outputs(ppnet, x)
+    cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
+    counts = _device_counts(counts, G, x.device)
+    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes)
+
+
+def _device_counts(counts, G, device):
+    c = default_counts(G) if counts is None else np.asarray(counts.cpu() if isinstance(counts, torch.Tensor) else counts)
+    if c.ndim != 1 or c.size < 2 or c.dtype.kind not in "iu" or c.min() < 0 or c.max() > G or (np.diff(c) <= 0).any():
+        raise ValueError(f"faithfulness: counts must be at least two strictly increasing integers in [0, {G}], got {c.tolist()}")
+    return torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32)).to(device)
+
+
+@torch.no_grad()
+def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=None, top_classes=1, against_label=False, baseline=0.0, seed=0,
+                 max_images=0, batch_size=None, scratch_bytes=1 << 30):
+    """The curves over a data set.  loader yields (x, labels) or (x, labels, ids); without ids an image's id is its running index.  Per
+    batch one eval forward serves every order; classes are the top `top_classes` of the logits, or with against_label the image's label.
+    The per-image curves stay on the device and are read back once at the end.  Returns dict(images, counts, grid_cells, orders:
+    {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
+    image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
+    G, kept, cls_kept, ids_kept, seen, dev_counts = int(ppnet.num_patches), {}, [], [], 0, None
+    for x, y, *rest in loader:
+        if max_images and seen >= max_images:
+            break
+        if max_images:
+            x, y, rest = x[:max_images - seen], y[:max_images - seen], [r[:max_images - seen] for r in rest]
+        x = (x if x.is_cuda else x.cuda()).float().contiguous()
+        B = x.shape[0]
+        ids = torch.as_tensor(rest[0]).to(torch.int64) if rest else torch.arange(seen, seen + B, dtype=torch.int64)
+        outs = _eval_outputs(ppnet, x)
+        cls = _pick_classes(ppnet, outs, torch.as_tensor(y).to(x.device) if against_label else None, top_classes, B)
+        if dev_counts is None:
+            dev_counts = _device_counts(counts, G, x.device)
+        for order in orders:
+            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes)
+            for mode in modes:
+                kept.setdefault((order, mode), []).append(f.curves[mode])
+        cls_kept.append(cls); ids_kept.append(ids)
+        seen += B
+    if not seen:
+        raise ValueError("faithfulness: the loader gave no image")
+    keys = list(kept)
+    host = torch.stack([torch.cat(kept[k]) for k in keys]).cpu().numpy()                    # the one read of the curves: [orders * modes, N, M, S]
+    classes, cnt = torch.cat(cls_kept).cpu().numpy(), dev_counts.cpu().numpy()
+    valid = classes >= 0
+    out = dict(images=seen, counts=cnt.tolist(), grid_cells=G, orders={}, per_image={}, classes=classes, image_ids=torch.cat([i.cpu() for i in ids_kept]).numpy())
+    for j, (order, mode) in enumerate(keys):
+        rows = host[j][valid].astype(np.float64)                                             # [rows, S]
+        out["orders"].setdefault(order, {})[mode] = dict(curve=rows.mean(0).tolist(), auc=float(curve_auc(rows, cnt, G).mean()))
+        out["per_image"].setdefault(order, {})[mode] = host[j]
+    return out

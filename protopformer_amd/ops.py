@@ -502,6 +502,113 @@ def explain_topk(act_max, weight, scale, ppc, logits, K, *, classes=None, top_cl
     return out
 
 
+# ---- faithfulness of an explanation (csrc/faithful.hip): cell order, perturbed images, class probability
+ORDER_MODES = {"evidence": 0, "attention": 1, "random": 2}
+
+
+def _dev_tensor(who, name, t, dtype, shape, device=None):
+    """Refuses what the C side cannot see -- device, dtype, layout, shape -- before the call."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or (device is not None and t.device != device):
+        raise ValueError(f"{who}: {name} must be a CUDA tensor" + (f" on {device}" if device is not None else ""))
+    if t.dtype != dtype:
+        raise ValueError(f"{who}: {name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be {list(shape)}, got {list(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous, got strides {tuple(t.stride())}")
+    return t
+
+
+def cell_order(classes, grid_cells, mode="evidence", *, act_full=None, idx=None, token_attn=None, weight=None, scale=1.0, image_ids=None, seed=0):
+    """A total order of the grid cells per (sample, class) row (ppf_cell_order, include/ppf_hip.h); one launch.  classes int32 [B, M];
+    evidence: act_full fp32 [B, P, T], idx int32 [B, T], token_attn fp32 [B, G], weight fp32 [C, P]; attention: token_attn (and weight
+    or nothing: the class count only decides which classes are valid); random: image_ids int64 [B].  Returns (order, rank int32 [B, M, G],
+    score fp32 [B, M, G])."""
+    who = "cell_order"
+    if mode not in ORDER_MODES:
+        raise ValueError(f"{who}: mode must be one of {sorted(ORDER_MODES)}, got {mode!r}")
+    if not isinstance(classes, torch.Tensor) or classes.dim() != 2:
+        raise ValueError(f"{who}: classes must be an int32 CUDA tensor [B, M]")
+    B, M = classes.shape
+    dev, G = classes.device, int(grid_cells)
+    _dev_tensor(who, "classes", classes, torch.int32, (B, M))
+    P = T = 0
+    C = 1 << 30                                  # without a weight every non-negative class is valid
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 2:
+            raise ValueError(f"{who}: weight must be an fp32 CUDA tensor [C, P]")
+        C, P = weight.shape
+        _dev_tensor(who, "weight", weight, torch.float32, (C, P), dev)
+    if mode == "evidence":
+        if weight is None or act_full is None or idx is None or token_attn is None:
+            raise ValueError(f"{who}: the evidence order needs act_full, idx, token_attn and weight")
+        T = idx.shape[1] if isinstance(idx, torch.Tensor) and idx.dim() == 2 else -1
+        _dev_tensor(who, "idx", idx, torch.int32, (B, T), dev)
+        if not isinstance(act_full, torch.Tensor) or act_full.numel() != B * P * T:
+            raise ValueError(f"{who}: act_full must hold [{B}, {P}, {T}] elements")
+        _dev_tensor(who, "act_full", act_full, torch.float32, act_full.shape, dev)
+    else:
+        act_full = idx = None
+    if mode == "random":
+        if image_ids is None:
+            raise ValueError(f"{who}: the random order needs image_ids")
+        _dev_tensor(who, "image_ids", image_ids, torch.int64, (B,), dev)
+        token_attn = None
+    else:
+        if token_attn is None:
+            raise ValueError(f"{who}: the {mode} order needs token_attn")
+        _dev_tensor(who, "token_attn", token_attn, torch.float32, (B, G), dev)
+        image_ids = None
+    order = torch.empty((B, M, max(G, 0)), dtype=torch.int32, device=dev)
+    rank, score = torch.empty_like(order), torch.empty(order.shape, dtype=torch.float32, device=dev)
+    _lib.call("ppf_cell_order", act_full, idx, token_attn, weight if mode == "evidence" else None, float(scale), classes, image_ids,
+              int(seed) & 0xFFFFFFFFFFFFFFFF, ORDER_MODES[mode], B, P, C, T, G, M, order, rank, score)
+    return order, rank, score
+
+
+def patch_perturb(x, rank, counts, insertion=False, baseline=0.0, out=None):
+    """The perturbed images out fp32 [S, B, M, Cc, H, W] of x fp32 [B, Cc, H, W] for rank int32 [B, M, G] and counts int32 [S] on the device
+    (ppf_patch_perturb, include/ppf_hip.h); one launch.  baseline: a number, or an fp32 tensor like x."""
+    who = "patch_perturb"
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [B, Cc, H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    B, Cc, H, W = x.shape
+    if not isinstance(rank, torch.Tensor) or rank.dim() != 3 or rank.shape[0] != B:
+        raise ValueError(f"{who}: rank must be an int32 CUDA tensor [{B}, M, G]")
+    _dev_tensor(who, "rank", rank, torch.int32, rank.shape, x.device)
+    M, G = rank.shape[1:]
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 1:
+        raise ValueError(f"{who}: counts must be an int32 CUDA tensor [S]")
+    _dev_tensor(who, "counts", counts, torch.int32, counts.shape, x.device)
+    S = counts.shape[0]
+    base_t, base_c = None, 0.0
+    if isinstance(baseline, torch.Tensor):
+        base_t = _dev_tensor(who, "baseline", baseline, torch.float32, x.shape, x.device)
+    else:
+        base_c = float(baseline)
+    shape = (S, B, M, Cc, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_tensor(who, "out", out, torch.float32, shape, x.device)
+    _lib.call("ppf_patch_perturb", x, rank, counts, S, 1 if insertion else 0, base_t, base_c, B, M, Cc, H, W, G, out)
+    return out
+
+
+def class_prob(logits, cls):
+    """prob fp32 [R] = softmax(logits[r])[cls[r]] of logits fp32 [R, C], cls int32 [R] (ppf_class_prob); one launch, no softmax rows."""
+    who = "class_prob"
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"{who}: logits must be an fp32 CUDA tensor [R, C]")
+    _dev_tensor(who, "logits", logits, torch.float32, logits.shape)
+    R, C = logits.shape
+    _dev_tensor(who, "cls", cls, torch.int32, (R,), logits.device)
+    prob = torch.empty(R, dtype=torch.float32, device=logits.device)
+    _lib.call("ppf_class_prob", logits, cls, R, C, prob)
+    return prob
+
+
 # ---- interpretability post-processing (csrc/interp.hip): activation maps [M, g, g] fp32 -> S x S, bit-identical to interpret.resize_cubic
 def _act_maps(name, grids, size):
     """(M, g, S) of the maps handed to a ppf_act_* entry point.  What the C side cannot see -- layout and dtype -- is refused here with
