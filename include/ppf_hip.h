@@ -71,6 +71,10 @@ size_t ppf_gemm_workspace_bytes(int M, int N, int K);
 
 /* Test hook (tests/test_gpu_gemm.py): force = 1 sends every shape the 224 x 128 NT kernel can legally take to it, 0 = the cost model. */
 int ppf_gemm_test_force_g224(int force);
+/* Test hook (tests/test_gpu_wgrad_dma.py): data path of the eight-wave weight-gradient kernel behind epi 6 with a workspace.  path = 0 the
+ * dispatch as shipped, 1 register-staged for every shape, 2 LDS-DMA for every shape it can take (K % 64 == 0; others stay register-staged).
+ * Both paths produce the same bits. */
+int ppf_gemm_test_wgrad_path(int path);
 
 /* Roofline probe of the split-K weight-gradient kernel (epi 6 with a workspace): HIP events (from a reused pool) on the launch
  * stream around the kernel itself.  ppf_gemm_probe(1) clears and starts, (0) stops, (2) stops and destroys the pool;

@@ -22,24 +22,21 @@
 #include "ppf_common.h"
 #include "ppf_hip.h"
 #include "gemm_common.h"
+#include "gemm_layout.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 using namespace ppfg;
 
-constexpr int BM = 128, BN = 128, BK = 64, NTHREADS = 256;
+constexpr int BM = 128, BN = 128, NTHREADS = 256;          // BK = 64: gemm_layout.h
 constexpr int TILE_BYTES = BM * BK * 2;          // 16 KiB per operand tile (either mode)
 constexpr int STAGE_LD = 68;                     // fp32 pitch of the per-wave epilogue strip (64 + 4: conflict-free float4 rows)
 constexpr int STAGE_BYTES = 4 * 32 * STAGE_LD * 4;   // 4 waves x 32 rows
 
 
 __device__ __forceinline__ int lds_off_mode0(int r, int c16) { return lds_row_off(r, c16); }      // row-major tile: the shared 128-byte-row swizzle
-// transposed tile [64 kc][ROWS r]: row pitch ROWS*2 bytes, 64-byte units XOR-swizzled by kc&3 inside each 256-byte group
-template <int ROWS>
-__device__ __forceinline__ int lds_off_mode1(int kc, int col) {
-    return kc * (ROWS * 2) + ((((col >> 5) ^ (kc & 3))) << 6) + ((col & 31) << 1);
-}
+// (the transposed tile's lds_off_mode1<ROWS> and the LDS-DMA piece mapping that fills it: gemm_layout.h)
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));       // a native 128-bit register tuple
 
@@ -169,15 +166,6 @@ __device__ __forceinline__ void epilogue_rows(const GemmParams& p, const float* 
             if (m < p.M && n < p.N) epi_store<EPI>(p, m, n, v.x, v.y, v.z, v.w, cc, rr[pass]);
         }
     }
-}
-
-// Contraction range [kbeg, kend) of K slice `zslice` of `nsplit`: multiples of BK except the tail; kbeg >= kend: an empty slice.  The K-tile
-// count is left to the caller, after its empty-slice return: computed in front of that return the kernels come out 5 % longer.
-struct KSlice { int kbeg, kend; };
-__device__ __forceinline__ KSlice k_slice(int K, int nsplit, int zslice) {
-    const int kchunk = (((K + nsplit - 1) / nsplit) + BK - 1) / BK * BK;
-    const int kbeg = zslice * kchunk;
-    return {kbeg, min(K, kbeg + kchunk)};
 }
 
 // Epilogue of the 32-row block mi of a wave's 64-column tile (acc[ni][mi]: 2 x MT MFMA tiles; the block's top-left corner is (mbase, nbase)).
@@ -338,10 +326,39 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_kernel(const GemmParams p_) 
 // out of L2 -- 45 GB per step, the largest L2 consumer -- and that traffic, not its arithmetic, is what it costs the main stream
 // (profiles/r4_wgrad_l2_knockout.txt: half the loads = +3.3 % of the step).  Two 128 x 128 sub-tiles that share one operand tile in LDS
 // read 25 % less; every wave keeps the 64 x 64 accumulator tile (64 VGPRs) of the four-wave kernel, so the footprint per wave is
-// unchanged and the launch has half as many, twice as large workgroups (48 KiB of operand tiles each).  Both operands transposed
-// (contraction = rows in memory), register-staged with one tile of prefetch, ordered split-K partial tiles (EPI_PARTIAL) only, never batched,
-// never kpad.
-template <int WMW, int WNW, bool COLSUM>
+// unchanged and the launch has half as many, twice as large workgroups.  Both operands transposed (contraction = rows in memory), ordered
+// split-K partial tiles (EPI_PARTIAL) only, never batched, never kpad.  Two data paths bring a K tile into its [64 kc][ROWS] LDS images;
+// the fragment reads, the MFMA order, the column sums and the epilogue are the same, so both produce the same bits:
+//   DMA = false  register-staged with one tile of prefetch into ONE 48 KiB image pair: two barriers and a ds_write_b128 pass per K tile.
+//                Any K (the tail tile is zero-filled by the store masks).
+//   DMA = true   a ring of two 48 KiB slots filled by LDS-DMA (global_load_lds_dwordx4, six 1 KiB pieces per wave and K tile, swizzle on
+//                the source address: wgrad_dma_piece in gemm_layout.h).  Tile kt + 1's pieces are issued two per k-substep inside tile
+//                kt's MFMA stream; ONE s_waitcnt vmcnt(0) + ONE barrier per K tile: behind it the tile has landed for every wave and every
+//                wave has finished reading the slot that is refilled next.  No staging registers, no ds_write pass.  LDS-DMA cannot
+//                zero-fill: K % 64 == 0 only, rows past the operand's edge re-read the last valid column group (masked in the epilogue).
+//                The pieces go through lds_dma16_hidden (ppf_common.h): the fragments are ds_read_tr builtins, in front of which the
+//                compiler would drain the builtin form's DMAs.
+#ifndef WG8_ISSUE_REGIONS
+#define WG8_ISSUE_REGIONS 3          // k-substeps of a K tile that carry the next tile's LDS-DMA pieces (1 .. 4; measurement builds set others)
+#endif
+template <bool COLSUM>
+__device__ __forceinline__ void wgrad8_mma(const bf16x8 (&fa)[2], const bf16x8 (&fb)[2], f32x16 (&acc)[2][2], f32x16 (&accs)[2], bool do_colsum) {
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
+    if constexpr (COLSUM) {
+        if (do_colsum) {
+            bf16x8 ones;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) accs[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fa[mi], accs[mi], 0, 0, 0);
+        }
+    }
+}
+
+template <int WMW, int WNW, bool COLSUM, bool DMA>
 __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmParams p_) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NTHR = 64 * WMW * WNW, TBM = 64 * WMW, TBN = 64 * WNW;
@@ -361,8 +378,6 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
     if (kbeg >= kend) return;
     const int nk = (kend - kbeg + BK - 1) / BK;
 
-    u32x4 ra[IOA::NLD], rb[IOB::NLD];
-    unsigned ma, mb;
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -378,46 +393,108 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
             for (int r = 0; r < 16; ++r) accs[j][r] = 0.f;
     }
     const bool do_colsum = COLSUM && p.colsum != nullptr && n0 == 0 && wn == 0;
-    unsigned char* tA = smem;
-    unsigned char* tB = smem + TBM * BK * 2;
-    ma = IOA::gload(ra, p.A, p.lda, p.M, m0, kbeg, kend, tid, 0);
-    mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, kbeg, kend, tid, 0);
-    IOA::sstore(ra, ma, tA, tid);
-    IOB::sstore(rb, mb, tB, tid);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        {                                                    // next tile into registers while this one is multiplied (past the end: a
-            const int k0 = kbeg + min(kt + 1, nk - 1) * BK;  // harmless re-read of the last tile, never stored)
-            ma = IOA::gload(ra, p.A, p.lda, p.M, m0, k0, kend, tid, 0);
-            mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, k0, kend, tid, 0);
-        }
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            bf16x8 fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = IOA::frag(tA, wm + 32 * i, ks, lane);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fb[i] = IOB::frag(tB, wn + 32 * i, ks, lane);
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi) acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
-            if constexpr (COLSUM) {
-                if (do_colsum) {
-                    bf16x8 ones;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-#pragma unroll
-                    for (int mi = 0; mi < 2; ++mi) accs[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fa[mi], accs[mi], 0, 0, 0);
-                }
+    constexpr int A_BYTES = TBM * BK * 2;
+    if constexpr (!DMA) {
+        u32x4 ra[IOA::NLD], rb[IOB::NLD];
+        unsigned ma, mb;
+        unsigned char* tA = smem;
+        unsigned char* tB = smem + A_BYTES;
+        ma = IOA::gload(ra, p.A, p.lda, p.M, m0, kbeg, kend, tid, 0);
+        mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, kbeg, kend, tid, 0);
+        IOA::sstore(ra, ma, tA, tid);
+        IOB::sstore(rb, mb, tB, tid);
+        __syncthreads();
+        for (int kt = 0; kt < nk; ++kt) {
+            {                                                    // next tile into registers while this one is multiplied (past the end: a
+                const int k0 = kbeg + min(kt + 1, nk - 1) * BK;  // harmless re-read of the last tile, never stored)
+                ma = IOA::gload(ra, p.A, p.lda, p.M, m0, k0, kend, tid, 0);
+                mb = IOB::gload(rb, p.B, p.ldb, p.N, n0, k0, kend, tid, 0);
             }
+#pragma unroll
+            for (int ks = 0; ks < BK / 16; ++ks) {
+                bf16x8 fa[2], fb[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) fa[i] = IOA::frag(tA, wm + 32 * i, ks, lane);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) fb[i] = IOB::frag(tB, wn + 32 * i, ks, lane);
+                wgrad8_mma<COLSUM>(fa, fb, acc, accs, do_colsum);
+            }
+            __syncthreads();
+            if (kt + 1 < nk) {
+                IOA::sstore(ra, ma, tA, tid);
+                IOB::sstore(rb, mb, tB, tid);
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        if (kt + 1 < nk) {
-            IOA::sstore(ra, ma, tA, tid);
-            IOB::sstore(rb, mb, tB, tid);
+    } else {
+        // ---- this wave's pieces: piece b = wave + 8 i of the slot's [A image | B image], i < NPA / 8: operand A ------------------------
+        constexpr int NPA = TBM / 8, NPB = TBN / 8, PPW = (NPA + NPB) / 8;      // 1 KiB pieces per image; per wave and K tile (6)
+        static_assert(NTHR == 512 && A_BYTES + TBN * BK * 2 == WG8_SLOT_BYTES && NPA % 8 == 0, "ring slot layout");
+        // Pieces b and b + 8 of an image are the same lanes' columns 4096 / ROWS kc rows further down (wgrad_dma_piece: 8 KiB of whole rows
+        // apart), so one 32-bit offset per operand and wave-uniform pointers do for all six: the kernel stays inside the 160 VGPRs of the
+        // register-staged form.
+        const unsigned offA = (unsigned)(wgrad_dma_src(wgrad_dma_piece<TBM>(wave, lane), 0, p.lda, m0, p.M) * 2);      // bytes from the K tile's first row
+        const unsigned offB = (unsigned)(wgrad_dma_src(wgrad_dma_piece<TBN>(wave, lane), 0, p.ldb, n0, p.N) * 2);
+        const size_t stepA = (size_t)p.lda * (BK * 2), stepB = (size_t)p.ldb * (BK * 2);        // bytes from one K tile to the next
+        const size_t pieceA = (size_t)p.lda * (4096 / TBM * 2), pieceB = (size_t)p.ldb * (4096 / TBN * 2);   // from piece b to piece b + 8
+        const unsigned char* gA = reinterpret_cast<const unsigned char*>(p.A) + (size_t)kbeg * p.lda * 2;
+        const unsigned char* gB = reinterpret_cast<const unsigned char*>(p.B) + (size_t)kbeg * p.ldb * 2;
+        const uint32_t ring = __builtin_amdgcn_readfirstlane(lds_offset_of(smem)) + wave * 1024;  // piece i of slot s: + s * SLOT + 8192 i
+        auto issue = [&](int i, uint32_t dst) __attribute__((always_inline)) {
+            if (8 * i < NPA) lds_dma16_hidden(gA + i * pieceA + offA, dst + 8192 * i);
+            else lds_dma16_hidden(gB + (i - NPA / 8) * pieceB + offB, dst + 8192 * i);
+        };
+
+        // One K tile out of the slot at `st`; with ISSUE the wave's pieces of the next tile go to the LDS address `nxt` (the other slot),
+        // two in front of each of the first three k-substeps: issued back to back they stall the wave in the issue stage, and the tile
+        // ends in a full drain, so the last substep carries none.  sched_barrier pins the order of the regions (the DMA statements are
+        // opaque to the scheduler); the fragments of substep ks + 1 are read in front of the MFMAs of substep ks.
+        auto tile = [&](const unsigned char* st, uint32_t nxt, auto issue_tag) __attribute__((always_inline)) {
+            constexpr bool ISSUE = decltype(issue_tag)::value;
+            constexpr int NKS = BK / 16, NRI = WG8_ISSUE_REGIONS;
+            const unsigned char* tA = st;
+            const unsigned char* tB = st + A_BYTES;
+            bf16x8 fa[2][2], fb[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) fa[0][i] = IOA::frag(tA, wm + 32 * i, 0, lane);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) fb[0][i] = IOB::frag(tB, wn + 32 * i, 0, lane);
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (ISSUE) {
+                    if (ks < NRI) {
+#pragma unroll
+                        for (int k = ks * PPW / NRI; k < (ks + 1) * PPW / NRI; ++k) issue(k, nxt);
+                    }
+                }
+                if (ks + 1 < NKS) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) fa[(ks + 1) & 1][i] = IOA::frag(tA, wm + 32 * i, ks + 1, lane);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) fb[(ks + 1) & 1][i] = IOB::frag(tB, wn + 32 * i, ks + 1, lane);
+                }
+                wgrad8_mma<COLSUM>(fa[ks & 1], fb[ks & 1], acc, accs, do_colsum);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) issue(i, ring);                 // prologue: tile 0 into slot 0
+        int slot = 0;
+        for (int kt = 0; kt + 1 < nk; ++kt) {
+            // own pieces of tile kt have landed, then everybody's; everybody has also finished reading tile kt - 1, whose slot is refilled
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            gA += stepA;
+            gB += stepB;
+            tile(smem + slot * WG8_SLOT_BYTES, ring + (slot ^ 1) * WG8_SLOT_BYTES, std::true_type());
+            slot ^= 1;
         }
-        __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        tile(smem + slot * WG8_SLOT_BYTES, 0u, std::false_type());
+        __syncthreads();                                         // every fragment read is done: the ring becomes the epilogue's strips
     }
     // epilogue: as gemm_kernel (a private 32 x 64 fp32 strip per wave, row-contiguous partial-tile stores)
 #pragma unroll
@@ -430,13 +507,25 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
     }
 }
 
+// Test hook (ppf_gemm_test_wgrad_path): 0 = dispatch as shipped, 1 = register-staged everywhere, 2 = LDS-DMA wherever it is eligible.
+int g_wgrad_path = 0;
+#ifndef PPF_WGRAD_DMA_DEFAULT
+#define PPF_WGRAD_DMA_DEFAULT 1      // what path 0 means for an eligible shape (a measurement build can flip it for a same-box A/B)
+#endif
+bool wgrad8_dma(const GemmParams& p) {
+    if (p.K % BK != 0 || g_wgrad_path == 1) return false;      // LDS-DMA cannot zero-fill a partial K tile
+    return g_wgrad_path == 2 || PPF_WGRAD_DMA_DEFAULT;
+}
+
 template <int WMW, int WNW>
 int launch_wgrad8(const GemmParams& p, int splitk, hipStream_t stream) {
     constexpr int NTHR = 64 * WMW * WNW, TBM = 64 * WMW, TBN = 64 * WNW;
     constexpr int opnd = (TBM + TBN) * BK * 2, strips = (NTHR / 64) * 32 * STAGE_LD * 4;
     constexpr int lds = opnd > strips ? opnd : strips;
+    static_assert(strips <= WG8_RING_BYTES, "the epilogue strips reuse the dead ring");
     const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN);
-    return ppf_launch<wgrad8_kernel<WMW, WNW, true>>(dim3(tiles * splitk), dim3(NTHR), lds, stream, "wgrad8", p);
+    if (wgrad8_dma(p)) return ppf_launch<wgrad8_kernel<WMW, WNW, true, true>>(dim3(tiles * splitk), dim3(NTHR), WG8_RING_BYTES, stream, "wgrad8 (dma)", p);
+    return ppf_launch<wgrad8_kernel<WMW, WNW, true, false>>(dim3(tiles * splitk), dim3(NTHR), lds, stream, "wgrad8", p);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -699,23 +788,7 @@ bool g_probe_on = false;
 // 3; the layout of the ABI is kept): the CALLER hands over a workspace used by ppf_gemm_bf16 calls of ONE stream only.
 constexpr size_t PPF_GEMM_COUNTER_BYTES = 16384;
 
-int pick_splitk(int M, int N, int K) {
-    // wgrad-style problems (small output, very long contraction)
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    // K slices: alone on the GPU the kernel is fastest with as many slices as fit in ONE round of 3 workgroups per CU (768:
-    // -17 % vs 540; one slice more spills into a second round and gives it all back).  In the train step these GEMMs run on
-    // the side stream under the dgrad chain, where a smaller footprint wins (step time: 432 <= 540 < 768), so that is the default.
-    // Narrow layers (an output side <= 256: the D = 192 models) take half as many: their reduce kernel reads every slab back and is a
-    // third of the side stream's time there (216: deit_tiny +1.5 %, cait_xxs24 +2.9 % same-box; 144: -2 %; at D = 384 288: -4 %).
-    const int target = min(M, N) <= 256 ? 216 : 432;
-    int s = target / tiles;
-    const int maxs = (K + 4 * BK - 1) / (4 * BK);      // at least 4 K-tiles per slice
-    if (s > maxs) s = maxs;
-    if (s < 1) s = 1;
-    // slices are BK-aligned chunks: drop the ones that would be empty (a partial-tile slice must always be written)
-    const int kchunk = (((K + s - 1) / s) + BK - 1) / BK * BK;
-    return (K + kchunk - 1) / kchunk;
-}
+// (pick_splitk, the K slices of a weight-gradient problem: gemm_layout.h)
 
 // Maps the runtime epilogue number to a compile-time constant: when epi is one of EPIS, rc = f(std::integral_constant<int, epi>()) and true;
 // false (f not called) for an epilogue the call site does not list -- the lists ARE the set of instantiated kernels.
@@ -731,6 +804,14 @@ extern "C" {
 // Test hook: force = 1 routes every shape the 224 x 128 kernel can legally take to it (tests/test_gpu_gemm.py covers its ragged edges at
 // shapes the cost model would give to other kernels); 0 restores the cost model.  Not thread-safe; never set on the product path.
 int ppf_gemm_test_force_g224(int force) { g_force_g224 = force != 0; return 0; }
+
+// Test hook: data path of the eight-wave weight-gradient kernel.  0 = dispatch as shipped, 1 = register-staged for every shape, 2 = LDS-DMA
+// for every shape it can take (K % 64 == 0; the others keep the register-staged kernel).  Not thread-safe; never set on the product path.
+int ppf_gemm_test_wgrad_path(int path) {
+    PPF_CHECK_ARG(path >= 0 && path <= 2, PPF_ERR_ARG, "ppf_gemm_test_wgrad_path: path must be 0, 1 or 2 (got %d)", path);
+    g_wgrad_path = path;
+    return 0;
+}
 
 // Bytes of split-K workspace ppf_gemm_bf16 needs for an accumulating (epi = 6) problem of this shape.
 size_t ppf_gemm_workspace_bytes(int M, int N, int K) {
