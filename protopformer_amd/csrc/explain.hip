@@ -23,6 +23,7 @@
 
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 namespace {
 
@@ -30,34 +31,13 @@ constexpr int NO_ID = INT_MAX;          // id of an unfilled list entry (sorts l
 constexpr int UNR = 4;                  // chunks whose loads are issued together (the wave's walk over P is a chain of memory round trips)
 constexpr int MAX_G = 8192;             // grid cells whose inverse index fits the static 48 KiB of LDS with room to spare
 
-// does (v, id) come before (w, jd) in the list order?
-__device__ __forceinline__ bool beats(float v, int id, float w, int jd) { return v > w || (v == w && id < jd); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Offers the candidate (v, id, pay) of every lane with `offered` set to the sorted list (sk, sid, sp) held one entry per lane (K entries).
+// Offers the candidate (v, id, pay) of every lane with `offered` set to the sorted list (sk, sid, sp) held one entry per lane (K entries):
+// the list steps of ppf_select.h, the payload shuffled from the source lane.
 __device__ __forceinline__ void offer_chunk(bool offered, float v, int id, float pay, int K, int lane, float& sk, int& sid, float& sp) {
-    const float kv = __shfl(sk, K - 1, 64);
-    const int ki = __shfl(sid, K - 1, 64);
-    unsigned long long surv = __ballot(offered && beats(v, id, kv, ki));
+    unsigned long long surv = list_survivors(offered, v, id, sk, sid, K);
     while (surv) {                                                            // wave-uniform loop over the survivors of the prefilter
-        const int src = __ffsll((long long)surv) - 1;
-        surv &= surv - 1;
-        const float cv = __shfl(v, src, 64), cp = __shfl(pay, src, 64);
-        const int cid = __shfl(id, src, 64);
-        // entries that come before the candidate: a prefix of the sorted list, so their count is the candidate's rank
-        const int rank = __popcll(__ballot(lane < K && beats(sk, sid, cv, cid)));
-        if (rank >= K) continue;                                              // the list moved on since the prefilter
-        const float uk = __shfl_up(sk, 1, 64), up = __shfl_up(sp, 1, 64);
-        const int ui = __shfl_up(sid, 1, 64);
-        if (lane < K) {
-            if (lane > rank) { sk = uk; sid = ui; sp = up; }
-            else if (lane == rank) { sk = cv; sid = cid; sp = cp; }
-        }
+        const ListCand<float> c = list_next(surv, v, id, pay, sk, sid, K, lane);
+        if (c.enters) list_place(c, K, lane, sk, sid, sp);
     }
 }
 

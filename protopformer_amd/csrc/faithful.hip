@@ -7,9 +7,9 @@
 //     contiguous run per pass -- and keeps the fp64 sum of its own token t = tid % T over the prototypes p = tid / T, + R, + 2R, ...  The R
 //     partial sums of a token meet in LDS and are added in ascending slice order by one thread, then rounded once to fp32.  Every product
 //     double(w) * double(a) of two fp32 values is exact, and every sum starts from +0 (a sum of -0 terms is +0, as numpy's).
-//     The cells are then ranked by counting in LDS as topk_sorted_kernel does: one 64-bit key per cell (tier, then the score's bits mapped
-//     to an ascending integer with -0 == +0 and NaN below -inf), rank = number of cells with a larger key, or the same key and a smaller
-//     cell.  The key is made from the fp32 score that is returned, so the order can be verified from the scores alone.
+//     The cells are then ranked by counting in LDS as topk_sorted_kernel does (count_before of ppf_select.h): one 64-bit key per cell (tier,
+//     then score_key: the score's bits mapped to an ascending integer with -0 == +0 and NaN below -inf), rank = number of cells with a larger
+//     key, or the same key and a smaller cell.  The key is made from the fp32 score that is returned, so the order can be verified from it.
 //   * patch_perturb_kernel: streaming.  A thread owns one 16-byte vector of x (it never straddles a cell: the patch width is a multiple
 //     of 4), reads it and the baseline once and writes it to all S * M copies from registers; counts [S] are wave-uniform loads.
 //     Workgroups of 128 threads: 294 of them at B = 1, 3 x 224 x 224.
@@ -21,6 +21,7 @@
 
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 namespace {
 
@@ -30,14 +31,6 @@ constexpr int NT_PERTURB = 128;
 constexpr int NT_PROB = 256;            // four rows per workgroup
 
 enum { MODE_EVIDENCE = 0, MODE_ATTENTION = 1, MODE_RANDOM = 2 };
-
-// ascending integer image of a score for the ranking: NaN lowest, then -inf .. -0 == +0 .. +inf
-__device__ __forceinline__ uint32_t score_key(float v) {
-    if (v != v) return 0u;
-    if (v == 0.0f) v = 0.0f;                                                  // -0 ranks as +0: the tie goes to the smaller cell
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);                        // -inf -> 0x007fffff, above the NaN key
-}
 
 // grid: B * M workgroups of NT_ORDER threads
 __global__ __launch_bounds__(NT_ORDER) void cell_order_kernel(const float* __restrict__ act_full, const int* __restrict__ idx,
@@ -103,12 +96,7 @@ __global__ __launch_bounds__(NT_ORDER) void cell_order_kernel(const float* __res
     }
     __syncthreads();
     if (tid < G) {
-        const unsigned long long mine = key[tid];
-        int rk = 0;
-        for (int j = 0; j < G; ++j) {
-            const unsigned long long kj = key[j];                             // the same address in every lane: a broadcast read
-            rk += (kj > mine) || (kj == mine && j < tid);
-        }
+        const int rk = count_before(key, G, tid);
         rank[out0 + tid] = rk;
         order[out0 + rk] = tid;                                               // the order is total: every rk in [0, G) is written once
     }
@@ -136,12 +124,6 @@ __global__ __launch_bounds__(NT_PERTURB) void patch_perturb_kernel(const float4*
             o[(size_t)st * copy] = make_float4(keep ? xv.x : bv.x, keep ? xv.y : bv.y, keep ? xv.z : bv.z, keep ? xv.w : bv.w);
         }
     }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // One wave per row.  grid: ceil(R / 4) workgroups of NT_PROB threads

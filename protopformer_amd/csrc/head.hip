@@ -7,6 +7,7 @@
 // All reductions run in a fixed order (per-sample partials + a single-workgroup tree), i.e. deterministic.
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 namespace {
 
@@ -141,12 +142,6 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* logits, const long
     for (int c = lane; c < C; c += 64) dlogits[(size_t)b * C + c] = (__expf(row[c] - lse) - (c == lab ? 1.0f : 0.0f)) * invB;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // Soft-target (target != nullptr, [B][C]) or label-smoothing (label + smoothing) cross-entropy: one wave per row as ce_kernel.  The row
 // statistics run in fp64 and lse - x_c is formed as (mx - x_c) + log(sum exp(x - mx)), so that logits of |x| ~ 3e4 lose nothing to the
 // cancellation of lse*sum(t) - sum(t*x), and every fp32 result is rounded once, from fp64.  The fp64 exp costs 7.4 against
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const float* logits, const
     const double mx = (double)wave_max(mxf);
     double s = 0.0;
     for (int c = lane; c < C; c += 64) s += exp((double)row[c] - mx);
-    const double ls = log(wave_sum_d(s));             // lse = mx + ls
+    const double ls = log(wave_sum_f64(s));           // lse = mx + ls
     const double invB = 1.0 / (double)B;
     if (target) {
         const float* t = target + (size_t)b * C;
@@ -172,8 +167,8 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const float* logits, const
             st += tc;
             acc += tc * ((mx - (double)row[c]) + ls);
         }
-        st = wave_sum_d(st);
-        acc = wave_sum_d(acc);
+        st = wave_sum_f64(st);
+        acc = wave_sum_f64(acc);
         if (lane == 0) per_sample[b] = (float)acc;
         for (int c = lane; c < C; c += 64)
             dlogits[(size_t)b * C + c] = (float)((exp((double)row[c] - mx - ls) * st - (double)t[c]) * invB);
@@ -185,8 +180,8 @@ __global__ __launch_bounds__(256) void soft_ce_kernel(const float* logits, const
             dsum += d;
             if (c == lab) dlab = d;
         }
-        dlab = wave_sum_d(dlab);
-        dsum = wave_sum_d(dsum);
+        dlab = wave_sum_f64(dlab);
+        dsum = wave_sum_f64(dsum);
         const double sm = (double)smoothing, conf = 1.0 - sm, off = sm / (double)C;
         if (lane == 0) per_sample[b] = (float)(conf * (dlab + ls) + sm * (dsum / (double)C + ls));
         for (int c = lane; c < C; c += 64)
@@ -211,12 +206,7 @@ __device__ __forceinline__ int wave_argmax_first(const float* row, int C, int la
         const float x = row[c];
         if (x > mx || at == 0x7fffffff) { mx = x; at = c; }        // strict >: a lane keeps the first index of its own maximum
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float omx = __shfl_xor(mx, o, 64);
-        const int oat = __shfl_xor(at, o, 64);
-        if (omx > mx || (omx == mx && oat < at)) { mx = omx; at = oat; }
-    }
+    wave_first(mx, at);
     mx_out = mx;
     return at;
 }
@@ -242,12 +232,10 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
         for (int c = lane; c < C; c += 64) {
             const float x = row[c];
             s += exp((double)x - mx);
-            ahead += (x > xt || (x == xt && c < t)) ? 1 : 0;
+            ahead += comes_before(x, c, xt, t) ? 1 : 0;
         }
-        ce += (mx - (double)xt) + log(wave_sum_d(s));              // lse - x_t as in soft_ce_kernel: nothing lost at |x| ~ 3e4
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ahead += __shfl_xor(ahead, o, 64);
-        hit5 += ahead < 5;
+        ce += (mx - (double)xt) + log(wave_sum_f64(s));            // lse - x_t as in soft_ce_kernel: nothing lost at |x| ~ 3e4
+        hit5 += wave_sum_i32(ahead) < 5;
         if (logits_global) hitg += wave_argmax_first(logits_global + (size_t)b * C, C, lane, mxf) == t;
         if (logits_local) hitl += wave_argmax_first(logits_local + (size_t)b * C, C, lane, mxf) == t;
     }

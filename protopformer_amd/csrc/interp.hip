@@ -17,8 +17,8 @@
 //     through LDS (equal values resolve to the smaller flat index = np.where(up == up.max())[..][0]), and optionally finishes with the
 //     part table of prototype_part_table (fused: the workgroup that found the peak tests it against its image's part list);
 //     act_box_kernel reduces the row / column extent of up >= thr; act_order_stats_kernel selects order statistics of the S*S fp32
-//     values exactly -- the 4-pass 8-bit radix select over order-preserving keys of rollout.hip, the map recomputed in every pass
-//     instead of being held (S*S values do not fit the registers), integer LDS atomics only.
+//     values exactly -- the 4-pass 8-bit radix select over order-preserving keys of rollout.hip (pass steps: ppf_select.h), the map
+//     recomputed in every pass instead of being held (S*S values do not fit the registers), integer LDS atomics only.
 //   * The stability score's two kernels live here too: gauss_noise_kernel adds N(0, sigma^2) noise that is a function of (seed, image id,
 //     element) alone (Philox4x32-10 + Box-Muller, accurate logf / sincospif), and part_meter_kernel adds a batch's part tables, and the
 //     row equality of a clean and a noisy table, into per-class int32 accumulators (interpret.PartMeter).
@@ -29,6 +29,7 @@
 
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 #pragma clang fp contract(off)
 
@@ -38,7 +39,7 @@ constexpr int NT = 256;          // threads per workgroup (4 waves)
 constexpr int BAND = 32;         // output rows per band
 constexpr int MAX_G = 64, MAX_S = 1024;
 constexpr int MAX_LDS = 48 << 10;   // dynamic LDS of a launch; with the 8 KiB of static histograms of the selection it stays inside 64 KiB
-constexpr int HCOPIES = 8, HSTRIDE = 257;      // histogram replicas of the radix select (odd pitch: replicas of a bin on different banks)
+constexpr int HCOPIES = 8;      // histogram replicas of the radix select (ppf_select.h)
 
 struct Lds {
     double* src;     // [g][g]
@@ -179,8 +180,6 @@ __device__ __forceinline__ unsigned char part_hit(const int* __restrict__ parts_
     return (valid != 0 && y0 <= py && py <= y1 && x0 <= px && px <= x1) ? 1 : 0;
 }
 
-__device__ __forceinline__ bool peak_before(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
 __global__ __launch_bounds__(NT) void act_peak_kernel(const float* __restrict__ grids, int g, int S, double ratio, float* __restrict__ peak_val,
                                                       int* __restrict__ peak_yx, const int* __restrict__ parts, int maps_per_img, int n_parts,
                                                       int half, unsigned char* __restrict__ table) {
@@ -200,21 +199,16 @@ __global__ __launch_bounds__(NT) void act_peak_kernel(const float* __restrict__ 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int i = row * S + col0 + q;
-                if (q < n && peak_before(v[q], i, bv, bi)) { bv = v[q]; bi = i; }
+                if (q < n && comes_before(v[q], i, bv, bi)) { bv = v[q]; bi = i; }
             }
         });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (peak_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+    wave_first(bv, bi);
     if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int w = 1; w < NT / 64; ++w)
-            if (peak_before(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
+            if (comes_before(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
         if (bi == INT_MAX) bi = 0;                        // nothing compared (NaNs only)
         const int y = bi / S, x = bi - y * S;
         peak_val[m] = bv;
@@ -279,17 +273,11 @@ __global__ __launch_bounds__(NT) void act_box_kernel(const float* __restrict__ g
 }
 
 // ---- order statistics of the S*S fp32 values
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t key) { return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key); }
-
 // ranks are 0-based in ascending order, k_lo <= k_hi <= k_lo + 1
 __global__ __launch_bounds__(NT) void act_order_stats_kernel(const float* __restrict__ grids, int g, int S, double ratio, int k_lo, int k_hi,
                                                              float* __restrict__ stats) {
     extern __shared__ __align__(16) unsigned char act_smem[];
-    __shared__ uint32_t hist[HCOPIES * HSTRIDE];
+    __shared__ uint32_t hist[HCOPIES * RADIX_HSTRIDE];
     __shared__ uint32_t misc[16];
     const int m = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const Lds L = act_carve(act_smem, g, S);
@@ -298,12 +286,11 @@ __global__ __launch_bounds__(NT) void act_order_stats_kernel(const float* __rest
     act_taps(T, L, g, S);
     uint32_t prefix = 0;
     int remaining = k_lo + 1;                             // 1-based rank among the keys that share the prefix
-    const int hcopy = (threadIdx.x & (HCOPIES - 1)) * HSTRIDE;
+    const int hcopy = radix_replica<HCOPIES>();
 #pragma unroll 1
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
-        for (int i = threadIdx.x; i < HCOPIES * HSTRIDE; i += NT) hist[i] = 0;
-        __syncthreads();
+        radix_clear<HCOPIES>(hist, NT);
         for (int r0 = 0; r0 < S; r0 += BAND)
             act_band(L, T, g, S, r0, min(BAND, S - r0), [&](int, int, const float (&v)[4], int n) {
 #pragma unroll
@@ -324,10 +311,11 @@ __global__ __launch_bounds__(NT) void act_order_stats_kernel(const float* __rest
                     }
                 }
             });
-        // inclusive scan of the 256 merged bins: one bin per thread, shuffles inside a wave, wave totals through misc
+        // The pass's closing scan, this kernel's own (every thread scans, a barrier behind the misc reads): through radix_close of
+        // ppf_select.h the kernel measured +1.3 % on near-constant maps against a parent spread of 0.7 % (MEASUREMENTS.md 5l).
         uint32_t cnt = 0;
 #pragma unroll
-        for (int c = 0; c < HCOPIES; ++c) cnt += hist[c * HSTRIDE + threadIdx.x];
+        for (int c = 0; c < HCOPIES; ++c) cnt += hist[c * RADIX_HSTRIDE + threadIdx.x];
         uint32_t cum = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {

@@ -16,6 +16,7 @@
 
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 namespace {
 
@@ -23,9 +24,6 @@ constexpr int TP = 32;                 // prototypes per workgroup
 constexpr int PW = 8;                  // prototypes per wave
 constexpr int CH = 64;                 // samples per staged chunk (one per lane)
 constexpr int LD = TP + 1;             // LDS leading dimension of the staged tile
-
-// does (v, id) come before (w, jd) in the list order?
-__device__ __forceinline__ bool beats(float v, int id, float w, int jd) { return v > w || (v == w && id < jd); }
 
 __global__ __launch_bounds__(256) void proto_topk_init_kernel(float* __restrict__ val, int* __restrict__ img, int* __restrict__ pos, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -35,7 +33,7 @@ __global__ __launch_bounds__(256) void proto_topk_init_kernel(float* __restrict_
     pos[i] = -1;
 }
 
-// grid: ceil(P / TP) workgroups of 256 threads
+// grid: ceil(P / TP) workgroups of 256 threads.  The list steps (survivors, rank, placement) are ppf_select.h's, shared with explain.hip.
 __global__ __launch_bounds__(256) void proto_topk_merge_kernel(const float* __restrict__ act_max, const int* __restrict__ argmax,
                                                                const int* __restrict__ idx, int k, const float* __restrict__ tok,
                                                                long long stride_b, int t0, int Dp, const long long* __restrict__ label,
@@ -79,30 +77,17 @@ __global__ __launch_bounds__(256) void proto_topk_merge_kernel(const float* __re
             if (p >= P) break;                                               // wave-uniform
             const float v = tile[lane * LD + wave * PW + q];
             const bool offered = row_in && (ppc <= 0 || my_label == (long long)(p / ppc));
-            const float kv = __shfl(sv[q], K - 1, 64);
-            const int ki = __shfl(si[q], K - 1, 64);
-            unsigned long long surv = __ballot(offered && beats(v, my_id, kv, ki));
+            unsigned long long surv = list_survivors(offered, v, my_id, sv[q], si[q], K);
             while (surv) {                                                    // wave-uniform loop over the survivors of the prefilter
-                const int src = __ffsll((long long)surv) - 1;
-                surv &= surv - 1;
-                const float cv = __shfl(v, src, 64);
-                const int cid = __shfl(my_id, src, 64);
-                // entries that come before the candidate: a prefix of the sorted list, so their count is the candidate's rank
-                const int rank = __popcll(__ballot(lane < K && beats(sv[q], si[q], cv, cid)));
-                if (rank >= K) continue;                                      // the list moved on since the prefilter
-                const int cb = b0 + src;
-                int cpos = -1;
-                if (argmax) {
+                ListCand<int> c = list_next(surv, v, my_id, -1, sv[q], si[q], K, lane);
+                if (!c.enters) continue;
+                const int cb = b0 + c.src;
+                if (argmax) {                                                 // the payload: looked up only for a candidate that enters
                     const int am = min(max(argmax[(size_t)cb * P + p], 0), k - 1);
-                    cpos = idx[(size_t)cb * k + am];
+                    c.pay = idx[(size_t)cb * k + am];
                 }
-                const float uv = __shfl_up(sv[q], 1, 64);
-                const int ui = __shfl_up(si[q], 1, 64), up = __shfl_up(sp[q], 1, 64);
-                if (lane < K) {
-                    if (lane > rank) { sv[q] = uv; si[q] = ui; sp[q] = up; }
-                    else if (lane == rank) { sv[q] = cv; si[q] = cid; sp[q] = cpos; }
-                }
-                if (rank == 0) best_b[q] = cb;
+                list_place(c, K, lane, sv[q], si[q], sp[q]);
+                if (c.rank == 0) best_b[q] = cb;
             }
         }
         __syncthreads();

@@ -11,14 +11,14 @@
 // sort of the reference), together with the 0/1 key policy for the next block.
 #include "ppf_common.h"
 #include "ppf_hip.h"
+#include "ppf_select.h"
 
 namespace {
 
 constexpr int NTHR = 1024, NWAVE = 16;
 constexpr int RPW = 14;      // rows per wave  (N <= 224)
 constexpr int CPL = 4;       // columns per lane (N <= 256)
-constexpr int HCOPIES = 16;  // histogram replicas
-constexpr int HSTRIDE = 257; // replica pitch (odd: replicas of one bin fall on different LDS banks)
+constexpr int HCOPIES = 16;  // histogram replicas (pitch RADIX_HSTRIDE)
 
 struct RolloutParams {
     const float* hm;         // [L][B][N][NP]
@@ -36,14 +36,10 @@ struct RolloutParams {
     float* policy;           // [B][1+Nk]
 };
 
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // Finds the key of the element with 1-based ascending rank `target` among the values for which valid(i) holds.
 // keys: per-thread register array; hist/scratch: LDS.  All threads must call; returns the key to every thread.
-// Padding entries are +inf (largest key): they are counted but can never be among the `target` smallest.
+// Padding entries are +inf (largest key): they are counted but can never be among the `target` smallest.  A pass is ppf_select.h's
+// shared steps (clear, replica offset, merge + scan + locate) around this kernel's own feed.
 template <int NV>
 __device__ uint32_t radix_select(const float (&v)[NV], int target, uint32_t* hist, uint32_t* misc) {
     uint32_t prefix = 0;
@@ -51,10 +47,8 @@ __device__ uint32_t radix_select(const float (&v)[NV], int target, uint32_t* his
 #pragma unroll 1
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
-        for (int i = threadIdx.x; i < HCOPIES * HSTRIDE; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-        const int hcopy = (threadIdx.x & (HCOPIES - 1)) * HSTRIDE;     // attention values cluster in 2-3 exponent bins: spread the
-                                                                    // LDS atomics over HCOPIES histogram replicas
+        radix_clear<HCOPIES>(hist, blockDim.x);
+        const int hcopy = radix_replica<HCOPIES>();                   // attention values cluster in 2-3 exponent bins: HCOPIES replicas
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const uint32_t key = order_key(v[i]);
@@ -63,35 +57,7 @@ __device__ uint32_t radix_select(const float (&v)[NV], int target, uint32_t* his
             if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // bound the live key/bin temporaries
         }
         __syncthreads();
-        // inclusive scan of the 256 bins by the first 4 waves
-        uint32_t cum = 0;
-        if (threadIdx.x < 256) {
-            const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-            uint32_t v = 0;
-#pragma unroll
-            for (int c = 0; c < HCOPIES; ++c) v += hist[c * HSTRIDE + threadIdx.x];
-            hist[threadIdx.x] = v;                                  // replica 0 now holds the merged bin (own slot only)
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t n = __shfl_up(v, o, 64);
-                if (lane >= o) v += n;
-            }
-            if (lane == 63) misc[w] = v;
-            cum = v;
-        }
-        __syncthreads();
-        if (threadIdx.x < 256) {
-            const int w = threadIdx.x >> 6;
-            uint32_t off = 0;
-            for (int j = 0; j < w; ++j) off += misc[j];
-            cum += off;
-            const uint32_t before = cum - hist[threadIdx.x];
-            if ((uint32_t)remaining > before && (uint32_t)remaining <= cum) { misc[8] = threadIdx.x; misc[9] = before; }
-        }
-        __syncthreads();
-        prefix = (prefix << 8) | misc[8];
-        remaining -= (int)misc[9];
-        __syncthreads();
+        radix_close<HCOPIES>(hist, misc, prefix, remaining);
     }
     return prefix;
 }
@@ -138,28 +104,16 @@ __device__ void rollout_emit(const RolloutParams& p, int b, const float* r, floa
     const int Nk = N - p.lead;
     if (tid < 256) vals[tid] = tid < Nk ? r[tid + p.lead] : -INFINITY;
     __syncthreads();
+    select_topk_ascending(vals, sel, Nk, p.k, p.idx + (size_t)b * p.k);
     if (tid < Nk) {
-        const float mine = vals[tid];
-        p.cls_attn[(size_t)b * Nk + tid] = mine;
-        int rank = 0;
-        for (int j = 0; j < Nk; ++j) {
-            const float o = vals[j];
-            rank += (o > mine) || (o == mine && j < tid);
-        }
-        sel[tid] = rank < p.k;
-    }
-    __syncthreads();
-    if (tid < Nk) {
-        int pos = 0;
-        for (int j = 0; j < tid; ++j) pos += sel[j];
-        if (sel[tid]) p.idx[(size_t)b * p.k + pos] = tid;
+        p.cls_attn[(size_t)b * Nk + tid] = vals[tid];
         p.policy[(size_t)b * (Nk + 1) + 1 + tid] = sel[tid] ? 1.0f : 0.0f;
     }
     if (tid == 0) p.policy[(size_t)b * (Nk + 1)] = 1.0f;
 }
 
 __global__ __launch_bounds__(NTHR) void rollout_kernel(const RolloutParams p) {
-    __shared__ uint32_t hist[HCOPIES * HSTRIDE];
+    __shared__ uint32_t hist[HCOPIES * RADIX_HSTRIDE];
     __shared__ uint32_t misc[16];
     __shared__ float r[256];               // current row vector
     __shared__ float rnew[NWAVE][256];     // per-wave partial column sums
@@ -229,7 +183,7 @@ __global__ __launch_bounds__(NTHR) void rollout_kernel(const RolloutParams p) {
 // on the chain): launched per layer right behind that layer's attn_headmean on the side stream, so that the rollout at the
 // reservation layer -- on the critical path -- is left with the row-vector chain only.  Same select, same key: identical results.
 __global__ __launch_bounds__(NTHR) void rollout_threshold_kernel(const float* __restrict__ f_layer, int N, int NP, int kdrop, uint32_t* __restrict__ thr_out) {
-    __shared__ uint32_t hist[HCOPIES * HSTRIDE];
+    __shared__ uint32_t hist[HCOPIES * RADIX_HSTRIDE];
     __shared__ uint32_t misc[16];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -260,18 +214,7 @@ __global__ __launch_bounds__(256) void topk_sorted_kernel(const float* scores, i
     const int tid = threadIdx.x, b = blockIdx.x;
     vals[tid] = tid < n ? scores[(size_t)b * n + tid] : -INFINITY;
     __syncthreads();
-    if (tid < n) {
-        const float mine = vals[tid];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) rank += (vals[j] > mine) || (vals[j] == mine && j < tid);
-        sel[tid] = rank < k;
-    }
-    __syncthreads();
-    if (tid < n && sel[tid]) {
-        int pos = 0;
-        for (int j = 0; j < tid; ++j) pos += sel[j];
-        idx[(size_t)b * k + pos] = tid;
-    }
+    select_topk_ascending(vals, sel, n, k, idx + (size_t)b * k);
 }
 
 }  // namespace

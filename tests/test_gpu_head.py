@@ -72,6 +72,64 @@ def test_rollout_with_precomputed_thresholds_is_identical():
         assert torch.equal(a, b)
 
 
+def _order_key_np(v):
+    """The kernels' order-preserving key of an fp32 array: negative values -> all bits flipped, the others -> sign bit set."""
+    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+
+
+@pytest.mark.parametrize("B,N,NP", [(3, 17, 20), (2, 197, 200)])
+def test_rollout_threshold_is_the_order_statistic_of_a_sort(B, N, NP):
+    """ppf_rollout_threshold against numpy's sort: the key of the int(N*N*0.9)-th smallest of the N x N valid entries of each sample (the
+    padding columns hold zeros, which would be among the smallest of the softmax maps and in the middle of the signed one).  Three maps:
+    a softmax, the same rounded to multiples of 1/64 (long runs of equal values: the selected rank falls inside a run), and a signed one
+    without -0.  Keys are integers: equality, no tolerance."""
+    from protopformer_amd import ops
+    g = torch.Generator().manual_seed(1000 + N)
+    soft = torch.softmax(2.0 * torch.randn(B, N, N, generator=g), dim=-1)
+    signed = torch.randn(B, N, N, generator=g)
+    signed[signed == 0] = 0.0                                               # any -0.0 becomes +0.0
+    kdrop = int(N * N * 0.9)
+    for name, m in (("softmax", soft), ("multiples of 1/64", torch.round(soft * 64) / 64), ("signed", signed)):
+        hm = torch.zeros(B, N, NP)
+        hm[..., :N] = m
+        thr = torch.empty(B, dtype=torch.int32, device="cuda")
+        ops.rollout_threshold(hm.cuda(), thr, N)
+        got = thr.cpu().numpy().view(np.uint32)
+        want = np.stack([_order_key_np(np.sort(m[b].numpy().reshape(-1))[kdrop - 1: kdrop])[0] for b in range(B)])
+        print(name, "got", got, "want", want)
+        assert np.array_equal(got, want), name
+
+
+def test_topk_ties_go_to_the_smaller_index():
+    """Known answers of the counting rule (an entry's rank = the entries with a larger score, or an equal score and a smaller index), through
+    ppf_topk_sorted and through the rollout.  The rollout case is the kernel's documented rule -- every entry <= the discard threshold is
+    dropped, ties in the top-k by smaller index -- and not the reference's torch.topk, whose tie order is unspecified."""
+    from protopformer_amd import ops
+    ninf = float("-inf")
+    g = torch.Generator().manual_seed(7)
+    near = torch.randperm(197, generator=g).float()                         # distinct scores 0 .. 196; rank r (0-based, descending) has score 196 - r
+    near[near == 196 - 81] = 196 - 80                                       # the 81st and the 82nd best are now equal
+    tied = torch.nonzero(near == 196 - 80).flatten().tolist()
+    cases = [(torch.tensor([1.0, 3.0, 3.0, 3.0, 0.0]), 2, [1, 2]),
+             (torch.full((256,), 0.25), 81, list(range(81))),
+             (near, 81, sorted(torch.nonzero(near > 196 - 80).flatten().tolist() + [min(tied)])),
+             (torch.tensor([ninf, 2.0, ninf, ninf, 5.0, ninf, ninf]), 4, [0, 1, 2, 4])]
+    assert len(tied) == 2
+    for row, k, want in cases:
+        got = ops.topk_sorted(row[None].cuda().contiguous(), k).cpu().tolist()
+        print(row.numel(), k, got)
+        assert got == [want], (row.numel(), k)
+
+    N, k = 17, 9
+    hm = torch.zeros(1, 1, N, 20)
+    hm[..., :N] = 1.0 / 17.0                                                # every entry ties with the threshold: all are dropped
+    cls_attn, idx, policy = ops.rollout(hm.cuda(), 1, 1, N, k, lead=1)
+    assert torch.equal(cls_attn.cpu(), torch.zeros(1, N - 1))
+    assert idx.cpu().tolist() == [list(range(k))]
+    assert policy.cpu().tolist() == [[1.0] * (1 + k) + [0.0] * (N - 1 - k)]
+
+
 def test_rollout_cait_golden():
     from protopformer_amd import ops
     z = load_npz("ops_real.npz")
