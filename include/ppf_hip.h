@@ -374,6 +374,29 @@ int ppf_cell_order(const float* act_full, const int* idx, const float* token_att
 int ppf_patch_perturb(const float* x, const int* rank, const int* counts, int S, int insertion, const float* baseline, float baseline_const, int B,
                       int M, int Cc, int H, int W, int G, float* out, ppf_stream_t stream);
 int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* prob, ppf_stream_t stream);
+/* Spatial alignment of prototypes (csrc/alignment.hip): the image gradient's last step and the two kernels of the misalignment test
+ * (Sacha et al., AAAI 2024): perturb only the pixels outside a prototype's box, follow its activation and its peak, and report the share
+ * of the pixel gradient inside the box; the forwards and backwards in between are the caller's.  The reference has no such pass.
+ * Additions of ABI 10: no existing entry point changed.
+ *   ppf_col2im_patch_f32  img fp32 [B][C][H][W] from cols fp32 [B*gh*gw][C*patch*patch]: the exact inverse of the column order
+ *                         ppf_im2col_patch / ppf_im2col_patch_f32 write (patch (gy, gx) row-major, columns (c, py, px)).  The patch
+ *                         stride equals the patch size, so every image element is written exactly once: no atomics, no zero fill.
+ *                         The image gradient is col2im(dtok . W_patch_embed) (autograd of deit:174).  patch divides H and W.
+ *   ppf_grad_box_mass     g fp32 [R][C][H][W], box int32 [R][4] = (y0, y1, x0, x1), half-open (the layout of ppf_act_box; the part
+ *                         outside the image is ignored; 16-byte aligned): per row total[r] = sum |g| and inside[r] = sum |g| over the box,
+ *                         both fp64.  A non-finite element counts as 0 in both sums; nonfinite[r] (int32, may be NULL) = how many there
+ *                         were.  One workgroup per row, fixed reduction order: repeated runs are bit-identical.  C*H*W <= 2^31 - 1.
+ *   ppf_pgd_step_box      one projected signed-gradient step on x fp32 [R][C][H][W] in place, x0 / g of the same shape, with per-channel
+ *                         alpha3 / eps3 / lo3 / hi3 fp32 [C] on the device and dir = +1 (ascend) or -1 (descend).  Outside the box of row r:
+ *                           x <- min(max(x + dir * alpha_c * sign(g), max(x0 - eps_c, lo_c)), min(x0 + eps_c, hi_c)),
+ *                         sign(+-0) = sign(NaN) = 0; inside the box: x <- x0.  Plain fp32, every operation rounded once (dir * alpha_c *
+ *                         sign is exact, so a fused multiply-add and the unfused form agree): bit-exact to interpret.pgd_step_box
+ *                         (device=False) for finite x and x0.  16-byte accesses when W % 4 == 0 and x, x0, g are 16-byte aligned. */
+int ppf_col2im_patch_f32(const float* cols, float* img, int B, int C, int H, int W, int patch, ppf_stream_t stream);
+int ppf_grad_box_mass(const float* g, const int* box, int R, int C, int H, int W, double* inside, double* total, int* nonfinite,
+                      ppf_stream_t stream);
+int ppf_pgd_step_box(float* x, const float* x0, const float* g, const int* box, const float* alpha3, const float* eps3, const float* lo3,
+                     const float* hi3, float dir, int R, int C, int H, int W, ppf_stream_t stream);
 /* last_layer / last_layer_global (protopformer.py:126-131, 314-316): C = alpha * A B^T + beta * C, arbitrary strides */
 int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, int64_t sam, int64_t sak, int64_t sbn, int64_t sbk,
               int ldc, float alpha, float beta, float* workspace, int64_t workspace_floats, ppf_stream_t stream);

@@ -1,0 +1,91 @@
+"""Do the prototypes look where they say they look?  The spatial-misalignment test (Sacha et al., AAAI 2024) over a split: for every
+image the strongest local prototypes of its predicted class, each with a box around the peak of its up-sampled activation map; the
+share of the pixel gradient of the prototype's activation that falls inside the box (against the box's share of the image area, what
+a spatially blind gradient would reach), and an attack that may change only the pixels OUTSIDE the box: how far the activation falls
+(PAC), how far the peak moves (PLC) and how often it leaves the box.  The reference has no such pass.
+
+Per pass one eval forward, one forward + backward for the gradients (`ppf_col2im_patch_f32` ends the backward, `ppf_grad_box_mass`
+sums the gradient) and per attack step one more forward + backward and one `ppf_pgd_step_box` (interpret.spatial_alignment); the rows
+stay on the device until the split is done.
+
+    python -m protopformer_amd.alignment --resume CKPT --data_set CUB2011U --data_path ... --output_dir OUT [--split test]
+                                         [--protos_per_image 3] [--half_size 36] [--attack_steps 10] [--eps 8] [--no-attack]
+                                         [--max_images N] [--precise]
+                                         + the model flags of train.py
+
+writes OUT/alignment.json: the image and row counts, the settings, and overall and per prototype the mean share, the mean area
+baseline, their ratio, the mean PAC, the mean PLC and the fraction of peaks that left the box."""
+import argparse
+import json
+import os
+
+import torch
+
+
+def get_args_parser():
+    from .train import get_args_parser as train_parser
+    p = argparse.ArgumentParser("ProtoPFormer spatial alignment: gradient locality and the misalignment attack", parents=[train_parser()])
+    a = p.add_argument
+    a("--split", type=str, default="test", choices=["train", "test"], help="which split is evaluated (no augmentation either way)")
+    a("--protos_per_image", type=int, default=3, help="the strongest local prototypes of the predicted class kept per image")
+    a("--half_size", type=int, default=36, help="the box reaches this many pixels to each side of the activation peak")
+    a("--attack_steps", type=int, default=10, help="signed-gradient steps of the attack (a forward and a backward each)")
+    a("--eps", type=float, default=8.0, help="L-inf budget of the attack in 1/255 pixel units")
+    a("--no-attack", dest="attack", action="store_false", default=True, help="gradient locality only")
+    a("--max_images", type=int, default=0, metavar="N", help="stop after N images (0: the whole split)")
+    a("--precise", action="store_true", default=False, help="run the model in the fp32 verification mode")
+    p.set_defaults(seed=0)
+    return p
+
+
+def summarize(result, args):
+    """The JSON record: counts, settings, the overall means and the per-prototype table (keys as strings, NaN as null)."""
+    def clean(d):
+        return {k: (None if isinstance(v, float) and v != v else v) for k, v in d.items()}
+    return dict(images=int(result["images"]), rows=int(result["rows"]),
+                settings=dict(protos_per_image=args.protos_per_image, half_size=args.half_size, attack=bool(args.attack), attack_steps=args.attack_steps,
+                              eps_255=args.eps, precise=bool(args.precise), split=args.split),
+                overall=clean(result["overall"]), per_prototype={str(p): clean(v) for p, v in sorted(result["per_prototype"].items())})
+
+
+def main(args, model=None, loader=None):
+    """loader: a ready iterable of (x, ...) batches with its model (tests, notebooks); by default both are built from the data flags as
+    the faithfulness tool builds them."""
+    from . import data as D
+    from . import engine as E
+    from .interpret import spatial_alignment
+    from .protopformer import construct_PPNet
+    from .train import set_seed
+    set_seed(args.seed)
+    device = torch.device(args.device)
+    if loader is not None and model is None:
+        raise ValueError("alignment.main: a ready loader comes with a ready model (the class count is the data set's)")
+    if loader is None:
+        view = D.build_view_transform(args)                # the eval geometry: Resize(256/224 * size) + CenterCrop
+        ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
+        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
+    if model is None:
+        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
+                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
+                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
+                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
+                                global_proto_per_class=args.global_proto_per_class,
+                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
+    model.to(device)
+    if args.resume:
+        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+    if args.precise:
+        model.precise = True
+    res = spatial_alignment(model, loader, protos_per_image=args.protos_per_image, half_size=args.half_size, attack=args.attack,
+                            attack_steps=args.attack_steps, eps=args.eps / 255.0, max_images=args.max_images, pass_images=args.batch_size)
+    os.makedirs(args.output_dir, exist_ok=True)
+    path = os.path.join(args.output_dir, "alignment.json")
+    with open(path, "w") as f:
+        json.dump(summarize(res, args), f, indent=1)
+    print(f"spatial alignment of {res['images']} {args.split} images ({res['rows']} image-prototype pairs): {path}", flush=True)
+    return path
+
+
+if __name__ == "__main__":
+    cli_args = get_args_parser().parse_args()
+    main(cli_args)

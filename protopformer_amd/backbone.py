@@ -505,7 +505,9 @@ def block_bwd(blk, store, L, dx, dyb, bias_done, below, *, next_dyb, attn_bwd, l
 
 
 def embed_bwd(ppnet, store, saved, dx, lead):
-    """Token assembly + patch embedding backward (dx fp32 [B*(Np+lead), D]), the last gradient chunk, and the lane joined."""
+    """Token assembly + patch embedding backward (dx fp32 [B*(Np+lead), D]), the last gradient chunk, and the lane joined.
+    Returns the image gradient fp32 [B, C, H, W] when the forward was asked for it (saved["img_shape"]: the image required a gradient),
+    else None: dcols = dtok W (fp32 out) and its col2im, two launches that exist on no other path."""
     feats = ppnet.features
     pe = feats.patch_embed
     Np, D = pe.num_patches, dx.shape[1]
@@ -513,15 +515,20 @@ def embed_bwd(ppnet, store, saved, dx, lead):
     dtok = ops.assemble_tokens_bwd(dx, gv(feats.pos_embed).reshape(Np + lead, D), gv(feats.cls_token).reshape(D) if lead else None,
                                    dx.shape[0] // (Np + lead), Np, D, lead)
     _wgrad(store, dtok, saved["cols"], pe.proj.weight, pe.proj.bias)
+    dimg = None
+    if saved.get("img_shape") is not None:
+        dcols = ops.gemm(dtok, store.w16(pe.proj.weight).reshape(D, -1), trans_b=True, epi=EPI_F32)
+        dimg = ops.col2im_patch(dcols, *saved["img_shape"], pe.patch_size)
     lane = wgrad_lane(store)
     gs = getattr(ppnet, "_grad_sync", None)
     if gs is not None:
         chunk_ready(gs, lane, gs.head_chunk)
     lane.join()
+    return dimg
 
 
 def deit_backward(ppnet, store, saved, df):
-    """Backward of image -> f. df: fp32 [B*(1+k), Dp] gradient w.r.t. the sigmoid outputs."""
+    """Backward of image -> f. df: fp32 [B*(1+k), Dp] gradient w.r.t. the sigmoid outputs.  Returns the image gradient or None (embed_bwd)."""
     feats = ppnet.features
     layers, head = saved["layers"], saved["head"]
     x_last = saved["x_last"]                      # [B, N, D] fp32 (pre-final-norm)
@@ -564,7 +571,7 @@ def deit_backward(ppnet, store, saved, df):
             chunk_ready(gs, lane, gs.block_chunk[i])
     if layers and layers[0]["rows"] is not None:          # reservation in front of block 0: the embedding sees all tokens
         dx = ops.scatter_rows(dx, layers[0]["rows"], B * (feats.patch_embed.num_patches + 1))
-    embed_bwd(ppnet, store, saved, dx, 1)
+    return embed_bwd(ppnet, store, saved, dx, 1)
 
 
 class TokensFn(torch.autograd.Function):
@@ -593,7 +600,9 @@ class TokensFn(torch.autograd.Function):
         x_out, cls_attn, idx, layers = fwd["blocks"](feats, store, x, layer, k, dp, save=need_bwd)
         f, head = head_tokens_fwd(ppnet, store, x_out, idx)
         if need_bwd:
-            saved.update(layers=layers, head=head, x_last=x_out, f=f)
+            # the image gradient (two more launches at the end of backward) only where the image itself asks for one
+            saved.update(layers=layers, head=head, x_last=x_out, f=f, img_shape=tuple(img.shape) if ctx.needs_input_grad[0] else None)
+            ctx.img_dtype = img.dtype
             ctx.saved = saved
             ctx.ppnet = ppnet
         ctx.mark_non_differentiable(cls_attn, idx)
@@ -604,9 +613,11 @@ class TokensFn(torch.autograd.Function):
         ppnet, saved = ctx.ppnet, ctx.saved
         store = ppnet.flat_store()
         store.attach_all_grads()
-        ppnet._arch_fns["backward"](ppnet, store, saved, df.contiguous().reshape(-1, df.shape[-1]))
+        dimg = ppnet._arch_fns["backward"](ppnet, store, saved, df.contiguous().reshape(-1, df.shape[-1]))
         ctx.saved = None
-        return (None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
+        if dimg is not None and dimg.dtype != ctx.img_dtype:
+            dimg = dimg.to(ctx.img_dtype)
+        return (dimg, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
 
 def t16_params(feats):

@@ -307,7 +307,7 @@ def cait_backward(ppnet, store, saved, df):
         dyb, bias_done = bwd(feats.blocks[i], store, sa[i], dx, dyb, bias_done, (feats.blocks[i - 1], sa[i - 1]) if i > 0 else None)
         if gs is not None and i in gs.block_chunk:
             chunk_ready(gs, lane, gs.block_chunk[i])
-    embed_bwd(ppnet, store, saved, dx, 0)
+    return embed_bwd(ppnet, store, saved, dx, 0)
 
 
 CAIT_FNS = dict(embed=functools.partial(embed_tokens, lead=0), blocks=cait_blocks_fwd, backward=cait_backward, t16_params=t16_params)

@@ -1144,3 +1144,309 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
         out["orders"].setdefault(order, {})[mode] = dict(curve=rows.mean(0).tolist(), auc=float(curve_auc(rows, cnt, G).mean()))
         out["per_image"].setdefault(order, {})[mode] = host[j]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ spatial alignment: does a cell's activation depend on its pixels?
+# Every token of a transformer backbone has attended to every other token before the prototype layer sees it, so a prototype's
+# activation at a grid cell need not depend on the pixels of that cell.  The spatial-misalignment benchmark (Sacha et al., AAAI 2024)
+# tests it: perturb only the pixels OUTSIDE the prototype's box and follow its activation (PAC, the relative activation change) and
+# its peak (PLC, the peak's displacement); next to it, the share of the pixel gradient that falls inside the box.  All of it rests on
+# the gradient with respect to the image, which the backbone's backward hands out when the image requires one (backbone.embed_bwd,
+# precise._embed_bwd: dcols = dtok W and ppf_col2im_patch_f32).  ppf_grad_box_mass and ppf_pgd_step_box (csrc/alignment.hip) do the
+# rest on the device; the numpy forms below (device=False) are the referees.  The reference has no such pass.
+def input_gradient(ppnet, x, target):
+    """Gradient of a model output with respect to the image: (grad fp32 [B, 3, H, W], value fp32 [B]) of x [B, 3, H, W] (CUDA).
+    target = ("logit", classes [B]): value = logits[b, classes[b]]; ("proto", "local" | "global", protos [B]): value = the prototype's
+    pooled activation act_max[b, protos[b]] of that branch.  Eval mode (DropPath off), ppnet.precise honoured; the backward of the
+    summed values is taken -- samples are independent, so row b is sample b's own gradient.
+    A backward accumulates weight gradients into the flat store and attaches .grad as any backward does, so this raises if a
+    parameter holds a pending gradient on entry -- a .grad with a non-zero (or NaN) element; the all-zero views the flat store attaches
+    when it is built do not count -- since a training step in flight would be corrupted, and sets every .grad back to None on exit."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError("input_gradient needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path)")
+    held = [(n, p.grad) for n, p in ppnet.named_parameters() if p.grad is not None]
+    if held:
+        # the flat store attaches zero-filled views when it is built (the first forward), and dropping an all-zero gradient loses nothing:
+        # a gradient is pending when it holds something.  One fused norm over the attached gradients and one read; only on a call that
+        # finds gradients attached (this function leaves none behind).
+        pending = (torch.stack(torch._foreach_norm([g.detach().float().reshape(-1) for _, g in held])) != 0).cpu().numpy()
+        if pending.any():
+            first = held[int(np.nonzero(pending)[0][0])][0]
+            raise RuntimeError(f"input_gradient: {int(pending.sum())} parameters already hold a .grad ({first}, ...): its backward accumulates into "
+                               "the same buffers; finish the training step and drop the gradients (zero_grad(set_to_none=True)) first")
+    B = x.shape[0]
+    kind = target[0] if isinstance(target, (tuple, list)) and target else None
+    if kind == "logit" and len(target) == 2:
+        branch, sel, n_out = None, target[1], ppnet.last_layer.weight.shape[0]
+    elif kind == "proto" and len(target) == 3 and target[1] in EXPLAIN_BRANCHES:
+        branch, sel = target[1], target[2]
+        n_out = ppnet.prototype_vectors.shape[0] if branch == "local" else ppnet.prototype_vectors_global.shape[0]
+    else:
+        raise ValueError('input_gradient: target must be ("logit", classes) or ("proto", "local" | "global", prototypes)')
+    sel = _explain_classes(sel, B, n_out, x.device)                       # [B, 1] int32, host values range-checked
+    if sel.shape[1] != 1:
+        raise ValueError(f"input_gradient: one target per sample expected, got {tuple(sel.shape)}")
+    xg = x.detach().float().contiguous().requires_grad_(True)
+    was_training = ppnet.training
+    ppnet.eval()
+    try:
+        with torch.enable_grad():
+            logits = ppnet._branches(xg, want_dist=False)[5]
+            out = logits if branch is None else ppnet._last_act_max[0 if branch == "local" else 1]
+            if out.grad_fn is None:
+                raise RuntimeError("input_gradient: the forward recorded no graph for the target")
+            value = out.gather(1, sel.long()).reshape(B)
+            value.sum().backward()
+    finally:
+        ppnet.train(was_training)
+        for p in ppnet.parameters():
+            p.grad = None
+    return xg.grad, value.detach()
+
+
+def _boxes_host(peaks_yx, half_size, size):
+    y, x = np.asarray(peaks_yx)[..., 0].astype(np.int64), np.asarray(peaks_yx)[..., 1].astype(np.int64)
+    return np.stack([np.maximum(y - half_size, 0), np.minimum(y + half_size, size), np.maximum(x - half_size, 0), np.minimum(x + half_size, size)],
+                    axis=-1).astype(np.int32)
+
+
+def _boxes_around(yx, half_size, size):
+    """int32 [R, 4] = (y0, y1, x0, x1), half-open: [peak - half_size, peak + half_size) clipped to the image, from peaks yx int32 [R, 2]."""
+    y, x = yx[:, 0], yx[:, 1]
+    return torch.stack([(y - half_size).clamp(min=0), (y + half_size).clamp(max=size), (x - half_size).clamp(min=0), (x + half_size).clamp(max=size)],
+                       dim=1).to(torch.int32).contiguous()
+
+
+def _proto_peaks(ppnet, outs, protos):
+    """The up-sampled peaks (values [R], yx int32 [R, 2]) of the local prototypes protos [B, K] on eval outputs: row r = b * K + j."""
+    from . import ops
+    B, K = protos.shape
+    k = ppnet.reserve_token_nums[0]
+    s = int(round(k ** 0.5))
+    act = outs["act_full"].reshape(B, -1, k)
+    own = torch.gather(act, 1, protos.long()[:, :, None].expand(B, K, k)).reshape(B, K, s, s)
+    grid = _grid_on_device(outs["token_attn"], own, k)
+    val, yx, _ = ops.act_peak(grid.reshape(B * K, grid.shape[-2], grid.shape[-1]), ppnet.img_size)
+    return val, yx
+
+
+def _proto_ids(who, ppnet, protos, B, device):
+    P = ppnet.prototype_vectors.shape[0]
+    t = protos if isinstance(protos, torch.Tensor) and protos.is_cuda else torch.as_tensor(np.asarray(protos)).to(device)
+    if t.is_floating_point() or t.dim() not in (1, 2) or t.shape[0] != B:
+        raise ValueError(f"{who}: protos must be integers [B] or [B, K] for a batch of {B}, got {tuple(t.shape)} {t.dtype}")
+    return (t[:, None] if t.dim() == 1 else t).to(torch.int32).contiguous(), P
+
+
+def prototype_boxes(ppnet, x_outputs, protos, half_size=36):
+    """int32 [R, 4] boxes (y0, y1, x0, x1), half-open, of the local prototypes protos [B] or [B, K] (row r = b * K + j): half_size pixels
+    to each side of the peak of the prototype's up-sampled activation map, clipped to the image -- the box rule of the consistency
+    score (prototype_part_table).  x_outputs: what one eval forward leaves (_eval_outputs: token_attn, act_full).  expand_to_grid of
+    the selected maps + one ppf_act_peak launch; stays on the device."""
+    protos, _ = _proto_ids("prototype_boxes", ppnet, protos, x_outputs["act_full"].shape[0], x_outputs["act_full"].device)
+    _, yx = _proto_peaks(ppnet, x_outputs, protos)
+    return _boxes_around(yx, int(half_size), int(ppnet.img_size))
+
+
+def box_mass_host(g, boxes):
+    """The numpy referee of ppf_grad_box_mass: (inside fp64 [R], total fp64 [R], nonfinite int32 [R]) of g [R, C, H, W], boxes [R, 4]."""
+    g, boxes = np.asarray(g, dtype=np.float32), np.asarray(boxes)
+    R, C, H, W = g.shape
+    fin = np.isfinite(g)
+    a = np.where(fin, np.abs(g), np.float32(0)).astype(np.float64)
+    ys, xs = np.arange(H)[None, :, None], np.arange(W)[None, None, :]
+    m = (ys >= boxes[:, 0, None, None]) & (ys < boxes[:, 1, None, None]) & (xs >= boxes[:, 2, None, None]) & (xs < boxes[:, 3, None, None])
+    return (a * m[:, None]).sum((1, 2, 3)), a.sum((1, 2, 3)), (~fin).sum((1, 2, 3)).astype(np.int32)
+
+
+def gradient_locality(grad, boxes, device=True):
+    """(inside, total, share) fp64 [R] of grad fp32 [R, C, H, W] and boxes int32 [R, 4]: the L1 mass of the gradient inside the box, its
+    total, and their ratio (NaN where total == 0); non-finite elements count as 0.  device=True: one ppf_grad_box_mass launch, device
+    tensors; device=False: the numpy referee."""
+    if not device:
+        g = grad.detach().cpu().numpy() if isinstance(grad, torch.Tensor) else grad
+        b = boxes.cpu().numpy() if isinstance(boxes, torch.Tensor) else boxes
+        inside, total, _ = box_mass_host(g, b)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return inside, total, np.where(total == 0, np.nan, inside / np.where(total == 0, 1.0, total))
+    from . import ops
+    inside, total, _ = ops.grad_box_mass(grad, boxes, want_nonfinite=False)
+    return inside, total, torch.where(total == 0, torch.full_like(total, float("nan")), inside / total)
+
+
+def pgd_step_box(x, x0, g, boxes, alpha, eps, lo, hi, direction, device=True):
+    """One projected signed-gradient step outside the boxes, the original pixel inside (ppf_pgd_step_box): per channel c
+    x <- min(max(x + direction * alpha_c * sign(g), max(x0 - eps_c, lo_c)), min(x0 + eps_c, hi_c)), sign(+-0) = sign(NaN) = 0.
+    device=True: in place on the CUDA tensor x, returns it.  device=False: the numpy referee, returns a new array (fp32 throughout,
+    every operation rounded once; for finite x and x0 bit-identical to the kernel)."""
+    if device:
+        from . import ops
+        return ops.pgd_step_box(x, x0, g, boxes, alpha, eps, lo, hi, direction)
+    if direction not in (1, -1):
+        raise ValueError(f"pgd_step_box: direction must be +1 or -1, got {direction!r}")
+    x, x0, g, boxes = (np.asarray(a) for a in (x, x0, g, boxes))
+    R, C, H, W = x.shape
+    a, e, l, h = (np.asarray(v, dtype=np.float32).reshape(1, C, 1, 1) for v in (alpha, eps, lo, hi))
+    x, x0, g = x.astype(np.float32), x0.astype(np.float32), g.astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        sign = (g > 0).astype(np.float32) - (g < 0).astype(np.float32)
+    moved = x + (np.float32(direction) * a) * sign
+    out = np.minimum(np.maximum(moved, np.maximum(x0 - e, l)), np.minimum(x0 + e, h)).astype(np.float32)
+    ys, xs = np.arange(H)[None, :, None], np.arange(W)[None, None, :]
+    m = (ys >= boxes[:, 0, None, None]) & (ys < boxes[:, 1, None, None]) & (xs >= boxes[:, 2, None, None]) & (xs < boxes[:, 3, None, None])
+    return np.where(m[:, None], x0, out)
+
+
+def attack_bounds(eps, alpha, steps, device=None, mean=None, std=None):
+    """The per-channel constants of the attack in normalised space, fp32 [3] each: (alpha, eps, lo, hi).  eps and alpha are in pixel
+    units ([0, 1] images) and are divided by the data-set std per channel; alpha defaults to 2.5 * eps / steps; lo / hi are the
+    normalised values of 0 and 1.  device None: numpy arrays."""
+    from .data import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
+    mean = np.asarray(IMAGENET_DEFAULT_MEAN if mean is None else mean, dtype=np.float64)
+    std = np.asarray(IMAGENET_DEFAULT_STD if std is None else std, dtype=np.float64)
+    if not (eps >= 0) or steps < 1:
+        raise ValueError(f"misalignment_attack: eps={eps} must be >= 0 and steps={steps} >= 1")
+    alpha = 2.5 * eps / steps if alpha is None else alpha
+    out = [(v).astype(np.float32) for v in (alpha / std, eps / std, (0.0 - mean) / std, (1.0 - mean) / std)]
+    return out if device is None else [torch.from_numpy(v).to(device) for v in out]
+
+
+def misalignment_attack(ppnet, x, protos, boxes, steps=10, eps=8 / 255, alpha=None, seed=None, return_images=False):
+    """The spatial-misalignment attack on local prototypes: `steps` signed-gradient steps that LOWER the prototype's activation, changing
+    only pixels outside its box, within eps (pixel units, L-inf) of the image and inside the valid pixel range.
+    x [B, 3, H, W] (CUDA, normalised); protos [B] or [B, K]; boxes int32 [R, 4] with row r = b * K + j (prototype_boxes).  Every row is
+    an attack of its own on a copy of its image.  seed None: start at the image; else a uniform start inside the eps-ball keyed by it.
+    Per step one input_gradient (a forward and a backward of R images) and one ppf_pgd_step_box launch with dir = -1.
+    Returns a dict of device tensors [R]: act_before, act_after, pac = (a0 - aT) / |a0|, peak_before / peak_after int32 [R, 2] (y, x of
+    the up-sampled peak), plc = their Chebyshev distance in pixels (int32), left_box (bool: the peak after lies outside the box),
+    boxes, protos; with return_images also images [R, 3, H, W]."""
+    from . import ops
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError("misalignment_attack needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path)")
+    B = x.shape[0]
+    protos, _ = _proto_ids("misalignment_attack", ppnet, protos, B, x.device)
+    K = protos.shape[1]
+    R = B * K
+    ops._dev_tensor("misalignment_attack", "boxes", boxes, torch.int32, (R, 4), x.device)
+    a3, e3, lo3, hi3 = attack_bounds(eps, alpha, steps, x.device)
+    x0 = x.detach().float().repeat_interleave(K, dim=0).contiguous()
+    rows = protos.reshape(R)
+    xr = x0.clone()
+    if seed is not None:
+        gen = torch.Generator(device=x.device).manual_seed(int(seed))
+        xr += (torch.rand(xr.shape, generator=gen, device=x.device) * 2 - 1) * e3.reshape(1, -1, 1, 1)
+        ops.pgd_step_box(xr, x0, ops.zeros(xr.shape, torch.float32, x.device), boxes, a3, e3, lo3, hi3, -1)       # a zero gradient: projection only
+    def measure(images):
+        with torch.no_grad():
+            outs = _eval_outputs(ppnet, images)
+            return outs["act_max"].gather(1, rows.long()[:, None]).reshape(R), _proto_peaks(ppnet, outs, rows[:, None])[1]
+    act0, yx0 = measure(x0)
+    for _ in range(int(steps)):
+        g, _ = input_gradient(ppnet, xr, ("proto", "local", rows))
+        ops.pgd_step_box(xr, x0, g, boxes, a3, e3, lo3, hi3, -1)
+    act1, yx1 = measure(xr)
+    plc = (yx1 - yx0).abs().max(dim=1)[0].to(torch.int32)
+    y, xx = yx1[:, 0], yx1[:, 1]
+    left = ~((y >= boxes[:, 0]) & (y < boxes[:, 1]) & (xx >= boxes[:, 2]) & (xx < boxes[:, 3]))
+    out = dict(act_before=act0, act_after=act1, pac=(act0.double() - act1.double()) / act0.double().abs(), peak_before=yx0, peak_after=yx1, plc=plc,
+               left_box=left, boxes=boxes, protos=rows)
+    if return_images:
+        out["images"] = xr
+    return out
+
+
+ALIGNMENT_STATS = ("share", "area", "pac", "plc", "left_box")
+
+
+def _regroup(loader, n, max_images):
+    """The loader's images in consecutive passes of exactly n images (the last may be shorter), whatever its own batch size: what
+    spatial_alignment computes then depends on the image sequence alone.  Yields fp32 batches on the device the loader's are on."""
+    held, have, seen = [], 0, 0
+    for x, *_ in loader:
+        if max_images and seen >= max_images:
+            break
+        x = x.float()
+        if max_images:
+            x = x[:max_images - seen]
+        seen += x.shape[0]
+        held.append(x); have += x.shape[0]
+        while have >= n:
+            full = torch.cat(held) if len(held) > 1 else held[0]
+            yield full[:n].contiguous()
+            held, have = ([full[n:]] if full.shape[0] > n else []), full.shape[0] - n
+    if have:
+        yield torch.cat(held).contiguous()
+
+
+def alignment_rows(ppnet, x, protos_per_image=3, half_size=36, attack=True, attack_steps=10, eps=8 / 255, alpha=None):
+    """The spatial-alignment measurements of one batch x [B, 3, H, W]: per image the predicted class's local prototypes ranked by
+    pooled activation (larger first, equal ones by smaller id), the first protos_per_image of them; one row per (image, prototype)
+    pair, row r = b * K + j.  Returns (protos int32 [R], stats fp64 [R, 5] on the device, columns ALIGNMENT_STATS: the gradient's share
+    inside the box (NaN for a zero gradient), box area / image area, PAC, PLC, peak left the box (0 / 1); the last three NaN without
+    the attack)."""
+    with torch.no_grad():
+        outs = _eval_outputs(ppnet, x)
+    B, ppc = x.shape[0], int(ppnet.num_prototypes_per_class)
+    K = min(int(protos_per_image), ppc)
+    own = outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
+    rank = torch.sort(outs["act_max"].gather(1, own), dim=1, descending=True, stable=True)[1][:, :K]
+    protos = own.gather(1, rank).to(torch.int32).contiguous()
+    boxes = prototype_boxes(ppnet, outs, protos, half_size)
+    rows = protos.reshape(-1)
+    grad, _ = input_gradient(ppnet, x.repeat_interleave(K, dim=0).contiguous(), ("proto", "local", rows))
+    _, _, share = gradient_locality(grad, boxes)
+    b64 = boxes.double()
+    area = (b64[:, 1] - b64[:, 0]) * (b64[:, 3] - b64[:, 2]) / float(x.shape[-1] * x.shape[-2])
+    nan = torch.full_like(share, float("nan"))
+    pac = plc = left = nan
+    if attack:
+        r = misalignment_attack(ppnet, x, protos, boxes, steps=attack_steps, eps=eps, alpha=alpha)
+        pac, plc, left = r["pac"], r["plc"].double(), r["left_box"].double()
+    return rows, torch.stack([share, area, pac, plc, left], dim=1)
+
+
+def alignment_summary(protos, stats):
+    """The report of spatial_alignment from all rows (device tensors protos [N], stats fp64 [N, 5]): fp64 sums on the device -- overall one
+    reduction over the rows in pair order, per prototype a one-hot product (no atomics: the same rows give the same bits) -- and ONE
+    read-back.  NaN entries (a zero gradient; no attack) are left out of their mean and counted out of its denominator."""
+    ok = ~torch.isnan(stats)
+    val = torch.where(ok, stats, torch.zeros_like(stats))
+    uniq, inv = torch.unique(protos.long(), return_inverse=True)                            # the prototypes that occurred, ascending
+    P, n = int(uniq.shape[0]), len(ALIGNMENT_STATS)
+    onehot = torch.nn.functional.one_hot(inv, P).double()                                    # [N, P]
+    packed = torch.cat([val.sum(0, keepdim=True), ok.double().sum(0, keepdim=True), onehot.t() @ val, onehot.t() @ ok.double(),
+                        uniq.double()[:, None].expand(P, n)]).cpu().numpy()
+
+    def means(s, c):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.where(c > 0, s / np.where(c > 0, c, 1.0), np.nan)
+        d = {f"mean_{k}": m[..., i] for i, k in enumerate(ALIGNMENT_STATS)}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d["share_over_area"] = d["mean_share"] / d["mean_area"]
+        d["rows"] = c[..., 1]                                                                # the area is never NaN: every row counts
+        return d
+    overall = {k: float(v) for k, v in means(packed[0], packed[1]).items()}
+    per = means(packed[2:2 + P], packed[2 + P:2 + 2 * P])
+    ids = packed[2 + 2 * P:, 0].astype(np.int64)
+    return dict(rows=int(overall.pop("rows")), overall=overall,
+                per_prototype={int(p): {k: (int(v[j]) if k == "rows" else float(v[j])) for k, v in per.items()} for j, p in enumerate(ids)})
+
+
+def spatial_alignment(ppnet, loader, protos_per_image=3, half_size=36, attack=True, attack_steps=10, eps=8 / 255, alpha=None, max_images=0,
+                      pass_images=16):
+    """The spatial-alignment test over a data set.  loader yields (x, ...); its images are regrouped into passes of pass_images images
+    (_regroup), so the result does not depend on the loader's batch size, and each pass is measured by alignment_rows.  The rows
+    stay on the device; their fp64 means are taken once at the end (alignment_summary) and read back once.  Returns dict(images, rows,
+    overall: mean_share, mean_area (box area / image area, the share a spatially blind gradient would reach), share_over_area, mean_pac,
+    mean_plc, mean_left_box; per_prototype: the same per prototype id that occurred, with its row count)."""
+    ids, stats, images = [], [], 0
+    for x in _regroup(loader, int(pass_images), int(max_images)):
+        x = x if x.is_cuda else x.cuda()
+        p, s = alignment_rows(ppnet, x, protos_per_image, half_size, attack, attack_steps, eps, alpha)
+        ids.append(p); stats.append(s)
+        images += x.shape[0]
+    if not images:
+        raise ValueError("spatial_alignment: the loader gave no image")
+    out = alignment_summary(torch.cat(ids), torch.cat(stats))
+    out["images"] = images
+    return out

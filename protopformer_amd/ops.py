@@ -609,6 +609,57 @@ def class_prob(logits, cls):
     return prob
 
 
+# ---- spatial alignment (csrc/alignment.hip): the image gradient's last step, gradient mass inside a box, the attack's step
+def col2im_patch(cols, B, C, H, W, patch):
+    """img fp32 [B, C, H, W] from cols fp32 [B*(H/patch)*(W/patch), C*patch*patch]: the inverse of im2col_patch / im2col_patch_f32
+    (ppf_col2im_patch_f32); one launch, every element written once."""
+    who = "col2im_patch"
+    B, C, H, W, patch = int(B), int(C), int(H), int(W), int(patch)
+    if min(B, C, H, W, patch) < 1 or H % patch or W % patch:
+        raise ValueError(f"{who}: bad shape B={B} C={C} H={H} W={W} patch={patch} (patch must divide H and W)")
+    _dev_tensor(who, "cols", cols, torch.float32, (B * (H // patch) * (W // patch), C * patch * patch))
+    img = torch.empty((B, C, H, W), dtype=torch.float32, device=cols.device)
+    _lib.call("ppf_col2im_patch_f32", cols, img, B, C, H, W, patch)
+    return img
+
+
+def _rows_and_boxes(who, name, t, box):
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{who}: {name} must be an fp32 CUDA tensor [R, C, H, W]")
+    _dev_tensor(who, name, t, torch.float32, t.shape)
+    _dev_tensor(who, "box", box, torch.int32, (t.shape[0], 4), t.device)
+    return tuple(t.shape)
+
+
+def grad_box_mass(g, box, want_nonfinite=True):
+    """(inside fp64 [R], total fp64 [R], nonfinite int32 [R] or None) of g fp32 [R, C, H, W] and box int32 [R, 4] = (y0, y1, x0, x1),
+    half-open (ppf_grad_box_mass): sums of |g|, non-finite elements left out and counted; one launch, fixed order."""
+    who = "grad_box_mass"
+    R, C, H, W = _rows_and_boxes(who, "g", g, box)
+    inside = torch.empty(R, dtype=torch.float64, device=g.device)
+    total = torch.empty_like(inside)
+    bad = torch.empty(R, dtype=torch.int32, device=g.device) if want_nonfinite else None
+    if R > 0:
+        _lib.call("ppf_grad_box_mass", g, box, R, C, H, W, inside, total, bad)
+    return inside, total, bad
+
+
+def pgd_step_box(x, x0, g, box, alpha, eps, lo, hi, direction):
+    """One projected signed-gradient step on x fp32 [R, C, H, W] IN PLACE outside box int32 [R, 4]; inside it x <- x0 (ppf_pgd_step_box).
+    alpha / eps / lo / hi: fp32 device tensors [C]; direction +1 or -1.  Returns x."""
+    who = "pgd_step_box"
+    R, C, H, W = _rows_and_boxes(who, "x", x, box)
+    for name, t in (("x0", x0), ("g", g)):
+        _dev_tensor(who, name, t, torch.float32, x.shape, x.device)
+    for name, t in (("alpha", alpha), ("eps", eps), ("lo", lo), ("hi", hi)):
+        _dev_tensor(who, name, t, torch.float32, (C,), x.device)
+    if direction not in (1, -1):
+        raise ValueError(f"{who}: direction must be +1 or -1, got {direction!r}")
+    if R > 0:
+        _lib.call("ppf_pgd_step_box", x, x0, g, box, alpha, eps, lo, hi, float(direction), R, C, H, W)
+    return x
+
+
 # ---- interpretability post-processing (csrc/interp.hip): activation maps [M, g, g] fp32 -> S x S, bit-identical to interpret.resize_cubic
 def _act_maps(name, grids, size):
     """(M, g, S) of the maps handed to a ppf_act_* entry point.  What the C side cannot see -- layout and dtype -- is refused here with

@@ -75,6 +75,14 @@ def _linear_bwd(store, dy, x, lin, want_dx=True):
     return ops.linear_dgrad_f32(dy, lin.weight) if want_dx else None
 
 
+def _embed_bwd(store, saved, dtok, pe):
+    """PatchEmbed backward: its weight gradients, and the image gradient fp32 [B, C, H, W] = col2im(dtok W) when the forward was asked
+    for it (saved["img_shape"]: the image required a gradient), else None."""
+    want = saved.get("img_shape") is not None
+    dcols = _linear_bwd(store, dtok, saved["cols"], pe.proj, want_dx=want)
+    return ops.col2im_patch(dcols, *saved["img_shape"], pe.patch_size) if want else None
+
+
 def _head_bwd(ppnet, store, saved, df, rows_total, D):
     """add-on conv + sigmoid + final norm on the reserved rows: gradient w.r.t. the last token matrix (rows outside the reservation zero)."""
     feats = ppnet.features
@@ -130,7 +138,7 @@ def deit_backward_f32(ppnet, saved, df):
     Np = pe.num_patches
     ops.assemble_tokens_bwd(dx, _gv(store, feats.pos_embed), _gv(store, feats.cls_token), B, Np, D, 1)       # dpos / dcls (fp32, fixed order)
     dtok = dx.reshape(B, N, D)[:, 1:].reshape(B * Np, D).contiguous()
-    _linear_bwd(store, dtok, saved["cols"], pe.proj, want_dx=False)
+    return _embed_bwd(store, saved, dtok, pe)
 
 
 class PreciseTokensFn(torch.autograd.Function):
@@ -141,15 +149,19 @@ class PreciseTokensFn(torch.autograd.Function):
         saved = {} if any(ctx.needs_input_grad) else None
         ctx.deit = _is_deit(ppnet)
         f, cls_attn, idx = (deit_tokens if ctx.deit else cait_tokens)(ppnet, img, dp, saved)
-        ctx.saved, ctx.ppnet = saved, ppnet
+        if saved is not None:
+            saved["img_shape"] = tuple(img.shape) if ctx.needs_input_grad[0] else None
+        ctx.saved, ctx.ppnet, ctx.img_dtype = saved, ppnet, img.dtype
         ctx.mark_non_differentiable(cls_attn, idx)
         return f, cls_attn, idx
 
     @staticmethod
     def backward(ctx, df, _dcls, _didx):
-        (deit_backward_f32 if ctx.deit else cait_backward_f32)(ctx.ppnet, ctx.saved, df.contiguous().reshape(-1, df.shape[-1]).float())
+        dimg = (deit_backward_f32 if ctx.deit else cait_backward_f32)(ctx.ppnet, ctx.saved, df.contiguous().reshape(-1, df.shape[-1]).float())
         ctx.saved = None
-        return (None,) * len(ctx.needs_input_grad)
+        if dimg is not None and dimg.dtype != ctx.img_dtype:
+            dimg = dimg.to(ctx.img_dtype)
+        return (dimg,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
 def cait_tokens(ppnet, img, dp, saved=None):
@@ -254,7 +266,7 @@ def cait_backward_f32(ppnet, saved, df):
         dn1 = _linear_bwd(store, dqkv, n1, a.qkv)
         ops.layernorm_bwd_f32(dn1, x_in, blk.norm1.weight, _gv(store, blk.norm1.weight), _gv(store, blk.norm1.bias), dx, dres_in=dx, eps=LN_EPS)
     ops.assemble_tokens_bwd(dx, _gv(store, feats.pos_embed), None, B, N, D, 0)
-    _linear_bwd(store, dx, saved["cols"], feats.patch_embed.proj, want_dx=False)
+    return _embed_bwd(store, saved, dx, feats.patch_embed)
 
 
 def _is_deit(ppnet):
@@ -263,6 +275,6 @@ def _is_deit(ppnet):
 
 
 def tokens(ppnet, img, dp):
-    if torch.is_grad_enabled() and any(p.requires_grad for p in ppnet.parameters()):
+    if torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for p in ppnet.parameters())):
         return PreciseTokensFn.apply(img, ppnet, dp, *ppnet._hook_params())
     return (deit_tokens if _is_deit(ppnet) else cait_tokens)(ppnet, img, dp)
