@@ -23,16 +23,16 @@ import torch
 
 
 def get_args_parser():
+    from .tooling import add_split_flags
     from .train import get_args_parser as train_parser
     p = argparse.ArgumentParser("ProtoPFormer spatial alignment: gradient locality and the misalignment attack", parents=[train_parser()])
     a = p.add_argument
-    a("--split", type=str, default="test", choices=["train", "test"], help="which split is evaluated (no augmentation either way)")
+    add_split_flags(p, "test", "evaluated")
     a("--protos_per_image", type=int, default=3, help="the strongest local prototypes of the predicted class kept per image")
     a("--half_size", type=int, default=36, help="the box reaches this many pixels to each side of the activation peak")
     a("--attack_steps", type=int, default=10, help="signed-gradient steps of the attack (a forward and a backward each)")
     a("--eps", type=float, default=8.0, help="L-inf budget of the attack in 1/255 pixel units")
     a("--no-attack", dest="attack", action="store_false", default=True, help="gradient locality only")
-    a("--max_images", type=int, default=0, metavar="N", help="stop after N images (0: the whole split)")
     a("--precise", action="store_true", default=False, help="run the model in the fp32 verification mode")
     p.set_defaults(seed=0)
     return p
@@ -51,29 +51,16 @@ def summarize(result, args):
 def main(args, model=None, loader=None):
     """loader: a ready iterable of (x, ...) batches with its model (tests, notebooks); by default both are built from the data flags as
     the faithfulness tool builds them."""
-    from . import data as D
-    from . import engine as E
     from .interpret import spatial_alignment
-    from .protopformer import construct_PPNet
+    from .tooling import eval_loader, load_for_eval, model_from_args
     from .train import set_seed
     set_seed(args.seed)
     device = torch.device(args.device)
     if loader is not None and model is None:
         raise ValueError("alignment.main: a ready loader comes with a ready model (the class count is the data set's)")
     if loader is None:
-        view = D.build_view_transform(args)                # the eval geometry: Resize(256/224 * size) + CenterCrop
-        ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
-        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
-    if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
-                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
-    model.to(device)
-    if args.resume:
-        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+        _, nb_classes, loader = eval_loader(args, device, with_ids=False)
+    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     if args.precise:
         model.precise = True
     res = spatial_alignment(model, loader, protos_per_image=args.protos_per_image, half_size=args.half_size, attack=args.attack,

@@ -227,28 +227,14 @@ def get_args_parser():
 
 
 def main(args, model=None):
-    from . import data as D
     from . import engine as E
     from .interpret import nearest_patches
-    from .protopformer import construct_PPNet
+    from .tooling import eval_loader, load_for_eval, model_from_args
     from .train import set_seed
     set_seed(args.seed)
     device = torch.device(args.device)
-    view = D.build_view_transform(args)                    # the eval geometry: Resize(256/224 * size) + CenterCrop
-    ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
-    if hasattr(ds, "return_id"):
-        ds.return_id = True
-    loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
-    if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
-                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
-    model.to(device)
-    if args.resume:
-        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+    ds, nb_classes, loader = eval_loader(args, device)
+    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     bank = nearest_patches(model, loader, topk=args.topk, class_specific=not args.all_classes)
     result = bank.result()
     index = image_index(ds)
@@ -256,7 +242,7 @@ def main(args, model=None):
     npz, js = write_bank(args.output_dir, result, index, bank.ppc, bank.side, patch)
     print(f"prototype bank over {len(ds)} {args.split} images: {npz} {js}", flush=True)
     if args.gallery:
-        written = write_gallery(args.output_dir, result, index, view, bank.side, patch)
+        written = write_gallery(args.output_dir, result, index, ds.transform, bank.side, patch)
         print(f"gallery: {len(written)} images under {args.output_dir}", flush=True)
     if args.project:
         n = bank.project_(model)

@@ -20,14 +20,14 @@ import torch
 
 
 def get_args_parser():
+    from .tooling import add_split_flags
     from .train import get_args_parser as train_parser
     p = argparse.ArgumentParser("ProtoPFormer local analysis: the prototypes behind each image's top classes", parents=[train_parser()])
     a = p.add_argument
-    a("--split", type=str, default="train", choices=["train", "test"], help="which split is explained (no augmentation either way)")
+    add_split_flags(p, "train", "explained")
     a("--topk", type=int, default=10, help="prototypes listed per (image, class) and branch (1..64)")
     a("--top_classes", type=int, default=1, help="classes explained per image, by logit (1..8)")
     a("--against", action="store_true", default=False, help="rank the strongest evidence against each class instead of for it")
-    a("--max_images", type=int, default=0, metavar="N", help="stop after N images (0: the whole split)")
     a("--bank", type=str, default="", metavar="PATH", help="prototype_bank.npz of the bank tool: attach each prototype's nearest training patches")
     a("--render", action="store_true", default=False, help="also write img_<id>/class<c>_rank<r>.jpg activation overlays")
     return p
@@ -69,42 +69,24 @@ def main(args, model=None, loader=None, index=None):
     """loader / index: a ready iterable of (x, labels[, ids]) CUDA batches and its {image id: (path, label)} (tests, notebooks); by
     default both are built from the data flags as the bank tool builds them."""
     from . import data as D
-    from . import engine as E
     from .bank import image_index
     from .interpret import explain
-    from .protopformer import construct_PPNet
+    from .tooling import eval_loader, load_for_eval, model_from_args, take_images
     from .train import set_seed
     set_seed(args.seed)
     device = torch.device(args.device)
     if loader is not None and model is None:
         raise ValueError("explain.main: a ready loader comes with a ready model (the class count is the data set's)")
     if loader is None:
-        view = D.build_view_transform(args)                # the eval geometry: Resize(256/224 * size) + CenterCrop
-        ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
-        if hasattr(ds, "return_id"):
-            ds.return_id = True
-        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
+        ds, nb_classes, loader = eval_loader(args, device)
         index = image_index(ds)
-    if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
-                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
-    model.to(device)
-    if args.resume:
-        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     bank = dict(np.load(args.bank)) if args.bank else None
     index = index or {}
     os.makedirs(args.output_dir, exist_ok=True)
     path, seen, rendered = os.path.join(args.output_dir, "explanations.jsonl"), 0, 0
     with open(path, "w") as out:
-        for x, y, *rest in loader:
-            if args.max_images and seen >= args.max_images:
-                break
-            if args.max_images:
-                x, y, rest = x[:args.max_images - seen], y[:args.max_images - seen], [r[:args.max_images - seen] for r in rest]
+        for x, y, *rest in take_images(loader, args.max_images):
             B = x.shape[0]
             ids = np.asarray(torch.as_tensor(rest[0]).cpu()) if rest else np.arange(seen, seen + B)
             ex = explain(model, x if x.is_cuda else x.to(device), top_classes=args.top_classes, topk=args.topk, against=args.against, maps=args.render)

@@ -24,15 +24,15 @@ import torch
 
 def get_args_parser():
     from .interpret import CURVE_MODES, ORDER_MODES
+    from .tooling import add_split_flags
     from .train import get_args_parser as train_parser
     p = argparse.ArgumentParser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", parents=[train_parser()])
     a = p.add_argument
-    a("--split", type=str, default="test", choices=["train", "test"], help="which split is evaluated (no augmentation either way)")
+    add_split_flags(p, "test", "evaluated")
     a("--steps", type=int, default=14, help="the curves have steps + 1 points: 0, G/steps, ... G cells removed / shown")
     a("--orders", type=str, nargs="+", default=list(ORDER_MODES), choices=list(ORDER_MODES), help="cell orders to evaluate (random is the control)")
     a("--modes", type=str, nargs="+", default=list(CURVE_MODES), choices=list(CURVE_MODES))
     a("--against_label", action="store_true", default=False, help="follow the probability of the image's label instead of its top class")
-    a("--max_images", type=int, default=0, metavar="N", help="stop after N images (0: the whole split)")
     a("--per-image", dest="per_image", action="store_true", default=False, help="also write faithfulness.npz with every image's curves")
     p.set_defaults(seed=0)                                 # keys the random order (train.py's --seed, with this tool's default)
     return p
@@ -57,31 +57,16 @@ def summarize(result):
 def main(args, model=None, loader=None):
     """loader: a ready iterable of (x, labels[, ids]) CUDA batches with its model (tests, notebooks); by default both are built from the
     data flags as the explain tool builds them."""
-    from . import data as D
-    from . import engine as E
     from .interpret import default_counts, faithfulness
-    from .protopformer import construct_PPNet
+    from .tooling import eval_loader, load_for_eval, model_from_args
     from .train import set_seed
     set_seed(args.seed)
     device = torch.device(args.device)
     if loader is not None and model is None:
         raise ValueError("faithfulness.main: a ready loader comes with a ready model (the class count is the data set's)")
     if loader is None:
-        view = D.build_view_transform(args)                # the eval geometry: Resize(256/224 * size) + CenterCrop
-        ds, nb_classes = D.build_dataset(args.split == "train", args, transform=view)
-        if hasattr(ds, "return_id"):
-            ds.return_id = True
-        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
-    if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
-                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
-    model.to(device)
-    if args.resume:
-        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+        _, nb_classes, loader = eval_loader(args, device)
+    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes), counts=default_counts(model.num_patches, args.steps),
                        against_label=args.against_label, seed=args.seed, max_images=args.max_images)
     os.makedirs(args.output_dir, exist_ok=True)

@@ -81,19 +81,12 @@ def main(args, model=None):
     from . import data as D
     from . import engine as E
     from .interpret import CubParts, interpretability_scores
-    from .protopformer import construct_PPNet
+    from .tooling import load_for_eval, model_from_args
     device = torch.device("cuda")
     nb_classes, n_parts, half_size, part_thresh = 200, 15, 36, 0.8
     if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=True, img_size=args.input_size,
-                                prototype_shape=args.prototype_shape, num_classes=nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
-    model.to(device)
-    if args.resume:
-        E.load_checkpoint(args.resume, model, strict=True, eval_only=True)
+        model = model_from_args(args, nb_classes, img_size=args.input_size, pretrained=True)
+    load_for_eval(model, args, device)
     model.eval()
     root, meta = cub_dirs(args.data_path)
     view = D.build_view_transform(args, square=True)          # the reference's Resize((size, size)); GpuFinisher normalises

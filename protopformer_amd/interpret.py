@@ -11,6 +11,8 @@ import os
 import numpy as np
 import torch
 
+from .tooling import take_images
+
 
 # ------------------------------------------------------------------------------------------------ activation maps
 def reserved_indices(token_attn, k):
@@ -247,6 +249,15 @@ def consistency_from_tables(tables, masks, part_thresh=0.8):
     return effect, max_part
 
 
+def own_prototype_maps(ppnet, x, targets):
+    """push_forward(x) with every image's maps narrowed to the prototypes of its own class: (attn (B, Np) rollout scores, own
+    (B, ppc, s, s) activations of prototypes targets[b] * ppc ... + ppc - 1)."""
+    ppc = ppnet.num_prototypes_per_class
+    ta, pa = ppnet.push_forward(x)
+    cols = (targets.to(pa.device) * ppc)[:, None] + torch.arange(ppc, device=pa.device)[None, :]
+    return ta, torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1]))
+
+
 @torch.no_grad()
 def consistency_score(ppnet, loader, parts, image_sizes, num_classes=200, part_thresh=0.8, half_size=36, n_parts=15, device=False):
     """eval_interpretability.py:136-290: push_forward over the test set, the class's own prototypes expanded to the patch grid, the
@@ -258,10 +269,8 @@ def consistency_score(ppnet, loader, parts, image_sizes, num_classes=200, part_t
     ppc, k, img_size = ppnet.num_prototypes_per_class, ppnet.reserve_token_nums[0], ppnet.img_size
     attn, acts, targets, ids, tables, masks = [], [], [], [], [], []
     for x, t, i in loader:
-        ta, pa = ppnet.push_forward(x.cuda() if not x.is_cuda else x)
         t = torch.as_tensor(t)
-        cols = (t.to(pa.device) * ppc)[:, None] + torch.arange(ppc, device=pa.device)[None, :]
-        own = torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1]))
+        ta, own = own_prototype_maps(ppnet, x.cuda() if not x.is_cuda else x, t)
         targets.append(t.cpu()); ids.append(torch.as_tensor(i).cpu())
         if device:
             tb, mk = _device_tables(_grid_on_device(ta, own, k), ids[-1].numpy(), parts, image_sizes, img_size, half_size, n_parts)
@@ -284,31 +293,15 @@ def consistency_from_outputs(attn, acts, targets, ids, parts, image_sizes, k, im
     reference's loop assumes every class has one).
     device=True: attn / acts go to (or stay on) the GPU, expand_to_grid runs there, one ppf_act_peak launch makes every part table, and
     only the (B, ppc, n_parts) uint8 tables are read back; the grid is returned as a CUDA tensor.  Same score, effects and fractions."""
-    if device:
-        attn, acts = torch.as_tensor(attn).cuda(), torch.as_tensor(acts).cuda()
-        targets, ids = np.asarray(targets), np.asarray(ids)
-        grid = _grid_on_device(attn, acts, k)
-        tables, masks = _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts)
-        return _score_from_tables(tables.cpu().numpy(), masks, targets, num_classes, part_thresh) + (grid,)
-    attn, acts = torch.as_tensor(attn), torch.as_tensor(acts)
     targets, ids = np.asarray(targets), np.asarray(ids)
-    grid = expand_to_grid(acts.float(), attn.float(), k).numpy() if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts.numpy()
-    effects, max_parts = [], []
-    for c in range(num_classes):
-        sel = np.nonzero(targets == c)[0]
-        if sel.size == 0:
-            continue
-        tables, masks = [], []
-        for j in sel:
-            w, h = image_sizes[int(ids[j])]
-            mask, labels = np.zeros(n_parts), []
-            for pid, x, y in parts.id_to_part_loc.get(int(ids[j]), []):
-                mask[pid - 1] = 1
-                labels.append((pid - 1, int(img_size * (x / w)), int(img_size * (y / h))))
-            tables.append(prototype_part_table(grid[j], labels, img_size, half_size, n_parts)); masks.append(mask)
-        e, m = consistency_from_tables(tables, masks, part_thresh)
-        effects.extend(e); max_parts.extend(m)
-    return (float(np.mean(effects)) if effects else 0.0), effects, max_parts, grid
+    if device:
+        grid = _grid_on_device(torch.as_tensor(attn).cuda(), torch.as_tensor(acts).cuda(), k)
+        tables, masks = _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts)
+        tables = tables.cpu().numpy()
+    else:
+        grid = _host_grid(attn, acts, k)
+        tables, masks = _host_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts)
+    return _score_from_tables(tables, masks, targets, num_classes, part_thresh) + (grid,)
 
 
 # ------------------------------------------------------------------------------------------------ the same post-processing on the device
@@ -363,24 +356,43 @@ def high_activation_boxes(grids, size, percentile=95):
     return ops.act_box(maps, size, thr).reshape(lead + (4,))
 
 
-def _grid_on_device(attn, acts, k):
-    """The (B, ppc, g, g) fp32 maps on the patch grid from device tensors (expand_to_grid is torch: it runs where its inputs are)."""
+def patch_grid(attn, acts, k):
+    """The (B, ppc, g, g) fp32 maps on the patch grid: expand_to_grid, unless the k tokens already are the grid.  Torch: it runs where
+    its inputs are."""
     attn, acts = attn.float(), acts.float()
-    return (expand_to_grid(acts, attn, k) if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts).contiguous()
+    return expand_to_grid(acts, attn, k) if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts
+
+
+def _grid_on_device(attn, acts, k):
+    return patch_grid(attn, acts, k).contiguous()
+
+
+def _host_grid(attn, acts, k):
+    return patch_grid(torch.as_tensor(attn).cpu(), torch.as_tensor(acts).cpu(), k).numpy()
+
+
+def scaled_parts(ids, parts, image_sizes, img_size, n_parts):
+    """The part annotations of a batch in resized-image pixels (eval_interpretability.py:192-200): (labels: per image the list of
+    (part_id0, x, y) in annotation order, as prototype_part_table takes it; masks (B, n_parts) of annotated parts).  The host referee
+    and the device path both take their pixels from here, so that they score the same boxes."""
+    labels, masks = [], np.zeros((len(ids), n_parts))
+    for j, i in enumerate(ids):
+        w, h = image_sizes[int(i)]
+        labels.append([(pid - 1, int(img_size * (x / w)), int(img_size * (y / h))) for pid, x, y in parts.id_to_part_loc.get(int(i), [])])
+        masks[j, [pid0 for pid0, _, _ in labels[-1]]] = 1
+    return labels, masks
 
 
 def _part_list(ids, parts, image_sizes, img_size, n_parts):
-    """The part annotations of a batch as the kernels take them: (plist (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image
-    pixels as consistency_from_outputs scales them; masks (B, n_parts) of annotated parts).  Host arrays, built once per batch."""
-    B = len(ids)
-    plist, masks = np.zeros((B, n_parts, 3), dtype=np.int32), np.zeros((B, n_parts))
-    for j in range(B):
-        w, h = image_sizes[int(ids[j])]
-        for pid, x, y in parts.id_to_part_loc.get(int(ids[j]), []):
-            if plist[j, pid - 1, 0]:
-                raise ValueError(f"image {int(ids[j])} lists part {pid} twice: the device path takes one location per part")
-            masks[j, pid - 1] = 1
-            plist[j, pid - 1] = (1, int(img_size * (x / w)), int(img_size * (y / h)))
+    """scaled_parts as the kernels take it: (plist (B, n_parts, 3) int32 (valid, x, y) by part id, masks).  Host arrays, built once per
+    batch."""
+    labels, masks = scaled_parts(ids, parts, image_sizes, img_size, n_parts)
+    plist = np.zeros((len(labels), n_parts, 3), dtype=np.int32)
+    for j, image in enumerate(labels):
+        for pid0, x, y in image:
+            if plist[j, pid0, 0]:
+                raise ValueError(f"image {int(ids[j])} lists part {pid0 + 1} twice: the device path takes one location per part")
+            plist[j, pid0] = (1, x, y)
     return plist, masks
 
 
@@ -395,8 +407,7 @@ def _tables_for_parts(grid, plist_dev, img_size, half_size):
 
 
 def _device_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
-    """Part tables of a batch: grid (B, ppc, g, g) CUDA -> (tables (B, ppc, n_parts) uint8 CUDA, masks (B, n_parts) numpy).  The part
-    list goes up as (B, n_parts, 3) int32 (valid, x, y) by part id, in resized-image pixels as consistency_from_outputs scales them."""
+    """Part tables of a batch: grid (B, ppc, g, g) CUDA -> (tables (B, ppc, n_parts) uint8 CUDA, masks (B, n_parts) numpy)."""
     plist, masks = _part_list(ids, parts, image_sizes, img_size, n_parts)
     return _tables_for_parts(grid, torch.from_numpy(plist).to(grid.device), img_size, half_size), masks
 
@@ -490,23 +501,12 @@ class PartMeter:
 
 
 def _host_tables(grid, ids, parts, image_sizes, img_size, half_size, n_parts):
-    """prototype_part_table of every image of a host grid (B, P, g, g): (tables (B, P, n_parts) of 0 / 1, masks (B, n_parts)), the part
-    locations scaled as consistency_from_outputs scales them."""
-    B = grid.shape[0]
-    tables, masks = np.zeros((B, grid.shape[1], n_parts)), np.zeros((B, n_parts))
-    for j in range(B):
-        w, h = image_sizes[int(ids[j])]
-        labels = []
-        for pid, x, y in parts.id_to_part_loc.get(int(ids[j]), []):
-            masks[j, pid - 1] = 1
-            labels.append((pid - 1, int(img_size * (x / w)), int(img_size * (y / h))))
-        tables[j] = prototype_part_table(grid[j], labels, img_size, half_size, n_parts)
+    """prototype_part_table of every image of a host grid (B, P, g, g): (tables (B, P, n_parts) of 0 / 1, masks (B, n_parts))."""
+    labels, masks = scaled_parts(ids, parts, image_sizes, img_size, n_parts)
+    tables = np.zeros((grid.shape[0], grid.shape[1], n_parts))
+    for j, image in enumerate(labels):
+        tables[j] = prototype_part_table(grid[j], image, img_size, half_size, n_parts)
     return tables, masks
-
-
-def _host_grid(attn, acts, k):
-    attn, acts = torch.as_tensor(attn).cpu(), torch.as_tensor(acts).cpu()
-    return expand_to_grid(acts.float(), attn.float(), k).numpy() if k != attn.reshape(attn.shape[0], -1).shape[-1] else acts.float().numpy()
 
 
 def stability_from_tables(tables, tables_noisy, targets, num_classes):
@@ -559,18 +559,13 @@ def interpretability_scores(ppnet, loader, parts, image_sizes, num_classes=200, 
     ppc, k, img_size = ppnet.num_prototypes_per_class, ppnet.reserve_token_nums[0], ppnet.img_size
     meter, kept = None, []
 
-    def own_maps(xb, t):
-        ta, pa = ppnet.push_forward(xb)
-        cols = (t * ppc)[:, None] + torch.arange(ppc, device=pa.device)[None, :]
-        return ta, torch.gather(pa, 1, cols[:, :, None, None].expand(-1, -1, pa.shape[-2], pa.shape[-1]))
-
     for x, t, i in loader:
         x = x.cuda() if not x.is_cuda else x
         ids = torch.as_tensor(i).cpu()
         t = torch.as_tensor(t).to(device=x.device, dtype=torch.int64)
-        passes = [own_maps(x, t)]
+        passes = [own_prototype_maps(ppnet, x, t)]
         if stability:
-            passes.append(own_maps(add_input_noise(x, ids, noise_std, seed), t))
+            passes.append(own_prototype_maps(ppnet, add_input_noise(x, ids, noise_std, seed), t))
         if device:
             if meter is None:
                 meter = PartMeter(num_classes, ppc, n_parts, x.device)
@@ -1114,11 +1109,7 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
     image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
     G, kept, cls_kept, ids_kept, seen, dev_counts = int(ppnet.num_patches), {}, [], [], 0, None
-    for x, y, *rest in loader:
-        if max_images and seen >= max_images:
-            break
-        if max_images:
-            x, y, rest = x[:max_images - seen], y[:max_images - seen], [r[:max_images - seen] for r in rest]
+    for x, y, *rest in take_images(loader, max_images):
         x = (x if x.is_cuda else x.cuda()).float().contiguous()
         B = x.shape[0]
         ids = torch.as_tensor(rest[0]).to(torch.int64) if rest else torch.arange(seen, seen + B, dtype=torch.int64)
@@ -1361,15 +1352,9 @@ ALIGNMENT_STATS = ("share", "area", "pac", "plc", "left_box")
 def _regroup(loader, n, max_images):
     """The loader's images in consecutive passes of exactly n images (the last may be shorter), whatever its own batch size: what
     spatial_alignment computes then depends on the image sequence alone.  Yields fp32 batches on the device the loader's are on."""
-    held, have, seen = [], 0, 0
-    for x, *_ in loader:
-        if max_images and seen >= max_images:
-            break
-        x = x.float()
-        if max_images:
-            x = x[:max_images - seen]
-        seen += x.shape[0]
-        held.append(x); have += x.shape[0]
+    held, have = [], 0
+    for x, in take_images(((b[0],) for b in loader), max_images):
+        held.append(x.float()); have += x.shape[0]
         while have >= n:
             full = torch.cat(held) if len(held) > 1 else held[0]
             yield full[:n].contiguous()

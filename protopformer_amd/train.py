@@ -24,7 +24,7 @@ import torch.distributed as dist
 from . import data as D
 from . import engine as E
 from .mixup import create_criterion, create_mixup
-from .protopformer import construct_PPNet
+from .tooling import model_from_args
 
 LOGGER_NAME = "protopformer_amd.train"
 SCALARS = ("epoch/train_loss", "epoch/val_acc1", "epoch/val_loss", "epoch/val_acc5", "epoch/global_acc1", "epoch/local_acc1")
@@ -304,12 +304,7 @@ def main(args, model=None):
                                                                 f"mixup_fn smoothing rate: {mixup_fn.label_smoothing}"))
 
     if model is None:
-        model = construct_PPNet(base_architecture=args.base_architecture, pretrained=not args.no_pretrained, img_size=args.img_size,
-                                prototype_shape=args.prototype_shape, num_classes=args.nb_classes, reserve_layers=args.reserve_layers,
-                                reserve_token_nums=args.reserve_token_nums, use_global=args.use_global, use_ppc_loss=args.use_ppc_loss,
-                                ppc_cov_thresh=args.ppc_cov_thresh, ppc_mean_thresh=args.ppc_mean_thresh, global_coe=args.global_coe,
-                                global_proto_per_class=args.global_proto_per_class,
-                                prototype_activation_function=args.prototype_activation_function, add_on_layers_type=args.add_on_layers_type)
+        model = model_from_args(args, args.nb_classes)
     model.to(device)
     n_parameters = sum(p.numel() for p in model.parameters() if p.requires_grad)
     logger.info(f"number of params: {n_parameters}")

@@ -27,28 +27,9 @@ sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
-P, DP, D, KTOK, CLASSES, IMG, PATCH = 2000, 384, 384, 81, 200, 224, 16
+from bench_common import deit_small_ppnet, row, timed      # noqa: E402
 
-
-def timed(fn, reps, warm=3):
-    """Median / min / max microseconds of fn(), one event pair per call, each call queued behind a running matrix product."""
-    busy = torch.randn((4096, 4096), device="cuda")
-    us = []
-    for rep in range(reps + warm):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        torch.mm(busy, busy)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if rep >= warm:
-            us.append(e0.elapsed_time(e1) * 1e3)
-    return dict(launches_timed=len(us), us_median=round(float(np.median(us)), 2), us_min=round(min(us), 2), us_max=round(max(us), 2))
-
-
-def row(what, t, nbytes, **extra):
-    return dict(what=what, **t, bytes_moved=int(nbytes), gb_per_s_at_median=round(nbytes / t["us_median"] / 1e3, 1), **extra)
+P, D, IMG, PATCH = 2000, 384, 224, 16
 
 
 def kernels(B, reps):
@@ -94,12 +75,8 @@ def model_rows(B, runs):
     """Forward and backward of deit_small with and without the image gradient, and the weight-gradient launches inside the backward."""
     from protopformer_amd import _lib
     from protopformer_amd.interpret import input_gradient
-    from protopformer_amd.protopformer import construct_PPNet
     dev = torch.device("cuda")
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=IMG, prototype_shape=(P, DP, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
+    m = deit_small_ppnet()
     x = torch.randn(B, 3, IMG, IMG, device=dev)
     protos = torch.randint(0, P, (B,), device=dev)
 

@@ -23,6 +23,8 @@ sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
+from bench_common import push_forward_row      # noqa: E402
+
 P, DP, KTOK, CLASSES = 2000, 384, 81, 200
 
 
@@ -69,26 +71,6 @@ def merge_launches(epoch, K, reps, local):
                 algorithmic_bytes=nbytes, gb_per_s_at_median=round(nbytes / med / 1e3, 1), filled_entries=int((img >= 0).sum()))
 
 
-def push_forward(B, reps):
-    from protopformer_amd.protopformer import construct_PPNet
-    dev = torch.device("cuda")
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=224, prototype_shape=(P, DP, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
-    x = torch.randn(B, 3, 224, 224, device=dev)
-    for _ in range(3):
-        m.push_forward(x)
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); m.push_forward(x); e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return dict(what=f"PPNet.push_forward, deit_small 2000x384, batch {B} (for scale)", runs=reps, ms_median=round(float(np.median(ms)), 3),
-                ms_min=round(min(ms), 3), ms_max=round(max(ms), 3))
-
-
 def host_alternative(epoch, K):
     torch.cuda.synchronize()
     per_batch, acts, args = [], [], []
@@ -119,7 +101,8 @@ def main():
         raise SystemExit("bench_bank.py measures on the GPU; none found")
     dev = torch.device("cuda")
     epoch = make_epoch(a.batches, a.batch, dev)
-    rows = [merge_launches(epoch, a.topk, a.reps, True), merge_launches(epoch, a.topk, a.reps, False), push_forward(a.batch, a.reps),
+    rows = [merge_launches(epoch, a.topk, a.reps, True), merge_launches(epoch, a.topk, a.reps, False),
+            push_forward_row(a.batch, a.reps, f"PPNet.push_forward, deit_small 2000x384, batch {a.batch} (for scale)"),
             host_alternative(epoch, a.topk)]
     head = [f"# prototype bank cost: {torch.cuda.get_device_name(0)}, one GPU, one process; torch {torch.__version__}",
             f"# produced by: python scripts/bench_bank.py {' '.join(sys.argv[1:])}".rstrip() + f"   ({datetime.date.today().isoformat()})",

@@ -24,15 +24,13 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
+from bench_common import deit_small_ppnet      # noqa: E402
+
 
 def epochs(warmup, timed, nbatch, B):
     from protopformer_amd.engine import evaluate, evaluate_epoch
-    from protopformer_amd.protopformer import construct_PPNet
     dev, C = torch.device("cuda"), 200
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=224, prototype_shape=(2000, 384, 1, 1), num_classes=C,
-                        reserve_layers=[11], reserve_token_nums=[81], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
+    m = deit_small_ppnet()
     g = torch.Generator(device=dev).manual_seed(1028)
     data = [(torch.randn(B, 3, 224, 224, device=dev, generator=g), torch.randint(0, C, (B,), device=dev, generator=g)) for _ in range(nbatch)]
     loops = {"evaluate": lambda: evaluate(data, m, dev), "evaluate_epoch": lambda: evaluate_epoch(data, m, dev)}

@@ -25,7 +25,9 @@ sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
-P, DP, KTOK, GRID, CLASSES, COE = 2000, 384, 81, 196, 200, 0.3
+from bench_common import push_forward_row, timed      # noqa: E402
+
+P, KTOK, GRID, CLASSES, COE = 2000, 81, 196, 200, 0.3
 
 
 def make_batch(B, dev):
@@ -48,45 +50,13 @@ def explain_launches(b, K, M, reps, local, maps):
     args = (b["act"], kw.get("argmax"), kw.get("idx"), KTOK if local else 0, kw.get("act_full"), b["weight"], scale, b["ppc"], b["logits"], None, 1, B, P,
             CLASSES, M, K, GRID if local else 0, out["classes"], out["class_logits"], out["prototypes"], out["contributions"], out["activations"],
             out["cells"], out["evidence"], out["maps"])
-    busy = torch.randn((4096, 4096), device=b["act"].device)
-    us = []
-    for rep in range(reps + 5):                                  # the first 5 warm up
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        torch.mm(busy, busy)                                     # keeps the queue busy while the three packets below are enqueued back to back
-        e0.record()
-        _lib.call("ppf_explain_topk", *args)
-        e1.record()
-        torch.cuda.synchronize()
-        if rep >= 5:
-            us.append(e0.elapsed_time(e1) * 1e3)
+    t = timed(lambda: _lib.call("ppf_explain_topk", *args), reps, warm=5)
     lists = B * M
     nbytes = lists * (P * 8 + CLASSES * 4 + K * 16 + 16) + (lists * K * 8 if local else 0) + (lists * K * (GRID + KTOK) * 4 + lists * KTOK * 4 if maps else 0)
-    med = float(np.median(us))
     form = ("local, with maps" if maps else "local, no maps") if local else "global"
-    return dict(what=f"ppf_explain_topk, {form}, B={B} P={P} C={CLASSES} M={M} K={K} T={KTOK} G={GRID}", launches_timed=len(us),
-                workgroups=lists, us_median=round(med, 2), us_min=round(min(us), 2), us_max=round(max(us), 2), algorithmic_bytes=nbytes,
-                gb_per_s_at_median=round(nbytes / med / 1e3, 1), filled_entries=int((out["prototypes"] >= 0).sum()))
-
-
-def push_forward(B, reps):
-    from protopformer_amd.protopformer import construct_PPNet
-    dev = torch.device("cuda")
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=224, prototype_shape=(P, DP, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
-    x = torch.randn(B, 3, 224, 224, device=dev)
-    for _ in range(3):
-        m.push_forward(x)
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); m.push_forward(x); e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return dict(what=f"PPNet.push_forward, deit_small 2000x384, batch {B} (for scale)", runs=reps, ms_median=round(float(np.median(ms)), 3),
-                ms_min=round(min(ms), 3), ms_max=round(max(ms), 3))
+    return dict(what=f"ppf_explain_topk, {form}, B={B} P={P} C={CLASSES} M={M} K={K} T={KTOK} G={GRID}", launches_timed=t["launches_timed"],
+                workgroups=lists, us_median=t["us_median"], us_min=t["us_min"], us_max=t["us_max"], algorithmic_bytes=nbytes,
+                gb_per_s_at_median=round(nbytes / t["us_median"] / 1e3, 1), filled_entries=int((out["prototypes"] >= 0).sum()))
 
 
 def host_alternative(b, K, M, reps):
@@ -138,7 +108,7 @@ def main():
     rows += [host_alternative(b, a.topk, M, min(a.reps, 10)) for M in (1, 5)]
     del b
     torch.cuda.empty_cache()
-    rows.append(push_forward(a.batch, 5))
+    rows.append(push_forward_row(a.batch, 5, f"PPNet.push_forward, deit_small 2000x384, batch {a.batch} (for scale)"))
     head = [f"# local analysis (explain) cost: {torch.cuda.get_device_name(0)}, one GPU, one process; torch {torch.__version__}",
             f"# produced by: python scripts/bench_explain.py {' '.join(sys.argv[1:])}".rstrip() + f"   ({datetime.date.today().isoformat()})",
             "# ppf_explain_topk: HIP events around single launches queued behind a running kernel (no host enqueue time inside); host times are perf_counter"]

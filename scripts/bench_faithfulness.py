@@ -21,31 +21,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
-P, DP, KTOK, GRID, CLASSES, COE, IMG = 2000, 384, 81, 196, 200, 0.3, 224
+from bench_common import push_forward_row, row, timed      # noqa: E402
 
-
-def timed(fn, reps, warm=3):
-    """Median / min / max microseconds of fn(), one event pair per call, each call queued behind a running matrix product."""
-    busy = torch.randn((4096, 4096), device="cuda")
-    us = []
-    for rep in range(reps + warm):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        torch.mm(busy, busy)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if rep >= warm:
-            us.append(e0.elapsed_time(e1) * 1e3)
-    return dict(launches_timed=len(us), us_median=round(float(np.median(us)), 2), us_min=round(min(us), 2), us_max=round(max(us), 2))
-
-
-def row(what, t, nbytes, **extra):
-    return dict(what=what, **t, bytes_moved=int(nbytes), gb_per_s_at_median=round(nbytes / t["us_median"] / 1e3, 1), **extra)
+P, KTOK, GRID, CLASSES, COE, IMG = 2000, 81, 196, 200, 0.3, 224
 
 
 def make_batch(B, dev):
@@ -114,26 +94,6 @@ def kernels(b, S, reps):
     return rows
 
 
-def push_forward(B, reps):
-    from protopformer_amd.protopformer import construct_PPNet
-    dev = torch.device("cuda")
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=224, prototype_shape=(P, DP, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
-    x = torch.randn(B, 3, IMG, IMG, device=dev)
-    for _ in range(3):
-        m.push_forward(x)
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); m.push_forward(x); e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return dict(what=f"for scale: PPNet.push_forward, deit_small 2000x384, batch {B}", runs=reps, ms_median=round(float(np.median(ms)), 3),
-                ms_min=round(min(ms), 3), ms_max=round(max(ms), 3))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -147,7 +107,7 @@ def main():
     rows = kernels(b, a.steps, a.reps)
     del b
     torch.cuda.empty_cache()
-    rows.append(push_forward(a.batch, 5))
+    rows.append(push_forward_row(a.batch, 5, f"for scale: PPNet.push_forward, deit_small 2000x384, batch {a.batch}"))
     head = [f"# faithfulness (deletion / insertion curves) cost: {torch.cuda.get_device_name(0)}, one GPU, one process; torch {torch.__version__}",
             f"# produced by: python scripts/bench_faithfulness.py {' '.join(sys.argv[1:])}".rstrip() + f"   ({datetime.date.today().isoformat()})",
             "# kernels: HIP events around single launches queued behind a running kernel (no host enqueue time inside)"]

@@ -25,6 +25,8 @@ sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
+from bench_common import push_forward_ms, timed_back_to_back      # noqa: E402
+
 G, S, KTOK, NPARTS, CLASSES = 14, 224, 81, 15, 200
 
 
@@ -70,37 +72,12 @@ def consistency(B, ppc):
 
 
 def push_forward(images, reps):
-    from protopformer_amd.protopformer import construct_PPNet
-    dev = torch.device("cuda")
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=S, prototype_shape=(2000, 384, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").to(dev).eval()
-    x = torch.randn(256, 3, S, S, device=dev)
-    for _ in range(3):
-        m.push_forward(x)
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); m.push_forward(x); e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = push_forward_ms(256, reps)
     med = float(np.median(ms))
     nb = -(-images // 256)
     return dict(what="PPNet.push_forward, deit_small 2000x384, batch 256 (the forward's share of a consistency run)", runs=reps,
                 ms_per_batch_median=round(med, 3), ms_min=round(min(ms), 3), ms_max=round(max(ms), 3), batches_for_the_test_set=nb,
                 forward_s_for_the_test_set=round(med * nb / 1e3, 3))
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-    torch.cuda.synchronize()
-    for e0, e1 in ev:
-        e0.record(); fn(); e1.record()
-    torch.cuda.synchronize()
-    return [e0.elapsed_time(e1) for e0, e1 in ev]
 
 
 def sweep(images, protos, reps):
@@ -112,7 +89,7 @@ def sweep(images, protos, reps):
     del d
     parts = torch.randint(0, S, (images, NPARTS, 3), device=dev, generator=g, dtype=torch.int32)
     parts[:, :, 0] = 1
-    ms = timed(lambda: ops.act_peak(maps, S, parts, 36), reps)
+    ms = timed_back_to_back({"peak": lambda: ops.act_peak(maps, S, parts, 36)}, reps)["peak"]
     med = float(np.median(ms))
     _, _, table = ops.act_peak(maps, S, parts, 36)
     return dict(what=f"all-prototype sweep: ppf_act_peak with the fused part table, {images} images x {protos} prototypes = {images * protos} maps "
@@ -125,7 +102,7 @@ def sweep(images, protos, reps):
 def upsample(reps, M=2560):
     from protopformer_amd import ops
     maps = torch.from_numpy(activation_like((M, G, G), 9)).cuda()
-    ms = timed(lambda: ops.act_upsample(maps, S), reps)
+    ms = timed_back_to_back({"up": lambda: ops.act_upsample(maps, S)}, reps)["up"]
     med = float(np.median(ms))
     nbytes = M * (G * G + S * S) * 4
     return dict(what=f"ppf_act_upsample alone, {M} maps {G}x{G} -> {S}x{S} (HIP event pairs; the output buffer is allocated inside the pair)", runs=reps,

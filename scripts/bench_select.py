@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 import torch            # noqa: E402
 
-from bench_faithfulness import timed      # noqa: E402
+from bench_common import timed      # noqa: E402
 
 B, N, NP, L, K, MAPS, GRID, SIZE = 256, 197, 200, 11, 81, 2560, 14, 224
 

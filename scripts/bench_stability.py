@@ -27,6 +27,8 @@ sys.path.insert(0, ROOT)
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 
+from bench_common import deit_small_ppnet, timed_back_to_back      # noqa: E402
+
 G, S, KTOK, NPARTS, CLASSES = 14, 224, 81, 15, 200
 
 
@@ -35,17 +37,8 @@ def spread(us):
 
 
 def alternate(fns, reps):
-    """{name: [us per repetition]}: every repetition times each function once, in turn (event pair around the single call)."""
-    for fn in fns.values():
-        for _ in range(3):
-            fn()
-    ev = {k: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)] for k in fns}
-    torch.cuda.synchronize()
-    for r in range(reps):
-        for k, fn in fns.items():
-            ev[k][r][0].record(); fn(); ev[k][r][1].record()
-    torch.cuda.synchronize()
-    return {k: [e0.elapsed_time(e1) * 1e3 for e0, e1 in v] for k, v in ev.items()}
+    """{name: [us per repetition]} of bench_common.timed_back_to_back."""
+    return {k: [ms * 1e3 for ms in v] for k, v in timed_back_to_back(fns, reps).items()}
 
 
 def noise(batch, reps, kernel_only=False):
@@ -152,11 +145,7 @@ class SyntheticSet:
 
 def end_to_end(images, batch, ppc):
     from protopformer_amd import interpret as I
-    from protopformer_amd.protopformer import construct_PPNet
-    torch.manual_seed(1028)
-    m = construct_PPNet("deit_small_patch16_224", pretrained=False, img_size=S, prototype_shape=(CLASSES * ppc, 384, 1, 1), num_classes=CLASSES,
-                        reserve_layers=[11], reserve_token_nums=[KTOK], use_global=True, use_ppc_loss=True, global_proto_per_class=10,
-                        add_on_layers_type="regular").cuda().eval()
+    m = deit_small_ppnet(prototypes=CLASSES * ppc)
     parts, sizes = make_parts(np.arange(1, images + 1), np.random.default_rng(7))
     I.interpretability_scores(m, SyntheticSet(min(images, 2 * batch), batch), parts, sizes, num_classes=CLASSES, device=True)      # warm-up
     torch.cuda.synchronize()

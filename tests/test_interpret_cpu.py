@@ -106,3 +106,66 @@ def test_consistency_pipeline_equals_the_reference_run():
     assert effects == z["class_proto_effect"].tolist()
     assert np.allclose(max_parts, z["class_max_part"], atol=1e-12)
     assert score == pytest.approx(float(z["score"]), abs=1e-12) and 0.3 < score < 0.8     # a non-trivial mix of consistent / inconsistent
+
+
+# ------------------------------------------------------------------------------------------------ one part-table path
+def test_scaled_parts_feeds_the_host_and_the_device_path_the_same_pixels():
+    """x / w * img_size on both sides of an integer boundary: 29 / 58 * 32 = 16 exactly, 57 / 114 * 32 = 16 exactly while 56 / 114 * 32 =
+    15.72 and 58 / 114 * 32 = 16.28; 33 / 67 * 32 = 15.76, 34 / 67 * 32 = 16.24."""
+    import types
+    img_size, n_parts = 32, 5
+    sizes = {3: (58, 40), 8: (114, 67), 9: (67, 114)}                       # (width, height) of three unequal originals
+    locs = {3: [[1, 29, 20], [4, 57, 39]], 8: [[2, 56, 33], [3, 57, 34], [5, 58, 0]], 9: [[5, 33, 56], [1, 34, 58], [2, 0, 113]]}
+    parts, ids = types.SimpleNamespace(id_to_part_loc=locs), np.array([8, 3, 9, 4])          # image 4 has a size and no annotation
+    sizes[4] = (50, 50)
+    labels, masks = I.scaled_parts(ids, parts, sizes, img_size, n_parts)
+    known = [[(pid - 1, int(img_size * (x / sizes[i][0])), int(img_size * (y / sizes[i][1]))) for pid, x, y in locs.get(i, [])] for i in ids.tolist()]
+    assert labels == known
+    assert labels[0] == [(1, 15, 15), (2, 16, 16), (4, 16, 0)] and labels[1] == [(0, 16, 16), (3, 31, 31)] and labels[3] == []
+    want_masks = np.zeros((4, n_parts))
+    for j, i in enumerate(ids.tolist()):
+        want_masks[j, [pid - 1 for pid, _, _ in locs.get(i, [])]] = 1
+    assert np.array_equal(masks, want_masks) and masks.dtype == np.float64
+    # the device form holds the same pixels by part id
+    plist, masks_dev = I._part_list(ids, parts, sizes, img_size, n_parts)
+    assert plist.dtype == np.int32 and plist.shape == (4, n_parts, 3) and np.array_equal(masks_dev, masks)
+    assert np.array_equal(plist[:, :, 0], masks.astype(np.int32))
+    for j, image in enumerate(labels):
+        assert [(p, int(plist[j, p, 1]), int(plist[j, p, 2])) for p, _, _ in image] == image
+    # a part listed twice: the host list keeps both entries in order, the device form refuses
+    locs[3].append([1, 10, 10])
+    labels, masks = I.scaled_parts(ids, parts, sizes, img_size, n_parts)
+    assert labels[1] == [(0, 16, 16), (3, 31, 31), (0, 5, 8)] and masks[1].tolist() == [1, 0, 0, 1, 0]
+    with pytest.raises(ValueError, match="image 3 lists part 1 twice"):
+        I._part_list(ids, parts, sizes, img_size, n_parts)
+
+
+def _frozen_case():
+    import types
+    rng = np.random.default_rng(0)
+    B, ppc, g, n_parts = 6, 2, 4, 5
+    attn = rng.random((B, g * g), dtype=np.float32)
+    acts = rng.random((B, ppc, 3, 3), dtype=np.float32)
+    targets = np.array([0, 2, 0, 2, 2, 0])                                  # class 1 has no image
+    ids = np.arange(11, 11 + B)
+    sizes = {int(i): (int(rng.integers(40, 90)), int(rng.integers(30, 70))) for i in ids}
+    locs = {}
+    for i in ids:
+        w, h = sizes[int(i)]
+        locs[int(i)] = [[p, int(rng.integers(0, w)), int(rng.integers(0, h))] for p in range(1, n_parts + 1) if rng.random() < 0.8]
+    return attn, acts, targets, ids, types.SimpleNamespace(id_to_part_loc=locs), sizes
+
+
+def test_consistency_from_outputs_host_path_keeps_its_results():
+    """6 images, 3 classes of which class 1 has no image, 2 prototypes per class, a 4 x 4 grid expanded from k = 9 reserved tokens,
+    img_size 32, half_size 6, 5 parts.  The literals were computed on the CPU with consistency_from_outputs of commit 676d7a3 (the one
+    before the host path was rebuilt from _host_tables and _score_from_tables, from an unpacked `git archive` of it) on this case; they
+    are ratios of small integers and a mean of 0 / 1, so the comparison is exact."""
+    case = _frozen_case()
+    for thresh, score, effects in ((0.8, 0.25, [0, 1, 0, 0]), (0.5, 0.75, [1, 1, 1, 0])):
+        s, e, m, grid = I.consistency_from_outputs(*case, 9, 32, num_classes=3, part_thresh=thresh, half_size=6, n_parts=5)
+        assert s == score and type(s) is float
+        assert e == effects and {type(v) for v in e} == {int}
+        assert m == [2 / 3, 1.0, 2 / 3, 1 / 3] and {type(v) for v in m} == {float}
+        assert isinstance(grid, np.ndarray) and grid.dtype == np.float32 and grid.shape == (6, 2, 4, 4)
+        assert np.array_equal(grid, I.expand_to_grid(torch.from_numpy(case[1]), torch.from_numpy(case[0]), 9).numpy())
