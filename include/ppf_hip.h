@@ -92,13 +92,6 @@ int ppf_gemm_probe_read(double* ms_total, int64_t* launches, double* flops, doub
 int ppf_path_probe(int enable);
 int ppf_path_probe_read(int tag, double* ms_total, int64_t* launches, double* flops, double* bytes);
 
-/* nbatch = batch_outer*batch_inner plain GEMMs; problem (o,i) uses A + o*sa_o + i*sa_i (elements), same for B / C.
- * kpad = 1: contraction-contiguous operands may read the (zero) padding up to the next multiple of 8 beyond K.
- * CaiT talking-heads attention per-(sample, head) products: A.V, dO.V^T, dS.K, dS^T.Q, A^T.dO (cait:128-130 and autograd). */
-int ppf_gemm_bf16_batched(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int trans_a,
-                          int trans_b, int out_f32, float alpha, int batch_outer, int batch_inner, int64_t sa_o, int64_t sa_i,
-                          int64_t sb_o, int64_t sb_i, int64_t sc_o, int64_t sc_i, int kpad, ppf_stream_t stream);
-
 /* ---- fp32 verification mode, backward (csrc/precise.hip, round 5; DeiT): never on the measured path -----------------------------
  * LayerNorm backward with the statistics recomputed from x (rows of dy <-> rows row_map[r] of x, dx_out written at the x rows -- dx_out may
  * alias dres_in; dw / db by fp32 atomics, either may be NULL for a frozen LayerNorm); elementwise pieces (kind 0 x gelu'(pre), 1 sigmoid', 2 DropPath row scale, 3 product, 4 row scale x LayerScale column, 5 ReLU' from its output); column sums; Attention backward with the
@@ -184,20 +177,12 @@ int ppf_attn_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
                  const float* zinv, float* delta, int B, int H, int N, int D, int self_keep, int eps_n, ppf_stream_t stream);
 
 /* ---- CaiT: talking-heads self-attention (cait:93-132) and class attention (cait:34-90) --------------------------------
- * th_scores: sp[b][g][q][key] = sum_h Wl[g][h]*(scale q_h.k_h) + bl[g];  th_softmax_mix (in place): sp <- softmax(sp),
- * a16 = bf16(proj_w(P)) [B][H][N][NPK], hm = mean over heads of proj_w(P) [B][N][NP] (rollout input, cait:228).
- * th_softmax_bwd: da (in dA, out dS'), ds16 = bf16(Wl^T dS'), dww/dbw/dbl +=;  th_dwl: dWl += sum dS' * raw scores. */
-int ppf_th_scores(const void* qkv, const float* wl, const float* bl, float* sp, int B, int H, int N, int D, int NP, ppf_stream_t stream);
-int ppf_th_dwl(const void* qkv, const float* ds_prime, float* dwl, int B, int H, int N, int D, int NP, ppf_stream_t stream);
-int ppf_th_softmax_mix(float* sp, void* a16, float* hm, const float* ww, const float* bw, int B, int H, int N, int NP, int NPK,
-                       ppf_stream_t stream);
-int ppf_th_softmax_bwd(const float* prob, float* da, void* ds16, const float* ww, const float* wl, float* dww, float* dbw, float* dbl,
-                       int B, int H, int N, int NP, int NPK, ppf_stream_t stream);
-/* Fused talking-heads attention (cait:119-126; replaces th_scores + th_softmax_mix and, in backward, the dA product + th_softmax_bwd +
- * th_dwl: no (B,H,N,N) fp32 tensor is materialised).  ppf_th_fused_supported: 1 when (heads, tokens, width) is covered (K and V images
- * of all heads must fit the 160 KiB LDS: head_dim in {32,48,64}, heads in {2,4}, N <= 224), else 0 -- callers then use the kernels above.
- * ppf_th_fwd: a16 = bf16 proj_w(softmax(proj_l(scale q k^T))) [B][H][N][NPK], hm = its head mean [B][N][NP], rowmax / zinv [B][H][N] =
- * softmax statistics of the mixed logits (saved for backward); out (optional) = the attention output A V, bf16 [B*N][D] (cait:128).
+ * Talking heads (cait:119-128) is one fused path: no (B,H,N,N) fp32 tensor is materialised and no float atomics are used.  A shape
+ * outside its cover is an error (PPF_ERR_SHAPE); there is no other route.  ppf_th_fused_supported: 1 when (heads, tokens, width) is
+ * covered (head_dim in {32,48,64}, heads in {2,4}, N <= 224, K and V images of all heads within the 160 KiB LDS), else 0.
+ * ppf_th_fwd: a16 = bf16 proj_w(softmax(proj_l(scale q k^T))) [B][H][N][NPK], hm = its head mean [B][N][NP] (rollout input, cait:228),
+ * rowmax / zinv [B][H][N] = softmax statistics of the mixed logits (saved for backward); out (optional) = the attention output A V,
+ * bf16 [B*N][D] (cait:128).
  * ppf_th_bwd: ds16 = bf16 dS [B][H][N][NPK] from dout = dO [B*N][D]; partial (>= ppf_th_bwd_partial_floats floats) receives one row of
  * parameter-gradient sums per workgroup; ppf_th_param_reduce adds their fixed-order (bit-reproducible) totals to dww, dbw, dbl, dwl. */
 int ppf_th_fused_supported(int H, int N, int D);
@@ -209,7 +194,7 @@ int ppf_th_bwd(const void* qkv, const void* dout, const float* wl, const float* 
 int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, float* dbw, float* dbl, float* dwl, ppf_stream_t stream);
 /* the three per-head products behind ppf_th_bwd in one launch: dqkv [B*N][3D] bf16 <- dQ_h = scale dS_h K_h | dK_h = scale dS_h^T Q_h |
  * dV_h = A_h^T dO_h from ds16 / a16 [B][H][N][NPK], packed qkv and dout [B*N][D] (ppf_th_grads_supported: N <= 208, head_dim 32/48/64;
- * otherwise three ppf_gemm_bf16_batched calls) */
+ * a shape it does not cover cannot be trained) */
 int ppf_th_grads_supported(int H, int N, int D);
 int ppf_th_grads(const void* qkv, const void* dout, const void* ds16, const void* a16, void* dqkv, int B, int H, int N, int D, int NPK,
                  ppf_stream_t stream);

@@ -98,26 +98,21 @@ class MyCait(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ forward
+def require_th_cover(H, N, D, training):
+    """Raises ValueError unless the talking-heads kernels cover (heads, tokens, width); training also needs th_grads' cover.  There is
+    no other path: a shape outside the cover is refused by name, not run slower.  Host predicates only (no GPU needed)."""
+    if ops.th_fused_ok(H, N, D) and (not training or ops.th_grads_ok(H, N, D)):
+        return
+    raise ValueError(f"talking-heads attention with H={H} heads, N={N} tokens, D={D} width is outside the kernels' cover"
+                     f"{' for training' if training and ops.th_fused_ok(H, N, D) else ''}: head width D/H must be 32, 48 or 64, "
+                     "with 2 or 4 heads, the K and V images of all heads (2*H*N*(D/H)*2 bytes) within 160 KiB, and N <= 208 to train, <= 224 to infer")
+
+
 def _th_attention_fwd(blk, qkv, B, H, N, D, hm_slot):
-    """Talking-heads attention (cait:115-130) from packed qkv; returns (out bf16 [B*N,D], P fp32, A bf16)."""
-    hd = D // H
-    if ops.th_fused_ok(H, N, D):
-        # one launch up to and including A.V, nothing of size N x N in fp32: only the softmax statistics (and the bf16 A the dV product reads)
-        # are kept for backward
-        a16, rowmax, zinv, ao = ops.th_fwd(qkv, blk.attn.proj_l.weight, blk.attn.proj_l.bias, blk.attn.proj_w.weight, blk.attn.proj_w.bias, hm_slot, B, H, N, D,
-                                           with_out=ops.th_pv_fused())
-        sp = (rowmax, zinv)
-        if ao is not None:
-            return ao, sp, a16
-    else:
-        sp = ops.th_scores(qkv, blk.attn.proj_l.weight, blk.attn.proj_l.bias, B, H, N, D)
-        a16 = ops.th_softmax_mix(sp, blk.attn.proj_w.weight, blk.attn.proj_w.bias, hm_slot)      # sp now holds P
-    NPK = a16.shape[-1]
-    ao = torch.empty((B * N, D), dtype=torch.bfloat16, device=qkv.device)
-    # O_h[q][d] = sum_key A_h[q][key] V_h[key][d]
-    ops.gemm_batched(a16, ops._Off(qkv, 2 * D), ao, N, hd, N, NPK, 3 * D, D, False, True, False, 1.0, B, H,
-                     (H * N * NPK, N * NPK), (N * 3 * D, hd), (N * D, hd), kpad=1)
-    return ao, sp, a16
+    """Talking-heads attention (cait:115-130) from packed qkv; returns (out bf16 [B*N,D], (rowmax, zinv), A bf16).  One launch up to and
+    including A.V, nothing of size N x N in fp32: only the softmax statistics (and the bf16 A the dV product reads) are kept for backward."""
+    a16, rowmax, zinv, ao = ops.th_fwd(qkv, blk.attn.proj_l.weight, blk.attn.proj_l.bias, blk.attn.proj_w.weight, blk.attn.proj_w.bias, hm_slot, B, H, N, D)
+    return ao, (rowmax, zinv), a16
 
 
 def cait_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save):
@@ -125,6 +120,7 @@ def cait_blocks_fwd(feats, store, x, reserve_layer, reserve_k, dp, save):
     x fp32 [B,Np,D] -> (u_out [B,1+Np,D] fp32 = cat(cls, x), cls_token_attn [B,Np], idx int32 [B,k], saved)."""
     B, N, D = x.shape
     H = feats.num_heads
+    require_th_cover(H, N, D, training=save)
     M = B * N
     NP = (N + 3) // 4 * 4
     depth = len(feats.blocks)
@@ -197,42 +193,15 @@ def _zero_rows(B, device):
 # ------------------------------------------------------------------------------------------------ backward
 def _th_attention_bwd(store, blk, L, dao, B, H, N, D):
     """Backward of the talking-heads attention: returns dqkv bf16 [B*N, 3D]; accumulates proj_l / proj_w grads."""
-    hd = D // H
-    qkv, prob, a16 = L["qkv"], L["prob"], L["a16"]
-    NPK = a16.shape[-1]
-    dev = qkv.device
-    scale = hd ** -0.5
-    dqkv = torch.empty_like(qkv)
+    qkv, (rowmax, zinv), a16 = L["qkv"], L["prob"], L["a16"]
     gv = store.grad_view
-    one_launch = isinstance(prob, tuple) and ops.th_grads_ok(H, N, D)      # dQ, dK, dV by ops.th_grads behind th_bwd
-    if not one_launch:
-        # dV_h[key][d] = sum_q A_h[q][key] dO_h[q][d]
-        ops.gemm_batched(a16, dao, ops._Off(dqkv, 2 * D), N, hd, N, NPK, D, 3 * D, True, True, False, 1.0, B, H,
-                         (H * N * NPK, N * NPK), (N * D, hd), (N * 3 * D, hd), kpad=1)
-    if isinstance(prob, tuple):
-        # fused: dA, the two head mixes and the softmax backward in registers; the parameter-gradient sums leave the main stream
-        rowmax, zinv = prob
-        ds16, partial = ops.th_bwd(qkv, dao, blk.attn.proj_l.weight, blk.attn.proj_l.bias, blk.attn.proj_w.weight, rowmax, zinv, B, H, N, D)
-        wgrad_lane(store).submit(lambda: ops.th_param_reduce(partial, B, H, N, gv(blk.attn.proj_w.weight), gv(blk.attn.proj_w.bias), gv(blk.attn.proj_l.bias),
-                                                             gv(blk.attn.proj_l.weight)), (partial,),
-                                 defer=True)    # launched with the qkv weight gradient: one event record
-    else:
-        NP = prob.shape[-1]
-        # dA_h[q][key] = sum_d dO_h[q][d] V_h[key][d]
-        da = torch.empty((B, H, N, NP), dtype=torch.float32, device=dev)
-        ops.gemm_batched(dao, ops._Off(qkv, 2 * D), da, N, N, hd, D, 3 * D, NP, False, False, True, 1.0, B, H,
-                         (N * D, hd), (N * 3 * D, hd), (H * N * NP, N * NP))
-        ds16 = ops.th_softmax_bwd(prob, da, blk.attn.proj_w.weight, blk.attn.proj_l.weight, gv(blk.attn.proj_w.weight), gv(blk.attn.proj_w.bias),
-                                  gv(blk.attn.proj_l.bias))
-        ops.th_dwl(qkv, da, gv(blk.attn.proj_l.weight), B, H, N, D)                # da now holds dS'
-    if one_launch:
-        return ops.th_grads(qkv, dao, ds16, a16, dqkv, B, H, N, D)
-    # dQ_h = scale * dS_h K_h ;  dK_h = scale * dS_h^T Q_h
-    ops.gemm_batched(ds16, ops._Off(qkv, D), dqkv, N, hd, N, NPK, 3 * D, 3 * D, False, True, False, scale, B, H,
-                     (H * N * NPK, N * NPK), (N * 3 * D, hd), (N * 3 * D, hd), kpad=1)
-    ops.gemm_batched(ds16, qkv, ops._Off(dqkv, D), N, hd, N, NPK, 3 * D, 3 * D, True, True, False, scale, B, H,
-                     (H * N * NPK, N * NPK), (N * 3 * D, hd), (N * 3 * D, hd), kpad=1)
-    return dqkv
+    dqkv = torch.empty_like(qkv)
+    # dA, the two head mixes and the softmax backward in registers; the parameter-gradient sums leave the main stream
+    ds16, partial = ops.th_bwd(qkv, dao, blk.attn.proj_l.weight, blk.attn.proj_l.bias, blk.attn.proj_w.weight, rowmax, zinv, B, H, N, D)
+    wgrad_lane(store).submit(lambda: ops.th_param_reduce(partial, B, H, N, gv(blk.attn.proj_w.weight), gv(blk.attn.proj_w.bias), gv(blk.attn.proj_l.bias),
+                                                         gv(blk.attn.proj_l.weight)), (partial,),
+                             defer=True)    # launched with the qkv weight gradient: one event record
+    return ops.th_grads(qkv, dao, ds16, a16, dqkv, B, H, N, D)      # dQ, dK, dV in one launch
 
 
 def cait_backward(ppnet, store, saved, df):

@@ -194,7 +194,7 @@ __device__ __forceinline__ void store_partial_colsum(const GemmParams& p, int m,
     p.ws[p.zslice * ((size_t)p.M * p.N + (size_t)p.cs_parts * p.M) + (size_t)p.M * p.N + m] = v;
 }
 
-// 128x128x64 per 256-thread workgroup (2 x 2 waves of 64 x 64), three workgroups per CU; batched problems along gridDim.y.  The next K tile is
+// 128x128x64 per 256-thread workgroup (2 x 2 waves of 64 x 64), three workgroups per CU.  The next K tile is
 // prefetched into registers while the current one is multiplied.  (A three-deep register pipeline with hand-counted waits was measured equal
 // stand-alone and 1.8 % slower in the step -- the kernel is not latency-bound, profiles/r2_wgrad_pmc.txt -- and removed in round 4.  256-row
 // tiles, four MFMA tiles per wave along m, lost at every shape: see launch() below.)
@@ -222,13 +222,6 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_kernel(const GemmParams p_) 
     const int m0 = (vid / tiles_n) * TBM, n0 = (vid % tiles_n) * BN;
     GemmParams p = p_;
     p.zslice = zslice;
-    if (gridDim.y > 1) {
-        const int bo = blockIdx.y / p.batch_inner, bi = blockIdx.y % p.batch_inner;
-        p.A += bo * p.sa_o + bi * p.sa_i;
-        p.B += bo * p.sb_o + bi * p.sb_i;
-        const long long co = bo * p.sc_o + bi * p.sc_i;
-        p.C = (EPI == EPI_BF16) ? (void*)(reinterpret_cast<bf16_t*>(p.C) + co) : (void*)(reinterpret_cast<float*>(p.C) + co);
-    }
 
     const auto [kbeg, kend] = k_slice(p.K, p.nsplit, zslice);
     if (kbeg >= kend) return;
@@ -327,7 +320,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_kernel(const GemmParams p_) 
 // (profiles/r4_wgrad_l2_knockout.txt: half the loads = +3.3 % of the step).  Two 128 x 128 sub-tiles that share one operand tile in LDS
 // read 25 % less; every wave keeps the 64 x 64 accumulator tile (64 VGPRs) of the four-wave kernel, so the footprint per wave is
 // unchanged and the launch has half as many, twice as large workgroups.  Both operands transposed (contraction = rows in memory), ordered
-// split-K partial tiles (EPI_PARTIAL) only, never batched, never kpad.  Two data paths bring a K tile into its [64 kc][ROWS] LDS images;
+// split-K partial tiles (EPI_PARTIAL) only, never kpad.  Two data paths bring a K tile into its [64 kc][ROWS] LDS images;
 // the fragment reads, the MFMA order, the column sums and the epilogue are the same, so both produce the same bits:
 //   DMA = false  register-staged with one tile of prefetch into ONE 48 KiB image pair: two barriers and a ds_write_b128 pass per K tile.
 //                Any K (the tail tile is zero-filled by the store masks).
@@ -729,12 +722,12 @@ bool g4_eligible(const GemmParams& p) {
 // 128x128 tiles at every shape.  (The 256x128 form of this kernel, for m extents tall enough to fill the chip with 256-row tiles, was
 // 5-30 % slower at every shape of these models -- profiles/r1_gemm_tile_ab.txt, r4_wgrad_tiles.txt -- and is no longer instantiated.)
 template <bool TA, bool TB, int EPI, bool COLSUM>
-int launch(const GemmParams& p, int splitk, hipStream_t stream, int nbatch = 1) {
+int launch(const GemmParams& p, int splitk, hipStream_t stream) {
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     constexpr int lds = 2 * TILE_BYTES > STAGE_BYTES ? 2 * TILE_BYTES : STAGE_BYTES;
     GemmParams q = p;
     q.nsplit = splitk;
-    return ppf_launch<gemm_kernel<TA, TB, EPI, COLSUM>>(dim3(tiles * splitk, nbatch, 1), dim3(NTHREADS), lds, stream, "gemm", q);
+    return ppf_launch<gemm_kernel<TA, TB, EPI, COLSUM>>(dim3(tiles * splitk), dim3(NTHREADS), lds, stream, "gemm", q);
 }
 
 // out[i] += sum_z ws[z][i] for the M*N tile elements (row stride ldc) and, when colsum != null, the cs_parts * M partial column sums.
@@ -841,7 +834,7 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.bias = bias; p.res = res; p.ldres = ldres; p.rowscale = rowscale; p.rows_per_group = rows_per_group > 0 ? rows_per_group : 1;
     p.colscale = colscale; p.aux_in = (const bf16_t*)aux_in; p.aux_out = (bf16_t*)aux_out; p.ldaux = ldaux; p.colsum = colsum; p.alpha = alpha; p.ws = nullptr;
-    p.batch_inner = 1; p.sa_o = p.sa_i = p.sb_o = p.sb_i = p.sc_o = p.sc_i = 0; p.kpad = 0; p.cs_parts = 1; p.nsplit = 1;
+    p.kpad = 0; p.cs_parts = 1; p.nsplit = 1;
     if (epi == EPI_RESID) PPF_CHECK_ARG(res != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=4 needs a residual");
     if (epi == EPI_GELU) PPF_CHECK_ARG(aux_out != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=2 needs aux_out");
     if (epi == EPI_DGELU) PPF_CHECK_ARG(aux_in != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=5 needs aux_in");
@@ -909,43 +902,6 @@ int ppf_gemm_probe(int enable) {
 // Synchronises the recorded events: total kernel milliseconds, launches, algorithmic flops and bytes since ppf_gemm_probe(1).
 int ppf_gemm_probe_read(double* ms_total, int64_t* launches, double* flops, double* bytes) {
     return g_probe.sum_ms("ppf_gemm_probe_read", ms_total, launches, flops, bytes);
-}
-
-// Batched plain GEMMs (no bias / fused epilogue): nbatch = batch_outer * batch_inner problems, problem (o, i) uses
-// A + o*sa_o + i*sa_i (elements) etc.  out_f32 selects fp32 or bf16 C.  kpad = 1 lets contraction-contiguous operands read the
-// zero/finite padding up to the next multiple of 8 beyond K (K need not be a multiple of 8 then).
-// Used by the CaiT talking-heads attention: per-(sample, head) P.V, dO.V^T, dS.K, dS^T.Q, A^T.dO products.
-int ppf_gemm_bf16_batched(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int trans_b,
-                          int out_f32, float alpha, int batch_outer, int batch_inner, int64_t sa_o, int64_t sa_i, int64_t sb_o, int64_t sb_i,
-                          int64_t sc_o, int64_t sc_i, int kpad, hipStream_t stream) {
-    PPF_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch_outer > 0 && batch_inner > 0, PPF_ERR_SHAPE, "ppf_gemm_bf16_batched: bad shape");
-    PPF_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0 && (ldc % 4) == 0 && (N % 4) == 0, PPF_ERR_ALIGN, "ppf_gemm_bf16_batched: ld alignment");
-    PPF_CHECK_ARG(kpad || (trans_a ? (M % 8 == 0) : (K % 8 == 0)), PPF_ERR_ALIGN, "ppf_gemm_bf16_batched: A inner extent must be a multiple of 8");
-    PPF_CHECK_ARG(kpad || (trans_b ? (N % 8 == 0) : (K % 8 == 0)), PPF_ERR_ALIGN, "ppf_gemm_bf16_batched: B inner extent must be a multiple of 8");
-    PPF_CHECK_ARG(((sa_o | sa_i | sb_o | sb_i) % 8) == 0 && ((sc_o | sc_i) % 4) == 0, PPF_ERR_ALIGN, "ppf_gemm_bf16_batched: batch strides alignment");
-    // the bf16-output epilogue stores 16 bytes per lane whenever ldc % 8 == 0: every problem's C must then start on a 16-byte boundary
-    PPF_CHECK_ARG(out_f32 || (ldc % 8) != 0 || ((sc_o | sc_i) % 8) == 0, PPF_ERR_ALIGN,
-                  "ppf_gemm_bf16_batched: bf16 output with ldc %% 8 == 0 needs batch strides of C that are multiples of 8 elements (sc_o=%lld sc_i=%lld)",
-                  (long long)sc_o, (long long)sc_i);
-    PPF_CHECK_ARG((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0, PPF_ERR_ALIGN, "ppf_gemm_bf16_batched: pointers must be 16-byte aligned");
-    GemmParams p;
-    p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.bias = nullptr; p.res = nullptr; p.ldres = 0; p.rowscale = nullptr; p.rows_per_group = 1; p.colscale = nullptr; p.aux_in = nullptr;
-    p.aux_out = nullptr; p.ldaux = 0; p.colsum = nullptr; p.ws = nullptr; p.alpha = alpha;
-    p.batch_inner = batch_inner; p.sa_o = sa_o; p.sa_i = sa_i; p.sb_o = sb_o; p.sb_i = sb_i; p.sc_o = sc_o; p.sc_i = sc_i; p.kpad = kpad;
-    const int nb = batch_outer * batch_inner;
-    const auto go = [&](auto ta, auto tb) {
-        int rc = PPF_ERR_ARG;
-        dispatch_epi<EPI_BF16, EPI_F32>(out_f32 ? EPI_F32 : EPI_BF16, rc, [&](auto e) {
-            return launch<decltype(ta)::value, decltype(tb)::value, decltype(e)::value, false>(p, 1, stream, nb);
-        });
-        return rc;
-    };
-    if (!trans_a && !trans_b) return go(std::false_type(), std::false_type());
-    if (!trans_a && trans_b) return go(std::false_type(), std::true_type());
-    if (trans_a && trans_b) return go(std::true_type(), std::true_type());
-    ppf_set_error("ppf_gemm_bf16_batched: (trans_a=1, trans_b=0) is not instantiated");
-    return PPF_ERR_ARG;
 }
 
 }  // extern "C"

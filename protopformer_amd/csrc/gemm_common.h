@@ -21,13 +21,11 @@ struct GemmParams {
     float* colsum;           // EPI_ATOMIC + TA: sum over kc of A(m,kc) accumulated atomically into colsum[m]
     float* ws;               // EPI_PARTIAL: split-K workspace [nsplit][M*N (+M)] fp32 partial tiles (+ partial column sums)
     float alpha;
-    // batched problems (blockIdx.y = outer*batch_inner + inner): element offsets added to A / B / C
-    int batch_inner;
-    long long sa_o, sa_i, sb_o, sb_i, sc_o, sc_i;
     int zslice;              // (device side) this workgroup's K slice
     int nsplit;              // split-K slices; grid.x = tiles * nsplit, slice-major so that an XCD owns whole K slices
     int cs_parts;            // EPI_PARTIAL: partial column sums per slice and row (1)
     int kpad;                // 1: contraction-contiguous operands may read up to the next multiple of 8 beyond K (zero/finite padding)
+                             // always 0 since the batched GEMM left; removing it cost gemm_kernel<0,1,EPI_F32,0> 128 -> 130 VGPRs, 4 -> 3 workgroups per CU (MEASUREMENTS.md 5m)
 };
 
 // gelu'(x) of the erf GELU lies in [-0.1290, 1.1290]: it is saved for the backward pass as an 8-bit linear code (round 4):

@@ -1,6 +1,4 @@
 """Thin host-side wrappers over the C-ABI kernels (no arithmetic here: allocation, shapes, launch)."""
-import os
-
 import torch
 
 from . import _lib
@@ -937,74 +935,19 @@ def scale_by_scalar(x, scalar):
 
 
 # ------------------------------------------------------------------------------------------------ CaiT
-def gemm_batched(a, b, c, M, N, K, lda, ldb, ldc, trans_a, trans_b, out_f32, alpha, bo, bi, sa, sb, sc, kpad=0):
-    """Raw batched GEMM on pointers with element offsets: sa/sb/sc = (outer stride, inner stride)."""
-    _lib.call("ppf_gemm_bf16_batched", a, b, c, M, N, K, lda, ldb, ldc, int(trans_a), int(trans_b), int(out_f32), float(alpha), bo, bi,
-              sa[0], sa[1], sb[0], sb[1], sc[0], sc[1], int(kpad))
-
-
-class _Off:
-    """A device pointer at an element offset into a tensor (for sub-matrix views handed to the C ABI)."""
-
-    def __init__(self, t, off):
-        self.t, self.off = t, off
-
-    def data_ptr(self):
-        return self.t.data_ptr() + self.off * self.t.element_size()
-
-
-def th_scores(qkv, wl, bl, B, H, N, D):
-    NP = (N + 3) // 4 * 4
-    sp = torch.empty((B, H, N, NP), dtype=torch.float32, device=qkv.device)
-    _lib.call("ppf_th_scores", qkv, wl, bl, sp, B, H, N, D, NP)
-    return sp
-
-
-def th_softmax_mix(sp, ww, bw, hm_out):
-    B, H, N, NP = sp.shape
-    NPK = (N + 7) // 8 * 8
-    a16 = torch.empty((B, H, N, NPK), dtype=torch.bfloat16, device=sp.device)
-    _lib.call("ppf_th_softmax_mix", sp, a16, hm_out, ww, bw, B, H, N, NP, NPK)
-    return a16
-
-
-def th_softmax_bwd(prob, da, ww, wl, dww, dbw, dbl):
-    B, H, N, NP = prob.shape
-    NPK = (N + 7) // 8 * 8
-    ds16 = torch.empty((B, H, N, NPK), dtype=torch.bfloat16, device=prob.device)
-    _lib.call("ppf_th_softmax_bwd", prob, da, ds16, ww, wl, dww, dbw, dbl, B, H, N, NP, NPK)
-    return ds16
-
-
-def th_dwl(qkv, ds_prime, dwl, B, H, N, D):
-    _lib.call("ppf_th_dwl", qkv, ds_prime, dwl, B, H, N, D, ds_prime.shape[-1])
-
-
-def _th_mode():
-    """PPF_TH_FUSED: "1" (default) the fused talking-heads kernels incl. A.V forward and one launch for dQ / dK / dV backward; "pv0" the fused
-    kernels up to A / dS with the per-head products as batched GEMMs; "0" the materialising kernels (what shapes outside the fused kernels'
-    cover get).  The two non-default values exist so that tests/test_gpu_cait.py exercises those fallback kernels at a shape the fused ones cover."""
-    return os.environ.get("PPF_TH_FUSED", "1")
-
-
 def th_fused_ok(H, N, D):
-    """The fused talking-heads kernels (csrc/cait.hip th_fwd / th_bwd) cover this (heads, tokens, width)."""
-    return _th_mode() != "0" and bool(_lib.lib().ppf_th_fused_supported(H, N, D))
+    """The talking-heads kernels th_fwd / th_bwd (csrc/cait.hip) cover this (heads, tokens, width)."""
+    return bool(_lib.lib().ppf_th_fused_supported(H, N, D))
 
 
-def th_pv_fused():
-    return _th_mode() == "1"
-
-
-def th_fwd(qkv, wl, bl, ww, bw, hm_out, B, H, N, D, with_out=True):
+def th_fwd(qkv, wl, bl, ww, bw, hm_out, B, H, N, D):
     """cait:119-128 in one launch: returns (a16 bf16 [B,H,N,NPK] = proj_w(softmax(proj_l(scale q k^T))), rowmax, zinv [B,H,N], out);
-    hm_out [B,N,NP] receives the head mean of the mixed probabilities (rollout input); out = a16 @ v as bf16 [B*N, D] (None when
-    with_out is False: the caller multiplies)."""
+    hm_out [B,N,NP] receives the head mean of the mixed probabilities (rollout input); out = a16 @ v as bf16 [B*N, D]."""
     NP, NPK = (N + 3) // 4 * 4, (N + 7) // 8 * 8
     a16 = torch.empty((B, H, N, NPK), dtype=torch.bfloat16, device=qkv.device)
     rowmax = torch.empty((B, H, N), dtype=torch.float32, device=qkv.device)
     zinv = torch.empty_like(rowmax)
-    out = torch.empty((B * N, D), dtype=torch.bfloat16, device=qkv.device) if with_out else None
+    out = torch.empty((B * N, D), dtype=torch.bfloat16, device=qkv.device)
     _lib.call("ppf_th_fwd", qkv, wl, bl, ww, bw, a16, hm_out, rowmax, zinv, out, B, H, N, D, NP, NPK)
     return a16, rowmax, zinv, out
 
@@ -1020,7 +963,8 @@ def th_bwd(qkv, dout, wl, bl, ww, rowmax, zinv, B, H, N, D):
 
 
 def th_grads_ok(H, N, D):
-    return _th_mode() == "1" and bool(_lib.lib().ppf_th_grads_supported(H, N, D))
+    """th_grads, and with it training, covers this (heads, tokens, width)."""
+    return bool(_lib.lib().ppf_th_grads_supported(H, N, D))
 
 
 def th_grads(qkv, dout, ds16, a16, dqkv, B, H, N, D):

@@ -392,7 +392,7 @@ extern "C" int ppf_gemm_nt256(const void* A, const void* B, void* C, int M, int 
     ppfg::GemmParams p{};
     p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = C; p.M = M; p.N = N; p.K = K; p.lda = K; p.ldb = K; p.ldc = N;
     p.bias = bias; p.res = res; p.ldres = N; p.rows_per_group = 1; p.aux_in = (const bf16_t*)aux; p.aux_out = (bf16_t*)aux; p.ldaux = N;
-    p.alpha = 1.0f; p.batch_inner = 1; p.cs_parts = 1; p.nsplit = 1;
+    p.alpha = 1.0f; p.cs_parts = 1; p.nsplit = 1;
     if (!ppfg::nt256_eligible(p, epi)) return PPF_ERR_SHAPE;
     return ppfg::launch_nt256(p, epi, stream);
 }

@@ -26,28 +26,17 @@ def _th_block(wl, bl, ww, bw):
 
 
 def _th_forward(qkv16, wl, bl, ww, bw, B, H, N, D):
-    """The product's forward helper (fused kernel or the materialising kernels, PPF_TH_FUSED): (ao, saved statistics / P, a16, head mean)."""
+    """The product's forward helper: (ao, saved softmax statistics, a16, head mean)."""
     from protopformer_amd.cait import _th_attention_fwd
     hm = torch.empty((B, N, (N + 3) // 4 * 4), dtype=torch.float32, device="cuda")
     ao, prob, a16 = _th_attention_fwd(_th_block(wl, bl, ww, bw), qkv16, B, H, N, D, hm)
     return ao, prob, a16, hm
 
 
-FUSED = pytest.mark.parametrize("fused", ["1", "pv0", "0"], ids=["fused", "fused-separate-products", "materialised"])
-
-
-def _set_th_mode(monkeypatch, fused):
-    """fused: one launch incl. A.V forward, th_bwd + one launch for dQ / dK / dV backward; pv0: the fused kernels up to A / dS, the
-    per-head products as batched GEMMs; 0: the materialising kernels."""
-    monkeypatch.setenv("PPF_TH_FUSED", fused)
-
-
-@FUSED
-def test_talking_heads_forward_golden(fused, monkeypatch):
+def test_talking_heads_forward_golden():
     """TalkingHeadAttn.forward on the reference's weights/inputs (ops_real.npz), qkv/proj through the GEMM kernel."""
     from protopformer_amd import ops
-    _set_th_mode(monkeypatch, fused)
-    assert ops.th_fused_ok(4, 196, 192) == (fused != "0")
+    assert ops.th_fused_ok(4, 196, 192) and ops.th_grads_ok(4, 196, 192)
     z = load_npz("ops_real.npz")
     c = gi.cait_inputs()
     B, H, N, D = c["B"], c["H"], c["N"], c["D"]
@@ -66,10 +55,8 @@ def test_talking_heads_forward_golden(fused, monkeypatch):
     assert rel_err(hm[..., :N], p_ref.mean(1)) < 2e-2, rel_err(hm[..., :N], p_ref.mean(1))
 
 
-@FUSED
-def test_talking_heads_backward_vs_oracle(fused, monkeypatch):
+def test_talking_heads_backward_vs_oracle():
     from protopformer_amd import ops
-    _set_th_mode(monkeypatch, fused)
     B, H, N, D = 2, 4, 196, 192
     hd = D // H
     g = torch.Generator().manual_seed(3)
@@ -103,7 +90,7 @@ def test_talking_heads_backward_vs_oracle(fused, monkeypatch):
     st = _S()
     dqkv = _th_attention_bwd(st, blk, dict(qkv=qd, prob=prob, a16=a16), dao.cuda(), B, H, N, D)
     from protopformer_amd.backbone import wgrad_lane
-    wgrad_lane(st).join()                       # the fused path sums the parameter-gradient partials on the side stream
+    wgrad_lane(st).join()                       # the backward sums the parameter-gradient partials on the side stream
     torch.cuda.synchronize()
     dqkv = dqkv.float().cpu()
     scale = float(t.grad.abs().max())

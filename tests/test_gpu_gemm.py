@@ -214,49 +214,6 @@ def test_gemm_wgrad_eight_wave_tiles(n_out, n_in, rows):
     assert torch.equal(o2, d2[7][:, None] * x2[7][None, :])
 
 
-def test_gemm_batched_packed_views():
-    """ppf_gemm_bf16_batched through ops.gemm_batched at a talking-heads-like shape (2 samples x 3 heads, 50 tokens, head width 48): every
-    instantiated (trans_a, trans_b, out_f32) key on views into packed buffers -- a qkv-style matrix (leading dimension 3 * 144) and a
-    probability-style one (rows of 56 = 50 rounded up to 8, pad columns zero, kpad = 1 where the 50 tokens are contracted) -- with a non-unit
-    alpha, written at a non-zero offset into a larger sentinel-filled buffer: a wrong batch stride or a dropped offset lands outside the
-    expected positions.  fp32 torch reference on the same bf16-rounded inputs."""
-    from protopformer_amd import ops
-    B, H, N, hd = 2, 3, 50, 48
-    D, NPK, alpha, SENT = H * hd, 56, 0.37, 7.0
-    qkv = _mk((B * N, 3 * D), 1.0, 1).bfloat16()
-    dao = _mk((B * N, D), 1.0, 2).bfloat16()
-    prob = torch.zeros(B, H, N, NPK, device="cuda")
-    prob[..., :N] = _mk((B, H, N, N), 0.3, 3)
-    prob = prob.bfloat16()
-    q4 = qkv.float().view(B, N, 3, H, hd)
-    Q, K, V = (q4[:, :, i].permute(0, 2, 1, 3) for i in range(3))               # [B, H, N, hd]
-    dO = dao.float().view(B, N, H, hd).permute(0, 2, 1, 3)
-    P = prob.float()[..., :N]
-    sprob = (H * N * NPK, N * NPK)
-    cases = {   # (trans_a, trans_b): (a, b, M, N, K, lda, ldb, sa, sb, kpad, reference [B, H, M, N])
-        (0, 0): (qkv, ops._Off(qkv, D), N, hd, hd, 3 * D, 3 * D, (N * 3 * D, hd), (N * 3 * D, hd), 0, Q @ K[:, :, :hd].transpose(2, 3)),
-        (0, 1): (prob, ops._Off(qkv, 2 * D), N, hd, N, NPK, 3 * D, sprob, (N * 3 * D, hd), 1, P @ V),
-        (1, 1): (prob, dao, N, hd, N, NPK, D, sprob, (N * D, hd), 1, P.transpose(2, 3) @ dO),
-    }
-    lead = 3 * D + 2 * D                                # one leading row, then the third column block of a [B * N, 3 * D] matrix
-    for (ta, tb), (a, b, M, Nn, Kk, lda, ldb, sa, sb, kpad, ref) in cases.items():
-        for out_f32 in (0, 1):
-            big = torch.full(((B * N + 2) * 3 * D,), SENT, dtype=torch.float32 if out_f32 else torch.bfloat16, device="cuda")
-            ops.gemm_batched(a, b, ops._Off(big, lead), M, Nn, Kk, lda, ldb, 3 * D, ta, tb, out_f32, alpha, B, H, sa, sb, (N * 3 * D, hd), kpad=kpad)
-            exp = torch.full((B * N + 2, 3 * D), SENT, device="cuda")
-            r = alpha * ref if out_f32 else (alpha * ref).bfloat16().float()
-            exp[1:1 + B * N, 2 * D:] = r.permute(0, 2, 1, 3).reshape(B * N, D)
-            got = big.float().view(B * N + 2, 3 * D)
-            inside = torch.zeros_like(exp, dtype=torch.bool)
-            inside[1:1 + B * N, 2 * D:] = True
-            assert bool((got[~inside] == SENT).all()), f"key {(ta, tb, out_f32)}: wrote outside its output"
-            tol = dict(rtol=1e-3, atol=1e-3) if out_f32 else dict(rtol=8e-3, atol=1e-3)
-            assert_close(got[inside], exp[inside], what=f"batched key {(ta, tb, out_f32)}", **tol)
-    big = torch.zeros((B * N + 2) * 3 * D, dtype=torch.bfloat16, device="cuda")
-    with pytest.raises(RuntimeError, match="not instantiated"):
-        ops.gemm_batched(prob, qkv, big, N, hd, N, NPK, 3 * D, 3 * D, True, False, False, 1.0, B, H, sprob, (N * 3 * D, hd), (N * 3 * D, hd), kpad=1)
-
-
 def test_gemm_wgrad_atomic_without_workspace():
     """EPI_ATOMIC with workspace=False: dW[192, 192] += dy[520, 192]^T x with x read at ldb = 5 * 192 (every fifth row of a [2600, 192] matrix)
     and the column sums of dy.  pick_splitk gives three K slices of 192 / 192 / 136 rows: real fp32 atomics from several slices, a ragged

@@ -39,8 +39,6 @@ CASES = [
     ("PPF_WGRAD_STREAM", "0", "cait", 0.0),
     ("PPF_COMPACT_RESERVED", "0", "deit", 2e-3),        # the reference's masked full-length last blocks: bf16 rounding of other row counts
     ("PPF_PROTO_KEEP_DIST", "1", "deit", 1e-5),         # backward from the saved distance map instead of the activation map
-    ("PPF_TH_FUSED", "0", "cait", 3e-3),                # materialising talking-heads kernels
-    ("PPF_TH_FUSED", "pv0", "cait", 3e-3),              # fused up to A / dS, per-head products as batched GEMMs
     ("PPF_PRECISE", "1", "deit", 2e-2),                 # fp32 verification mode against the bf16 product path
     ("PPF_PRECISE", "1", "cait", 2e-2),
 ]
