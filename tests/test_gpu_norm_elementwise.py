@@ -24,6 +24,7 @@ def test_layernorm_fwd_bwd(rows, D):
     y, mean, rstd = ops.layernorm_fwd(x.cuda(), w.cuda(), b.cuda())
     assert_close(y.float(), y_ref.detach().bfloat16().float(), rtol=8e-3, atol=1e-3, what="ln fwd")
     assert_close(mean, x.mean(-1), rtol=1e-4, atol=1e-5, what="mean")
+    assert_close(rstd, 1.0 / torch.sqrt(x.double().var(-1, unbiased=False) + 1e-6), rtol=1e-4, atol=1e-5, what="rstd")
     dw = torch.zeros(D, device="cuda"); db = torch.zeros(D, device="cuda")
     dx = torch.empty(rows, D, device="cuda")
     rs = torch.tensor([0.0, 1.0 / 0.9, 1.0], device="cuda")
