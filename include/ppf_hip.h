@@ -325,6 +325,25 @@ int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx
 int ppf_explain_topk(const float* act_max, const int* argmax, const int* idx, int T, const float* act_full, const float* weight, float scale,
                      int ppc, const float* logits, const int* cls_in, int sign, int B, int P, int C, int M, int K, int G, int* cls_out,
                      float* cls_logit, int* proto, float* contrib, float* act, int* cell, float* evidence, float* maps, ppf_stream_t stream);
+/* Prototype statistics over a data set (csrc/proto_stats.hip): which prototypes does the model use?  ProtoPNet's pruning pass and the
+ * activation percentiles of its local analysis both need, per prototype, the distribution of the pooled activation over the own-class
+ * and the other-class images; the reference has no such pass.  One call adds a batch into persistent int32 accumulators in device
+ * memory, zeroed once by the caller.  Addition of ABI 10: no existing entry point changed.
+ *   act_max [B][P], argmax [B][P]: as ppf_proto_fwd writes them; idx [B][T] int32: the grid positions of the reserved tokens.
+ *   argmax == NULL: the global / cls branch; idx must be NULL too, coloc may be NULL and is not touched.  label_i64 [B]; C = P / ppc.
+ *   hist [P][2][NB]: hist[p][slot][bin(act_max[b][p])] += 1 with slot 0 when label[b] == p / ppc (own class), else slot 1.
+ *     bin(a): t = fl(fl(a - lo) * inv_width) in fp32, two separate roundings, nothing fused; bin 0 when t < 0 (-inf included),
+ *     bin NB-1 when t >= NB (+inf included), else (int)t.  The caller passes inv_width = fl(NB / fl(hi - lo)), rounded on the host.
+ *   nan_count [P][2]: a NaN activation is not binned; nan_count[p][slot] += 1 instead.
+ *   coloc [P][ppc] (local branch): fed by own-class samples only.  For sample b of class c and prototypes p, q of class c:
+ *     cell(p) = idx[b][argmax[b][p]], invalid when that argmax lies outside [0, T); coloc[p][q % ppc] += 1 when both cells are valid
+ *     and equal.  The diagonal counts the own-class images in which p has a valid cell.
+ *   images [C]: images[label[b]] += 1.  A label outside [0, C) adds one to bad[0], reads nothing else and adds nothing else (the
+ *     ppf_part_meter_update convention).
+ * 1 <= B <= 1024, P >= 1, P % ppc == 0, 1 <= ppc <= 64, 8 <= NB <= 128, T >= 1 on the local branch, lo finite, inv_width finite
+ * and > 0 (else PPF_ERR_SHAPE).  Integer atomics only: any split of the same images into batches, in any order, gives the same tables. */
+int ppf_proto_stats_update(const float* act_max, const int* argmax, const int* idx, int T, const void* label_i64, int ppc, int B, int P, int NB,
+                           float lo, float inv_width, int* hist, int* nan_count, int* coloc, int* images, int* bad, ppf_stream_t stream);
 /* Faithfulness of an explanation (csrc/faithful.hip): deletion / insertion curves (Petsiuk et al., RISE, 2018).  Rank the G cells of the
  * patch grid by their evidence for a class, remove (or show only) the first counts[s] of them, and read the class probability off the
  * model's logits for the perturbed images; the forwards in between are the caller's.  The reference has no such pass.  Additions of

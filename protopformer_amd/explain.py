@@ -5,11 +5,13 @@ Per batch one eval forward and one `ppf_explain_topk` launch per branch (interpr
 logit, the grid cell each of them fired at and, with --render, their activation maps come back; nothing of size [B, P] is read.
 
     python -m protopformer_amd.explain --resume CKPT --data_set CUB2011U --data_path ... --output_dir OUT [--split train|test] [--topk 10]
-                                       [--top_classes 1] [--against] [--max_images N] [--bank OUT/prototype_bank.npz] [--render]
+                                       [--top_classes 1] [--against] [--max_images N] [--bank OUT/prototype_bank.npz] [--stats OUT/prototype_stats.npz] [--render]
                                        + the model flags of train.py
 
 writes OUT/explanations.jsonl, one line per image (Explanation.report's record plus image_id, image path and label); with
 --bank every listed prototype carries its nearest training patches from the prototype bank (python -m protopformer_amd.bank); with
+--stats its activation's percentile among all and among the own-class images of the prototype statistics (python -m
+protopformer_amd.protostats); with
 --render also img_<id>/class<c>_rank<r>.jpg: the activation overlay of the rank-r local prototype with its high-activation box."""
 import argparse
 import json
@@ -29,6 +31,7 @@ def get_args_parser():
     a("--top_classes", type=int, default=1, help="classes explained per image, by logit (1..8)")
     a("--against", action="store_true", default=False, help="rank the strongest evidence against each class instead of for it")
     a("--bank", type=str, default="", metavar="PATH", help="prototype_bank.npz of the bank tool: attach each prototype's nearest training patches")
+    a("--stats", type=str, default="", metavar="PATH", help="prototype_stats.npz of the protostats tool: attach each activation's percentiles")
     a("--render", action="store_true", default=False, help="also write img_<id>/class<c>_rank<r>.jpg activation overlays")
     return p
 
@@ -82,6 +85,10 @@ def main(args, model=None, loader=None, index=None):
         index = image_index(ds)
     model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     bank = dict(np.load(args.bank)) if args.bank else None
+    stats = None
+    if args.stats:
+        from .protostats import load_stats
+        stats = load_stats(args.stats)
     index = index or {}
     os.makedirs(args.output_dir, exist_ok=True)
     path, seen, rendered = os.path.join(args.output_dir, "explanations.jsonl"), 0, 0
@@ -92,7 +99,7 @@ def main(args, model=None, loader=None, index=None):
             ex = explain(model, x if x.is_cuda else x.to(device), top_classes=args.top_classes, topk=args.topk, against=args.against, maps=args.render)
             host = ex.cpu()
             labels = np.asarray(torch.as_tensor(y).cpu())
-            for rec in host.report(bank=bank):
+            for rec in host.report(bank=bank, stats=stats):
                 b = rec["image"]
                 file, _ = index.get(int(ids[b]), (None, None))
                 rec.update(image_id=int(ids[b]), image=file, label=int(labels[b]) if labels.ndim == 1 else None)

@@ -745,12 +745,14 @@ class Explanation:
             out[br][k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
         return Explanation(out["local"], out["global"], self.ppc, self.scale, self.side, self.patch_size, self.img_size, self.against)
 
-    def report(self, index=None, bank=None):
+    def report(self, index=None, bank=None, stats=None):
         """JSON-able records, one per image (index: None = every image of the batch, or one batch position, or a sequence of them):
         {'image': b, 'against', 'classes': [{'class', 'logit', 'local': branch, 'global': branch}]} with branch = {'scale', 'evidence_own',
         'evidence_other', 'prototypes': [{'rank', 'prototype', 'prototype_class', 'weight', 'activation', 'contribution'; on the local
         branch also 'cell', 'patch_box' [x0, y0, x1, y1] and (with maps) 'activation_box' [y0, y1, x0, x1]; with `bank` (the arrays of
-        prototype_bank.npz) 'nearest': that prototype's ranked training patches [{'rank', 'image_id', 'activation', 'grid_pos'}]}]}.
+        prototype_bank.npz) 'nearest': that prototype's ranked training patches [{'rank', 'image_id', 'activation', 'grid_pos'}]; with
+        `stats` (protostats.PrototypeStats.result() or load_stats of prototype_stats.npz) 'percentile_all' and 'percentile_own': where the
+        activation stands among all / the own-class images the statistics recorded (protostats.percentile)}]}.
         Unfilled slots and classes that could not be explained (class -1) are dropped."""
         h = self.cpu()
         B = h.branches["local"]["classes"].shape[0]
@@ -766,12 +768,12 @@ class Explanation:
                     continue
                 entry = {"class": c, "logit": float(h.branches["local"]["class_logits"][b, m])}
                 for br in EXPLAIN_BRANCHES:
-                    entry[br] = h._branch_record(br, b, m, bank)
+                    entry[br] = h._branch_record(br, b, m, bank, stats)
                 classes.append(entry)
             records.append({"image": b, "against": h.against, "classes": classes})
         return records
 
-    def _branch_record(self, br, b, m, bank):
+    def _branch_record(self, br, b, m, bank, stats=None):
         f = self.branches[br]
         protos = []
         for k in range(f["prototypes"].shape[2]):
@@ -790,6 +792,10 @@ class Explanation:
                 n = int(bank[f"{br}_filled"][p])
                 e["nearest"] = [dict(rank=r, image_id=int(bank[f"{br}_image_ids"][p, r]), activation=float(bank[f"{br}_values"][p, r]),
                                      grid_pos=int(bank[f"{br}_grid_pos"][p, r])) for r in range(n)]
+            if stats is not None:
+                from .protostats import percentile
+                e["percentile_all"] = percentile(stats[br], p, e["activation"], "all")
+                e["percentile_own"] = percentile(stats[br], p, e["activation"], "own")
             protos.append(e)
         return dict(scale=self.scale[br], evidence_own=float(f["evidence"][b, m, 0]), evidence_other=float(f["evidence"][b, m, 1]), prototypes=protos)
 

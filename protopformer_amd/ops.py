@@ -454,6 +454,35 @@ def proto_topk_merge(act_max, argmax, idx, tokens, t0, label, image_id, ppc, val
               val, img, pos, best_feat)
 
 
+def proto_stats_update(act_max, argmax, idx, label, ppc, lo, inv_width, hist, nan_count, coloc, images, bad):
+    """Add one batch into the int32 prototype statistics hist [P, 2, NB], nan_count [P, 2], coloc [P, ppc] (None on the global branch),
+    images [P // ppc], bad [1] (ppf_proto_stats_update, include/ppf_hip.h); launches only.  act_max [B, P] fp32 and argmax [B, P] int32 as
+    proto_fwd returns them (argmax None: global branch, then idx None too and coloc is not touched); idx [B, T] int32; label int64 [B];
+    lo and inv_width = fl(NB / fl(hi - lo)) as fp32 values.  The limits on B, ppc, NB, lo and inv_width are the entry point's."""
+    _chk(act_max, torch.float32)
+    if act_max.dim() != 2 or hist.dim() != 3:
+        raise ValueError(f"proto_stats_update: act_max [B, P] and hist [P, 2, NB] expected, got {tuple(act_max.shape)} and {tuple(hist.shape)}")
+    (B, P), NB, dev, ppc = act_max.shape, hist.shape[2], act_max.device, int(ppc)
+    if (argmax is None) != (idx is None):
+        raise ValueError("proto_stats_update: argmax and idx come together (both None on the global branch)")
+    T = 0
+    if argmax is not None:
+        _chk(argmax, torch.int32), _chk(idx, torch.int32)
+        T = idx.shape[1] if idx.dim() == 2 else -1
+        if argmax.shape != act_max.shape or idx.shape != (B, T) or coloc is None:
+            raise ValueError(f"proto_stats_update: argmax {tuple(argmax.shape)} / idx {tuple(idx.shape)} do not fit act_max {tuple(act_max.shape)}, "
+                             "or the local branch came without coloc")
+    if label.dtype != torch.int64 or label.shape != (B,) or not label.is_contiguous() or label.device != dev:
+        raise ValueError(f"proto_stats_update: label must be a contiguous int64 tensor [{B}] on {dev}")
+    tables = [("hist", hist, (P, 2, NB)), ("nan_count", nan_count, (P, 2)), ("bad", bad, (1,))]
+    if ppc >= 1 and P % ppc == 0:                          # (a ppc the entry point refuses is left for it to name)
+        tables += [("images", images, (P // ppc,))] + ([("coloc", coloc, (P, ppc))] if coloc is not None else [])
+    for name, t, shape in tables:
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"proto_stats_update: {name} must be a contiguous int32 tensor {shape} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    _lib.call("ppf_proto_stats_update", act_max, argmax, idx, T, label, ppc, B, P, NB, float(lo), float(inv_width), hist, nan_count, coloc, images, bad)
+
+
 def explain_topk(act_max, weight, scale, ppc, logits, K, *, classes=None, top_classes=1, sign=1, argmax=None, idx=None, act_full=None,
                  grid_cells=0, want_maps=False):
     """The K strongest class evidences per (sample, class) of one branch (ppf_explain_topk, include/ppf_hip.h); one launch.
