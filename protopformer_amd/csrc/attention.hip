@@ -1031,9 +1031,7 @@ int ppf_attn_fwd(const void* qkv, void* out, const float* policy, float* rowmax,
     PpfProbeScope probe(PPF_PROBE_ATTN_FWD, stream, 4.0 * B * H * (double)N * N * (D / H), 8.0 * B * N * (double)D + 8.0 * B * H * N);
     return dispatch(D / H, N, "ppf_attn_fwd", [&](auto hd, auto nt) {
         using G = Geo<decltype(nt)::value>;
-        hipLaunchKernelGGL((attn_fwd_kernel<decltype(hd)::value, decltype(nt)::value>), dim3((N + G::NW * 32 - 1) / (G::NW * 32), H, B), dim3(G::NTHR), 0, stream, p);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<attn_fwd_kernel<decltype(hd)::value, decltype(nt)::value>>(dim3((N + G::NW * 32 - 1) / (G::NW * 32), H, B), dim3(G::NTHR), 0, stream, "ppf_attn_fwd", p);
     });
 }
 
@@ -1077,12 +1075,11 @@ int ppf_attn_headmean(const void* qkv, const float* policy, const float* rowmax,
     const int hd = D / H;
     constexpr int KT = 4;
     dim3 grid((N + 127) / 128, (N + KT * 32 - 1) / (KT * 32), B);
-    if (hd == 64) hipLaunchKernelGGL((attn_headmean_kernel<64, KT>), grid, dim3(256), 0, stream, p);
-    else if (hd == 48) hipLaunchKernelGGL((attn_headmean_kernel<48, KT>), grid, dim3(256), 0, stream, p);
-    else if (hd == 32) hipLaunchKernelGGL((attn_headmean_kernel<32, KT>), grid, dim3(256), 0, stream, p);
-    else { ppf_set_error("ppf_attn_headmean: unsupported head_dim=%d", hd); return PPF_ERR_SHAPE; }
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (hd == 64) return ppf_launch<attn_headmean_kernel<64, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
+    if (hd == 48) return ppf_launch<attn_headmean_kernel<48, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
+    if (hd == 32) return ppf_launch<attn_headmean_kernel<32, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
+    ppf_set_error("ppf_attn_headmean: unsupported head_dim=%d", hd);
+    return PPF_ERR_SHAPE;
 }
 
 // dqkv[B*N][3D] from dout[B*N][D]; needs out, rowmax, zinv of the forward; delta[B][H][N] is scratch.

@@ -806,9 +806,7 @@ int ppf_th_grads(const void* qkv, const void* dout, const void* ds16, const void
 int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, float* dbw, float* dbl, float* dwl, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && (H == 2 || H == 4) && N > 0, PPF_ERR_SHAPE, "ppf_th_param_reduce: bad shape");
     const int PW = 2 * H * H + 2 * H;
-    hipLaunchKernelGGL(th_param_reduce_kernel, dim3(PW), dim3(256), 0, stream, partial, B * th_groups(N), PW, H, dww, dbw, dbl, dwl);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<th_param_reduce_kernel>(dim3(PW), dim3(256), 0, stream, "ppf_th_param_reduce", partial, B * th_groups(N), PW, H, dww, dbw, dbl, dwl);
 }
 
 // Class attention (cait:71-90, policy softmax cait:50-69): q [B][D] (cls rows), k/v [B*N1][D]; out [B][D],
@@ -818,9 +816,7 @@ int ppf_class_attn_fwd(const void* q, const void* k, const void* v, const float*
     PPF_CHECK_ARG(B > 0 && H >= 1 && H <= 4 && N1 <= 256 && D % H == 0 && (D / H) <= 64 && (D / H) % 2 == 0, PPF_ERR_SHAPE, "ppf_class_attn_fwd: bad shape");
     CaParams p = CaParams(); p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.policy = policy; p.attn = attn; p.zinv = zinv;
     p.rowmean = rowmean; p.out = (bf16_t*)out; p.B = B; p.H = H; p.N1 = N1; p.D = D; p.scale = 1.0f / sqrtf((float)(D / H));
-    hipLaunchKernelGGL(class_attn_fwd_kernel, dim3(B), dim3(256), 0, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<class_attn_fwd_kernel>(dim3(B), dim3(256), 0, stream, "ppf_class_attn_fwd", p);
 }
 
 int ppf_class_attn_bwd(const void* q, const void* k, const void* v, const float* attn, const float* zinv, const void* dout, void* dq, void* dk,
@@ -829,18 +825,14 @@ int ppf_class_attn_bwd(const void* q, const void* k, const void* v, const float*
     CaParams p = CaParams(); p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.attn = (float*)attn; p.zinv = (float*)zinv;
     p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.B = B; p.H = H; p.N1 = N1; p.D = D;
     p.scale = 1.0f / sqrtf((float)(D / H));
-    hipLaunchKernelGGL(class_attn_bwd_kernel, dim3(B), dim3(256), 0, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<class_attn_bwd_kernel>(dim3(B), dim3(256), 0, stream, "ppf_class_attn_bwd", p);
 }
 
 // out bf16 [rows][D] = a + b (+ cq[row / N1] on rows that are a multiple of N1)
 int ppf_merge3_cast(const float* a, const float* b, const float* cq, void* out, int rows, int D, int N1, hipStream_t stream) {
     PPF_CHECK_ARG(rows > 0 && D % 2 == 0 && N1 > 0, PPF_ERR_SHAPE, "ppf_merge3_cast: bad shape");
     const size_t total = (size_t)rows * D / 2;
-    hipLaunchKernelGGL(merge3_cast_kernel, dim3((int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256)), dim3(256), 0, stream, a, b, cq, (bf16_t*)out, rows, D, N1);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<merge3_cast_kernel>(dim3((int)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256)), dim3(256), 0, stream, "ppf_merge3_cast", a, b, cq, (bf16_t*)out, rows, D, N1);
 }
 
 }  // extern "C"

@@ -365,40 +365,30 @@ extern "C" {
 
 int ppf_cast_f32_bf16(const float* in, void* out, int64_t n, hipStream_t stream) {
     PPF_CHECK_ARG(n > 0 && (n % 8) == 0, PPF_ERR_SHAPE, "ppf_cast_f32_bf16: n=%lld must be a positive multiple of 8", (long long)n);
-    hipLaunchKernelGGL(cast_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, in, (bf16_t*)out, n / 8);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<cast_kernel>(dim3(grid_for(n / 8)), dim3(256), 0, stream, "ppf_cast_f32_bf16", in, (bf16_t*)out, n / 8);
 }
 
 int ppf_cast_bf16_f32(const void* in, float* out, int64_t n, hipStream_t stream) {
     PPF_CHECK_ARG(in && out && n > 0 && (n % 8) == 0, PPF_ERR_SHAPE, "ppf_cast_bf16_f32: n=%lld must be a positive multiple of 8", (long long)n);
-    hipLaunchKernelGGL(widen_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16_t*)in, out, n / 8);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<widen_kernel>(dim3(grid_for(n / 8)), dim3(256), 0, stream, "ppf_cast_bf16_f32", (const bf16_t*)in, out, n / 8);
 }
 
 int ppf_im2col_patch(const float* img, void* cols, int B, int C, int H, int W, int patch, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && C > 0 && patch % 8 == 0 && H % patch == 0 && W % patch == 0, PPF_ERR_SHAPE,
                   "ppf_im2col_patch: bad shape B=%d C=%d H=%d W=%d patch=%d", B, C, H, W, patch);
     const int64_t total8 = (int64_t)B * C * H * W / 8;
-    hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total8)), dim3(256), 0, stream, img, (bf16_t*)cols, B, C, H, W, patch, total8);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<im2col_kernel>(dim3(grid_for(total8)), dim3(256), 0, stream, "ppf_im2col_patch", img, (bf16_t*)cols, B, C, H, W, patch, total8);
 }
 
 int ppf_assemble_tokens(const float* tok, const float* cls, const float* pos, float* x, int B, int Np, int D, int lead, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && Np > 0 && D % 4 == 0 && (lead == 0 || lead == 1), PPF_ERR_SHAPE, "ppf_assemble_tokens: bad shape");
-    hipLaunchKernelGGL(assemble_kernel, dim3(grid_for((int64_t)B * (Np + lead) * D / 4)), dim3(256), 0, stream, tok, cls, pos, x, B, Np, D, lead);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<assemble_kernel>(dim3(grid_for((int64_t)B * (Np + lead) * D / 4)), dim3(256), 0, stream, "ppf_assemble_tokens", tok, cls, pos, x, B, Np, D, lead);
 }
 
 int ppf_assemble_tokens_bwd(const float* dx, void* dtok, float* dpos, float* dcls, int B, int Np, int D, int lead, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && Np > 0 && D % 2 == 0 && (lead == 0 || lead == 1), PPF_ERR_SHAPE, "ppf_assemble_tokens_bwd: bad shape");
     const int T = Np + lead, cblocks = (D / 2 + 63) / 64;
-    hipLaunchKernelGGL(assemble_bwd_kernel, dim3(T * cblocks), dim3(256), 0, stream, dx, (bf16_t*)dtok, dpos, dcls, B, Np, D, lead);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<assemble_bwd_kernel>(dim3(T * cblocks), dim3(256), 0, stream, "ppf_assemble_tokens_bwd", dx, (bf16_t*)dtok, dpos, dcls, B, Np, D, lead);
 }
 
 static inline int sigmoid_rows_per_block(int rows) { int rpb = 16; while ((rows + rpb - 1) / rpb > 2048) rpb *= 2; return rpb; }
@@ -410,9 +400,8 @@ int ppf_sigmoid_bwd(const float* df, const float* f, void* dz, float* dbias, int
     const int rpb = sigmoid_rows_per_block(rows), nblk = (rows + rpb - 1) / rpb;
     PPF_CHECK_ARG(partial == nullptr || partial_bytes >= (size_t)nblk * cols * sizeof(float), PPF_ERR_ARG, "ppf_sigmoid_bwd: partial buffer too small");
     if (!dbias) partial = nullptr;
-    hipLaunchKernelGGL(sigmoid_bwd_kernel, dim3(nblk), dim3(256), 0, stream, df, f, (bf16_t*)dz, dbias, partial, rows, cols, rpb);
-    if (partial) hipLaunchKernelGGL(sigmoid_bias_reduce_kernel, dim3((cols + 63) / 64), dim3(1024), 0, stream, partial, dbias, nblk, cols);
-    PPF_LAUNCH_CHECK();
+    if (int rc = ppf_launch<sigmoid_bwd_kernel>(dim3(nblk), dim3(256), 0, stream, "ppf_sigmoid_bwd", df, f, (bf16_t*)dz, dbias, partial, rows, cols, rpb)) return rc;
+    if (partial) return ppf_launch<sigmoid_bias_reduce_kernel>(dim3((cols + 63) / 64), dim3(1024), 0, stream, "ppf_sigmoid_bwd", partial, dbias, nblk, cols);
     return 0;
 }
 
@@ -432,9 +421,7 @@ int ppf_adamw_step(float* p, const float* g, float* m, float* v, float* ema, voi
     a.bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
     a.ema_decay = ema_decay; a.grad_scale = grad_scale; a.hyper = nullptr;
     a.guard = nullptr; a.nonfinite = nullptr;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, a);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<adamw_kernel>(dim3(grid_for(n / 4)), dim3(256), 0, stream, "ppf_adamw_step", a);
 }
 
 // The same step with lr / weight decay / bias corrections / gradient scale read from device memory (`hyper`, 20 floats, layout
@@ -456,9 +443,7 @@ int ppf_adamw_step_guarded(float* p, const float* g, float* m, float* v, float* 
     }
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.bc1 = a.bc2_sqrt = 1.f; a.ema_decay = ema_decay; a.grad_scale = 1.f; a.hyper = hyper;
     a.guard = loss; a.nonfinite = nonfinite_flag;
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4)), dim3(256), 0, stream, a);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<adamw_kernel>(dim3(grid_for(n / 4)), dim3(256), 0, stream, "ppf_adamw_step_guarded", a);
 }
 
 // The plain form (no loss check).
@@ -475,9 +460,7 @@ int ppf_hyper_set(float* hyper, const float* host_vals, int n, hipStream_t strea
     HyperVals h;
     for (int i = 0; i < 20; ++i) h.v[i] = i < n ? host_vals[i] : 0.f;
     h.n = n;
-    hipLaunchKernelGGL(hyper_set_kernel, dim3(1), dim3(64), 0, stream, hyper, h);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<hyper_set_kernel>(dim3(1), dim3(64), 0, stream, "ppf_hyper_set", hyper, h);
 }
 
 int ppf_clip_grad_blocks(void) { return 512; }
@@ -486,32 +469,24 @@ int ppf_clip_grad_scale(const float* g, int64_t n, float max_norm, float pre_sca
                         hipStream_t stream) {
     PPF_CHECK_ARG(n > 0 && (n % 4) == 0 && max_norm > 0.f && partial && hyper, PPF_ERR_ARG, "ppf_clip_grad_scale: bad arguments");
     const int nblk = ppf_clip_grad_blocks();
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nblk), dim3(256), 0, stream, g, n / 4, partial);
-    hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, stream, partial, nblk, max_norm, pre_scale, hyper, norm_out);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<sumsq_partial_kernel>(dim3(nblk), dim3(256), 0, stream, "ppf_clip_grad_scale", g, n / 4, partial)) return rc;
+    return ppf_launch<clip_finish_kernel>(dim3(1), dim3(256), 0, stream, "ppf_clip_grad_scale", partial, nblk, max_norm, pre_scale, hyper, norm_out);
 }
 
 int ppf_droppath_scales(float* out, const float* keep, int nslot, int B, uint64_t seed, void* state_u64, hipStream_t stream) {
     PPF_CHECK_ARG(nslot > 0 && B > 0 && out && keep && state_u64, PPF_ERR_ARG, "ppf_droppath_scales: bad arguments");
-    hipLaunchKernelGGL(droppath_kernel, dim3(1), dim3(256), 0, stream, out, keep, nslot, B, seed, (unsigned long long*)state_u64);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<droppath_kernel>(dim3(1), dim3(256), 0, stream, "ppf_droppath_scales", out, keep, nslot, B, seed, (unsigned long long*)state_u64);
 }
 
 int ppf_reserved_rows_map(const int* idx, int* rows, int B, int k, int N, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && k > 0 && N > k, PPF_ERR_SHAPE, "ppf_reserved_rows_map: bad shape B=%d k=%d N=%d", B, k, N);
-    hipLaunchKernelGGL(rows_map_kernel, dim3((B * (k + 1) + 255) / 256), dim3(256), 0, stream, idx, rows, B, k, N);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<rows_map_kernel>(dim3((B * (k + 1) + 255) / 256), dim3(256), 0, stream, "ppf_reserved_rows_map", idx, rows, B, k, N);
 }
 
 int ppf_gather_rows(const void* src, const int* rows, void* dst, int nrows, int row_bytes, hipStream_t stream) {
     PPF_CHECK_ARG(nrows > 0 && row_bytes > 0 && row_bytes % 16 == 0, PPF_ERR_ALIGN, "ppf_gather_rows: row_bytes=%d must be a positive multiple of 16", row_bytes);
-    hipLaunchKernelGGL(move_rows_kernel, dim3(grid_for((int64_t)nrows * (row_bytes / 16))), dim3(256), 0, stream, (const uint4*)src, rows, (uint4*)dst,
-                       nrows, row_bytes / 16, 0);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<move_rows_kernel>(dim3(grid_for((int64_t)nrows * (row_bytes / 16))), dim3(256), 0, stream, "ppf_gather_rows", (const uint4*)src, rows,
+                                        (uint4*)dst, nrows, row_bytes / 16, 0);
 }
 
 // dst (nrows_dst rows) = 0 everywhere except dst[rows[r]] = src[r]
@@ -519,10 +494,8 @@ int ppf_scatter_rows(const void* src, const int* rows, void* dst, int nrows_src,
     PPF_CHECK_ARG(nrows_src > 0 && nrows_dst >= nrows_src && row_bytes > 0 && row_bytes % 16 == 0, PPF_ERR_ALIGN, "ppf_scatter_rows: bad arguments");
     hipError_t e = ppf_memset_async(dst, 0, (size_t)nrows_dst * row_bytes, stream);
     if (e != hipSuccess) { ppf_set_error("ppf_scatter_rows: memset failed: %s", hipGetErrorString(e)); return (int)e; }
-    hipLaunchKernelGGL(move_rows_kernel, dim3(grid_for((int64_t)nrows_src * (row_bytes / 16))), dim3(256), 0, stream, (const uint4*)src, rows, (uint4*)dst,
-                       nrows_src, row_bytes / 16, 1);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<move_rows_kernel>(dim3(grid_for((int64_t)nrows_src * (row_bytes / 16))), dim3(256), 0, stream, "ppf_scatter_rows", (const uint4*)src, rows,
+                                        (uint4*)dst, nrows_src, row_bytes / 16, 1);
 }
 
 int ppf_image_finish_u8(const void* in_u8_hwc, float* out_nchw, int B, int H, int W, const float* mean3, const float* std3, const int* rects,
@@ -533,9 +506,7 @@ int ppf_image_finish_u8(const void* in_u8_hwc, float* out_nchw, int B, int H, in
     p.in = (const unsigned char*)in_u8_hwc; p.out = out_nchw; p.rects = rects; p.B = B; p.H = H; p.W = W; p.seed = seed;
     p.state = (const unsigned long long*)state_u64;
     for (int c = 0; c < 3; ++c) { p.mean[c] = mean3[c]; p.inv_std[c] = 1.0f / std3[c]; }
-    hipLaunchKernelGGL(image_finish_kernel, dim3(grid_for((int64_t)B * H * W / 4)), dim3(256), 0, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<image_finish_kernel>(dim3(grid_for((int64_t)B * H * W / 4)), dim3(256), 0, stream, "ppf_image_finish_u8", p);
 }
 
 int ppf_memset_zero(void* ptr, size_t bytes, hipStream_t stream) {
@@ -547,16 +518,12 @@ int ppf_memset_zero(void* ptr, size_t bytes, hipStream_t stream) {
 
 int ppf_scale_by_scalar(const float* x, const float* scalar_dev, float* out, int64_t n, hipStream_t stream) {
     PPF_CHECK_ARG(n > 0 && x && scalar_dev && out, PPF_ERR_ARG, "ppf_scale_by_scalar: bad arguments");
-    hipLaunchKernelGGL(scale_by_kernel, dim3(grid_for(n)), dim3(256), 0, stream, x, scalar_dev, out, n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<scale_by_kernel>(dim3(grid_for(n)), dim3(256), 0, stream, "ppf_scale_by_scalar", x, scalar_dev, out, n);
 }
 
 int ppf_transpose_bf16_batched(const void* src, void* dst, const void* desc_i64, int n, int total_tiles, hipStream_t stream) {
     PPF_CHECK_ARG(src && dst && desc_i64 && n > 0 && total_tiles > 0, PPF_ERR_ARG, "ppf_transpose_bf16_batched: bad arguments");
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3(total_tiles), dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, (const long long*)desc_i64, n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<transpose_bf16_kernel>(dim3(total_tiles), dim3(256), 0, stream, "ppf_transpose_bf16_batched", (const bf16_t*)src, (bf16_t*)dst, (const long long*)desc_i64, n);
 }
 
 // dst[r][0 .. width) = src[r][0 .. width) for `rows` rows with independent row pitches (bytes): the strided sub-matrix copies of the CaiT
@@ -568,10 +535,8 @@ int ppf_copy_2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch
         // 16-byte aligned on every side: a plain kernel of this library instead of the runtime's rectangular blit (same step time on
         // cait_xxs24, 10 016 vs 10 028 img/s; one launch path for everything a recorded step contains)
         const int w16 = (int)(width / 16);
-        hipLaunchKernelGGL(copy_2d_kernel, dim3(grid_for(rows * w16)), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst, (int)rows, w16,
-                           (long long)(src_pitch / 16), (long long)(dst_pitch / 16));
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<copy_2d_kernel>(dim3(grid_for(rows * w16)), dim3(256), 0, stream, "ppf_copy_2d", (const uint4*)src, (uint4*)dst, (int)rows, w16,
+                                          (long long)(src_pitch / 16), (long long)(dst_pitch / 16));
     }
     hipError_t e = ppf_memcpy2d_async(dst, (size_t)dst_pitch, src, (size_t)src_pitch, (size_t)width, (size_t)rows, hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) { ppf_set_error("ppf_copy_2d: %s", hipGetErrorString(e)); return (int)e; }

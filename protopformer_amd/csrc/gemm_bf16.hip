@@ -881,9 +881,7 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
         }
         const size_t work = (size_t)M * N / 4 + (colsum ? M : 0);
         const int grid = (int)((work + 255) / 256);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, p.ws, (float*)C, colsum, M, N, ldc, ns, p.cs_parts);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<splitk_reduce_kernel>(dim3(grid), dim3(256), 0, stream, "ppf_gemm_bf16", p.ws, (float*)C, colsum, M, N, ldc, ns, p.cs_parts);
     } else if (epi == EPI_F32) {
         return launch<true, true, EPI_F32, false>(p, 1, stream);
     }

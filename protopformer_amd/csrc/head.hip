@@ -473,30 +473,22 @@ int ppf_ppc_loss(const float* act, const int* idx, const void* label, int B, int
     PpcParams p;
     p.act = act; p.idx = idx; p.label = (const long long*)label; p.B = B; p.P = P; p.T = T; p.ppc = ppc; p.side = side;
     p.cov_thresh = cov_thresh; p.mean_thresh = mean_thresh; p.partial = partial; p.gcov = gcov; p.gmean = gmean;
-    hipLaunchKernelGGL(ppc_kernel, dim3(B), dim3(256), 0, stream, p);
-    PPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, partial, B, 2, 2, 1.0f / ((float)B * ppc), 1.0f / ((float)B * ppc * ppc), loss);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<ppc_kernel>(dim3(B), dim3(256), 0, stream, "ppf_ppc_loss", p)) return rc;
+    return ppf_launch<reduce_cols_kernel>(dim3(1), dim3(256), 0, stream, "ppf_ppc_loss", partial, B, 2, 2, 1.0f / ((float)B * ppc), 1.0f / ((float)B * ppc * ppc), loss);
 }
 
 // Scatter up_cov*gcov + up_mean*gmean into the label rows of g_full [B][P][T] (caller zero-fills g_full).
 int ppf_ppc_loss_bwd(const float* gcov, const float* gmean, const float* up_cov, const float* up_mean, const void* label, float* g_full, int B,
                      int P, int T, int ppc, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && P > 0 && T > 0 && ppc >= 1, PPF_ERR_SHAPE, "ppf_ppc_loss_bwd: bad shape");
-    hipLaunchKernelGGL(ppc_bwd_kernel, dim3(B), dim3(256), 0, stream, gcov, gmean, up_cov, up_mean, (const long long*)label, g_full, B, P, T, ppc);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<ppc_bwd_kernel>(dim3(B), dim3(256), 0, stream, "ppf_ppc_loss_bwd", gcov, gmean, up_cov, up_mean, (const long long*)label, g_full, B, P, T, ppc);
 }
 
 // Mean cross-entropy over the batch and d(loss)/d(logits); per_sample is [B] scratch.
 int ppf_cross_entropy(const float* logits, const void* label, float* per_sample, float* dlogits, float* loss, int B, int C, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && C > 0, PPF_ERR_SHAPE, "ppf_cross_entropy: bad shape");
-    hipLaunchKernelGGL(ce_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, (const long long*)label, per_sample, dlogits, B, C);
-    PPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<ce_kernel>(dim3((B + 3) / 4), dim3(256), 0, stream, "ppf_cross_entropy", logits, (const long long*)label, per_sample, dlogits, B, C)) return rc;
+    return ppf_launch<reduce_cols_kernel>(dim3(1), dim3(256), 0, stream, "ppf_cross_entropy", per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
 }
 
 // Mean soft-target (dense target [B][C]) or label-smoothing (label [B] + smoothing) cross-entropy and d(loss)/d(logits).
@@ -507,12 +499,9 @@ int ppf_soft_cross_entropy(const float* logits, const float* target, const void*
     PPF_CHECK_ARG((target == nullptr) != (label == nullptr), PPF_ERR_ARG, "ppf_soft_cross_entropy: pass exactly one of target / label");
     PPF_CHECK_ARG(target || (smoothing >= 0.f && smoothing <= 1.f), PPF_ERR_ARG, "ppf_soft_cross_entropy: smoothing %g outside [0, 1]",
                   (double)smoothing);
-    hipLaunchKernelGGL(soft_ce_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, target, (const long long*)label, smoothing, per_sample,
-                       dlogits, B, C);
-    PPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(reduce_cols_kernel, dim3(1), dim3(256), 0, stream, per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<soft_ce_kernel>(dim3((B + 3) / 4), dim3(256), 0, stream, "ppf_soft_cross_entropy", logits, target, (const long long*)label, smoothing,
+                                            per_sample, dlogits, B, C)) return rc;
+    return ppf_launch<reduce_cols_kernel>(dim3(1), dim3(256), 0, stream, "ppf_soft_cross_entropy", per_sample, B, 1, 1, 1.0f / (float)B, 0.f, loss);
 }
 
 // Evaluation metrics of one batch added into acc (device double[8], include/ppf_hip.h); two launches, no host read.
@@ -521,11 +510,8 @@ int ppf_eval_metrics(const float* logits, const float* logits_global, const floa
     PPF_CHECK_ARG(B > 0 && C > 0, PPF_ERR_SHAPE, "ppf_eval_metrics: bad shape B=%d C=%d", B, C);
     PPF_CHECK_ARG(logits && label && acc, PPF_ERR_ARG, "ppf_eval_metrics: null pointer");
     const int nwg = (B + 3) / 4 < EVAL_MAX_WG ? (B + 3) / 4 : EVAL_MAX_WG;
-    hipLaunchKernelGGL(eval_metrics_kernel, dim3(nwg), dim3(256), 0, stream, logits, logits_global, logits_local, (const long long*)label, B, C);
-    PPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eval_metrics_finish_kernel, dim3(1), dim3(256), 0, stream, acc, nwg, B, logits_global != nullptr, logits_local != nullptr);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<eval_metrics_kernel>(dim3(nwg), dim3(256), 0, stream, "ppf_eval_metrics", logits, logits_global, logits_local, (const long long*)label, B, C)) return rc;
+    return ppf_launch<eval_metrics_finish_kernel>(dim3(1), dim3(256), 0, stream, "ppf_eval_metrics", acc, nwg, B, logits_global != nullptr, logits_local != nullptr);
 }
 
 // Small strided fp32 GEMM for the frozen class-connection layers: C = alpha * A B^T + beta * C.
@@ -539,22 +525,20 @@ int ppf_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, in
     if (S < 1) S = 1;
     const int kchunk = ((K + S - 1) / S + 31) / 32 * 32;
     S = (K + kchunk - 1) / kchunk;                          // no empty slices
+    int rc;
     // large problems (the bottleneck add-on head's tail): the fp32-MFMA kernel; the small deep ones (class-connection logits) stay on the VALU tiles
     if ((int64_t)M * N * K >= (int64_t(1) << 28) && M >= 64 && N >= 64) {
         const int tiles = ((N + SM_T - 1) / SM_T) * ((M + SM_T - 1) / SM_T);
         if (tiles >= 128) S = 1;                              // enough workgroups without splitting the contraction
         else if (S > 1) { const int kc = ((K + S - 1) / S + SM_K - 1) / SM_K * SM_K; S = (K + kc - 1) / kc; }
-        hipLaunchKernelGGL(sgemm_mfma_kernel, dim3((N + SM_T - 1) / SM_T, (M + SM_T - 1) / SM_T, S), dim3(256), 0, stream, A, Bm, C, workspace, M, N, K,
-                           sam, sak, sbn, sbk, ldc, alpha, beta);
+        rc = ppf_launch<sgemm_mfma_kernel>(dim3((N + SM_T - 1) / SM_T, (M + SM_T - 1) / SM_T, S), dim3(256), 0, stream, "ppf_sgemm", A, Bm, C, workspace, M, N, K,
+                                           sam, sak, sbn, sbk, ldc, alpha, beta);
     } else {
-        hipLaunchKernelGGL(sgemm_kernel, dim3((N + 31) / 32, (M + 31) / 32, S), dim3(256), 0, stream, A, Bm, C, workspace, M, N, K, sam, sak, sbn, sbk,
-                           ldc, alpha, beta);
+        rc = ppf_launch<sgemm_kernel>(dim3((N + 31) / 32, (M + 31) / 32, S), dim3(256), 0, stream, "ppf_sgemm", A, Bm, C, workspace, M, N, K, sam, sak, sbn, sbk,
+                                      ldc, alpha, beta);
     }
-    PPF_LAUNCH_CHECK();
-    if (S > 1) {
-        hipLaunchKernelGGL(sgemm_reduce_kernel, dim3((M * N + 255) / 256), dim3(256), 0, stream, workspace, C, M, N, ldc, S, alpha, beta);
-        PPF_LAUNCH_CHECK();
-    }
+    if (rc) return rc;
+    if (S > 1) return ppf_launch<sgemm_reduce_kernel>(dim3((M * N + 255) / 256), dim3(256), 0, stream, "ppf_sgemm", workspace, C, M, N, ldc, S, alpha, beta);
     return 0;
 }
 
@@ -580,28 +564,21 @@ int ppf_sgemm_pair(const float* A0, const float* B0, float* out0, int N0, int K0
     q1.S = pair_slices(K1); q1.kchunk = ((K1 + q1.S - 1) / q1.S + 31) / 32 * 32;
     q0.part_off = 0; q1.part_off = (int64_t)M * N0 * q0.S;
     const int nmax = N0 > N1 ? N0 : N1;
-    hipLaunchKernelGGL(sgemm_pair_kernel, dim3((nmax + 31) / 32, (M + 31) / 32, q0.S + q1.S), dim3(256), 0, stream, q0, q1, workspace, M);
-    PPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sgemm_pair_reduce_kernel, dim3((M * nmax + 255) / 256), dim3(256), 0, stream, q0, q1, workspace, sum, ldsum, M);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (int rc = ppf_launch<sgemm_pair_kernel>(dim3((nmax + 31) / 32, (M + 31) / 32, q0.S + q1.S), dim3(256), 0, stream, "ppf_sgemm_pair", q0, q1, workspace, M)) return rc;
+    return ppf_launch<sgemm_pair_reduce_kernel>(dim3((M * nmax + 255) / 256), dim3(256), 0, stream, "ppf_sgemm_pair", q0, q1, workspace, sum, ldsum, M);
 }
 
 // out = a x + b y + c z  (the train loop's loss = CE + 0.1 cov + 0.5 mean in one launch, engine_proto.py:61-64)
 int ppf_axpbypcz(const float* x, const float* y, const float* z, float* out, float a, float b, float c, int64_t n, hipStream_t stream) {
     PPF_CHECK_ARG(n > 0 && x && y && z && out, PPF_ERR_ARG, "ppf_axpbypcz: bad arguments");
     const int64_t g = (n + 255) / 256;
-    hipLaunchKernelGGL(axpbypcz_kernel, dim3((int)(g > 1024 ? 1024 : g)), dim3(256), 0, stream, x, y, z, out, a, b, c, n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<axpbypcz_kernel>(dim3((int)(g > 1024 ? 1024 : g)), dim3(256), 0, stream, "ppf_axpbypcz", x, y, z, out, a, b, c, n);
 }
 
 int ppf_axpby(const float* x, const float* y, float* out, float a, float b, int64_t n, hipStream_t stream) {
     PPF_CHECK_ARG(n > 0, PPF_ERR_SHAPE, "ppf_axpby: bad length");
     const int64_t g = (n + 255) / 256;
-    hipLaunchKernelGGL(axpby_kernel, dim3((int)(g > 1024 ? 1024 : g)), dim3(256), 0, stream, x, y, out, a, b, n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<axpby_kernel>(dim3((int)(g > 1024 ? 1024 : g)), dim3(256), 0, stream, "ppf_axpby", x, y, out, a, b, n);
 }
 
 }  // extern "C"

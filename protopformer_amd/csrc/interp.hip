@@ -478,13 +478,10 @@ int ppf_act_upsample(const float* grids, float* out, int M, int g, int S, hipStr
     const int bands = (S + BAND - 1) / BAND;
     PPF_CHECK_ARG((long long)M * bands <= INT_MAX, PPF_ERR_SHAPE, "ppf_act_upsample: M=%d maps of %d bands exceed the grid", M, bands);
     if (S % 4 == 0 && ((uintptr_t)out & 15) == 0)
-        hipLaunchKernelGGL(act_upsample_kernel<true>, dim3((unsigned)(M * bands)), dim3(NT), act_lds_bytes(g, S), stream, grids, out, g, S,
-                           (double)g / (double)S, bands);
-    else
-        hipLaunchKernelGGL(act_upsample_kernel<false>, dim3((unsigned)(M * bands)), dim3(NT), act_lds_bytes(g, S), stream, grids, out, g, S,
-                           (double)g / (double)S, bands);
-    PPF_LAUNCH_CHECK();
-    return 0;
+        return ppf_launch<act_upsample_kernel<true>>(dim3((unsigned)(M * bands)), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_upsample", grids, out, g, S,
+                                                     (double)g / (double)S, bands);
+    return ppf_launch<act_upsample_kernel<false>>(dim3((unsigned)(M * bands)), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_upsample", grids, out, g, S,
+                                                  (double)g / (double)S, bands);
 }
 
 int ppf_act_peak(const float* grids, int M, int g, int S, float* peak_val, int* peak_yx, const int* parts, int maps_per_img, int n_parts,
@@ -494,10 +491,8 @@ int ppf_act_peak(const float* grids, int M, int g, int S, float* peak_val, int* 
     PPF_CHECK_ARG((parts == nullptr) == (table_u8 == nullptr), PPF_ERR_ARG, "ppf_act_peak: parts and table_u8 must both be given or both be NULL");
     if (parts != nullptr)
         if (int rc = parts_check("ppf_act_peak", M, parts, maps_per_img, n_parts, half_size, table_u8)) return rc;
-    hipLaunchKernelGGL(act_peak_kernel, dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, grids, g, S, (double)g / (double)S, peak_val,
-                       peak_yx, parts, maps_per_img, n_parts, half_size, (unsigned char*)table_u8);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<act_peak_kernel>(dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_peak", grids, g, S, (double)g / (double)S, peak_val,
+                                       peak_yx, parts, maps_per_img, n_parts, half_size, (unsigned char*)table_u8);
 }
 
 int ppf_act_part_table(const int* peak_yx, int M, int S, const int* parts, int maps_per_img, int n_parts, int half_size, void* table_u8,
@@ -507,10 +502,8 @@ int ppf_act_part_table(const int* peak_yx, int M, int S, const int* parts, int m
     PPF_CHECK_ARG(peak_yx != nullptr, PPF_ERR_ARG, "ppf_act_part_table: null pointer");
     const long long total = (long long)M * n_parts, blocks = (total + NT - 1) / NT;
     PPF_CHECK_ARG(blocks <= INT_MAX, PPF_ERR_SHAPE, "ppf_act_part_table: M=%d x n_parts=%d exceeds the grid", M, n_parts);
-    hipLaunchKernelGGL(act_part_table_kernel, dim3((unsigned)blocks), dim3(NT), 0, stream, peak_yx, total, S, parts, maps_per_img, n_parts,
-                       half_size, (unsigned char*)table_u8);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<act_part_table_kernel>(dim3((unsigned)blocks), dim3(NT), 0, stream, "ppf_act_part_table", peak_yx, total, S, parts, maps_per_img, n_parts,
+                                             half_size, (unsigned char*)table_u8);
 }
 
 int ppf_act_order_stats(const float* grids, int M, int g, int S, int k_lo, int k_hi, float* stats, hipStream_t stream) {
@@ -518,18 +511,14 @@ int ppf_act_order_stats(const float* grids, int M, int g, int S, int k_lo, int k
     PPF_CHECK_ARG(k_lo >= 0 && k_hi >= k_lo && k_hi <= k_lo + 1 && k_hi < S * S, PPF_ERR_ARG,
                   "ppf_act_order_stats: ranks k_lo=%d k_hi=%d must satisfy 0 <= k_lo <= k_hi <= k_lo + 1, k_hi < S*S=%d", k_lo, k_hi, S * S);
     PPF_CHECK_ARG(stats != nullptr, PPF_ERR_ARG, "ppf_act_order_stats: null pointer");
-    hipLaunchKernelGGL(act_order_stats_kernel, dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, grids, g, S, (double)g / (double)S, k_lo,
-                       k_hi, stats);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<act_order_stats_kernel>(dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_order_stats", grids, g, S, (double)g / (double)S, k_lo,
+                                              k_hi, stats);
 }
 
 int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int* box, hipStream_t stream) {
     if (int rc = act_check("ppf_act_box", grids, M, g, S)) return rc;
     PPF_CHECK_ARG(thr != nullptr && box != nullptr, PPF_ERR_ARG, "ppf_act_box: null pointer");
-    hipLaunchKernelGGL(act_box_kernel, dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, grids, thr, g, S, (double)g / (double)S, box);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<act_box_kernel>(dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_box", grids, thr, g, S, (double)g / (double)S, box);
 }
 
 int ppf_add_gauss_noise(const float* x, float* out, int B, int64_t n_per_img, const void* image_id_i64, float sigma, uint64_t seed, hipStream_t stream) {

@@ -332,6 +332,8 @@ int ln_bwd_grid(int rows) {
     return g < cap ? g : cap;
 }
 
+template <int I> using Int = std::integral_constant<int, I>;
+
 template <typename F>
 int dispatch_nj(int D, F&& f) {
     const int nj = (D + 127) / 128;
@@ -357,9 +359,7 @@ int ppf_layernorm_fwd(const float* x, const int* row_map, const float* w, const 
     PPF_CHECK_ARG(rows > 0 && D > 0 && (D % 2) == 0 && D <= 128 * MAXJ, PPF_ERR_SHAPE, "ppf_layernorm_fwd: bad shape rows=%d D=%d", rows, D);
     const int grid = min((rows + WAVES - 1) / WAVES, 256 * 16);
     return dispatch_nj(D, [&](auto nj) {
-        hipLaunchKernelGGL((ln_fwd_kernel<decltype(nj)::value>), dim3(grid), dim3(256), 0, stream, x, row_map, w, b, (bf16_t*)y, mean, rstd, rows, D, eps);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<ln_fwd_kernel<decltype(nj)::value>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_fwd", x, row_map, w, b, (bf16_t*)y, mean, rstd, rows, D, eps);
     });
 }
 
@@ -378,16 +378,19 @@ int ppf_layernorm_bwd(const void* dy, const float* x, const int* row_map, const 
                   "ppf_layernorm_bwd: partial-sum workspace needs ppf_layernorm_bwd_blocks(rows)*4*D*4 = %zu bytes", (size_t)(grid + LN_RS) * 4 * D * sizeof(float));
     p.partial = partial;
     const bool ls = colscale != nullptr || branch != nullptr || dcolscale != nullptr;
-#define PPF_LN2(V, NJ) { if (ls) hipLaunchKernelGGL((ln_bwd2_kernel<V, NJ, true>), dim3(grid), dim3(256), 0, stream, p); \
-                         else hipLaunchKernelGGL((ln_bwd2_kernel<V, NJ, false>), dim3(grid), dim3(256), 0, stream, p); \
-                         PPF_LAUNCH_CHECK(); return 0; }
-    if (D % 128 == 0 && D <= 512) { switch (D / 128) { case 1: PPF_LN2(4, 1) case 2: PPF_LN2(4, 2) case 3: PPF_LN2(4, 3) case 4: PPF_LN2(4, 4) } }
-    if (D % 64 == 0 && D <= 512) { switch (D / 64) { case 1: PPF_LN2(2, 1) case 3: PPF_LN2(2, 3) case 5: PPF_LN2(2, 5) case 7: PPF_LN2(2, 7) } }
-#undef PPF_LN2
+    auto ln2 = [&](auto v, auto nj) {                                      // the ln_bwd2_kernel of V values per lane and NJ of them per row, with or without LayerScale
+        constexpr int V = decltype(v)::value, NJ = decltype(nj)::value;
+        if (ls) return ppf_launch<ln_bwd2_kernel<V, NJ, true>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
+        return ppf_launch<ln_bwd2_kernel<V, NJ, false>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
+    };
+    if (D % 128 == 0 && D <= 512) switch (D / 128) {
+        case 1: return ln2(Int<4>(), Int<1>()); case 2: return ln2(Int<4>(), Int<2>()); case 3: return ln2(Int<4>(), Int<3>()); case 4: return ln2(Int<4>(), Int<4>());
+    }
+    if (D % 64 == 0 && D <= 512) switch (D / 64) {
+        case 1: return ln2(Int<2>(), Int<1>()); case 3: return ln2(Int<2>(), Int<3>()); case 5: return ln2(Int<2>(), Int<5>()); case 7: return ln2(Int<2>(), Int<7>());
+    }
     return dispatch_nj(D, [&](auto nj) {
-        hipLaunchKernelGGL((ln_bwd_kernel<decltype(nj)::value>), dim3(grid), dim3(256), 0, stream, p);
-        PPF_LAUNCH_CHECK();
-        return 0;
+        return ppf_launch<ln_bwd_kernel<decltype(nj)::value>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
     });
 }
 
@@ -399,9 +402,7 @@ int ppf_layernorm_bwd_blocks(int rows) { return ln_bwd_grid(rows) + LN_RS; }
 int ppf_layernorm_bwd_reduce(const float* partial, int rows, int D, float* dw, float* db, float* dbias_next, float* dcolscale, hipStream_t stream) {
     PPF_CHECK_ARG(partial && rows > 0 && D > 0, PPF_ERR_ARG, "ppf_layernorm_bwd_reduce: bad arguments");
     const int nb = ln_bwd_grid(rows);
-    hipLaunchKernelGGL(ln_colsum_reduce_kernel, dim3((D + 63) / 64, 4), dim3(1024), 0, stream, partial, nb, D, dw, db, dbias_next, dcolscale);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<ln_colsum_reduce_kernel>(dim3((D + 63) / 64, 4), dim3(1024), 0, stream, "ppf_layernorm_bwd_reduce", partial, nb, D, dw, db, dbias_next, dcolscale);
 }
 
 }  // extern "C"

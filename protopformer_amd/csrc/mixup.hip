@@ -120,20 +120,16 @@ int ppf_mixup_apply(float* x, const int* table_host, int* table_dev, int B, int 
     const bool vec = W % 4 == 0 && ((uintptr_t)x & 15) == 0;
     const int units = vec ? n / 4 : n;
     const dim3 grid((units + 255) / 256, (B + 1) / 2);
-    if (vec) hipLaunchKernelGGL(mixup_apply_kernel<4>, grid, dim3(256), 0, stream, x, (const int*)table_dev, B, H, W, units);
-    else hipLaunchKernelGGL(mixup_apply_kernel<1>, grid, dim3(256), 0, stream, x, (const int*)table_dev, B, H, W, units);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    if (vec) return ppf_launch<mixup_apply_kernel<4>>(grid, dim3(256), 0, stream, "ppf_mixup_apply", x, (const int*)table_dev, B, H, W, units);
+    return ppf_launch<mixup_apply_kernel<1>>(grid, dim3(256), 0, stream, "ppf_mixup_apply", x, (const int*)table_dev, B, H, W, units);
 }
 
 int ppf_mixup_target(const void* label, const float* lam, int lam_stride, float off_value, float on_value, float* target, int B, int C,
                      hipStream_t stream) {
     PPF_CHECK_ARG(label && lam && target, PPF_ERR_ARG, "ppf_mixup_target: null pointer");
     PPF_CHECK_ARG(B > 0 && C > 0 && lam_stride >= 0, PPF_ERR_SHAPE, "ppf_mixup_target: bad shape B=%d C=%d lam_stride=%d", B, C, lam_stride);
-    hipLaunchKernelGGL(mixup_target_kernel, dim3((C + 255) / 256, B), dim3(256), 0, stream, (const long long*)label, lam, lam_stride, off_value,
-                       on_value, target, B, C);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<mixup_target_kernel>(dim3((C + 255) / 256, B), dim3(256), 0, stream, "ppf_mixup_target", (const long long*)label, lam, lam_stride, off_value,
+                                           on_value, target, B, C);
 }
 
 }  // extern "C"

@@ -29,15 +29,6 @@ extern "C" void ppf_set_error(const char* fmt, ...);
         }                                                  \
     } while (0)
 
-#define PPF_LAUNCH_CHECK()                                                         \
-    do {                                                                           \
-        hipError_t e__ = hipGetLastError();                                        \
-        if (e__ != hipSuccess) {                                                   \
-            ppf_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e__)); \
-            return (int)e__;                                                       \
-        }                                                                          \
-    } while (0)
-
 // Path probe (bench.py's roofline.named_path, ppf_runtime.hip): HIP events from a reused pool around the launches of one of the kernels
 // the north star names, on the launch stream; off (two loads and a branch) unless ppf_path_probe(1) switched it on.
 enum { PPF_PROBE_ATTN_FWD = 0, PPF_PROBE_ATTN_BWD = 1, PPF_PROBE_PROTO_FWD = 2, PPF_PROBE_NTAGS = 3 };
@@ -181,20 +172,13 @@ __device__ __forceinline__ int row_off(int row, int c16) { return row * 128 + ((
 // the producer's own completion signal is what the other stream waits for and no extra packet enters the producer's queue.  A stream is
 // "armed" for the duration of one library call by the replay loop (ppf_stream_arm, when the recorded list shows that the call is followed by
 // a wait on its stream); every launch of that call then takes an event from the library's ring, and ppf_stream_wait_stream uses the last
-// one instead of recording.  Unarmed launches (everything outside a replayed step) are plain <<< >>> launches.
-// RULE: the wait uses the stop event of the LAST macro launch on the stream, so whatever else the library enqueues on a stream (memset,
+// one instead of recording.  Unarmed launches (everything outside a replayed step) are plain launches.
+// RULE: the wait uses the stop event of the LAST ppf_launch on the stream, so whatever else the library enqueues on a stream (memset,
 // copy) goes through the wrappers of ppf_launch.h, which tell the runtime that the last operation is no longer such a launch; raw
-// hipMemsetAsync / hipMemcpy*Async / <<< >>> appear nowhere else in csrc (tests/test_launch_cpu.py).
+// launches and raw memset / copy calls appear nowhere else in csrc (tests/test_launch_cpu.py).
 #ifdef __cplusplus
 #include <hip/hip_ext.h>
 hipEvent_t ppf_take_stop_event(hipStream_t s);          // csrc/ppf_runtime.hip; nullptr unless `s` is armed
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernelName, numBlocks, numThreads, memPerBlock, streamId, ...)                                              \
-    do {                                                                                                                               \
-        hipEvent_t ppf_ev_ = ppf_take_stop_event(streamId);                                                                            \
-        if (ppf_ev_) hipExtLaunchKernelGGL(kernelName, dim3(numBlocks), dim3(numThreads), memPerBlock, streamId, nullptr, ppf_ev_, 0, __VA_ARGS__); \
-        else kernelName<<<(numBlocks), (numThreads), (memPerBlock), (streamId)>>>(__VA_ARGS__);                                          \
-    } while (0)
 #include "ppf_launch.h"
 #endif
 

@@ -12,9 +12,10 @@ __attribute__((visibility("hidden"))) void ppf_note_enqueue(hipStream_t s);    /
 template <auto Kernel>
 static int ppf_lds_granted = 0;
 
-// Launches Kernel<<<grid, block, lds_bytes, stream>>>(args...) through the hipLaunchKernelGGL macro of ppf_common.h (armed streams get
-// their stop event) and returns 0 or the hipError_t, with ppf_set_error("<who>: ...") filled in.  The dynamic-LDS opt-in is raised only
-// when lds_bytes exceeds what this kernel was granted before: the steady-state cost is one compare against a static.
+// Launches Kernel on `stream` with grid, block, lds_bytes and args (on an armed stream the dispatch carries the stop event
+// ppf_stream_wait_stream will wait for, see ppf_common.h) and returns 0 or the hipError_t, with ppf_set_error("<who>: ...") filled in.
+// The dynamic-LDS opt-in is raised only when lds_bytes exceeds what this kernel was granted before: the steady-state cost is one compare
+// against a static.
 template <auto Kernel, typename... Args>
 static inline int ppf_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const char* who, const Args&... args) {
     if ((int)lds_bytes > ppf_lds_granted<Kernel>) {
@@ -22,7 +23,8 @@ static inline int ppf_launch(dim3 grid, dim3 block, size_t lds_bytes, hipStream_
         if (e != hipSuccess) { ppf_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e)); return (int)e; }
         ppf_lds_granted<Kernel> = (int)lds_bytes;
     }
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+    if (hipEvent_t ev = ppf_take_stop_event(stream)) hipExtLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, nullptr, ev, 0, args...);
+    else Kernel<<<grid, block, lds_bytes, stream>>>(args...);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { ppf_set_error("%s: launch failed: %s", who, hipGetErrorString(e)); return (int)e; }
     return 0;

@@ -117,7 +117,7 @@ hipEvent_t ppf_take_stop_event(hipStream_t s) {
         if (a.used && a.armed && a.s == s) { a.ev = ring_event(g_seq++); a.have = true; return a.ev; }
     return nullptr;
 }
-// Something that is not a macro launch (memset, copy: ppf_launch.h) was enqueued on `s`: the stop event taken last no longer covers the
+// Something that is not a ppf_launch (memset, copy: ppf_launch.h) was enqueued on `s`: the stop event taken last no longer covers the
 // stream's last operation, so the next ppf_stream_wait_stream(dst, s) records an event instead of using it.
 void ppf_note_enqueue(hipStream_t s) {
     for (auto& a : g_arm)

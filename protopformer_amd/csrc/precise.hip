@@ -389,26 +389,20 @@ extern "C" {
 int ppf_im2col_patch_f32(const float* img, float* cols, int B, int C, int H, int W, int patch, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && C > 0 && patch > 0 && H % patch == 0 && W % patch == 0, PPF_ERR_SHAPE, "ppf_im2col_patch_f32: bad shape");
     const int64_t total = (int64_t)B * C * H * W;
-    hipLaunchKernelGGL(im2col_f32_kernel, dim3(grid_for(total)), dim3(256), 0, stream, img, cols, B, C, H, W, patch, total);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<im2col_f32_kernel>(dim3(grid_for(total)), dim3(256), 0, stream, "ppf_im2col_patch_f32", img, cols, B, C, H, W, patch, total);
 }
 
 int ppf_layernorm_fwd_f32(const float* x, const int* row_map, const float* w, const float* b, float* y, int rows, int D, float eps,
                           hipStream_t stream) {
     PPF_CHECK_ARG(rows > 0 && D > 0, PPF_ERR_SHAPE, "ppf_layernorm_fwd_f32: bad shape");
-    hipLaunchKernelGGL(ln_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, row_map, w, b, y, rows, D, eps);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<ln_f32_kernel>(dim3((rows + 3) / 4), dim3(256), 0, stream, "ppf_layernorm_fwd_f32", x, row_map, w, b, y, rows, D, eps);
 }
 
 int ppf_epilogue_f32(float* C, const float* bias, int kind, const float* res, const float* rowscale, int rows_per_group, const float* colscale,
                      int M, int N, hipStream_t stream) {
     PPF_CHECK_ARG(M > 0 && N > 0 && kind >= 0 && kind <= 4 && (kind != 3 || res), PPF_ERR_ARG, "ppf_epilogue_f32: bad arguments");
-    hipLaunchKernelGGL(epilogue_f32_kernel, dim3(grid_for((int64_t)M * N)), dim3(256), 0, stream, C, bias, kind, res, rowscale,
-                       rows_per_group > 0 ? rows_per_group : 1, colscale, M, N);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<epilogue_f32_kernel>(dim3(grid_for((int64_t)M * N)), dim3(256), 0, stream, "ppf_epilogue_f32", C, bias, kind, res, rowscale,
+                                           rows_per_group > 0 ? rows_per_group : 1, colscale, M, N);
 }
 
 int ppf_attn_fwd_f32(const float* qkv, float* out, const float* policy, float* headmean, int NP, int B, int H, int N, int D, int self_keep,
@@ -423,18 +417,14 @@ int ppf_th_attn_fwd_f32(const float* qkv, const float* wl, const float* bl, cons
                         int B, int H, int N, int D, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && H > 0 && H <= 16 && N > 0 && N <= 256 && D % H == 0 && (!headmean || NP >= N), PPF_ERR_SHAPE, "ppf_th_attn_fwd_f32: bad shape");
     const size_t lds = ((size_t)D + 2 * (size_t)H * N + 256) * sizeof(float);
-    hipLaunchKernelGGL(th_attn_f32_kernel, dim3(B * N), dim3(256), lds, stream, qkv, wl, bl, ww, bw, out, headmean, NP, H, N, D);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<th_attn_f32_kernel>(dim3(B * N), dim3(256), lds, stream, "ppf_th_attn_fwd_f32", qkv, wl, bl, ww, bw, out, headmean, NP, H, N, D);
 }
 
 int ppf_class_attn_fwd_f32(const float* q, const float* k, const float* v, const float* policy, float* attn_mean, float* out, int B, int H, int N1,
                            int D, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && H > 0 && N1 > 0 && N1 <= 256 && D % H == 0, PPF_ERR_SHAPE, "ppf_class_attn_fwd_f32: bad shape");
     const size_t lds = ((size_t)H * N1 + 256) * sizeof(float);
-    hipLaunchKernelGGL(class_attn_f32_kernel, dim3(B), dim3(256), lds, stream, q, k, v, policy, attn_mean, out, H, N1, D);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<class_attn_f32_kernel>(dim3(B), dim3(256), lds, stream, "ppf_class_attn_fwd_f32", q, k, v, policy, attn_mean, out, H, N1, D);
 }
 
 
@@ -600,25 +590,19 @@ __global__ __launch_bounds__(256) void class_attn_bwd_f32_kernel(const float* __
 int ppf_layernorm_bwd_f32(const float* dy, const float* x, const int* row_map, const float* w, const float* dres_in, float* dx_out, float* dw, float* db,
                           int rows, int D, float eps, hipStream_t stream) {
     PPF_CHECK_ARG(dy && x && w && dx_out && rows > 0 && D > 0, PPF_ERR_ARG, "ppf_layernorm_bwd_f32: bad arguments");
-    hipLaunchKernelGGL(ln_bwd_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dy, x, row_map, w, dres_in, dx_out, dw, db, rows, D, eps);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<ln_bwd_f32_kernel>(dim3((rows + 3) / 4), dim3(256), 0, stream, "ppf_layernorm_bwd_f32", dy, x, row_map, w, dres_in, dx_out, dw, db, rows, D, eps);
 }
 
 // kind 0: out = a * gelu'(b) | 1: out = a * b * (1 - b) | 2: out = a * rowscale[m / rows_per_group] (rowscale NULL: copy) | 3: out = a * b |
 // 4: out = a * rowscale[..] * b[n] (LayerScale column vector) | 5: out = b > 0 ? a : 0; out may alias a
 int ppf_ew_bwd_f32(int kind, const float* a, const float* b, float* out, const float* rowscale, int rows_per_group, int M, int N, hipStream_t stream) {
     PPF_CHECK_ARG(a && out && M > 0 && N > 0 && kind >= 0 && kind <= 5 && (kind == 2 || b), PPF_ERR_ARG, "ppf_ew_bwd_f32: bad arguments");
-    hipLaunchKernelGGL(ew_bwd_f32_kernel, dim3(grid_for((int64_t)M * N)), dim3(256), 0, stream, kind, a, b, out, rowscale, rows_per_group > 0 ? rows_per_group : 1, M, N);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<ew_bwd_f32_kernel>(dim3(grid_for((int64_t)M * N)), dim3(256), 0, stream, "ppf_ew_bwd_f32", kind, a, b, out, rowscale, rows_per_group > 0 ? rows_per_group : 1, M, N);
 }
 
 int ppf_colsum_f32(const float* in, float* out, int M, int N, hipStream_t stream) {
     PPF_CHECK_ARG(in && out && M > 0 && N > 0, PPF_ERR_ARG, "ppf_colsum_f32: bad arguments");
-    hipLaunchKernelGGL(colsum_f32_kernel, dim3((N + 31) / 32), dim3(1024), 0, stream, in, out, M, N);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<colsum_f32_kernel>(dim3((N + 31) / 32), dim3(1024), 0, stream, "ppf_colsum_f32", in, out, M, N);
 }
 
 // dqkv fp32 [B*N][3D] from dout fp32 [B*N][D]; scratch: B*H*2*N*N floats
@@ -645,9 +629,7 @@ int ppf_class_attn_bwd_f32(const float* q, const float* k, const float* v, const
     PPF_CHECK_ARG(q && k && v && dout && dq && dk && dv && B > 0 && H > 0 && N1 > 0 && N1 <= 256 && D % H == 0, PPF_ERR_SHAPE,
                   "ppf_class_attn_bwd_f32: bad shape");
     const size_t lds = ((size_t)H * N1 + 256) * sizeof(float);
-    hipLaunchKernelGGL(class_attn_bwd_f32_kernel, dim3(B), dim3(256), lds, stream, q, k, v, policy, dout, dq, dk, dv, H, N1, D);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<class_attn_bwd_f32_kernel>(dim3(B), dim3(256), lds, stream, "ppf_class_attn_bwd_f32", q, k, v, policy, dout, dq, dk, dv, H, N1, D);
 }
 
 }  // extern "C"

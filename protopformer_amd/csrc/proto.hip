@@ -1008,6 +1008,7 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
     p.act_max = act_max; p.argmax = argmax; p.dist_full = dist_full; p.act_full = act_full;
     p.t_magic = T >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)T - 1) / (uint64_t)T) : 0u;
     const int gx = (P + PB - 1) / PB;
+    const char* who = "ppf_proto_fwd";
     // algorithmic work: the (B T) x Dp . Dp x P contraction; tokens + prototypes in, the maps that are asked for + max / arg-max out
     PpfProbeScope probe(PPF_PROBE_PROTO_FWD, stream, 2.0 * B * T * (double)Dp * P,
                         4.0 * ((double)B * T * Dp + (double)P * Dp + (double)B * P * T * ((dist_full ? 1 : 0) + (act_full ? 1 : 0)) + 2.0 * B * P));
@@ -1018,39 +1019,26 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
         p.pre = reinterpret_cast<const uint4*>(workspace);
         float* p2 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)gx * PB * Dp * 6);
         p.pre_p2 = p2;
-        hipLaunchKernelGGL(proto_presplit_kernel, dim3(gx * (PB / 32)), dim3(256), 0, stream, protos, P, Dp, reinterpret_cast<uint4*>(workspace), p2);
+        if (int rc = ppf_launch<proto_presplit_kernel>(dim3(gx * (PB / 32)), dim3(256), 0, stream, who, protos, P, Dp, reinterpret_cast<uint4*>(workspace), p2)) return rc;
     } else { p.pre = nullptr; p.pre_p2 = nullptr; }
     if (T == 1) {
-        if (x6) hipLaunchKernelGGL((proto_fwd6_kernel<2, false, false>), dim3(gx, (B + 63) / 64), dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((proto_fwd_kernel<2, false>), dim3(gx, (B + 63) / 64), dim3(256), 0, stream, p);
-    } else {
-        const int tt = (T + 31) / 32;
-        if (x6) {
-            switch (tt) {
-                case 1: if (pre) hipLaunchKernelGGL((proto_fwd6_kernel<1, true, true>), dim3(gx, B), dim3(256), 0, stream, p);
-                        else hipLaunchKernelGGL((proto_fwd6_kernel<1, true, false>), dim3(gx, B), dim3(256), 0, stream, p);
-                        break;
-                case 2: if (pre) hipLaunchKernelGGL((proto_fwd6_kernel<2, true, true>), dim3(gx, B), dim3(256), 0, stream, p);
-                        else hipLaunchKernelGGL((proto_fwd6_kernel<2, true, false>), dim3(gx, B), dim3(256), 0, stream, p);
-                        break;
-                case 3: if (pre) hipLaunchKernelGGL((proto_fwd6_kernel<3, true, true>), dim3(gx, B), dim3(256), 0, stream, p);
-                        else hipLaunchKernelGGL((proto_fwd6_kernel<3, true, false>), dim3(gx, B), dim3(256), 0, stream, p);
-                        break;
-                default: if (pre) hipLaunchKernelGGL((proto_fwd6_kernel<4, true, true>), dim3(gx, B), dim3(256), 0, stream, p);
-                        else hipLaunchKernelGGL((proto_fwd6_kernel<4, true, false>), dim3(gx, B), dim3(256), 0, stream, p);
-                        break;
-            }
-        } else {
-            switch (tt) {
-                case 1: hipLaunchKernelGGL((proto_fwd_kernel<1, true>), dim3(gx, B), dim3(256), 0, stream, p); break;
-                case 2: hipLaunchKernelGGL((proto_fwd_kernel<2, true>), dim3(gx, B), dim3(256), 0, stream, p); break;
-                case 3: hipLaunchKernelGGL((proto_fwd_kernel<3, true>), dim3(gx, B), dim3(256), 0, stream, p); break;
-                default: hipLaunchKernelGGL((proto_fwd_kernel<4, true>), dim3(gx, B), dim3(256), 0, stream, p); break;
-            }
-        }
+        if (x6) return ppf_launch<proto_fwd6_kernel<2, false, false>>(dim3(gx, (B + 63) / 64), dim3(256), 0, stream, who, p);
+        return ppf_launch<proto_fwd_kernel<2, false>>(dim3(gx, (B + 63) / 64), dim3(256), 0, stream, who, p);
     }
-    PPF_LAUNCH_CHECK();
-    return 0;
+    auto on_tt = [&](auto&& f) -> int {                // f(TT): the pooled kernels hold TT tiles of 32 tokens
+        switch ((T + 31) / 32) {
+            case 1: return f(std::integral_constant<int, 1>());
+            case 2: return f(std::integral_constant<int, 2>());
+            case 3: return f(std::integral_constant<int, 3>());
+            default: return f(std::integral_constant<int, 4>());
+        }
+    };
+    if (x6) return on_tt([&](auto tt) {
+        constexpr int TT = decltype(tt)::value;
+        if (pre) return ppf_launch<proto_fwd6_kernel<TT, true, true>>(dim3(gx, B), dim3(256), 0, stream, who, p);
+        return ppf_launch<proto_fwd6_kernel<TT, true, false>>(dim3(gx, B), dim3(256), 0, stream, who, p);
+    });
+    return on_tt([&](auto tt) { return ppf_launch<proto_fwd_kernel<decltype(tt)::value, true>>(dim3(gx, B), dim3(256), 0, stream, who, p); });
 }
 
 // Backward of ppf_proto_fwd given upstream grads of act_max (g_max) and act_full (g_full and / or its block form g_rows), any may be null.
@@ -1164,28 +1152,23 @@ int ppf_proto_bwd_single(const float* tok, int64_t stride_b, int t0, const float
     float* sums = G + (size_t)B * P;
     float* gemm_ws = sums + (B > P ? B : P);
     const float* tok0 = tok + (size_t)t0 * Dp;
+    const char* who = "ppf_proto_bwd_single";
     if (dtok) {
         float* out = dtok + (size_t)t0 * Dp;
-        hipLaunchKernelGGL(proto_single_gd_rows_kernel, dim3(B), dim3(256), 0, stream, dist, g, P, act_kind, eps, G, sums);
-        PPF_LAUNCH_CHECK();
+        if (int rc = ppf_launch<proto_single_gd_rows_kernel>(dim3(B), dim3(256), 0, stream, who, dist, g, P, act_kind, eps, G, sums)) return rc;
         // out[b][d] = -2 sum_p G[b][p] protos[p][d]
-        int rc = ppf_sgemm(G, protos, out, B, Dp, P, P, 1, 1, Dp, (int)dstride_b, -2.0f, 0.0f, gemm_ws, (int64_t)16 * B * Dp, stream);
-        if (rc) return rc;
+        if (int rc = ppf_sgemm(G, protos, out, B, Dp, P, P, 1, 1, Dp, (int)dstride_b, -2.0f, 0.0f, gemm_ws, (int64_t)16 * B * Dp, stream)) return rc;
         const int64_t n = (int64_t)B * Dp;
-        hipLaunchKernelGGL(proto_single_fixup_kernel, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, out, dstride_b,
-                           tok0, stride_b, sums, B, Dp);
-        PPF_LAUNCH_CHECK();
+        if (int rc = ppf_launch<proto_single_fixup_kernel>(dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, who, out, dstride_b,
+                                                           tok0, stride_b, sums, B, Dp)) return rc;
     }
     if (dprotos) {
-        hipLaunchKernelGGL(proto_single_gd_cols_kernel, dim3((P + 63) / 64), dim3(256), 0, stream, dist, g, B, P, act_kind, eps, G, sums);
-        PPF_LAUNCH_CHECK();
+        if (int rc = ppf_launch<proto_single_gd_cols_kernel>(dim3((P + 63) / 64), dim3(256), 0, stream, who, dist, g, B, P, act_kind, eps, G, sums)) return rc;
         // dprotos[p][d] += -2 sum_b G[b][p] tok[b][d]
-        int rc = ppf_sgemm(G, tok0, dprotos, P, Dp, B, 1, P, 1, stride_b, Dp, -2.0f, 1.0f, gemm_ws, (int64_t)16 * P * Dp, stream);
-        if (rc) return rc;
+        if (int rc = ppf_sgemm(G, tok0, dprotos, P, Dp, B, 1, P, 1, stride_b, Dp, -2.0f, 1.0f, gemm_ws, (int64_t)16 * P * Dp, stream)) return rc;
         const int64_t n = (int64_t)P * Dp;
-        hipLaunchKernelGGL(proto_single_fixup_kernel, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, dprotos, (int64_t)Dp,
-                           protos, (int64_t)Dp, sums, P, Dp);
-        PPF_LAUNCH_CHECK();
+        if (int rc = ppf_launch<proto_single_fixup_kernel>(dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, who, dprotos, (int64_t)Dp,
+                                                           protos, (int64_t)Dp, sums, P, Dp)) return rc;
     }
     return 0;
 }

@@ -119,9 +119,7 @@ int ppf_proto_topk_init(float* val, int* img, int* pos, int P, int K, hipStream_
     PPF_CHECK_ARG(P >= 1 && K >= 1 && K <= 64, PPF_ERR_SHAPE, "ppf_proto_topk_init: bad shape P=%d K=%d (P >= 1, 1 <= K <= 64)", P, K);
     PPF_CHECK_ARG(val && img && pos, PPF_ERR_ARG, "ppf_proto_topk_init: null pointer");
     const size_t n = (size_t)P * K;
-    hipLaunchKernelGGL(proto_topk_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, val, img, pos, n);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<proto_topk_init_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, "ppf_proto_topk_init", val, img, pos, n);
 }
 
 int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx, int k, const float* tok, int64_t stride_b, int t0, int Dp,
@@ -138,10 +136,8 @@ int ppf_proto_topk_merge(const float* act_max, const int* argmax, const int* idx
                   "ppf_proto_topk_merge: null pointer");
     PPF_CHECK_ARG(stride_b % 4 == 0 && (((uintptr_t)tok | (uintptr_t)best_feat) & 15) == 0, PPF_ERR_ALIGN,
                   "ppf_proto_topk_merge: tok / best_feat must be 16-byte aligned and stride_b a multiple of 4");
-    hipLaunchKernelGGL(proto_topk_merge_kernel, dim3((P + TP - 1) / TP), dim3(256), 0, stream, act_max, argmax, idx, k, tok, (long long)stride_b,
-                       t0, Dp, (const long long*)label_i64, image_id, ppc, B, P, K, val, img, pos, best_feat);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<proto_topk_merge_kernel>(dim3((P + TP - 1) / TP), dim3(256), 0, stream, "ppf_proto_topk_merge", act_max, argmax, idx, k, tok, (long long)stride_b,
+                                               t0, Dp, (const long long*)label_i64, image_id, ppc, B, P, K, val, img, pos, best_feat);
 }
 
 }  // extern "C"

@@ -223,9 +223,7 @@ extern "C" {
 
 int ppf_topk_sorted(const float* scores, int B, int n, int k, int* idx, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && n >= 1 && n <= 256 && k >= 1 && k <= n, PPF_ERR_SHAPE, "ppf_topk_sorted: bad shape B=%d n=%d k=%d", B, n, k);
-    hipLaunchKernelGGL(topk_sorted_kernel, dim3(B), dim3(256), 0, stream, scores, n, k, idx);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<topk_sorted_kernel>(dim3(B), dim3(256), 0, stream, "ppf_topk_sorted", scores, n, k, idx);
 }
 
 
@@ -237,9 +235,7 @@ int ppf_rollout_threshold(const float* hm_layer, int B, int N, int NP, int kdrop
                   "ppf_rollout_threshold: the map's row pitch NP=%d must be a multiple of 4 (<= 256) and the map 16-byte aligned", NP);
     PPF_CHECK_ARG(B >= 1 && N >= 2 && N <= 16 * RPW && N <= 64 * CPL - 1 && NP >= N && kdrop >= 0 && kdrop < N * N && hm_layer && thr_out_u32, PPF_ERR_SHAPE,
                   "ppf_rollout_threshold: bad arguments B=%d N=%d NP=%d kdrop=%d", B, N, NP, kdrop);
-    hipLaunchKernelGGL(rollout_threshold_kernel, dim3(B), dim3(NTHR), 0, stream, hm_layer, N, NP, kdrop, (uint32_t*)thr_out_u32);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<rollout_threshold_kernel>(dim3(B), dim3(NTHR), 0, stream, "ppf_rollout_threshold", hm_layer, N, NP, kdrop, (uint32_t*)thr_out_u32);
 }
 
 int ppf_rollout(const float* hm, int64_t layer_stride, int L, int B, int N, int NP, const float* init_rows, int n_init, int lead,
@@ -254,9 +250,7 @@ int ppf_rollout(const float* hm, int64_t layer_stride, int L, int B, int N, int 
     p.hm = hm; p.layer_stride = layer_stride; p.L = L; p.B = B; p.N = N; p.NP = NP; p.init_rows = init_rows; p.n_init = n_init; p.lead = lead;
     p.kdrop = kdrop; p.kdrop_init = kdrop_init; p.identity = identity; p.k = k; p.cls_attn = cls_attn; p.idx = idx; p.policy = policy;
     p.thr = (const uint32_t*)thr_u32;
-    hipLaunchKernelGGL(rollout_kernel, dim3(B), dim3(NTHR), 0, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<rollout_kernel>(dim3(B), dim3(NTHR), 0, stream, "ppf_rollout", p);
 }
 
 }  // extern "C"

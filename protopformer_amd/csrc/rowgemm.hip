@@ -539,9 +539,7 @@ int ppf_rowgemm_lnbwd(const void* A, const void* B, int M, int D, int K, int lda
 // fixed order (may run on another stream); a NULL destination skips its array
 int ppf_rowgemm_colsum(const float* partial, int tiles, int D, int nparts, float* dw, float* db, float* dg, hipStream_t stream) {
     PPF_CHECK_ARG(partial && tiles > 0 && D > 0 && (nparts == 2 || nparts == 3), PPF_ERR_ARG, "ppf_rowgemm_colsum: bad arguments");
-    hipLaunchKernelGGL(rowgemm_colsum_kernel, dim3((D + 63) / 64, nparts), dim3(1024), 0, stream, partial, tiles, D, nparts, dw, db, dg);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<rowgemm_colsum_kernel>(dim3((D + 63) / 64, nparts), dim3(1024), 0, stream, "ppf_rowgemm_colsum", partial, tiles, D, nparts, dw, db, dg);
 }
 
 }  // extern "C"

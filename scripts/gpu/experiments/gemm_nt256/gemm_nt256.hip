@@ -339,18 +339,9 @@ int num_cus() {
 
 template <int EPI>
 int launch_one(const GemmParams& p, hipStream_t stream) {
-    auto kern = gemm_nt256_kernel<EPI>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(gemm_nt256): %s", hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     const int tiles = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN) * p.nsplit;
     const int ncu = num_cus();
-    hipLaunchKernelGGL(kern, dim3(tiles < ncu ? tiles : ncu), dim3(NTHR), LDS_BYTES, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<gemm_nt256_kernel<EPI>>(dim3(tiles < ncu ? tiles : ncu), dim3(NTHR), LDS_BYTES, stream, "ppf_gemm_nt256", p);
 }
 
 }  // namespace

@@ -395,18 +395,8 @@ __global__ __launch_bounds__(MF_NTHR, 1) void mlp_fwd_kernel(const MlpFwdParams 
 
 template <int D>
 int mf_launch(const MlpFwdParams& p, hipStream_t stream) {
-    const int lds = mf_lds_bytes<D>(p.hid);
-    auto kern = mlp_fwd_kernel<D>;
-    static int attr_lds = 0;
-    if (attr_lds < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) { ppf_set_error("hipFuncSetAttribute(mlp_fwd): %s", hipGetErrorString(e)); return (int)e; }
-        attr_lds = lds;
-    }
     const int tiles = (p.M + p.rows_per_tile - 1) / p.rows_per_tile;
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(MF_NTHR), lds, stream, p);
-    PPF_LAUNCH_CHECK();
-    return 0;
+    return ppf_launch<mlp_fwd_kernel<D>>(dim3(tiles), dim3(MF_NTHR), mf_lds_bytes<D>(p.hid), stream, "ppf_mlp_fwd", p);
 }
 
 }  // namespace

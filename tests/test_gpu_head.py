@@ -194,6 +194,35 @@ def test_proto_fwd_bwd_vs_oracle(B, T, Dp, P):
         assert_close(dpro_a, dpro, rtol=1e-4, atol=2e-5 * float(dpro.abs().max()), what="from activations vs from distances, prototypes")
 
 
+@pytest.mark.parametrize("Dp", [32, 20])                                     # the split-bf16 kernel, the fp32-MFMA kernel
+@pytest.mark.parametrize("T,workspace", [(1, False), (9, True), (9, False), (40, True), (40, False), (70, True), (70, False), (121, True), (121, False)])
+def test_proto_fwd_every_dispatch_branch(T, workspace, Dp):
+    """ppf_proto_fwd's dispatch: the T == 1 branch and 1 to 4 token tiles of 32, each with the pre-split prototype planes (a workspace) and
+    without (NULL: every workgroup splits its own rows); B = 2, P = 40: one partly filled workgroup of 128 prototypes."""
+    from protopformer_amd import _lib, ops
+    B, P = 2, 40
+    g = torch.Generator().manual_seed(100 * T + Dp)
+    tokens = torch.rand(B, T + 1, Dp, generator=g)
+    protos = torch.rand(P, Dp, generator=g)
+    t0 = 1 if T > 1 else 0
+    _, d_ref, _ = O.proto_activations(tokens[:, t0:t0 + T], protos)
+    tok, pro = tokens.cuda(), protos.cuda()
+    if workspace or T == 1:
+        act_max, argmax, dist, act = ops.proto_fwd(tok, t0, T, pro)
+    else:
+        act_max = torch.empty((B, P), dtype=torch.float32, device="cuda")
+        argmax = torch.empty((B, P), dtype=torch.int32, device="cuda")
+        dist = torch.empty((B, P, T), dtype=torch.float32, device="cuda")
+        act = torch.empty((B, P, T), dtype=torch.float32, device="cuda")
+        _lib.call("ppf_proto_fwd", tok, (T + 1) * Dp, t0, T, pro, B, P, Dp, 0, 1e-4, act_max, argmax, dist, act, None, 0)
+    assert_close(dist, d_ref, rtol=1e-3, atol=1e-6 * Dp, what="dist")
+    # internal consistency: max / argmax agree with the materialised map
+    assert torch.equal(act.max(dim=-1)[0], act_max)
+    if T > 1:
+        assert int(argmax.min()) >= 0 and int(argmax.max()) < T
+        assert torch.equal(torch.gather(act, 2, argmax.long()[..., None])[..., 0], act_max)
+
+
 @pytest.mark.parametrize("B,T,Dp,P,ppc", [(5, 9, 32, 20, 2), (3, 121, 192, 200, 10), (6, 81, 384, 300, 10), (300, 9, 64, 40, 4), (2, 121, 384, 48, 16),
                                           (4, 16, 100, 60, 20)])
 def test_proto_bwd_block_rows_vs_oracle(B, T, Dp, P, ppc):

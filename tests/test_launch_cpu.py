@@ -1,13 +1,13 @@
 """The launch rule of the C-ABI library, checked on its sources: kernels are launched and copies enqueued only through the helpers of
-csrc/ppf_launch.h (ppf_common.h holds the launch macro itself), so every launch gets its dynamic-LDS opt-in and its error check, and
-an armed ppf_stream_wait_stream never waits on a kernel that is no longer its stream's last operation."""
+csrc/ppf_launch.h, so every launch gets its dynamic-LDS opt-in and its error check, and an armed ppf_stream_wait_stream never waits on a
+kernel that is no longer its stream's last operation."""
 import glob
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "protopformer_amd", "csrc")
-ALLOWED = {"ppf_launch.h", "ppf_common.h"}
-RAW = ("hipFuncSetAttribute", "hipMemsetAsync", "hipMemcpyAsync", "hipMemcpy2DAsync", "<<<")
+ALLOWED = {"ppf_launch.h"}
+RAW = ("hipFuncSetAttribute", "hipMemsetAsync", "hipMemcpyAsync", "hipMemcpy2DAsync", "<<<", "hipLaunchKernelGGL", "PPF_LAUNCH_CHECK")
 
 
 def _sources():
@@ -18,13 +18,14 @@ def _sources():
 
 def test_raw_launch_plumbing_only_in_the_launch_header():
     bad = [(name, word) for name, text in _sources().items() if name not in ALLOWED for word in RAW if word in text]
-    assert not bad, f"raw runtime calls outside ppf_launch.h / ppf_common.h (use ppf_launch / ppf_memset_async / ppf_memcpy*_async): {bad}"
+    assert not bad, f"raw runtime calls outside ppf_launch.h (use ppf_launch / ppf_memset_async / ppf_memcpy*_async): {bad}"
 
 
 def test_helpers_wrap_each_raw_call():
     text = _sources()["ppf_launch.h"]
     for word in RAW[:4]:
         assert text.count(word + "(") == 1, word
+    assert text.count("<<<") == 1
 
 
 def test_cu_count_queried_in_one_place():
