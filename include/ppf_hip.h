@@ -378,6 +378,39 @@ int ppf_cell_order(const float* act_full, const int* idx, const float* token_att
 int ppf_patch_perturb(const float* x, const int* rank, const int* counts, int S, int insertion, const float* baseline, float baseline_const, int B,
                       int M, int Cc, int H, int W, int G, float* out, ppf_stream_t stream);
 int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* prob, ppf_stream_t stream);
+/* RISE saliency (csrc/rise.hip): the model-agnostic baseline the deletion / insertion metric was published with (Petsiuk et al., 2018):
+ * N random masks per image, the class probability of each masked image (the forwards and ppf_class_prob are the caller's), saliency =
+ * the probability-weighted mean mask.  The reference has no such pass.  Additions of ABI 10: no existing entry point changed.
+ * The masks are integer-exact; this is the contract the numpy referees (interpret.rise_*) keep bit for bit.
+ *   sizes     image H x W with H == W and W % 4 == 0; s low-resolution cells per side, 1 <= s <= 14; node spacing c = ceil(H / s) <= 4096;
+ *             L = s + 2 nodes per side; N masks per image, 1 <= N <= 2^31 - 2; keep threshold thr in [1, 2^24], computed once by the
+ *             host as round(p * 2^24): the effective keep probability is thr / 2^24.
+ *   draws     Philox4x32-10 with key = seed (64 bits, as ppf_cell_order) and counter = (k, 1 + n, image id low, image id high) for mask n
+ *             of image id (the random cell order uses counter word 1 = 0: the streams are disjoint).  Node q = i * L + j is on when
+ *             (word[q % 4] of call k = q / 4) >> 8 < thr.  The shift comes from call k = 0xFFFFFFFF: dy = ((w.x >> 8) * c) >> 24,
+ *             dx = ((w.y >> 8) * c) >> 24, both in [0, c).  A mask depends on (seed, image id, n) alone, not on the batch.
+ *   value     pixel (y, x): uy = y + dy, i = uy / c, ry = uy % c, likewise j and rx from x + dx (i + 1 <= s + 1 always); numerator
+ *             K = (c-ry) * ((c-rx) * g[i][j] + rx * g[i][j+1]) + ry * ((c-rx) * g[i+1][j] + rx * g[i+1][j+1]) in [0, c^2];
+ *             mask value m = fdiv_rn((float)K, (float)(c*c)), one rounding.
+ *   ppf_rise_nodes       nodes uint8 [B][N][L*L] (0 / 1) and shift int32 [B][N][2] = (dy, dx) of image_id_i64 [B]; H enters through c only.
+ *   ppf_rise_apply       out fp32 [Nc][B][Cc][H][W] for masks n0 .. n0 + Nc - 1 (0 <= n0, n0 + Nc <= N) of the tables above:
+ *                        out = fadd_rn(fmul_rn(m, x), fmul_rn(fsub_rn(1, m), base)), base = baseline fp32 [B][Cc][H][W] or, NULL, the
+ *                        constant baseline_const (as ppf_patch_perturb).  The mask does not depend on the class: one image per
+ *                        (mask, sample).  x and the baseline are read once, the copies written from registers; the node table is read,
+ *                        Philox is not run.  Shifts in the table are clamped into [0, c).  x, baseline, out 16-byte aligned.
+ *   ppf_rise_accumulate  from the tables and prob fp32 [N][B][M], 1 <= M <= 8, with norm = N * (thr / 2^24) * c^2 in fp64 (evaluated
+ *                        left to right):  sal fp32 [B][M][H][W] = (float)(acc / norm), acc = the fp64 sum over n ascending of
+ *                        (double)prob * (double)K (every product exact);  cell fp32 [B][M][G] = (float)(accW / (norm * patch^2)), accW =
+ *                        the fp64 sum over n ascending of (double)prob * (double)W[n][g], W = the int32 sum of K over the pixels of cell
+ *                        g of the side x side grid, side = sqrt(G), patch = H / side (side divides H, G <= 1024, patch^2 * c^2 <= 2^29
+ *                        so these products are exact too).  The masks are regenerated from the node table, never stored at pixel
+ *                        resolution; no floating-point atomics; a NaN probability makes its (sample, class) row NaN by propagation.
+ *                        sal 16-byte aligned.  Two launches (pixels, cells). */
+int ppf_rise_nodes(const void* image_id_i64, uint64_t seed, int thr, int B, int N, int s, int H, void* nodes_u8, int* shift, ppf_stream_t stream);
+int ppf_rise_apply(const float* x, const void* nodes_u8, const int* shift, int N, int n0, int Nc, int s, const float* baseline, float baseline_const,
+                   int B, int Cc, int H, int W, float* out, ppf_stream_t stream);
+int ppf_rise_accumulate(const void* nodes_u8, const int* shift, const float* prob, int B, int N, int M, int s, int thr, int H, int W, int G, float* sal,
+                        float* cell, ppf_stream_t stream);
 /* Spatial alignment of prototypes (csrc/alignment.hip): the image gradient's last step and the two kernels of the misalignment test
  * (Sacha et al., AAAI 2024): perturb only the pixels outside a prototype's box, follow its activation and its peak, and report the share
  * of the pixel gradient inside the box; the forwards and backwards in between are the caller's.  The reference has no such pass.

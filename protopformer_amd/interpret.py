@@ -867,6 +867,7 @@ def explain(ppnet, x, classes=None, top_classes=1, topk=10, against=False, maps=
 # ppf_class_prob reads the one probability per image (csrc/faithful.hip).  The reference has no such pass; the numpy forms below
 # (device=False) are the referees.
 ORDER_MODES = ("evidence", "attention", "random")
+EXTRA_ORDERS = ("rise",)                # opt-in orders of faithfulness_curves / faithfulness: the black-box baseline (rise_saliency, below)
 CURVE_MODES = ("deletion", "insertion")
 
 _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -982,12 +983,13 @@ def perturb_patches(x, rank, counts, insertion=False, baseline=0.0, device=True)
 class Faithfulness:
     """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
     class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
-    order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G."""
+    order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G.  rise: the Rise the 'rise' order ranked by
+    (its cell scores are `score`), None for every other order."""
     FIELDS = ("counts", "classes", "order", "rank", "score")
 
-    def __init__(self, curves, counts, classes, order, rank, score, grid_cells):
+    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None):
         self.curves, self.counts, self.classes, self.order, self.rank, self.score = dict(curves), counts, classes, order, rank, score
-        self.grid_cells = int(grid_cells)
+        self.grid_cells, self.rise = int(grid_cells), rise
 
     @property
     def on_host(self):
@@ -1005,7 +1007,8 @@ class Faithfulness:
             a = host[o:o + v.numel()]
             o += v.numel()
             out[k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
-        return Faithfulness({k[6:]: v for k, v in out.items() if k.startswith("curve:")}, *(out[k] for k in self.FIELDS), self.grid_cells)
+        return Faithfulness({k[6:]: v for k, v in out.items() if k.startswith("curve:")}, *(out[k] for k in self.FIELDS), self.grid_cells,
+                            rise=None if self.rise is None else self.rise.cpu())
 
     def auc(self):
         """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
@@ -1034,13 +1037,22 @@ def _eval_outputs(ppnet, x):
                 act_max=act_l)
 
 
-def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes):
+def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None):
     from . import ops
     B, G = x.shape[0], int(ppnet.num_patches)
     M, S = cls.shape[1], counts.shape[0]
     w_l = ppnet.last_layer.weight.detach().contiguous()
-    ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G, mode=order,
-                                                seed=seed, image_ids=image_ids)
+    found = None
+    if order in EXTRA_ORDERS:
+        # the cells ranked by their mean RISE saliency: ppf_cell_order's attention mode over the B * M (sample, class) rows, so the total
+        # order, the NaN rule and the -1 rows of an invalid class are that kernel's
+        found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
+                                   **{**RISE_DEFAULTS, **(rise or {})})
+        ordr, rank, score = (t.reshape(B, M, G) for t in ops.cell_order(cls.reshape(B * M, 1).contiguous(), G, "attention",
+                                                                        token_attn=found.cell.reshape(B * M, G), weight=w_l))
+    else:
+        ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G,
+                                                    mode=order, seed=seed, image_ids=image_ids)
     # scratch: the perturbed images of one chunk of steps, steps_per_chunk * B * M images, never more than scratch_bytes (one step at least)
     per_step = B * M * x[0].numel() * 4
     chunk = max(1, min(S, int(scratch_bytes) // per_step))
@@ -1064,7 +1076,7 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
             curves[mode] = prob.permute(1, 2, 0).contiguous()
     finally:
         ppnet.train(was_training)
-    return Faithfulness(curves, counts, cls, ordr, rank, score, G)
+    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found)
 
 
 def _pick_classes(ppnet, outs, classes, top_classes, B):
@@ -1079,15 +1091,17 @@ def _pick_classes(ppnet, outs, classes, top_classes, B):
 
 @torch.no_grad()
 def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, modes=CURVE_MODES, order="evidence", baseline=0.0, seed=0, image_ids=None,
-                        batch_size=None, scratch_bytes=1 << 30):
+                        batch_size=None, scratch_bytes=1 << 30, rise=None):
     """Deletion / insertion curves of a batch x [B, 3, H, W] (CUDA): one eval forward, one ppf_cell_order launch, then per mode
     ppf_patch_perturb in chunks of steps, the model's forward over each chunk in sub-batches of `batch_size` images (default B; the
     images of a chunk are ordered step, sample, class) and one ppf_class_prob per chunk.  The chunk's images are the one large scratch
     buffer: steps-per-chunk = scratch_bytes // (B * M * image bytes), at least one step, so at most max(scratch_bytes, one step) bytes.
     classes: as in explain (None: the top `top_classes` of the logits).  counts: the numbers of cells removed / shown (default
-    default_counts(G)).  order: 'evidence', 'attention' or 'random' (seed, image_ids: the random order's key).  baseline: what a removed
-    pixel becomes, a number in normalised space (0 = the data-set mean colour) or a tensor like x.  Returns a Faithfulness (device
-    tensors; nothing is read back here)."""
+    default_counts(G)).  order: 'evidence', 'attention' or 'random' (seed, image_ids: the random order's key), or 'rise': the cells ranked
+    by their RISE saliency for the class (rise_saliency with the same baseline, seed, image_ids, batch_size and scratch_bytes;
+    rise = dict(masks=, cells=, p=) overrides RISE_DEFAULTS; the result carries the Rise).  baseline: what a removed pixel becomes, a
+    number in normalised space (0 = the data-set mean colour) or a tensor like x.  Returns a Faithfulness (device tensors; nothing is read
+    back here)."""
     if not x.is_cuda:
         raise RuntimeError("faithfulness_curves needs a CUDA/HIP batch (no CPU fallback path; cell_order_from_outputs / perturb_patches with "
                            "device=False are the host referees)")
@@ -1096,7 +1110,7 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     outs = _eval_outputs(ppnet, x)
     cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
     counts = _device_counts(counts, G, x.device)
-    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes)
+    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise)
 
 
 def _device_counts(counts, G, device):
@@ -1108,9 +1122,9 @@ def _device_counts(counts, G, device):
 
 @torch.no_grad()
 def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=None, top_classes=1, against_label=False, baseline=0.0, seed=0,
-                 max_images=0, batch_size=None, scratch_bytes=1 << 30):
+                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None):
     """The curves over a data set.  loader yields (x, labels) or (x, labels, ids); without ids an image's id is its running index.  Per
-    batch one eval forward serves every order; classes are the top `top_classes` of the logits, or with against_label the image's label.
+    batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
     The per-image curves stay on the device and are read back once at the end.  Returns dict(images, counts, grid_cells, orders:
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
     image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
@@ -1124,7 +1138,7 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
         if dev_counts is None:
             dev_counts = _device_counts(counts, G, x.device)
         for order in orders:
-            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes)
+            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise)
             for mode in modes:
                 kept.setdefault((order, mode), []).append(f.curves[mode])
         cls_kept.append(cls); ids_kept.append(ids)
@@ -1141,6 +1155,205 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
         out["orders"].setdefault(order, {})[mode] = dict(curve=rows.mean(0).tolist(), auc=float(curve_auc(rows, cnt, G).mean()))
         out["per_image"].setdefault(order, {})[mode] = host[j]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ RISE: the black-box baseline of the faithfulness test
+# RISE (Petsiuk et al., 2018) is the saliency the deletion / insertion metric was published with: N random masks per image, the class
+# probability of every masked image, saliency = the probability-weighted mean mask.  It needs forwards alone, so it answers whether the
+# prototype evidence is as faithful as what a model-agnostic method finds.  The masks are integer-exact (the contract is in
+# include/ppf_hip.h): ppf_rise_nodes draws the node tables, ppf_rise_apply writes the masked images of a chunk of masks, the model's
+# forward and ppf_class_prob score them, ppf_rise_accumulate regenerates the masks and sums (csrc/rise.hip).  The numpy forms below
+# (device=False) are the referees, bit for bit.  The reference has no such pass.
+RISE_DEFAULTS = dict(masks=512, cells=7, p=0.5)
+
+
+def rise_threshold(p):
+    """The integer keep threshold round(p * 2^24) in [1, 2^24]: a node is on when its 24-bit draw lies below it."""
+    thr = int(round(float(p) * (1 << 24)))
+    if not 1 <= thr <= 1 << 24:
+        raise ValueError(f"rise: the keep probability p={p} gives thr={thr} outside [1, 2^24]")
+    return thr
+
+
+def _rise_sizes(size, cells):
+    """(H, s, c, L) of the mask contract: node spacing c = ceil(H / s), L = s + 2 nodes per side."""
+    H, s = int(size), int(cells)
+    if not 1 <= s <= 14 or H < 4 or H % 4:
+        raise ValueError(f"rise: cells={s} outside [1, 14] or size={H} no positive multiple of 4")
+    c = -(-H // s)
+    if c > 4096:
+        raise ValueError(f"rise: node spacing c={c} = ceil({H} / {s}) exceeds 4096")
+    return H, s, c, s + 2
+
+
+def rise_nodes_from_ids(image_ids, size, masks=512, cells=7, p=0.5, seed=0, device=True):
+    """(nodes uint8 [B, N, (cells + 2)^2] of 0 / 1, shift int32 [B, N, 2] = (dy, dx)) of the N = masks RISE masks of the images image_ids
+    [B] at size x size pixels: a function of (seed, image id, mask) alone, not of the batch.  device=True: one ppf_rise_nodes launch
+    (image_ids a CUDA tensor or anything torch.as_tensor takes, then put on the current device); device=False: the numpy Philox."""
+    H, s, c, L = _rise_sizes(size, cells)
+    N, thr = int(masks), rise_threshold(p)
+    if not 1 <= N <= 2 ** 31 - 2:
+        raise ValueError(f"rise: masks={N} outside [1, 2^31 - 2]")
+    if device:
+        from . import ops
+        ids = torch.as_tensor(image_ids)
+        ids = ids.to(device=ids.device if ids.is_cuda else "cuda", dtype=torch.int64).contiguous()
+        return ops.rise_nodes(ids, H, N, s, thr, seed)
+    ids = _host(image_ids, np.int64).reshape(-1).astype(np.uint64)
+    B, LL = ids.shape[0], L * L
+    Q, sd = (LL + 3) // 4, int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((B, N, Q + 1, 4), dtype=np.uint64)
+    ctr[..., 0] = np.concatenate([np.arange(Q), [0xFFFFFFFF]]).astype(np.uint64)                  # the call after the node words: the shift
+    ctr[..., 1] = (1 + np.arange(N, dtype=np.uint64))[None, :, None]
+    ctr[..., 2], ctr[..., 3] = (ids & np.uint64(0xFFFFFFFF))[:, None, None], (ids >> np.uint64(32))[:, None, None]
+    w = philox4x32_10(ctr, np.array([sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint64)) >> np.uint32(8)    # [B, N, Q + 1, 4], 24 bits each
+    nodes = (w[:, :, :Q].reshape(B, N, Q * 4)[:, :, :LL] < np.uint32(thr)).astype(np.uint8)
+    shift = ((w[:, :, Q, :2].astype(np.uint64) * np.uint64(c)) >> np.uint64(24)).astype(np.int32)
+    return nodes, shift
+
+
+def rise_masks(nodes, shift, size, cells):
+    """The integer numerators K int32 [B, N, H, H] of the masks (mask value = K / c^2): bilinear interpolation of the L x L node grid with
+    spacing c, shifted by (dy, dx), in integers."""
+    H, s, c, L = _rise_sizes(size, cells)
+    nodes, shift = _host(nodes, np.int64), _host(shift, np.int64)
+    B, N = nodes.shape[:2]
+    g = nodes.reshape(B, N, L, L)
+    if (shift < 0).any() or (shift >= c).any():
+        raise ValueError(f"rise_masks: shifts outside [0, c={c})")
+    u = np.arange(H)[None, None, :, None] + shift[:, :, None, :]                                  # [B, N, H, 2]: (y + dy, x + dx)
+    (i, j), (ry, rx) = np.moveaxis(u // c, -1, 0), np.moveaxis(u % c, -1, 0)
+    bi, ni = np.arange(B)[:, None, None, None], np.arange(N)[None, :, None, None]
+    I, J, RY, RX = i[:, :, :, None], j[:, :, None, :], ry[:, :, :, None], rx[:, :, None, :]
+    K = (c - RY) * ((c - RX) * g[bi, ni, I, J] + RX * g[bi, ni, I, J + 1]) + RY * ((c - RX) * g[bi, ni, I + 1, J] + RX * g[bi, ni, I + 1, J + 1])
+    return K.astype(np.int32)
+
+
+def rise_apply(x, nodes, shift, cells, n0=0, count=None, baseline=0.0, device=True, out=None):
+    """The masked images [Nc, B, Cc, H, W] of x [B, Cc, H, W] under masks n0 .. n0 + count - 1 (default: to the last):
+    m * x + (1 - m) * baseline with m = K / c^2, every operation rounded once to fp32.  baseline: a number or a tensor like x.
+    device=True: one ppf_rise_apply launch; device=False: numpy."""
+    if device:
+        from . import ops
+        return ops.rise_apply(x, nodes, shift, cells, n0, count, baseline, out=out)
+    x, nodes, shift = _host(x, np.float32), _host(nodes, np.uint8), _host(shift, np.int32)
+    H, s, c, L = _rise_sizes(x.shape[2], cells)
+    if x.shape[2] != x.shape[3]:
+        raise ValueError(f"rise_apply: H={x.shape[2]} W={x.shape[3]}: square images only")
+    n0, N = int(n0), nodes.shape[1]
+    Nc = N - n0 if count is None else int(count)
+    if n0 < 0 or Nc < 1 or n0 + Nc > N:
+        raise ValueError(f"rise_apply: masks {n0} .. {n0 + Nc - 1} outside [0, {N})")
+    K = rise_masks(nodes[:, n0:n0 + Nc], shift[:, n0:n0 + Nc], H, s)
+    m = (K.astype(np.float32) / np.float32(c * c)).transpose(1, 0, 2, 3)[:, :, None]              # [Nc, B, 1, H, W], one rounding
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    with np.errstate(all="ignore"):
+        return (m * x[None] + (np.float32(1) - m) * base[None]).astype(np.float32)
+
+
+def rise_accumulate(nodes, shift, prob, size, cells, grid_cells, p=0.5, device=True):
+    """(sal fp32 [B, M, H, H], cell fp32 [B, M, G]) from the node tables and prob fp32 [N, B, M]: sal = (fp64 sum over n ascending of
+    prob * K) / norm with norm = N * (thr / 2^24) * c^2, cell = (fp64 sum over n ascending of prob * W) / (norm * patch^2) with W = K summed
+    over the cell's pixels; each rounded once to fp32.  device=True: ppf_rise_accumulate; device=False: numpy, mask by mask."""
+    H, s, c, L = _rise_sizes(size, cells)
+    thr, G = rise_threshold(p), int(grid_cells)
+    if device:
+        from . import ops
+        return ops.rise_accumulate(nodes, shift, prob, H, s, G, thr)
+    prob = _host(prob, np.float32)
+    N, B, M = prob.shape
+    side = int(round(G ** 0.5))
+    if side * side != G or H % side or not 1 <= M <= 8:
+        raise ValueError(f"rise_accumulate: G={G} must be a square grid whose side divides H={H}, and M={M} lie in [1, 8]")
+    patch = H // side
+    if patch * patch * c * c > 1 << 29:
+        raise ValueError(f"rise_accumulate: cell mass patch^2 * c^2 = {patch * patch * c * c} exceeds 2^29")
+    K = rise_masks(nodes, shift, H, s)                                                            # [B, N, H, H]
+    W = K.reshape(B, N, side, patch, side, patch).sum(axis=(3, 5), dtype=np.int64).reshape(B, N, G)
+    norm = float(N) * (thr / 16777216.0) * float(c * c)
+    acc, acc_w = np.zeros((B, M, H, H), dtype=np.float64), np.zeros((B, M, G), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        for n in range(N):                                                                        # ascending: the order is the contract
+            pn = prob[n].astype(np.float64)
+            acc += pn[:, :, None, None] * K[:, n, None].astype(np.float64)
+            acc_w += pn[:, :, None] * W[:, n, None].astype(np.float64)
+        return (acc / norm).astype(np.float32), (acc_w / (norm * float(patch * patch))).astype(np.float32)
+
+
+class Rise:
+    """What rise_saliency returns, as device tensors (numpy arrays after cpu()): saliency fp32 [B, M, H, W], cell fp32 [B, M, G] (the mean
+    saliency of each grid cell), prob fp32 [N, B, M] (the class probabilities of the masked images), nodes uint8 [B, N, L*L], shift int32
+    [B, N, 2], classes int32 [B, M]; cells, p: the mask parameters."""
+    FIELDS = ("saliency", "cell", "prob", "shift", "classes", "nodes")                            # the byte-sized table last: the others stay aligned
+
+    def __init__(self, saliency, cell, prob, shift, classes, nodes, cells, p):
+        self.saliency, self.cell, self.prob, self.shift, self.classes, self.nodes = saliency, cell, prob, shift, classes, nodes
+        self.cells, self.p = int(cells), float(p)
+
+    @property
+    def on_host(self):
+        return not isinstance(self.nodes, torch.Tensor)
+
+    def cpu(self):
+        """The same object with numpy arrays: every field in ONE host read."""
+        if self.on_host:
+            return self
+        items = [(k, getattr(self, k)) for k in self.FIELDS]
+        host = torch.cat([v.contiguous().view(torch.uint8).reshape(-1) for _, v in items]).cpu().numpy()
+        out, o = [], 0
+        for k, v in items:
+            nbytes = v.numel() * v.element_size()
+            dtype = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}[v.dtype]
+            out.append(host[o:o + nbytes].view(dtype).reshape(tuple(v.shape)).copy())
+            o += nbytes
+        return Rise(*out, self.cells, self.p)
+
+
+def _rise_from_classes(ppnet, x, cls, masks, cells, p, baseline, seed, image_ids, batch_size, scratch_bytes):
+    from . import ops
+    B, G, H = x.shape[0], int(ppnet.num_patches), x.shape[2]
+    M, N, thr = cls.shape[1], int(masks), rise_threshold(p)
+    ids = (torch.arange(B, dtype=torch.int64, device=x.device) if image_ids is None
+           else torch.as_tensor(image_ids).to(device=x.device, dtype=torch.int64).contiguous())
+    nodes, shift = ops.rise_nodes(ids, H, N, cells, thr, seed)
+    # scratch: the masked images of one chunk of masks, masks_per_chunk * B images, never more than scratch_bytes (one mask at least)
+    chunk = max(1, min(N, int(scratch_bytes) // (x.numel() * 4)))
+    bs = int(batch_size) if batch_size else B
+    cols = [cls[:, m].reshape(1, B).expand(chunk, B).reshape(-1).contiguous() for m in range(M)]
+    buf = torch.empty((chunk,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    prob = torch.empty((N, B, M), dtype=torch.float32, device=x.device)
+    was_training = ppnet.training
+    ppnet.eval()
+    try:
+        for n0 in range(0, N, chunk):
+            n = min(chunk, N - n0)
+            imgs = ops.rise_apply(x, nodes, shift, cells, n0, n, baseline, out=buf[:n]).reshape((n * B,) + tuple(x.shape[1:]))
+            logits = torch.cat([ppnet._branches(imgs[i:i + bs], want_dist=False)[5] for i in range(0, n * B, bs)]).contiguous()
+            for m in range(M):                                                                    # the mask does not depend on the class: one image serves all M
+                prob[n0:n0 + n, :, m] = ops.class_prob(logits, cols[m][:n * B]).reshape(n, B)
+    finally:
+        ppnet.train(was_training)
+    sal, cell = ops.rise_accumulate(nodes, shift, prob, H, cells, G, thr)
+    return Rise(sal, cell, prob, shift, cls, nodes, cells, p)
+
+
+@torch.no_grad()
+def rise_saliency(ppnet, x, classes=None, top_classes=1, masks=512, cells=7, p=0.5, baseline=0.0, seed=0, image_ids=None, batch_size=None,
+                  scratch_bytes=1 << 30):
+    """RISE saliency of a batch x [B, 3, H, W] (CUDA) for the classes of explain (None: the top `top_classes` of the logits): one eval
+    forward and the class pick, one ppf_rise_nodes launch, then per chunk of masks ppf_rise_apply into the one scratch buffer
+    (masks-per-chunk = scratch_bytes // (B * image bytes), at least one), the model's forward over the chunk in sub-batches of
+    `batch_size` images (default B; the images of a chunk are ordered mask, sample) and ppf_class_prob once per class column; one
+    ppf_rise_accumulate at the end.  masks = N, cells = s low-resolution cells per side, p the keep probability, baseline what a masked
+    pixel tends to (a number in normalised space or a tensor like x); seed, image_ids [B] (None: 0 .. B-1) key the masks, so an image's
+    result does not depend on its batch.  Returns a Rise (device tensors; nothing is read back here)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("rise_saliency needs a CUDA/HIP batch (no CPU fallback path; rise_nodes_from_ids / rise_apply / rise_accumulate with "
+                           "device=False are the host referees)")
+    x = x.float().contiguous()
+    outs = _eval_outputs(ppnet, x)
+    cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
+    return _rise_from_classes(ppnet, x, cls, masks, cells, p, baseline, seed, image_ids, batch_size, scratch_bytes)
 
 
 # ------------------------------------------------------------------------------------------------ spatial alignment: does a cell's activation depend on its pixels?

@@ -636,6 +636,73 @@ def class_prob(logits, cls):
     return prob
 
 
+# ---- RISE saliency (csrc/rise.hip): node tables, masked images, the probability-weighted mean mask
+def _rise_tables(who, nodes, shift, cells):
+    LL = (int(cells) + 2) ** 2
+    if not isinstance(nodes, torch.Tensor) or nodes.dim() != 3:
+        raise ValueError(f"{who}: nodes must be a uint8 CUDA tensor [B, N, {LL}]")
+    B, N = nodes.shape[:2]
+    _dev_tensor(who, "nodes", nodes, torch.uint8, (B, N, LL))
+    _dev_tensor(who, "shift", shift, torch.int32, (B, N, 2), nodes.device)
+    return B, N
+
+
+def rise_nodes(image_ids, size, masks, cells, thr, seed=0):
+    """The node tables of `masks` RISE masks per image (ppf_rise_nodes, include/ppf_hip.h); one launch.  image_ids int64 [B]; size = H;
+    thr = round(p * 2^24).  Returns (nodes uint8 [B, N, (cells + 2)^2], shift int32 [B, N, 2])."""
+    who = "rise_nodes"
+    if not isinstance(image_ids, torch.Tensor) or image_ids.dim() != 1:
+        raise ValueError(f"{who}: image_ids must be an int64 CUDA tensor [B]")
+    B, N, s = image_ids.shape[0], int(masks), int(cells)
+    _dev_tensor(who, "image_ids", image_ids, torch.int64, (B,))
+    nodes = torch.empty((B, max(N, 0), max(s + 2, 0) ** 2), dtype=torch.uint8, device=image_ids.device)
+    shift = torch.empty((B, max(N, 0), 2), dtype=torch.int32, device=image_ids.device)
+    _lib.call("ppf_rise_nodes", image_ids, int(seed) & 0xFFFFFFFFFFFFFFFF, int(thr), B, N, s, int(size), nodes, shift)
+    return nodes, shift
+
+
+def rise_apply(x, nodes, shift, cells, n0=0, count=None, baseline=0.0, out=None):
+    """The masked images out fp32 [Nc, B, Cc, H, W] of x fp32 [B, Cc, H, W] under masks n0 .. n0 + count - 1 (default: to the last) of the
+    tables rise_nodes wrote (ppf_rise_apply, include/ppf_hip.h); one launch.  baseline: a number, or an fp32 tensor like x."""
+    who = "rise_apply"
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [B, Cc, H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    B, Cc, H, W = x.shape
+    Bn, N = _rise_tables(who, nodes, shift, cells)
+    if Bn != B or nodes.device != x.device:
+        raise ValueError(f"{who}: nodes must be [{B}, N, L*L] on {x.device}, got {list(nodes.shape)} on {nodes.device}")
+    n0 = int(n0)
+    Nc = N - n0 if count is None else int(count)
+    base_t, base_c = None, 0.0
+    if isinstance(baseline, torch.Tensor):
+        base_t = _dev_tensor(who, "baseline", baseline, torch.float32, x.shape, x.device)
+    else:
+        base_c = float(baseline)
+    shape = (max(Nc, 0), B, Cc, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_tensor(who, "out", out, torch.float32, shape, x.device)
+    _lib.call("ppf_rise_apply", x, nodes, shift, N, n0, Nc, int(cells), base_t, base_c, B, Cc, H, W, out)
+    return out
+
+
+def rise_accumulate(nodes, shift, prob, size, cells, grid_cells, thr):
+    """(sal fp32 [B, M, H, H], cell fp32 [B, M, G]) = the probability-weighted mean mask per pixel and per grid cell, from the tables
+    rise_nodes wrote and prob fp32 [N, B, M] (ppf_rise_accumulate, include/ppf_hip.h); masks regenerated, never stored."""
+    who = "rise_accumulate"
+    B, N = _rise_tables(who, nodes, shift, cells)
+    if not isinstance(prob, torch.Tensor) or prob.dim() != 3:
+        raise ValueError(f"{who}: prob must be an fp32 CUDA tensor [N, B, M]")
+    M, H, G = prob.shape[2], int(size), int(grid_cells)
+    _dev_tensor(who, "prob", prob, torch.float32, (N, B, M), nodes.device)
+    sal = torch.empty((B, M, max(H, 0), max(H, 0)), dtype=torch.float32, device=nodes.device)
+    cell = torch.empty((B, M, max(G, 0)), dtype=torch.float32, device=nodes.device)
+    _lib.call("ppf_rise_accumulate", nodes, shift, prob, B, N, M, int(cells), int(thr), H, H, G, sal, cell)
+    return sal, cell
+
+
 # ---- spatial alignment (csrc/alignment.hip): the image gradient's last step, gradient mass inside a box, the attack's step
 def col2im_patch(cols, B, C, H, W, patch):
     """img fp32 [B, C, H, W] from cols fp32 [B*(H/patch)*(W/patch), C*patch*patch]: the inverse of im2col_patch / im2col_patch_f32
