@@ -60,18 +60,10 @@ class PrototypeBank:
 
     @torch.no_grad()
     def update(self, x, labels, ids):
-        """One batch through the model's eval branch (PPNet._branches), then both branches into the lists."""
-        m = self.ppnet
-        was_training = m.training
-        m.eval()
-        try:
-            f, _, idx, *_ = m._branches(x, want_dist=False)
-            act_l, act_g = m._last_act_max
-            argmax = m._last_argmax
-        finally:
-            m.train(was_training)
-        self.merge("local", act_l, argmax, idx, f, labels, ids)
-        self.merge("global", act_g, None, None, f, labels, ids)
+        """One batch through the model's eval branch (PPNet.eval_branches), then both branches into the lists."""
+        r = self.ppnet.eval_branches(x)
+        self.merge("local", r.act_max_local, r.argmax, r.idx, r.f, labels, ids)
+        self.merge("global", r.act_max_global, None, None, r.f, labels, ids)
 
     def merge(self, branch, act_max, argmax, idx, f, labels, ids):
         """Low-level: fold one batch's pooled activations of `branch` into its lists.  act_max [B, P] fp32, argmax [B, P] int32 and
@@ -96,20 +88,10 @@ class PrototypeBank:
     def result(self):
         """One host read.  {'local' | 'global': dict(values [P, K] fp32, image_ids [P, K], grid_pos [P, K] (index in the side x side patch
         grid, -1 on the global branch), filled [P] = number of valid entries)} as numpy arrays; unfilled slots hold -inf / -1 / -1."""
-        parts = []
-        for br in BRANCHES:
-            s = self.state[br]
-            parts += [s["val"].view(torch.int32).reshape(-1), s["img"].reshape(-1), s["pos"].reshape(-1)]
-        host = torch.cat(parts).cpu().numpy()
-        out, o = {}, 0
-        for br in BRANCHES:
-            n = self.num[br] * self.topk
-            shape = (self.num[br], self.topk)
-            val = host[o:o + n].view(np.float32).reshape(shape).copy()
-            img, pos = host[o + n:o + 2 * n].reshape(shape).copy(), host[o + 2 * n:o + 3 * n].reshape(shape).copy()
-            o += 3 * n
-            out[br] = dict(values=val, image_ids=img, grid_pos=pos, filled=(img >= 0).sum(axis=1).astype(np.int32))
-        return out
+        from .tooling import read_once
+        host = read_once({(br, k): self.state[br][k] for br in BRANCHES for k in ("val", "img", "pos")})
+        return {br: dict(values=host[br, "val"], image_ids=host[br, "img"], grid_pos=host[br, "pos"],
+                         filled=(host[br, "img"] >= 0).sum(axis=1).astype(np.int32)) for br in BRANCHES}
 
     @torch.no_grad()
     def project_(self, ppnet=None, branches=BRANCHES):

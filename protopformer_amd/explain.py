@@ -74,7 +74,7 @@ def main(args, model=None, loader=None, index=None):
     from . import data as D
     from .bank import image_index
     from .interpret import explain
-    from .tooling import eval_loader, load_for_eval, model_from_args, take_images
+    from .tooling import batches_with_ids, eval_loader, load_for_eval, model_from_args
     from .train import set_seed
     set_seed(args.seed)
     device = torch.device(args.device)
@@ -93,9 +93,8 @@ def main(args, model=None, loader=None, index=None):
     os.makedirs(args.output_dir, exist_ok=True)
     path, seen, rendered = os.path.join(args.output_dir, "explanations.jsonl"), 0, 0
     with open(path, "w") as out:
-        for x, y, *rest in take_images(loader, args.max_images):
-            B = x.shape[0]
-            ids = np.asarray(torch.as_tensor(rest[0]).cpu()) if rest else np.arange(seen, seen + B)
+        for x, y, ids in batches_with_ids(loader, args.max_images):
+            ids = ids.cpu().numpy()
             ex = explain(model, x if x.is_cuda else x.to(device), top_classes=args.top_classes, topk=args.topk, against=args.against, maps=args.render)
             host = ex.cpu()
             labels = np.asarray(torch.as_tensor(y).cpu())
@@ -106,7 +105,7 @@ def main(args, model=None, loader=None, index=None):
                 out.write(json.dumps(rec) + "\n")
             if args.render:
                 rendered += len(render_overlays(args.output_dir, host, view_images_bgr(x, D.IMAGENET_DEFAULT_MEAN, D.IMAGENET_DEFAULT_STD), ids))
-            seen += B
+            seen += x.shape[0]
     print(f"explained {seen} {args.split} images: {path}" + (f", {rendered} overlays under {args.output_dir}" if args.render else ""), flush=True)
     return path
 

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import torch
 
-from .tooling import take_images
+from .tooling import batches_with_ids, read_once, take_images
 
 
 # ------------------------------------------------------------------------------------------------ activation maps
@@ -611,12 +611,8 @@ def nearest_patches(ppnet, loader, topk=10, class_specific=True):
     not shuffle.  Ids must be unique over the loader."""
     from .bank import PrototypeBank
     bank = PrototypeBank(ppnet, topk=topk, class_specific=class_specific)
-    seen = 0
-    for x, y, *rest in loader:
-        B = x.shape[0]
-        ids = rest[0] if rest else torch.arange(seen, seen + B, dtype=torch.int32)
+    for x, y, ids in batches_with_ids(loader):
         bank.update(x.cuda() if not x.is_cuda else x, y, ids)
-        seen += B
     return bank
 
 
@@ -735,14 +731,8 @@ class Explanation:
         """The same explanation with numpy arrays: every field of both branches in ONE host read."""
         if self.on_host:
             return self
-        items = [(br, k, v) for br in EXPLAIN_BRANCHES for k, v in self.branches[br].items() if v is not None]
-        flat = [(v if v.dtype == torch.int32 else v.float().contiguous().view(torch.int32)).reshape(-1) for _, _, v in items]
-        host = torch.cat(flat).cpu().numpy()
-        out, o = {br: dict.fromkeys(EXPLAIN_FIELDS) for br in EXPLAIN_BRANCHES}, 0
-        for br, k, v in items:
-            a = host[o:o + v.numel()]
-            o += v.numel()
-            out[br][k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
+        host = read_once({(br, k): v for br in EXPLAIN_BRANCHES for k, v in self.branches[br].items()})
+        out = {br: {k: host[br, k] for k in self.branches[br]} for br in EXPLAIN_BRANCHES}
         return Explanation(out["local"], out["global"], self.ppc, self.scale, self.side, self.patch_size, self.img_size, self.against)
 
     def report(self, index=None, bank=None, stats=None):
@@ -834,22 +824,15 @@ def explain(ppnet, x, classes=None, top_classes=1, topk=10, against=False, maps=
         raise RuntimeError("explain needs a CUDA/HIP batch (no CPU fallback path; explain_from_outputs(device=False) is the host referee)")
     B, C = x.shape[0], ppnet.last_layer.weight.shape[0]
     cls = None if classes is None else _explain_classes(classes, B, C, x.device)
-    was_training = ppnet.training
-    ppnet.eval()
-    try:
-        _, _, idx, act_full, _, logits, _, _ = ppnet._branches(x, want_dist=False)
-        act_l, act_g = ppnet._last_act_max
-        argmax = ppnet._last_argmax
-    finally:
-        ppnet.train(was_training)
+    r = ppnet.eval_branches(x)
     coe, sign = float(ppnet.global_coe), -1 if against else 1
     G = int(ppnet.num_patches)
     side = int(round(G ** 0.5))
     w_l, w_g = ppnet.last_layer.weight.detach().contiguous(), ppnet.last_layer_global.weight.detach().contiguous()
-    logits = logits.contiguous()
-    local = ops.explain_topk(act_l, w_l, 1.0 - coe, ppnet.num_prototypes_per_class, logits, topk, classes=cls, top_classes=top_classes, sign=sign,
-                             argmax=argmax, idx=idx.contiguous(), act_full=act_full.contiguous(), grid_cells=G, want_maps=maps)
-    glob = ops.explain_topk(act_g, w_g, coe, ppnet.global_proto_per_class, logits, topk, classes=local["classes"], sign=sign)
+    logits = r.logits.contiguous()
+    local = ops.explain_topk(r.act_max_local, w_l, 1.0 - coe, ppnet.num_prototypes_per_class, logits, topk, classes=cls, top_classes=top_classes,
+                             sign=sign, argmax=r.argmax, idx=r.idx.contiguous(), act_full=r.act_full.contiguous(), grid_cells=G, want_maps=maps)
+    glob = ops.explain_topk(r.act_max_global, w_g, coe, ppnet.global_proto_per_class, logits, topk, classes=local["classes"], sign=sign)
     for f, w in ((local, w_l), (glob, w_g)):
         f["weights"] = w[f["classes"].clamp(min=0).long()[:, :, None], f["prototypes"].clamp(min=0).long()]       # raw weights of the listed pairs
     if maps:
@@ -907,11 +890,7 @@ def cell_order_from_outputs(act_full, idx, token_attn, weight, scale, classes, g
     G = int(grid_cells)
     if device:
         from . import ops
-        B = classes.shape[0]
-        ids = None
-        if mode == "random":
-            ids = (torch.arange(B, dtype=torch.int64, device=classes.device) if image_ids is None
-                   else torch.as_tensor(image_ids).to(device=classes.device, dtype=torch.int64).contiguous())
+        ids = _image_ids(image_ids, classes.shape[0], classes.device) if mode == "random" else None
         return ops.cell_order(classes, G, mode, act_full=act_full, idx=idx, token_attn=token_attn, weight=weight, scale=scale, image_ids=ids, seed=seed)
     weight, cls = _host(weight, np.float32), _host(classes, np.int32)
     (B, M), (C, P) = cls.shape, weight.shape
@@ -999,15 +978,8 @@ class Faithfulness:
         """The same object with numpy arrays: every field in ONE host read."""
         if self.on_host:
             return self
-        items = [(k, getattr(self, k)) for k in self.FIELDS] + [("curve:" + k, v) for k, v in self.curves.items()]
-        flat = [(v if v.dtype == torch.int32 else v.float().contiguous().view(torch.int32)).reshape(-1) for _, v in items]
-        host = torch.cat(flat).cpu().numpy()
-        out, o = {}, 0
-        for k, v in items:
-            a = host[o:o + v.numel()]
-            o += v.numel()
-            out[k] = (a if v.dtype == torch.int32 else a.view(np.float32)).reshape(tuple(v.shape)).copy()
-        return Faithfulness({k[6:]: v for k, v in out.items() if k.startswith("curve:")}, *(out[k] for k in self.FIELDS), self.grid_cells,
+        out = read_once({**{k: getattr(self, k) for k in self.FIELDS}, **{("curve", k): v for k, v in self.curves.items()}})
+        return Faithfulness({k: out["curve", k] for k in self.curves}, *(out[k] for k in self.FIELDS), self.grid_cells,
                             rise=None if self.rise is None else self.rise.cpu())
 
     def auc(self):
@@ -1025,16 +997,29 @@ def curve_auc(curves, counts, grid_cells):
 
 def _eval_outputs(ppnet, x):
     """One eval forward: what the cell orders and the class pick need, all on the device."""
-    was_training = ppnet.training
-    ppnet.eval()
-    try:
-        _, token_attn, idx, act_full, _, logits, _, _ = ppnet._branches(x, want_dist=False)
-        act_l = ppnet._last_act_max[0]
-    finally:
-        ppnet.train(was_training)
-    B = x.shape[0]
-    return dict(token_attn=token_attn.reshape(B, -1).float().contiguous(), idx=idx.contiguous(), act_full=act_full.contiguous(), logits=logits.contiguous(),
-                act_max=act_l)
+    r = ppnet.eval_branches(x)
+    return dict(token_attn=r.cls_attn.reshape(x.shape[0], -1).float().contiguous(), idx=r.idx.contiguous(), act_full=r.act_full.contiguous(),
+                logits=r.logits.contiguous(), act_max=r.act_max_local)
+
+
+def _image_ids(image_ids, B, device):
+    """image_ids [B], or 0 .. B-1 for None, as int64 on the device."""
+    if image_ids is None:
+        return torch.arange(B, dtype=torch.int64, device=device)
+    return torch.as_tensor(image_ids).to(device=device, dtype=torch.int64).contiguous()
+
+
+def _chunk_items(total, scratch_bytes, bytes_per_item):
+    """How many of `total` items one scratch buffer of scratch_bytes holds: one at least."""
+    return max(1, min(total, int(scratch_bytes) // bytes_per_item))
+
+
+def _class_probs(ppnet, imgs, cols, batch_size):
+    """The probabilities fp32 [R] of the classes cols[j] int32 [R] of the images imgs [R, C, H, W], per column: the model's forward in
+    sub-batches of batch_size images, then one ppf_class_prob per column.  The caller holds eval mode and no_grad."""
+    from . import ops
+    logits = torch.cat([ppnet._branches(imgs[i:i + batch_size], want_dist=False).logits for i in range(0, imgs.shape[0], batch_size)]).contiguous()
+    return [ops.class_prob(logits, c) for c in cols]
 
 
 def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None):
@@ -1054,15 +1039,11 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
         ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G,
                                                     mode=order, seed=seed, image_ids=image_ids)
     # scratch: the perturbed images of one chunk of steps, steps_per_chunk * B * M images, never more than scratch_bytes (one step at least)
-    per_step = B * M * x[0].numel() * 4
-    chunk = max(1, min(S, int(scratch_bytes) // per_step))
-    bs = int(batch_size) if batch_size else B
+    chunk = _chunk_items(S, scratch_bytes, B * M * x[0].numel() * 4)
     cls_flat = cls.reshape(1, B * M).expand(chunk, B * M).reshape(-1).contiguous()
     buf = torch.empty((chunk, B, M) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
     curves = {}
-    was_training = ppnet.training
-    ppnet.eval()
-    try:
+    with ppnet.eval_mode():
         for mode in modes:
             if mode not in CURVE_MODES:
                 raise ValueError(f"faithfulness_curves: modes must come from {CURVE_MODES}, got {mode!r}")
@@ -1071,11 +1052,8 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
                 n = min(chunk, S - s0)
                 imgs = ops.patch_perturb(x, rank, counts[s0:s0 + n].contiguous(), mode == "insertion", baseline, out=buf[:n])
                 imgs = imgs.reshape((n * B * M,) + tuple(x.shape[1:]))
-                logits = torch.cat([ppnet._branches(imgs[i:i + bs], want_dist=False)[5] for i in range(0, imgs.shape[0], bs)])
-                prob[s0:s0 + n] = ops.class_prob(logits.contiguous(), cls_flat[:n * B * M]).reshape(n, B, M)
+                prob[s0:s0 + n] = _class_probs(ppnet, imgs, [cls_flat[:n * B * M]], int(batch_size or B))[0].reshape(n, B, M)
             curves[mode] = prob.permute(1, 2, 0).contiguous()
-    finally:
-        ppnet.train(was_training)
     return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found)
 
 
@@ -1129,10 +1107,9 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
     image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
     G, kept, cls_kept, ids_kept, seen, dev_counts = int(ppnet.num_patches), {}, [], [], 0, None
-    for x, y, *rest in take_images(loader, max_images):
+    for x, y, ids in batches_with_ids(loader, max_images):
         x = (x if x.is_cuda else x.cuda()).float().contiguous()
-        B = x.shape[0]
-        ids = torch.as_tensor(rest[0]).to(torch.int64) if rest else torch.arange(seen, seen + B, dtype=torch.int64)
+        B, ids = x.shape[0], ids.to(x.device)               # on the device once: the random / rise orders key by them, the closing read takes them
         outs = _eval_outputs(ppnet, x)
         cls = _pick_classes(ppnet, outs, torch.as_tensor(y).to(x.device) if against_label else None, top_classes, B)
         if dev_counts is None:
@@ -1146,10 +1123,11 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
     if not seen:
         raise ValueError("faithfulness: the loader gave no image")
     keys = list(kept)
-    host = torch.stack([torch.cat(kept[k]) for k in keys]).cpu().numpy()                    # the one read of the curves: [orders * modes, N, M, S]
-    classes, cnt = torch.cat(cls_kept).cpu().numpy(), dev_counts.cpu().numpy()
+    read = read_once(dict(curves=torch.stack([torch.cat(kept[k]) for k in keys]), classes=torch.cat(cls_kept), counts=dev_counts,
+                          image_ids=torch.cat(ids_kept)))                                    # the one read; curves: [orders * modes, N, M, S]
+    host, classes, cnt = read["curves"], read["classes"], read["counts"]
     valid = classes >= 0
-    out = dict(images=seen, counts=cnt.tolist(), grid_cells=G, orders={}, per_image={}, classes=classes, image_ids=torch.cat([i.cpu() for i in ids_kept]).numpy())
+    out = dict(images=seen, counts=cnt.tolist(), grid_cells=G, orders={}, per_image={}, classes=classes, image_ids=read["image_ids"])
     for j, (order, mode) in enumerate(keys):
         rows = host[j][valid].astype(np.float64)                                             # [rows, S]
         out["orders"].setdefault(order, {})[mode] = dict(curve=rows.mean(0).tolist(), auc=float(curve_auc(rows, cnt, G).mean()))
@@ -1284,7 +1262,7 @@ class Rise:
     """What rise_saliency returns, as device tensors (numpy arrays after cpu()): saliency fp32 [B, M, H, W], cell fp32 [B, M, G] (the mean
     saliency of each grid cell), prob fp32 [N, B, M] (the class probabilities of the masked images), nodes uint8 [B, N, L*L], shift int32
     [B, N, 2], classes int32 [B, M]; cells, p: the mask parameters."""
-    FIELDS = ("saliency", "cell", "prob", "shift", "classes", "nodes")                            # the byte-sized table last: the others stay aligned
+    FIELDS = ("saliency", "cell", "prob", "shift", "classes", "nodes")                            # the constructor's order
 
     def __init__(self, saliency, cell, prob, shift, classes, nodes, cells, p):
         self.saliency, self.cell, self.prob, self.shift, self.classes, self.nodes = saliency, cell, prob, shift, classes, nodes
@@ -1298,41 +1276,26 @@ class Rise:
         """The same object with numpy arrays: every field in ONE host read."""
         if self.on_host:
             return self
-        items = [(k, getattr(self, k)) for k in self.FIELDS]
-        host = torch.cat([v.contiguous().view(torch.uint8).reshape(-1) for _, v in items]).cpu().numpy()
-        out, o = [], 0
-        for k, v in items:
-            nbytes = v.numel() * v.element_size()
-            dtype = {torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}[v.dtype]
-            out.append(host[o:o + nbytes].view(dtype).reshape(tuple(v.shape)).copy())
-            o += nbytes
-        return Rise(*out, self.cells, self.p)
+        return Rise(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.cells, self.p)
 
 
 def _rise_from_classes(ppnet, x, cls, masks, cells, p, baseline, seed, image_ids, batch_size, scratch_bytes):
     from . import ops
     B, G, H = x.shape[0], int(ppnet.num_patches), x.shape[2]
     M, N, thr = cls.shape[1], int(masks), rise_threshold(p)
-    ids = (torch.arange(B, dtype=torch.int64, device=x.device) if image_ids is None
-           else torch.as_tensor(image_ids).to(device=x.device, dtype=torch.int64).contiguous())
-    nodes, shift = ops.rise_nodes(ids, H, N, cells, thr, seed)
+    nodes, shift = ops.rise_nodes(_image_ids(image_ids, B, x.device), H, N, cells, thr, seed)
     # scratch: the masked images of one chunk of masks, masks_per_chunk * B images, never more than scratch_bytes (one mask at least)
-    chunk = max(1, min(N, int(scratch_bytes) // (x.numel() * 4)))
-    bs = int(batch_size) if batch_size else B
+    chunk = _chunk_items(N, scratch_bytes, x.numel() * 4)
     cols = [cls[:, m].reshape(1, B).expand(chunk, B).reshape(-1).contiguous() for m in range(M)]
     buf = torch.empty((chunk,) + tuple(x.shape), dtype=torch.float32, device=x.device)
     prob = torch.empty((N, B, M), dtype=torch.float32, device=x.device)
-    was_training = ppnet.training
-    ppnet.eval()
-    try:
+    with ppnet.eval_mode():
         for n0 in range(0, N, chunk):
             n = min(chunk, N - n0)
             imgs = ops.rise_apply(x, nodes, shift, cells, n0, n, baseline, out=buf[:n]).reshape((n * B,) + tuple(x.shape[1:]))
-            logits = torch.cat([ppnet._branches(imgs[i:i + bs], want_dist=False)[5] for i in range(0, n * B, bs)]).contiguous()
-            for m in range(M):                                                                    # the mask does not depend on the class: one image serves all M
-                prob[n0:n0 + n, :, m] = ops.class_prob(logits, cols[m][:n * B]).reshape(n, B)
-    finally:
-        ppnet.train(was_training)
+            # the mask does not depend on the class: one image serves all M columns
+            for m, pr in enumerate(_class_probs(ppnet, imgs, [c[:n * B] for c in cols], int(batch_size or B))):
+                prob[n0:n0 + n, :, m] = pr.reshape(n, B)
     sal, cell = ops.rise_accumulate(nodes, shift, prob, H, cells, G, thr)
     return Rise(sal, cell, prob, shift, cls, nodes, cells, p)
 
@@ -1397,18 +1360,15 @@ def input_gradient(ppnet, x, target):
     if sel.shape[1] != 1:
         raise ValueError(f"input_gradient: one target per sample expected, got {tuple(sel.shape)}")
     xg = x.detach().float().contiguous().requires_grad_(True)
-    was_training = ppnet.training
-    ppnet.eval()
     try:
-        with torch.enable_grad():
-            logits = ppnet._branches(xg, want_dist=False)[5]
-            out = logits if branch is None else ppnet._last_act_max[0 if branch == "local" else 1]
+        with ppnet.eval_mode(), torch.enable_grad():
+            r = ppnet._branches(xg, want_dist=False)
+            out = {None: r.logits, "local": r.act_max_local, "global": r.act_max_global}[branch]
             if out.grad_fn is None:
                 raise RuntimeError("input_gradient: the forward recorded no graph for the target")
             value = out.gather(1, sel.long()).reshape(B)
             value.sum().backward()
     finally:
-        ppnet.train(was_training)
         for p in ppnet.parameters():
             p.grad = None
     return xg.grad, value.detach()

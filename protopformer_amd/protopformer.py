@@ -5,9 +5,11 @@ return tuples, attribute names and state-dict keys; underneath, every FLOP runs 
 (protopformer_amd/lib/libppf_hip.so, C ABI in include/ppf_hip.h).  Python here wires shapes, autograd and buffers.
 There is no CPU / eager fallback: without the built library or off a GPU, forward() raises.
 """
+import contextlib
 import math
 import os
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -140,18 +142,16 @@ class ProtoLayerFn(torch.autograd.Function):
         act_l, argmax, dist, act_full = ops.proto_fwd(f, 1, k, pl, act_kind, ppnet.epsilon, want_dist=keep_dist or want_dist, want_act=True)
         act_g, _, dist_g, _ = ops.proto_fwd(f, 0, 1, pg, act_kind, ppnet.epsilon, want_dist=need_bwd, want_act=False)
         ctx.set_materialize_grads(False)
-        ppnet._last_argmax = argmax              # (B, P) int32: the token each local prototype's max-pool selected (tests, visualisation)
-        ppnet._last_act_max = (act_l, act_g)     # (B, P) / (B, P_global) pooled activations of this call (bank.PrototypeBank.update)
         if need_bwd:
             ctx.save_for_backward(f, protos_local, protos_global, dist if keep_dist else act_full)
             ctx.aux = (argmax, not keep_dist, dist_g, act_kind, ppnet)
         if dist is None:
             dist = act_full.new_empty(0)
-        ctx.mark_non_differentiable(dist)
-        return act_l, act_full, act_g, dist
+        ctx.mark_non_differentiable(*(t for t in (dist, argmax) if t is not None))
+        return act_l, act_full, act_g, dist, argmax          # argmax: None when the local branch has one token (ops.proto_fwd)
 
     @staticmethod
-    def backward(ctx, g_l, g_full, g_g, _g_dist):
+    def backward(ctx, g_l, g_full, g_g, _g_dist, _g_argmax):
         f, _, _, dist = ctx.saved_tensors                 # dist: the distance map, or (from_act) the activation map
         argmax, from_act, dist_g, act_kind, ppnet = ctx.aux
         protos_local, protos_global = ppnet.prototype_vectors, ppnet.prototype_vectors_global
@@ -291,6 +291,24 @@ class CrossEntropyLoss(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ PPNet
+class Branches(NamedTuple):
+    """What one pass of PPNet._branches leaves on the device.  f (B, 1 + k, Dp) latent tokens (cls first), cls_attn (B, Np) rollout scores,
+    idx (B, k) int32 grid cells of the reserved tokens, act_full (B, P, k) the local activation map, dist its distance map (empty unless
+    asked for), logits / logits_global / logits_local (B, C), act_max_local (B, P) / act_max_global (B, P_global) the pooled activations
+    (ProtoLayerFn's own outputs: they carry its grad_fn), argmax (B, P) int32 the token each local max-pool selected (None when k == 1)."""
+    f: torch.Tensor
+    cls_attn: torch.Tensor
+    idx: torch.Tensor
+    act_full: torch.Tensor
+    dist: torch.Tensor
+    logits: torch.Tensor
+    logits_global: torch.Tensor
+    logits_local: torch.Tensor
+    act_max_local: torch.Tensor
+    act_max_global: torch.Tensor
+    argmax: Optional[torch.Tensor]
+
+
 class PPNet(nn.Module):
     def __init__(self, features, img_size, prototype_shape, proto_layer_rf_info, num_classes, reserve_layers=[],
                  reserve_token_nums=[], use_global=False, use_ppc_loss=False, ppc_cov_thresh=2., ppc_mean_thresh=2,
@@ -421,9 +439,25 @@ class PPNet(nn.Module):
 
     def _branches(self, x, want_dist):
         f, cls_attn, idx = self._tokens(x)
-        act_l, act_full, act_g, dist = ProtoLayerFn.apply(f, self.prototype_vectors, self.prototype_vectors_global, self, want_dist)
+        act_l, act_full, act_g, dist, argmax = ProtoLayerFn.apply(f, self.prototype_vectors, self.prototype_vectors_global, self, want_dist)
         logits, lg, ll = LogitsFn.apply(act_g, act_l, self.last_layer_global.weight, self.last_layer.weight, float(self.global_coe))
-        return f, cls_attn, idx, act_full, dist, logits, lg, ll
+        self._last_argmax = argmax               # test-facing only; the tools take everything from the record
+        return Branches(f, cls_attn, idx, act_full, dist, logits, lg, ll, act_l, act_g, argmax)
+
+    @contextlib.contextmanager
+    def eval_mode(self):
+        """Eval mode for the block, then the mode that was found (also when the block raises).  Needs nothing of PPNet but nn.Module."""
+        was_training = self.training
+        self.eval()
+        try:
+            yield self
+        finally:
+            self.train(was_training)
+
+    def eval_branches(self, x):
+        """The record of one eval pass without a graph; the training mode is left as found."""
+        with self.eval_mode(), torch.no_grad():
+            return self._branches(x, want_dist=False)
 
     def forward(self, x):
         if not x.is_cuda:
@@ -433,20 +467,20 @@ class PPNet(nn.Module):
         s = int(round(math.sqrt(k)))
         if not self.training:
             with torch.no_grad():
-                f, cls_attn, idx, act_full, dist, logits, lg, ll = self._branches(x, want_dist=True)
-            return logits, (cls_attn, dist.reshape(B, self.num_prototypes, s, s), lg, ll)
-        f, cls_attn, idx, act_full, dist, logits, lg, ll = self._branches(x, want_dist=False)
-        self._ppc_cache = (cls_attn, idx)
-        total_proto_act = act_full.reshape(B, self.num_prototypes, s, s)
-        attn_loss = ops.const_scalar(logits.device, 0.0).reshape(1)      # protopformer.py:333 (a constant zero: cached, never written)
-        return logits, (None, attn_loss, total_proto_act, cls_attn, self.num_patches)
+                r = self._branches(x, want_dist=True)
+            return r.logits, (r.cls_attn, r.dist.reshape(B, self.num_prototypes, s, s), r.logits_global, r.logits_local)
+        r = self._branches(x, want_dist=False)
+        self._ppc_cache = (r.cls_attn, r.idx)
+        total_proto_act = r.act_full.reshape(B, self.num_prototypes, s, s)
+        attn_loss = ops.const_scalar(r.logits.device, 0.0).reshape(1)    # protopformer.py:333 (a constant zero: cached, never written)
+        return r.logits, (None, attn_loss, total_proto_act, r.cls_attn, self.num_patches)
 
     def push_forward(self, x):
         with torch.no_grad():
-            f, cls_attn, idx, act_full, dist, logits, lg, ll = self._branches(x, want_dist=False)
+            r = self._branches(x, want_dist=False)
         k = self.reserve_token_nums[0]
         s = int(round(math.sqrt(k)))
-        return cls_attn, act_full.reshape(x.shape[0], self.num_prototypes, s, s)
+        return r.cls_attn, r.act_full.reshape(x.shape[0], self.num_prototypes, s, s)
 
     def get_PPC_loss(self, total_proto_act, cls_attn_rollout, original_fea_len, label):
         if label.is_floating_point() or label.dim() != 1:

@@ -268,18 +268,10 @@ class PrototypeStats:
 
     @torch.no_grad()
     def update(self, x, labels):
-        """One batch through the model's eval branch (PPNet._branches), then both branches into the tables."""
-        m = self.ppnet
-        was_training = m.training
-        m.eval()
-        try:
-            _, _, idx, *_ = m._branches(x, want_dist=False)
-            act_l, act_g = m._last_act_max
-            argmax = m._last_argmax
-        finally:
-            m.train(was_training)
-        self.merge("local", act_l, argmax, idx, labels)
-        self.merge("global", act_g, None, None, labels)
+        """One batch through the model's eval branch (PPNet.eval_branches), then both branches into the tables."""
+        r = self.ppnet.eval_branches(x)
+        self.merge("local", r.act_max_local, r.argmax, r.idx, labels)
+        self.merge("global", r.act_max_global, None, None, labels)
 
     def merge(self, branch, act_max, argmax, idx, labels):
         """Low-level: add one batch's pooled activations of `branch`.  act_max [B, P] fp32, argmax [B, P] int32 and idx [B, T] int32

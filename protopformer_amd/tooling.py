@@ -51,3 +51,31 @@ def take_images(loader, max_images):
             return
         yield batch
         left -= n
+
+
+def batches_with_ids(loader, max_images=0):
+    """take_images as (x, y, ids): the int64 image ids the loader supplies as a third element, else the running index in loader order
+    (so such a loader must not shuffle)."""
+    import torch
+    seen = 0
+    for x, y, *rest in take_images(loader, max_images):
+        n = len(x)
+        yield x, y, torch.as_tensor(rest[0]).to(torch.int64) if rest else torch.arange(seen, seen + n, dtype=torch.int64)
+        seen += n
+
+
+def read_once(named):
+    """{name: device tensor or None} -> {name: numpy array of the same dtype and shape, or None} in ONE device-to-host transfer.  The
+    fields are packed as bytes, larger element sizes first, so that each starts at a multiple of its own; nothing is converted, and the
+    arrays are independent copies."""
+    import numpy as np
+    import torch
+    live = sorted(((k, v) for k, v in named.items() if v is not None), key=lambda kv: -kv[1].element_size())
+    out = dict.fromkeys(named)
+    if live:
+        host, o = torch.cat([v.detach().contiguous().reshape(-1).view(torch.uint8) for _, v in live]).cpu().numpy(), 0
+        for k, v in live:
+            n = v.numel() * v.element_size()
+            out[k] = host[o:o + n].view(str(v.dtype).split(".")[1]).reshape(tuple(v.shape)).copy()
+            o += n
+    return out

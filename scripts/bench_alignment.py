@@ -87,8 +87,7 @@ def model_rows(B, runs):
         torch.cuda.synchronize()
         ev[0].record()
         with torch.enable_grad():
-            m._branches(xg, want_dist=False)
-            value = m._last_act_max[0].gather(1, protos[:, None]).sum()
+            value = m._branches(xg, want_dist=False).act_max_local.gather(1, protos[:, None]).sum()
         ev[1].record()
         if probe:
             _lib.call("ppf_gemm_probe", 1)

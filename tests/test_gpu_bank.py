@@ -192,9 +192,9 @@ def _capture(m, batches):
     rows = []
     with torch.no_grad():
         for x, y, ids in batches:
-            f, _, idx, *_ = m._branches(x, want_dist=False)
-            act_l, act_g = m._last_act_max
-            rows.append(dict(f=f.cpu(), idx=idx.cpu(), act_l=act_l.cpu(), act_g=act_g.cpu(), argmax=m._last_argmax.cpu(), y=y.cpu(), ids=ids))
+            r = m._branches(x, want_dist=False)
+            rows.append(dict(f=r.f.cpu(), idx=r.idx.cpu(), act_l=r.act_max_local.cpu(), act_g=r.act_max_global.cpu(), argmax=r.argmax.cpu(), y=y.cpu(),
+                             ids=ids))
     return {k: torch.cat([r[k] for r in rows]) for k in rows[0]}
 
 

@@ -265,8 +265,8 @@ def test_explain_on_the_default_path_equals_the_referee_on_its_own_tensors(fixtu
     assert m.training, "explain must leave the training flag as it found it"
     m.eval()
     with torch.no_grad():
-        _, _, idx, act_full, _, logits, _, _ = m._branches(x, want_dist=False)
-    (act_l, act_g), argmax = m._last_act_max, m._last_argmax
+        r = m._branches(x, want_dist=False)
+    idx, act_full, logits, act_l, act_g, argmax = r.idx, r.act_full, r.logits, r.act_max_local, r.act_max_global, r.argmax
     h = ex.cpu()
     ref_l = explain_from_outputs(act_l, m.last_layer.weight, 1.0 - coe, m.num_prototypes_per_class, logits, K, top_classes=M, argmax=argmax, idx=idx,
                                  act_full=act_full, grid_cells=m.num_patches, maps=True, device=False)

@@ -244,7 +244,7 @@ def test_class_prob_against_fp64(C):
 def forward_logits(m, imgs, bs):
     """The model's eval logits of imgs [N, 3, H, W] (host array), forwarded in consecutive sub-batches of bs images."""
     with torch.no_grad():
-        parts = [m._branches(torch.from_numpy(np.ascontiguousarray(imgs[i:i + bs])).cuda(), want_dist=False)[5] for i in range(0, len(imgs), bs)]
+        parts = [m._branches(torch.from_numpy(np.ascontiguousarray(imgs[i:i + bs])).cuda(), want_dist=False).logits for i in range(0, len(imgs), bs)]
         return torch.cat(parts).cpu().numpy()
 
 
@@ -262,7 +262,8 @@ def test_curves_equal_the_referee_pipeline(fixture):
     S = len(counts)
     assert np.array_equal(h.counts, counts) and h.classes.shape == (B, M) and (h.classes >= 0).all() and set(h.curves) == {"deletion", "insertion"}
     with torch.no_grad():
-        _, attn, idx, act_full, _, logits, _, _ = m._branches(x, want_dist=False)
+        r = m._branches(x, want_dist=False)
+    attn, idx, act_full, logits = r.cls_attn, r.idx, r.act_full, r.logits
     assert np.array_equal(h.classes[:, 0], logits.argmax(1).cpu().numpy())
     order, rank, score = cell_order_from_outputs(act_full, idx, attn, m.last_layer.weight.detach(), 1.0 - coe, h.classes, G, device=False)
     assert np.array_equal(h.order, order) and np.array_equal(h.rank, rank) and same_bits(h.score, score), f"{fixture}: the order differs from the referee"
@@ -337,7 +338,7 @@ def test_tool_on_the_miniature_cub_tree(tmp_path):
     for x, y, i in D.DeviceLoader(ds, 4, torch.device("cuda"), D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=0):
         x, i = x[:6 - seen], i[:6 - seen]
         with torch.no_grad():
-            logits = m._branches(x.float().contiguous(), want_dist=False)[5].cpu().numpy()
+            logits = m._branches(x.float().contiguous(), want_dist=False).logits.cpu().numpy()
         p, b = prob_reference(logits, logits.argmax(1))
         probs += p.tolist(); ids += torch.as_tensor(i).tolist()
         worst = max(worst, float(b.max()))

@@ -305,7 +305,7 @@ def test_input_gradient_guards_the_parameter_gradients():
     assert all(q.grad is None for q in m.parameters()) and m.training == was and x.grad is None
     with torch.no_grad():
         m.eval()
-        logits = m._branches(x, want_dist=False)[5]
+        logits = m._branches(x, want_dist=False).logits
     assert rel_err(v, logits[torch.arange(4), label.cuda()]) < TOL               # the value is the eval logit (a forward that saves for backward)
     for bad in (("logit",), ("proto", "both", label), ("logits", label), ("logit", label[:2]), ("logit", label + 1000)):
         with pytest.raises(ValueError):

@@ -187,9 +187,8 @@ def _capture(m, batches):
     rows = []
     with torch.no_grad():
         for x, y in batches:
-            _, _, idx, *_ = m._branches(x, want_dist=False)
-            act_l, act_g = m._last_act_max
-            rows.append(dict(idx=idx.cpu(), act_l=act_l.cpu(), act_g=act_g.cpu(), argmax=m._last_argmax.cpu(), y=y.cpu()))
+            r = m._branches(x, want_dist=False)
+            rows.append(dict(idx=r.idx.cpu(), act_l=r.act_max_local.cpu(), act_g=r.act_max_global.cpu(), argmax=r.argmax.cpu(), y=y.cpu()))
     return {k: torch.cat([r[k] for r in rows]).numpy() for k in rows[0]}
 
 
@@ -249,8 +248,8 @@ def test_prune():
         assert bool((before[br][:, ~k] != 0).any())
     m.eval()
     with torch.no_grad():
-        _, _, _, _, _, logits, _, _ = m._branches(x, want_dist=False)
-        act_l, act_g = m._last_act_max
+        r = m._branches(x, want_dist=False)
+        logits, act_l, act_g = r.logits, r.act_max_local, r.act_max_global
     coe = float(m.global_coe)
     wl = (before["local"] * torch.from_numpy(keep["local"]).cuda()).double().cpu()
     wg = (before["global"] * torch.from_numpy(keep["global"]).cuda()).double().cpu()
@@ -260,7 +259,7 @@ def test_prune():
     fresh = build_micro(cfg, {k: v.detach().cpu() for k, v in m.state_dict().items()})
     fresh.eval()
     with torch.no_grad():
-        _, _, _, _, _, again, _, _ = fresh._branches(x, want_dist=False)
+        again = fresh._branches(x, want_dist=False).logits
     assert torch.equal(again.view(torch.int32), logits.view(torch.int32)), "the pruned checkpoint must give bit-identical logits"
 
 

@@ -149,7 +149,7 @@ def prob_reference(logits, cls):
 def forward_logits(m, imgs, bs):
     """The model's eval logits of imgs [R, 3, H, W] (host array), forwarded in consecutive sub-batches of bs images."""
     with torch.no_grad():
-        return torch.cat([m._branches(dev(imgs[i:i + bs]), want_dist=False)[5] for i in range(0, len(imgs), bs)]).cpu().numpy()
+        return torch.cat([m._branches(dev(imgs[i:i + bs]), want_dist=False).logits for i in range(0, len(imgs), bs)]).cpu().numpy()
 
 
 @pytest.fixture(scope="module", params=["micro_deit.npz", "micro_cait.npz"])

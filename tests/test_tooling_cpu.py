@@ -1,5 +1,6 @@
-"""protopformer_amd.tooling: what the command-line tools set up alike -- the "stop after N images" iteration, and the model built from
-the training flags.  No GPU: list "loaders" and CPU construction only."""
+"""protopformer_amd.tooling: what the command-line tools set up alike -- the "stop after N images" iteration with and without image
+ids, the one host read, and the model built from the training flags; with them PPNet.eval_mode and the source rules of the forward's
+named record.  No GPU: list "loaders", CPU tensors and CPU construction only."""
 import pytest
 import torch
 
@@ -41,6 +42,101 @@ def test_regroup_over_take_images():
     passes = list(_regroup([(x[i:i + 4], None) for i in range(0, 14, 4)], 3, 10))
     assert [p.shape[0] for p in passes] == [3, 3, 3, 1]
     assert torch.equal(torch.cat(passes), x[:10]) and all(p.dtype == torch.float32 and p.is_contiguous() for p in passes)
+
+
+@pytest.mark.parametrize("width", [3, 2])
+@pytest.mark.parametrize("max_images, sizes", [(0, [4, 4, 4]), (6, [4, 2]), (3, [3])])
+def test_batches_with_ids_takes_or_counts_the_ids(width, max_images, sizes):
+    loader = _loader(width)
+    pulled = []
+
+    def counting():
+        for b in loader:
+            pulled.append(1)
+            yield b
+
+    got = list(T.batches_with_ids(counting(), max_images))
+    n = sum(sizes)
+    assert all(len(b) == 3 for b in got) and [b[0].shape[0] for b in got] == sizes and len(pulled) == len(sizes)
+    assert torch.equal(torch.cat([b[0] for b in got]), torch.arange(float(n)).reshape(n, 1))
+    assert torch.cat([b[1] for b in got]).tolist() == [10 * i for i in range(n)]                 # the last batch is cut in every element
+    ids = torch.cat([b[2] for b in got])
+    assert all(b[2].dtype == torch.int64 and b[2].shape == (b[0].shape[0],) for b in got)
+    assert ids.tolist() == [(100 if width == 3 else 0) + i for i in range(n)]                    # the loader's ids, else the running index
+
+
+def test_read_once_keeps_dtype_shape_and_bits_in_one_transfer(monkeypatch):
+    import numpy as np
+    f32 = torch.tensor([[1.5, float("nan"), -0.0], [3.0e38, -1.0e-40, 2.0]])
+    named = {"u8": torch.arange(7, dtype=torch.uint8) + 250, "f32": f32, "i64": torch.tensor([-1, 2 ** 40 + 3, -2 ** 62]), "none": None,
+             "i32": torch.tensor([-5, 4, 3, 2 ** 31 - 1, -2 ** 31], dtype=torch.int32), "f64": torch.tensor([1.0 / 3.0], dtype=torch.float64),
+             "empty": torch.zeros((0, 4)), "u8b": torch.tensor([9], dtype=torch.uint8)}
+    want = {k: None if v is None else v.numpy().copy() for k, v in named.items()}
+    calls, real = [], torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **k: calls.append(1) or real(self, *a, **k))
+    got = T.read_once(named)
+    monkeypatch.undo()
+    assert len(calls) == 1, f"{len(calls)} device-to-host transfers"
+    assert list(got) == list(named) and got["none"] is None
+    for k, w in want.items():
+        if w is not None:
+            assert isinstance(got[k], np.ndarray) and got[k].dtype == w.dtype and got[k].shape == w.shape, k
+            assert got[k].tobytes() == w.tobytes(), f"{k}: the bits changed"
+    assert got["empty"].size == 0 and np.signbit(got["f32"][0, 2]) and np.isnan(got["f32"][0, 1])
+    for k in got:                                                   # independent copies: writing one array changes no other
+        if got[k] is not None and got[k].size:
+            got[k].reshape(-1).view(np.uint8)[:] ^= 0xFF
+            assert all(got[j].tobytes() == want[j].tobytes() for j in got if j != k and want[j] is not None)
+            got[k].reshape(-1).view(np.uint8)[:] ^= 0xFF
+    assert T.read_once({"a": None}) == {"a": None}
+
+
+def test_eval_mode_restores_the_mode_it_found():
+    from protopformer_amd.protopformer import PPNet
+
+    class Net(torch.nn.Module):
+        eval_mode = PPNet.eval_mode
+
+        def __init__(self):
+            super().__init__()
+            self.drop = torch.nn.Dropout(0.5)
+
+    m = Net()
+    for start in (True, False):
+        m.train(start)
+        with m.eval_mode() as inside:
+            assert inside is m and not m.training and not m.drop.training
+        assert m.training is start and m.drop.training is start
+        with pytest.raises(KeyError):
+            with m.eval_mode():
+                assert not m.training
+                raise KeyError("body")
+        assert m.training is start and m.drop.training is start
+
+
+def test_forward_outputs_travel_by_name_not_by_side_channel():
+    """The source rules of the record: no stashed activations, one assignment of the test-facing arg-max and no reader outside tests/, one
+    place that switches the training flag by hand, no indexing of _branches by number."""
+    import glob
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = sorted(glob.glob(os.path.join(root, "protopformer_amd", "*.py")) + glob.glob(os.path.join(root, "scripts", "**", "*.py"), recursive=True))
+    assert len(files) > 20
+    argmax, switching = [], set()
+    for path in files:
+        with open(path) as f:
+            text = f.read()
+        assert "_last_act_max" not in text, path
+        assert not re.search(r"_branches\([^)]*\)\s*\[", text), path
+        func = None
+        for line in text.splitlines():
+            func = (re.match(r"\s*def (\w+)", line) or [None, func])[1]
+            argmax += [(path, line)] * line.count("_last_argmax")
+            if "was_training" in line:
+                switching.add((os.path.basename(path), func))
+    assert len(argmax) == 1 and re.search(r"self\._last_argmax = ", argmax[0][1]) and argmax[0][0].endswith("protopformer.py"), argmax
+    assert switching == {("protopformer.py", "eval_mode")}, switching
 
 
 def _args(*argv):
