@@ -411,6 +411,68 @@ int ppf_rise_apply(const float* x, const void* nodes_u8, const int* shift, int N
                    int B, int Cc, int H, int W, float* out, ppf_stream_t stream);
 int ppf_rise_accumulate(const void* nodes_u8, const int* shift, const float* prob, int B, int N, int M, int s, int thr, int H, int W, int G, float* sal,
                         float* cell, ppf_stream_t stream);
+/* "This looks like that, because ..." (csrc/because.hip; Nauta et al., 2021): suppress one visual characteristic of an image -- hue,
+ * saturation, contrast, texture or shape --, run the model again and read the prototype's similarity at the same grid cell; the forwards
+ * in between are the caller's.  The reference has no such pass.  Additions of ABI 10: no existing entry point changed.
+ * The arithmetic is the contract the numpy referees (interpret.color_affine, gray_sum, contrast_offset, bilateral, warp_nodes_from_ids,
+ * warp_apply, because_score) keep bit for bit: plain fp32, fl() = one rounding to nearest, nothing fused or reassociated, every
+ * division correctly rounded, no transcendental function on the device.
+ *   images    x, out fp32 [B][3][H][W], normalised; mean3 / std3 / matrix9 / ws / wr256 are HOST pointers (as ppf_image_finish_u8's).
+ *             B <= 65535, H * W <= 2^22.  16-byte accesses when W % 4 == 0 and the pointers are 16-byte aligned, scalar ones otherwise:
+ *             the values do not depend on it (ppf_warp_apply is a gather: one pixel per lane either way; the bilateral filter reads
+ *             through LDS).
+ *   pixel     v_c = clamp(fl(fl(x_c * std_c) + mean_c)); clamp(v) = v > 0 ? (v < 1 ? v : 1) : 0, so NaN becomes 0.  A result u_c is
+ *             written as fl(fl(clamp(u_c) - mean_c) / std_c).
+ *   luma      y = fl(fl(fl(0.299 r) + fl(0.587 g)) + fl(0.114 b)) of the clamped (r, g, b) = v; q8 = min(max((int)floor(fl(fl(255 y) +
+ *             0.5)), 0), 255).
+ *   ppf_color_affine     u_k = fl(fl(fl(fl(M[k][0] r) + fl(M[k][1] g)) + fl(M[k][2] b)) + offset[b][k]), matrix9 = M row-major; offset
+ *                        fp32 [B][3] on the device, or NULL: that addition is left out.  Saturation f: M = f I + (1 - f) [w; w; w] with
+ *                        w = (0.299, 0.587, 0.114); hue: M = T^-1 R(theta) T with T = RGB -> YIQ; contrast f: M = f I and
+ *                        offset[b][k] = (1 - f) * the image's mean luma (below); each formed in fp64 by the host, rounded once.
+ *   ppf_gray_sum         sum int32 [B] = the integer sum of q8 over the image's pixels (zeroed by the call; integer atomics: exact and
+ *                        the same at any launch shape; 255 * H * W < 2^31).
+ *   ppf_contrast_offset  offset[b][k] = fl(one_minus_f * fl(fl((float)sum[b] / (float)(H * W)) / 255)) for k = 0 .. 2, on the device: no
+ *                        host read between the sum and the colour transform.
+ *   ppf_bilateral        joint bilateral filter of window radius r, 1 <= r <= 8, guided by q8: for pixel p, over the taps q = p + (dy,
+ *                        dx) in row-major window order (dy outer, both ascending from -r), taps outside the image skipped:
+ *                          w = fl(ws[dy + r][dx + r] * wr256[|q8(p) - q8(q)|]);  sw = fl(sw + w);  s_k = fl(s_k + fl(w * v_k(q)))
+ *                        from sw = s_k = 0, the same w for the three channels; u_k = fl(s_k / sw).  ws: (2r + 1)^2 spatial weights,
+ *                        wr256: 256 range weights, all finite and >= 0 (Gaussians, computed by the caller in fp64 and rounded).  sw = 0
+ *                        gives 0 / 0 = NaN, which the clamp writes as 0.  out != x.  One workgroup stages a 32 x 16 tile and its halo in
+ *                        LDS once (dynamic LDS <= 30 KiB).
+ *   ppf_warp_nodes       nodes int32 [B][(s + 1)^2][2] = (dy, dx) of node q = i * (s + 1) + j in units of 1 / 256 pixel, uniform in
+ *                        [-amp256, amp256]: d = (((word >> 8) * (2 amp256 + 1)) >> 24) - amp256 with word = .x (dy) / .y (dx) of
+ *                        Philox4x32-10, key = seed, counter = (q, 0x80000000, image id low, image id high) -- disjoint from the random
+ *                        cell order (word 1 = 0) and the RISE masks (word 1 = 1 + n < 2^31).  A function of (seed, image id, node) alone.
+ *                        1 <= s <= 16, 0 <= amp256 <= 2^15.
+ *   ppf_warp_apply       out fp32 [B][Cc][H][W] from x of the same shape (any normalisation: the blend is linear) and the node table;
+ *                        H == W, node spacing c = ceil(H / s) <= 2048, c^2 * amp256 <= 2^31 - 1.  Pixel (y, x): i = y / c, ry = y % c,
+ *                        j = x / c, rx = x % c; K = ((c-ry)(c-rx), (c-ry) rx, ry (c-rx), ry rx) on nodes (i, j), (i, j+1), (i+1, j),
+ *                        (i+1, j+1) (sum c^2); displacement d = floor(sum K_n d_n / c^2) per axis, in int32 (node values are clamped
+ *                        into [-amp256, amp256] first).  Y = min(max(256 y + dy, 0), 256 (H - 1)), likewise X; (sy, sx) = (Y >> 8,
+ *                        X >> 8), (fy, fx) = (Y & 255, X & 255), sy1 = min(sy + 1, H - 1), sx1 likewise; a = fx / 256, e = fy / 256 (exact):
+ *                          top = fx ? fl(fl((1 - a) * x[sy][sx]) + fl(a * x[sy][sx1])) : x[sy][sx]
+ *                          bot = fx ? fl(fl((1 - a) * x[sy1][sx]) + fl(a * x[sy1][sx1])) : x[sy1][sx]
+ *                          out = fy ? fl(fl((1 - e) * top) + fl(e * bot)) : top
+ *                        so amplitude 0 copies x bit for bit.  out != x.
+ *   ppf_because_score    row (b, k), one wave each, of protos int32 [B][K] and cells int32 [B][K] (the clean forward's cell of the
+ *                        prototype) against a PERTURBED forward's act_full [B][P][T], idx int32 [B][T] and act_max [B][P]:
+ *                          best[b][k] = act_max[b][p];  same[b][k] = act_full[b][p][t] for the smallest t with idx[b][t] == cell and
+ *                          lost[b][k] = 0;  no such t (the perturbed image no longer reserves the cell; cell outside [0, G), so an idx
+ *                          entry outside the grid never matches): same = 0 -- the zero interpret.expand_to_grid puts there -- and lost = 1.
+ *                        A NaN activation is written as it is.  p outside [0, P): best = NaN, same = 0, lost = 1, nothing read.
+ *                        idx == NULL: the global / cls branch, which has no cells: only best is written (act_full, cells, same, lost
+ *                        may be NULL).  same, best fp32 and lost int32 [B][K]. */
+int ppf_color_affine(const float* x, const float* matrix9, const float* offset, const float* mean3, const float* std3, int B, int H, int W, float* out,
+                     ppf_stream_t stream);
+int ppf_gray_sum(const float* x, const float* mean3, const float* std3, int B, int H, int W, int* sum, ppf_stream_t stream);
+int ppf_contrast_offset(const int* gray_sum, int B, int H, int W, float one_minus_f, float* offset, ppf_stream_t stream);
+int ppf_bilateral(const float* x, const float* ws, const float* wr256, int r, const float* mean3, const float* std3, int B, int H, int W, float* out,
+                  ppf_stream_t stream);
+int ppf_warp_nodes(const void* image_id_i64, uint64_t seed, int B, int s, int amp256, int* nodes, ppf_stream_t stream);
+int ppf_warp_apply(const float* x, const int* nodes, int s, int amp256, int B, int Cc, int H, int W, float* out, ppf_stream_t stream);
+int ppf_because_score(const float* act_full, const int* idx, const float* act_max, const int* protos, const int* cells, int B, int P, int T, int G, int K,
+                      float* same, float* best, int* lost, ppf_stream_t stream);
 /* Spatial alignment of prototypes (csrc/alignment.hip): the image gradient's last step and the two kernels of the misalignment test
  * (Sacha et al., AAAI 2024): perturb only the pixels outside a prototype's box, follow its activation and its peak, and report the share
  * of the pixel gradient inside the box; the forwards and backwards in between are the caller's.  The reference has no such pass.

@@ -999,7 +999,7 @@ def _eval_outputs(ppnet, x):
     """One eval forward: what the cell orders and the class pick need, all on the device."""
     r = ppnet.eval_branches(x)
     return dict(token_attn=r.cls_attn.reshape(x.shape[0], -1).float().contiguous(), idx=r.idx.contiguous(), act_full=r.act_full.contiguous(),
-                logits=r.logits.contiguous(), act_max=r.act_max_local)
+                logits=r.logits.contiguous(), act_max=r.act_max_local, act_max_global=r.act_max_global, argmax=r.argmax)
 
 
 def _image_ids(image_ids, B, device):
@@ -1613,4 +1613,491 @@ def spatial_alignment(ppnet, loader, protos_per_image=3, half_size=36, attack=Tr
         raise ValueError("spatial_alignment: the loader gave no image")
     out = alignment_summary(torch.cat(ids), torch.cat(stats))
     out["images"] = images
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ "this looks like that, because ...": colour, texture or shape?
+# Two patches a human finds alike can be far apart for the model, and the reverse; an overlay does not show which.  Nauta et al., "This
+# Looks Like That, Because ... Explaining Prototypes for Interpretable Image Recognition" (2021), answer by perturbation: suppress one
+# visual characteristic of the image -- hue, saturation, contrast, texture or shape --, run the model again, and measure how far the
+# prototype's similarity at the same patch falls.  That is a local importance per (image, prototype, characteristic); weighted over a
+# prototype's own-class images it is a global one per prototype.  Hue, saturation and contrast are one 3 x 3 colour transform
+# (ppf_color_affine; contrast pivots on the image's mean luma, ppf_gray_sum + ppf_contrast_offset), texture is a joint bilateral filter
+# guided by the 8-bit luma (ppf_bilateral: edge-preserving, so contours survive), shape a smooth integer warp (ppf_warp_nodes,
+# ppf_warp_apply); ppf_because_score reads the perturbed forward (csrc/because.hip).  The arithmetic is a written contract
+# (include/ppf_hip.h): the numpy forms below (device=False) are the referees, bit for bit.  The reference has no such pass.
+CHARACTERISTICS = ("hue", "saturation", "contrast", "texture", "shape")
+LUMA_WEIGHTS = (0.299, 0.587, 0.114)
+_RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.5959, -0.2746, -0.3213), (0.2115, -0.5227, 0.3112))
+# The strengths are choices, not tuned values: nobody has run this on a trained checkpoint.  hue: the turn of the IQ plane as a fraction
+# of a full turn; saturation / contrast: the factor that is left (0 = none); texture: window radius and the two Gaussian widths (pixels;
+# 8-bit luma steps); shape: grid cells per side and the largest node displacement in pixels.
+BECAUSE_DEFAULTS = dict(hue=0.5, saturation=0.0, contrast=0.25, radius=4, sigma_space=3.0, sigma_range=25.0, cells=4, amplitude=6.0, mean=None, std=None)
+
+
+def because_params(params=None):
+    """BECAUSE_DEFAULTS overridden by `params`, checked; mean / std default to the data set's normalisation (ImageNet's)."""
+    from .data import IMAGENET_DEFAULT_MEAN, IMAGENET_DEFAULT_STD
+    unknown = set(params or {}) - set(BECAUSE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"because: unknown parameters {sorted(unknown)} (known: {sorted(BECAUSE_DEFAULTS)})")
+    p = {**BECAUSE_DEFAULTS, **(params or {})}
+    p["mean"] = np.asarray(IMAGENET_DEFAULT_MEAN if p["mean"] is None else p["mean"], dtype=np.float32).reshape(3)
+    p["std"] = np.asarray(IMAGENET_DEFAULT_STD if p["std"] is None else p["std"], dtype=np.float32).reshape(3)
+    p["radius"], p["cells"] = int(p["radius"]), int(p["cells"])
+    if not 1 <= p["radius"] <= 8 or not 1 <= p["cells"] <= 16:
+        raise ValueError(f"because: radius={p['radius']} outside [1, 8] or cells={p['cells']} outside [1, 16]")
+    if not (p["sigma_space"] > 0 and p["sigma_range"] > 0 and 0 <= p["amplitude"] <= 128 and (p["std"] > 0).all()):
+        raise ValueError("because: sigma_space and sigma_range must be > 0, amplitude in [0, 128] pixels, std > 0")
+    return p
+
+
+def saturation_matrix(f):
+    """fp32 [3, 3]: f I + (1 - f) [w; w; w], formed in fp64 and rounded once.  f = 0: three equal rows, the grey image."""
+    return (float(f) * np.eye(3) + (1.0 - float(f)) * np.tile(np.asarray(LUMA_WEIGHTS, dtype=np.float64), (3, 1))).astype(np.float32)
+
+
+def hue_matrix(theta):
+    """fp32 [3, 3]: T^-1 R(theta) T with T = RGB -> YIQ and R the rotation of the IQ plane, formed in fp64 and rounded once.  The first
+    row of T is the luma, which the turn keeps; colours that leave [0, 1] are clamped by the transform."""
+    t = np.asarray(_RGB_TO_YIQ, dtype=np.float64)
+    c, s = np.cos(float(theta)), np.sin(float(theta))
+    return (np.linalg.inv(t) @ np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]]) @ t).astype(np.float32)
+
+
+def contrast_matrix(f):
+    """fp32 [3, 3]: f I; the pivot (1 - f) * mean luma is the per-image offset (contrast_offset)."""
+    return (float(f) * np.eye(3)).astype(np.float32)
+
+
+def bilateral_tables(radius, sigma_space, sigma_range):
+    """(ws fp32 [(2r + 1), (2r + 1)], wr fp32 [256]): exp(-(dy^2 + dx^2) / (2 sigma_space^2)) and exp(-d^2 / (2 sigma_range^2)) over the
+    8-bit luma difference d, in fp64, rounded once."""
+    r = int(radius)
+    d = np.arange(-r, r + 1, dtype=np.float64)
+    ws = np.exp(-(d[:, None] ** 2 + d[None, :] ** 2) / (2.0 * float(sigma_space) ** 2))
+    wr = np.exp(-np.arange(256, dtype=np.float64) ** 2 / (2.0 * float(sigma_range) ** 2))
+    return ws.astype(np.float32), wr.astype(np.float32)
+
+
+def _norm3(mean, std):
+    return np.asarray(mean, dtype=np.float32).reshape(1, 3, 1, 1), np.asarray(std, dtype=np.float32).reshape(1, 3, 1, 1)
+
+
+def _clamp01(v):
+    return np.where(v > 0, np.where(v < 1, v, np.float32(1)), np.float32(0)).astype(np.float32)       # NaN -> 0, as the kernels
+
+
+def _denorm(x, mean, std):
+    """clamp(fl(fl(x * std) + mean)): the de-normalised pixel of the contract."""
+    m, s = _norm3(mean, std)
+    with np.errstate(all="ignore"):
+        return _clamp01((_host(x, np.float32) * s).astype(np.float32) + m)
+
+
+def _renorm(u, mean, std):
+    m, s = _norm3(mean, std)
+    with np.errstate(all="ignore"):
+        return ((_clamp01(u) - m).astype(np.float32) / s).astype(np.float32)
+
+
+def _luma_q8(v):
+    """int32 [B, H, W]: the 8-bit luma of clamped pixels v [B, 3, H, W], operation for operation as the contract."""
+    w = [np.float32(a) for a in LUMA_WEIGHTS]
+    y = ((w[0] * v[:, 0]).astype(np.float32) + (w[1] * v[:, 1]).astype(np.float32)).astype(np.float32) + (w[2] * v[:, 2]).astype(np.float32)
+    q = np.floor((np.float32(255) * y).astype(np.float32) + np.float32(0.5)).astype(np.int32)
+    return np.clip(q, 0, 255)
+
+
+def color_affine(x, matrix, mean, std, offset=None, device=True, out=None):
+    """The 3 x 3 colour transform of x [B, 3, H, W] in de-normalised space (the contract is ppf_color_affine's, include/ppf_hip.h): matrix
+    [3, 3] on the host, offset [B, 3] optional.  device=True: one launch on CUDA tensors; device=False: the numpy referee."""
+    if device:
+        from . import ops
+        return ops.color_affine(x, matrix, mean, std, offset, out)
+    v, M = _denorm(x, mean, std), np.asarray(matrix, dtype=np.float32).reshape(3, 3)
+    with np.errstate(all="ignore"):
+        u = np.stack([((M[k, 0] * v[:, 0]).astype(np.float32) + (M[k, 1] * v[:, 1]).astype(np.float32)).astype(np.float32)
+                      + (M[k, 2] * v[:, 2]).astype(np.float32) for k in range(3)], axis=1).astype(np.float32)
+        if offset is not None:
+            u = (u + _host(offset, np.float32).reshape(-1, 3, 1, 1)).astype(np.float32)
+    return _renorm(u, mean, std)
+
+
+def gray_sum(x, mean, std, device=True):
+    """int32 [B]: the integer sum of the 8-bit luma over each image (ppf_gray_sum)."""
+    if device:
+        from . import ops
+        return ops.gray_sum(x, mean, std)
+    return _luma_q8(_denorm(x, mean, std)).sum(axis=(1, 2), dtype=np.int64).astype(np.int32)
+
+
+def contrast_offset(total, size, f, device=True):
+    """fp32 [B, 3]: fl(fl32(1 - f) * fl(fl(sum / (H W)) / 255)) in every channel, from gray_sum's sums (ppf_contrast_offset); size = (H, W).
+    1 - f is formed in fp64 and rounded once."""
+    g = np.float32(1.0 - float(f))
+    if device:
+        from . import ops
+        return ops.contrast_offset(total, size, float(g))
+    m = (_host(total, np.int32).astype(np.float32) / np.float32(int(size[0]) * int(size[1]))).astype(np.float32) / np.float32(255)
+    return np.repeat((g * m.astype(np.float32)).astype(np.float32)[:, None], 3, axis=1)
+
+
+def bilateral(x, ws, wr, mean, std, device=True, out=None):
+    """The joint bilateral filter of x [B, 3, H, W] guided by the 8-bit luma (the contract is ppf_bilateral's): ws [(2r + 1), (2r + 1)]
+    spatial and wr [256] range weights; taps in row-major window order, those outside the image skipped.  device=False: numpy."""
+    ws = np.asarray(ws, dtype=np.float32)
+    D = int(round(ws.size ** 0.5))
+    r = (D - 1) // 2
+    if D * D != ws.size or D != 2 * r + 1 or not 1 <= r <= 8:
+        raise ValueError(f"bilateral: ws must hold (2r + 1)^2 weights with 1 <= r <= 8, got {ws.size}")
+    ws, wr = ws.reshape(D, D), np.asarray(wr, dtype=np.float32).reshape(256)
+    if device:
+        from . import ops
+        return ops.bilateral(x, ws, wr, r, mean, std, out)
+    v = _denorm(x, mean, std)
+    B, _, H, W = v.shape
+    q = _luma_q8(v)
+    vp = np.pad(v, ((0, 0), (0, 0), (r, r), (r, r)))
+    qp = np.pad(q, ((0, 0), (r, r), (r, r)), constant_values=-1)
+    sw, s = np.zeros((B, 1, H, W), dtype=np.float32), np.zeros((B, 3, H, W), dtype=np.float32)
+    for dy in range(D):
+        for dx in range(D):
+            qq = qp[:, dy:dy + H, dx:dx + W]
+            w = np.where(qq >= 0, (ws[dy, dx] * wr[np.minimum(np.abs(q - qq), 255)]).astype(np.float32), np.float32(0))[:, None]
+            sw = (sw + w).astype(np.float32)                      # a skipped tap adds an exact zero to both sums
+            s = (s + (w * vp[:, :, dy:dy + H, dx:dx + W]).astype(np.float32)).astype(np.float32)
+    with np.errstate(all="ignore"):
+        return _renorm((s / sw).astype(np.float32), mean, std)
+
+
+def _warp_sizes(size, cells, amp256):
+    H, s, A = int(size), int(cells), int(amp256)
+    c = -(-H // max(s, 1))
+    if not 1 <= s <= 16 or not 0 <= A <= 1 << 15 or H < 1 or c > 2048 or c * c * max(A, 1) > 2 ** 31 - 1:
+        raise ValueError(f"warp: cells={s} outside [1, 16], amplitude {A}/256 outside [0, 2^15/256] or c={c}: c <= 2048, c^2 * amplitude <= 2^31 - 1")
+    return H, s, c, A
+
+
+def warp_amplitude(pixels):
+    """The node amplitude in 1/256 pixel units."""
+    return int(round(float(pixels) * 256))
+
+
+def warp_nodes_from_ids(image_ids, cells, amp256, seed=0, device=True):
+    """int32 [B, (cells + 1)^2, 2]: the displacements (dy, dx) of the warp's nodes in 1/256 pixel, uniform in [-amp256, amp256]: a function
+    of (seed, image id, node) alone (ppf_warp_nodes).  device=False: the numpy Philox."""
+    s, A = int(cells), int(amp256)
+    if not 1 <= s <= 16 or not 0 <= A <= 1 << 15:
+        raise ValueError(f"warp: cells={s} outside [1, 16] or amplitude {A}/256 outside [0, 2^15/256]")
+    if device:
+        from . import ops
+        ids = torch.as_tensor(image_ids)
+        return ops.warp_nodes(ids.to(device=ids.device if ids.is_cuda else "cuda", dtype=torch.int64).contiguous(), s, A, seed)
+    ids = _host(image_ids, np.int64).reshape(-1).astype(np.uint64)
+    B, Q, sd = ids.shape[0], (s + 1) ** 2, int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((B, Q, 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1] = np.arange(Q, dtype=np.uint64)[None, :], np.uint64(0x80000000)
+    ctr[..., 2], ctr[..., 3] = (ids & np.uint64(0xFFFFFFFF))[:, None], (ids >> np.uint64(32))[:, None]
+    w = (philox4x32_10(ctr, np.array([sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint64))[..., :2] >> np.uint32(8)).astype(np.uint64)
+    return (((w * np.uint64(2 * A + 1)) >> np.uint64(24)).astype(np.int64) - A).astype(np.int32)
+
+
+def warp_apply(x, nodes, cells, amp256, device=True, out=None):
+    """x [B, Cc, H, H] resampled under the smooth integer warp of the node table (the contract is ppf_warp_apply's): the displacement of a
+    pixel is the bilinear interpolation of its four nodes in integers, the blend has weights n / 256 and skips zero weights, so amplitude
+    0 is the identity bit for bit.  device=False: numpy."""
+    if device:
+        from . import ops
+        return ops.warp_apply(x, nodes, cells, amp256, out)
+    x, nd = _host(x, np.float32), _host(nodes, np.int64)
+    B, Cc, H, W = x.shape
+    if H != W:
+        raise ValueError(f"warp_apply: H={H} W={W}: square images only")
+    H, s, c, A = _warp_sizes(H, cells, amp256)
+    L = s + 1
+    nd = np.clip(nd.reshape(B, L, L, 2), -A, A)
+    p = np.arange(H)
+    i, ry = p // c, p % c
+    I, J, RY, RX = i[:, None], i[None, :], ry[:, None], ry[None, :]
+    D = ((c - RY) * (c - RX))[None, :, :, None] * nd[:, I, J] + ((c - RY) * RX)[None, :, :, None] * nd[:, I, J + 1] \
+        + (RY * (c - RX))[None, :, :, None] * nd[:, I + 1, J] + (RY * RX)[None, :, :, None] * nd[:, I + 1, J + 1]
+    d = D // (c * c)                                                                              # floor division, [B, H, W, 2]
+    Y = np.clip(256 * p[None, :, None] + d[..., 0], 0, 256 * (H - 1))
+    X = np.clip(256 * p[None, None, :] + d[..., 1], 0, 256 * (W - 1))
+    sy, fy, sx, fx = Y >> 8, Y & 255, X >> 8, X & 255
+    sy1, sx1 = np.minimum(sy + 1, H - 1), np.minimum(sx + 1, W - 1)
+    bi = np.arange(B)[:, None, None, None]
+    ci = np.arange(Cc)[None, :, None, None]
+    g = lambda yy, xx: x[bi, ci, yy[:, None], xx[:, None]]
+    a, e = (fx.astype(np.float32) / np.float32(256))[:, None], (fy.astype(np.float32) / np.float32(256))[:, None]
+    one = np.float32(1)
+    with np.errstate(all="ignore"):
+        mix = lambda w, lo, hi: ((one - w) * lo).astype(np.float32) + (w * hi).astype(np.float32)
+        top = np.where(fx[:, None] != 0, mix(a, g(sy, sx), g(sy, sx1)), g(sy, sx))
+        bot = np.where(fx[:, None] != 0, mix(a, g(sy1, sx), g(sy1, sx1)), g(sy1, sx))
+        return np.where(fy[:, None] != 0, mix(e, top, bot), top).astype(np.float32)
+
+
+def because_score(act_max, protos, grid_cells=0, act_full=None, idx=None, cells=None, device=True):
+    """(same, best fp32 [B, K], lost int32 [B, K]) of a perturbed forward for the rows protos / cells [B, K] (the contract is
+    ppf_because_score's): same = the prototype's activation at the clean forward's cell, 0 with lost = 1 when the perturbed image no
+    longer reserves it; best = its pooled activation wherever it is.  idx None: the global branch, (None, best, None)."""
+    if device:
+        from . import ops
+        return ops.because_score(act_max, protos, grid_cells, act_full=act_full, idx=idx, cells=cells)
+    am, pr = _host(act_max, np.float32), _host(protos, np.int64)
+    (B, P), K = am.shape, pr.shape[1]
+    ok = (pr >= 0) & (pr < P)
+    best = np.where(ok, am[np.arange(B)[:, None], np.where(ok, pr, 0)], np.float32(np.nan)).astype(np.float32)
+    if idx is None:
+        return None, best, None
+    ix, ce = _host(idx, np.int64), _host(cells, np.int64)
+    T, G = ix.shape[1], int(grid_cells)
+    af = _host(act_full, np.float32).reshape(B, P, T)
+    same, lost = np.zeros((B, K), dtype=np.float32), np.ones((B, K), dtype=np.int32)
+    for b in range(B):
+        for k in range(K):
+            if ok[b, k] and 0 <= ce[b, k] < G:
+                t = np.flatnonzero(ix[b] == ce[b, k])
+                if t.size:
+                    same[b, k], lost[b, k] = af[b, pr[b, k], t[0]], 0
+    return same, best, lost
+
+
+def because_perturb(x, characteristic, params=None, seed=0, image_ids=None, device=True, out=None):
+    """The image batch x [B, 3, H, W] with one characteristic suppressed at the strengths of because_params(params): 'hue', 'saturation'
+    or 'contrast' (one colour transform; contrast after the luma sum and its offset), 'texture' (the bilateral filter) or 'shape' (the
+    warp, keyed by seed and image_ids, None: 0 .. B-1).  device=True: launches only, into `out` when given; device=False: numpy."""
+    p = because_params(params)
+    mean, std = p["mean"], p["std"]
+    B, H = x.shape[0], x.shape[2]
+    if characteristic == "hue":
+        return color_affine(x, hue_matrix(2.0 * np.pi * float(p["hue"])), mean, std, device=device, out=out)
+    if characteristic == "saturation":
+        return color_affine(x, saturation_matrix(p["saturation"]), mean, std, device=device, out=out)
+    if characteristic == "contrast":
+        off = contrast_offset(gray_sum(x, mean, std, device=device), x.shape[2:], p["contrast"], device=device)
+        return color_affine(x, contrast_matrix(p["contrast"]), mean, std, offset=off, device=device, out=out)
+    if characteristic == "texture":
+        ws, wr = bilateral_tables(p["radius"], p["sigma_space"], p["sigma_range"])
+        return bilateral(x, ws, wr, mean, std, device=device, out=out)
+    if characteristic == "shape":
+        A = warp_amplitude(p["amplitude"])
+        _warp_sizes(H, p["cells"], A)
+        ids = _image_ids(image_ids, B, x.device) if device else (np.arange(B, dtype=np.int64) if image_ids is None else _host(image_ids, np.int64))
+        return warp_apply(x, warp_nodes_from_ids(ids, p["cells"], A, seed, device=device), p["cells"], A, device=device, out=out)
+    raise ValueError(f"because: characteristics must come from {CHARACTERISTICS}, got {characteristic!r}")
+
+
+class Because:
+    """What because returns, as device tensors (numpy arrays after cpu()): protos int32 [B, K]; base fp32 [B, K] the clean pooled
+    activation of each prototype; cell int32 [B, K] the grid cell it was found at (-1 on the global branch); per characteristic n:
+    same fp32 [n, B, K] its activation at that cell after the perturbation (0 where lost), best fp32 [n, B, K] its pooled activation
+    wherever it is, lost int32 [n, B, K] = 1 where the perturbed image no longer reserves the cell.  On the global branch same and lost
+    are None."""
+    FIELDS = ("base", "cell", "same", "best", "lost", "protos")
+
+    def __init__(self, base, cell, same, best, lost, protos, characteristics, branch):
+        self.base, self.cell, self.same, self.best, self.lost, self.protos = base, cell, same, best, lost, protos
+        self.characteristics, self.branch = tuple(characteristics), branch
+
+    @property
+    def on_host(self):
+        return not isinstance(self.base, torch.Tensor)
+
+    def local(self):
+        """The local importance [n, B, K] = base - same: how far the similarity at the same patch fell (best on the global branch)."""
+        return self.base[None] - (self.best if self.same is None else self.same)
+
+    def cpu(self):
+        """The same object with numpy arrays: every field in ONE host read."""
+        if self.on_host:
+            return self
+        return Because(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.characteristics, self.branch)
+
+    def report(self, index):
+        """The JSON records of image `index`: per prototype its id, cell, clean activation and per characteristic the local importance,
+        the location-free one (base - best) and whether the cell was lost."""
+        h = self.cpu()
+        loc = h.local()
+        out = []
+        for k in range(h.protos.shape[1]):
+            per = {}
+            for n, name in enumerate(h.characteristics):
+                per[name] = dict(importance=float(loc[n, index, k]), importance_best=float(h.base[index, k] - h.best[n, index, k]),
+                                 lost=None if h.lost is None else bool(h.lost[n, index, k]))
+            out.append(dict(prototype=int(h.protos[index, k]), cell=int(h.cell[index, k]), activation=float(h.base[index, k]), characteristics=per))
+        return out
+
+
+def _because_forward(ppnet, imgs, batch_size):
+    """The model's eval forward over imgs in sub-batches of batch_size images: (act_full [R, P, T], idx [R, T], act_max local [R, P],
+    act_max global [R, Pg]) on the device.  The caller holds eval mode and no_grad."""
+    rs = [ppnet._branches(imgs[i:i + batch_size], want_dist=False) for i in range(0, imgs.shape[0], batch_size)]
+    cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
+    return (cat([r.act_full.reshape(r.act_max_local.shape[0], r.act_max_local.shape[1], -1) for r in rs]).contiguous(),
+            cat([r.idx for r in rs]).contiguous(), cat([r.act_max_local for r in rs]).contiguous(), cat([r.act_max_global for r in rs]).contiguous())
+
+
+def _because_rows(ppnet, outs, protos, branch, B, device):
+    """(protos int32 [B, K], base fp32 [B, K], cell int32 [B, K]) of the clean forward; protos None: the predicted class's."""
+    local = branch == "local"
+    act = outs["act_max"] if local else outs["act_max_global"]
+    ppc = int(ppnet.num_prototypes_per_class) if local else act.shape[1] // outs["logits"].shape[1]
+    if protos is None:
+        protos = (outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=device)[None, :]).to(torch.int32).contiguous()
+    else:
+        t = protos if isinstance(protos, torch.Tensor) and protos.is_cuda else torch.as_tensor(np.asarray(protos)).to(device)
+        if t.is_floating_point() or t.dim() not in (1, 2) or t.shape[0] != B:
+            raise ValueError(f"because: protos must be integers [B] or [B, K] for a batch of {B}, got {tuple(t.shape)} {t.dtype}")
+        protos = (t[:, None] if t.dim() == 1 else t).to(torch.int32).contiguous()
+    valid = (protos >= 0) & (protos < act.shape[1])               # an id outside the branch: NaN rows, nothing read (as the score kernel)
+    protos_in = protos.long().clamp(0, act.shape[1] - 1)
+    base = torch.where(valid, act.detach().gather(1, protos_in), torch.full_like(act[:, :1], float("nan")).expand(protos.shape)).contiguous()
+    if not local:
+        return protos, base, torch.full_like(protos, -1)
+    idx = outs["idx"]
+    tok = outs["argmax"].gather(1, protos_in).long() if outs["argmax"] is not None else torch.zeros_like(protos, dtype=torch.int64)
+    ok = valid & (tok >= 0) & (tok < idx.shape[1])
+    cell = torch.where(ok, idx.gather(1, tok.clamp(0, idx.shape[1] - 1)), torch.full_like(protos, -1)).to(torch.int32).contiguous()
+    return protos, base, cell
+
+
+@torch.no_grad()
+def because(ppnet, x, protos=None, branch="local", characteristics=CHARACTERISTICS, params=None, seed=0, image_ids=None, batch_size=None,
+            scratch_bytes=1 << 30):
+    """Why does this patch look like that prototype: its hue, saturation, contrast, texture or shape?  For a batch x [B, 3, H, W] (CUDA)
+    one eval forward; then per characteristic the perturbed images are written into ONE scratch buffer (as many images at a time as
+    scratch_bytes holds, one at least), the model runs over them in sub-batches of batch_size images (default B), and one
+    ppf_because_score launch reads the prototype's activation at the clean forward's cell.  No perturbed image and no activation map
+    passes through the host.  protos: int [B] or [B, K], None: the prototypes of the predicted class; branch 'local' or 'global' (no
+    cells: the pooled activation only); params: overrides of BECAUSE_DEFAULTS; seed, image_ids [B] (None: 0 .. B-1) key the warp, so an
+    image warps the same way in every batch.  Returns a Because (device tensors; nothing is read back here)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError("because needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path; color_affine / bilateral / warp_apply / because_score "
+                           "with device=False are the host referees)")
+    if branch not in EXPLAIN_BRANCHES:
+        raise ValueError(f"because: branch must be one of {EXPLAIN_BRANCHES}, got {branch!r}")
+    names = tuple(characteristics)
+    if not names or any(n not in CHARACTERISTICS for n in names):
+        raise ValueError(f"because: characteristics must come from {CHARACTERISTICS}, got {names}")
+    from . import ops
+    p = because_params(params)
+    x = x.float().contiguous()
+    B, G = x.shape[0], int(ppnet.num_patches)
+    outs = _eval_outputs(ppnet, x)
+    protos, base, cell = _because_rows(ppnet, outs, protos, branch, B, x.device)
+    ids = _image_ids(image_ids, B, x.device)
+    chunk = _chunk_items(B, scratch_bytes, x[0].numel() * 4)
+    buf = torch.empty((chunk,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    same, best, lost = [], [], []
+    with ppnet.eval_mode():
+        for name in names:
+            parts = []
+            for i in range(0, B, chunk):
+                n = min(chunk, B - i)
+                imgs = because_perturb(x[i:i + n], name, p, seed, ids[i:i + n], out=buf[:n])
+                parts.append(_because_forward(ppnet, imgs, int(batch_size or B)))
+            act_full, idx, act_l, act_g = (parts[0][j] if len(parts) == 1 else torch.cat([q[j] for q in parts]) for j in range(4))
+            if branch == "local":
+                s, b, l = ops.because_score(act_l, protos, G, act_full=act_full, idx=idx, cells=cell)
+                same.append(s); lost.append(l)
+            else:
+                b = ops.because_score(act_g, protos)[1]
+            best.append(b)
+    return Because(base, cell, torch.stack(same) if same else None, torch.stack(best), torch.stack(lost) if lost else None, protos, names, branch)
+
+
+def _ordered_sum(v):
+    """The fp64 sum of v in index order (one addition after the other: the order is part of the result)."""
+    return float(np.cumsum(np.asarray(v, dtype=np.float64))[-1]) if len(v) else 0.0
+
+
+def importance_from_rows(image_ids, protos, base, same, best, lost, characteristics):
+    """The global importances from the rows of a data set, in fp64 on the host: image_ids [N], protos [N, K], base [N, K], same / best /
+    lost [n, N, K] (same, lost None on the global branch: best stands in).  Per prototype that occurred, over its rows in image-id order
+    (equal ids in row order): importance[i] = sum g (g - g_i) / sum g, the paper's weighted form with g = base and g_i = same;
+    mean[i] = the unweighted mean of g - g_i; importance_best[i] = the same with best; lost[i] = the share of lost cells; rows; and
+    dominant = the characteristic of the largest importance (ties: the earlier name).  Everything is None when there are no rows or
+    sum g == 0.  Returns dict(per_prototype={id: ...}, overall=...), overall over all rows."""
+    names = tuple(characteristics)
+    ids, pr = np.asarray(image_ids).reshape(-1), np.asarray(protos)
+    N, K = pr.shape if pr.ndim == 2 else (0, 0)
+    g = np.asarray(base, dtype=np.float64).reshape(N, K)
+    be = np.asarray(best, dtype=np.float64).reshape(len(names), N, K)
+    sa = be if same is None else np.asarray(same, dtype=np.float64).reshape(len(names), N, K)
+    lo = None if lost is None else np.asarray(lost, dtype=np.float64).reshape(len(names), N, K)
+    order = np.argsort(np.repeat(ids, K), kind="stable") if N else np.zeros(0, dtype=np.int64)
+    pf, gf = pr.reshape(-1)[order], g.reshape(-1)[order]
+    saf, bef = sa.reshape(len(names), -1)[:, order], be.reshape(len(names), -1)[:, order]
+    lof = None if lo is None else lo.reshape(len(names), -1)[:, order]
+
+    def summary(sel):
+        rows = int(sel.sum())
+        gs = gf[sel]
+        tot = _ordered_sum(gs)
+        out = dict(rows=rows, importance={}, mean={}, importance_best={}, lost={}, dominant=None)
+        for i, name in enumerate(names):
+            live = rows > 0 and tot != 0.0
+            out["importance"][name] = _ordered_sum(gs * (gs - saf[i][sel])) / tot if live else None
+            out["importance_best"][name] = _ordered_sum(gs * (gs - bef[i][sel])) / tot if live else None
+            out["mean"][name] = _ordered_sum(gs - saf[i][sel]) / rows if rows else None
+            out["lost"][name] = None if lof is None or not rows else _ordered_sum(lof[i][sel]) / rows
+        vals = [out["importance"][n] for n in names]
+        if all(v is not None and v == v for v in vals) and vals:
+            out["dominant"] = names[int(np.argmax(vals))]                  # the first of equal maxima: the earlier name
+        return out
+    return dict(per_prototype={int(p): summary(pf == p) for p in np.unique(pf)}, overall=summary(np.ones(pf.shape, dtype=bool)))
+
+
+def _regroup_fields(loader, n, max_images):
+    """_regroup for (x, labels, ids) batches: consecutive passes of exactly n images (the last may be shorter), whatever the loader's
+    batch size; x fp32, labels and ids int64, all on the device of the loader's images."""
+    held, have = [], 0
+    for x, y, ids in batches_with_ids(loader, max_images):
+        held.append((x.float(), torch.as_tensor(y).to(x.device, torch.int64), ids.to(x.device))); have += x.shape[0]
+        while have >= n:
+            full = tuple(torch.cat(f) if len(held) > 1 else f[0] for f in zip(*held))
+            yield tuple(f[:n].contiguous() for f in full)
+            held, have = ([tuple(f[n:] for f in full)] if have > n else []), have - n
+    if have:
+        yield tuple(torch.cat(f).contiguous() for f in zip(*held))
+
+
+def characteristic_importance(ppnet, loader, protos="own", branch="local", characteristics=CHARACTERISTICS, params=None, seed=0, max_images=0,
+                              pass_images=16, protos_per_image=3, scratch_bytes=1 << 30, per_image=False):
+    """The importance of every characteristic for every prototype over a data set.  loader yields (x, labels) or (x, labels, ids); its
+    images are regrouped into passes of pass_images images, so the result does not depend on the loader's batch size, and each pass is
+    one `because` call.  protos 'own': all prototypes of the image's label class (the paper's own-class images); 'top': the
+    protos_per_image strongest prototypes of the predicted class (larger pooled activation first, equal ones by smaller id).  The rows
+    stay on the device and are read once at the end; the sums are importance_from_rows's.  Returns its dict plus images, characteristics,
+    branch and, with per_image, rows = dict(image_ids, labels, protos, cell, base, same, best, lost) as numpy arrays."""
+    if protos not in ("own", "top"):
+        raise ValueError(f"characteristic_importance: protos must be 'own' or 'top', got {protos!r}")
+    names, local = tuple(characteristics), branch == "local"
+    keep, images = [], 0
+    for x, y, ids in _regroup_fields(loader, int(pass_images), int(max_images)):
+        x = x if x.is_cuda else x.cuda()
+        y, ids = y.to(x.device), ids.to(x.device)
+        C = ppnet.last_layer.weight.shape[0]
+        ppc = int(ppnet.num_prototypes_per_class) if local else ppnet.prototype_vectors_global.shape[0] // C
+        if protos == "own":
+            pr = y.clamp(0, C - 1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
+        else:
+            outs = _eval_outputs(ppnet, x.float().contiguous())
+            own = outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
+            act = outs["act_max"] if local else outs["act_max_global"]
+            pr = own.gather(1, torch.sort(act.gather(1, own), dim=1, descending=True, stable=True)[1][:, :min(int(protos_per_image), ppc)])
+        r = because(ppnet, x, pr.to(torch.int32), branch, names, params, seed, ids, None, scratch_bytes)
+        keep.append(dict(image_ids=ids, labels=y, protos=r.protos, cell=r.cell, base=r.base, same=r.same, best=r.best, lost=r.lost))
+        images += x.shape[0]
+    if not images:
+        raise ValueError("characteristic_importance: the loader gave no image")
+    cat = lambda k, dim: None if keep[0][k] is None else torch.cat([d[k] for d in keep], dim=dim)
+    rows = read_once({k: cat(k, 1 if k in ("same", "best", "lost") else 0) for k in keep[0]})            # the one read
+    out = importance_from_rows(rows["image_ids"], rows["protos"], rows["base"], rows["same"], rows["best"], rows["lost"], names)
+    out.update(images=images, characteristics=list(names), branch=branch)
+    if per_image:
+        out["rows"] = rows
     return out

@@ -703,6 +703,122 @@ def rise_accumulate(nodes, shift, prob, size, cells, grid_cells, thr):
     return sal, cell
 
 
+# ---- "this looks like that, because" (csrc/because.hip): colour transform, bilateral filter, warp, and the score of a perturbed forward
+def _host_f32(who, name, a, n):
+    """A host table as a contiguous fp32 numpy array of n entries: the C side takes its address."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"{who}: {name} must hold {n} values, got {a.size}")
+    return a
+
+
+def _image_batch(who, x, out, channels=3):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or (channels is not None and x.shape[1] != channels):
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [B, {channels or 'Cc'}, H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    if out is None:
+        return torch.empty_like(x)
+    return _dev_tensor(who, "out", out, torch.float32, x.shape, x.device)
+
+
+def color_affine(x, matrix, mean, std, offset=None, out=None):
+    """out = the 3 x 3 colour transform `matrix` (host) of the de-normalised, clamped pixels of x fp32 [B, 3, H, W], plus the optional
+    per-image offset fp32 [B, 3] on the device, clamped and normalised again (ppf_color_affine, include/ppf_hip.h); one launch."""
+    who = "color_affine"
+    out = _image_batch(who, x, out)
+    B, _, H, W = x.shape
+    m, mean, std = _host_f32(who, "matrix", matrix, 9), _host_f32(who, "mean", mean, 3), _host_f32(who, "std", std, 3)
+    if offset is not None:
+        _dev_tensor(who, "offset", offset, torch.float32, (B, 3), x.device)
+    _lib.call("ppf_color_affine", x, m.ctypes.data, offset, mean.ctypes.data, std.ctypes.data, B, H, W, out)
+    return out
+
+
+def gray_sum(x, mean, std):
+    """int32 [B]: the integer sum of the 8-bit luma over each image of x fp32 [B, 3, H, W] (ppf_gray_sum); a memset and one launch."""
+    who = "gray_sum"
+    _image_batch(who, x, x)
+    B, _, H, W = x.shape
+    mean, std = _host_f32(who, "mean", mean, 3), _host_f32(who, "std", std, 3)
+    total = torch.empty(B, dtype=torch.int32, device=x.device)
+    _lib.call("ppf_gray_sum", x, mean.ctypes.data, std.ctypes.data, B, H, W, total)
+    return total
+
+
+def contrast_offset(total, size, one_minus_f):
+    """fp32 [B, 3]: (1 - f) * the mean luma of each image from gray_sum's int32 [B] (ppf_contrast_offset); one launch, no host read.
+    size = (H, W)."""
+    who = "contrast_offset"
+    if not isinstance(total, torch.Tensor) or total.dim() != 1:
+        raise ValueError(f"{who}: total must be an int32 CUDA tensor [B]")
+    _dev_tensor(who, "total", total, torch.int32, total.shape)
+    off = torch.empty((total.shape[0], 3), dtype=torch.float32, device=total.device)
+    _lib.call("ppf_contrast_offset", total, total.shape[0], int(size[0]), int(size[1]), float(one_minus_f), off)
+    return off
+
+
+def bilateral(x, ws, wr, radius, mean, std, out=None):
+    """out = the joint bilateral filter of x fp32 [B, 3, H, W] with the host tables ws [(2r + 1)^2] (spatial) and wr [256] (range over the
+    8-bit luma difference) (ppf_bilateral, include/ppf_hip.h); one launch."""
+    who = "bilateral"
+    out = _image_batch(who, x, out)
+    B, _, H, W = x.shape
+    r = int(radius)
+    ws, wr = _host_f32(who, "ws", ws, max(2 * r + 1, 1) ** 2), _host_f32(who, "wr", wr, 256)
+    mean, std = _host_f32(who, "mean", mean, 3), _host_f32(who, "std", std, 3)
+    _lib.call("ppf_bilateral", x, ws.ctypes.data, wr.ctypes.data, r, mean.ctypes.data, std.ctypes.data, B, H, W, out)
+    return out
+
+
+def warp_nodes(image_ids, cells, amp256, seed=0):
+    """int32 [B, (cells + 1)^2, 2]: the node displacements (dy, dx) in 1/256 pixel of the images image_ids int64 [B] (ppf_warp_nodes)."""
+    who = "warp_nodes"
+    if not isinstance(image_ids, torch.Tensor) or image_ids.dim() != 1:
+        raise ValueError(f"{who}: image_ids must be an int64 CUDA tensor [B]")
+    B, s = image_ids.shape[0], int(cells)
+    _dev_tensor(who, "image_ids", image_ids, torch.int64, (B,))
+    nodes = torch.empty((B, max(s + 1, 0) ** 2, 2), dtype=torch.int32, device=image_ids.device)
+    _lib.call("ppf_warp_nodes", image_ids, int(seed) & 0xFFFFFFFFFFFFFFFF, B, s, int(amp256), nodes)
+    return nodes
+
+
+def warp_apply(x, nodes, cells, amp256, out=None):
+    """out = x fp32 [B, Cc, H, H] resampled at the positions the node table warp_nodes wrote displaces its pixels to (ppf_warp_apply,
+    include/ppf_hip.h); one launch."""
+    who = "warp_apply"
+    out = _image_batch(who, x, out, channels=None)
+    B, Cc, H, W = x.shape
+    _dev_tensor(who, "nodes", nodes, torch.int32, (B, (int(cells) + 1) ** 2, 2), x.device)
+    _lib.call("ppf_warp_apply", x, nodes, int(cells), int(amp256), B, Cc, H, W, out)
+    return out
+
+
+def because_score(act_max, protos, grid_cells=0, *, act_full=None, idx=None, cells=None):
+    """(same, best fp32 [B, K], lost int32 [B, K]) of a perturbed forward's act_max fp32 [B, P], act_full fp32 [B, P, T] and idx int32
+    [B, T] for the rows protos / cells int32 [B, K] (ppf_because_score, include/ppf_hip.h); one launch.  idx None: the global branch,
+    (None, best, None)."""
+    who = "because_score"
+    if not isinstance(act_max, torch.Tensor) or act_max.dim() != 2 or not isinstance(protos, torch.Tensor) or protos.dim() != 2:
+        raise ValueError(f"{who}: act_max must be an fp32 CUDA tensor [B, P] and protos an int32 CUDA tensor [B, K]")
+    (B, P), K, dev = act_max.shape, protos.shape[1], act_max.device
+    _dev_tensor(who, "act_max", act_max, torch.float32, (B, P))
+    _dev_tensor(who, "protos", protos, torch.int32, (B, K), dev)
+    best = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if idx is None:
+        _lib.call("ppf_because_score", None, None, act_max, protos, None, B, P, 0, 0, K, None, best, None)
+        return None, best, None
+    T = idx.shape[1] if isinstance(idx, torch.Tensor) and idx.dim() == 2 else -1
+    _dev_tensor(who, "idx", idx, torch.int32, (B, T), dev)
+    if not isinstance(act_full, torch.Tensor) or act_full.numel() != B * P * T:
+        raise ValueError(f"{who}: act_full must hold [{B}, {P}, {T}] elements")
+    _dev_tensor(who, "act_full", act_full, torch.float32, act_full.shape, dev)
+    _dev_tensor(who, "cells", cells, torch.int32, (B, K), dev)
+    same, lost = torch.empty_like(best), torch.empty((B, K), dtype=torch.int32, device=dev)
+    _lib.call("ppf_because_score", act_full, idx, act_max, protos, cells, B, P, T, int(grid_cells), K, same, best, lost)
+    return same, best, lost
+
+
 # ---- spatial alignment (csrc/alignment.hip): the image gradient's last step, gradient mass inside a box, the attack's step
 def col2im_patch(cols, B, C, H, W, patch):
     """img fp32 [B, C, H, W] from cols fp32 [B*(H/patch)*(W/patch), C*patch*patch]: the inverse of im2col_patch / im2col_patch_f32

@@ -1,4 +1,4 @@
-"""What the command-line tools (train, bank, explain, faithfulness, alignment, interp_eval) set up alike: the PPNet of the training
+"""What the command-line tools (train, bank, explain, faithfulness, alignment, because, interp_eval) set up alike: the PPNet of the training
 flags, a checkpoint loaded for evaluation, the eval-view loader over a split, the --split / --max_images flags and the "stop after N
 images" iteration.  Plain functions over `args`; nothing GPU-related is imported with the module."""
 
