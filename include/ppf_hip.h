@@ -75,6 +75,11 @@ int ppf_gemm_test_force_g224(int force);
  * dispatch as shipped, 1 register-staged for every shape, 2 LDS-DMA for every shape it can take (K % 64 == 0; others stay register-staged).
  * Both paths produce the same bits. */
 int ppf_gemm_test_wgrad_path(int path);
+/* Test hook (tests/test_gpu_gemm_paths.py): the kernel the last ppf_gemm_bf16 call launched, recorded on the host in front of the launch:
+ * 0 none yet | 1 gemm_kernel NT | 2 gemm_kernel NN | 3 gemm_kernel TT f32 | 4 gemm_kernel TT atomic | 5 gemm_kernel TT partial + reduce |
+ * 6 gemm128g | 7 gemm224g | 8 wgrad8<4,2> register-staged | 9 wgrad8<4,2> DMA | 10 wgrad8<2,4> register-staged | 11 wgrad8<2,4> DMA.
+ * Not thread-safe; tests only. */
+int ppf_gemm_test_last_kernel(void);
 
 /* Roofline probe of the split-K weight-gradient kernel (epi 6 with a workspace): HIP events (from a reused pool) on the launch
  * stream around the kernel itself.  ppf_gemm_probe(1) clears and starts, (0) stops, (2) stops and destroys the pool;

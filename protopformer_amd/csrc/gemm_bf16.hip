@@ -500,6 +500,11 @@ __global__ __launch_bounds__(64 * WMW * WNW, 1) void wgrad8_kernel(const GemmPar
     }
 }
 
+// Test hook (ppf_gemm_test_last_kernel): which kernel the last ppf_gemm_bf16 call launched; set on the host immediately before each launch.
+enum Route { ROUTE_NONE = 0, ROUTE_NT = 1, ROUTE_NN = 2, ROUTE_TT_F32 = 3, ROUTE_TT_ATOMIC = 4, ROUTE_TT_PARTIAL = 5, ROUTE_G128 = 6, ROUTE_G224 = 7,
+             ROUTE_WG8_42 = 8, ROUTE_WG8_42_DMA = 9, ROUTE_WG8_24 = 10, ROUTE_WG8_24_DMA = 11 };
+int g_last_kernel = ROUTE_NONE;
+
 // Test hook (ppf_gemm_test_wgrad_path): 0 = dispatch as shipped, 1 = register-staged everywhere, 2 = LDS-DMA wherever it is eligible.
 int g_wgrad_path = 0;
 #ifndef PPF_WGRAD_DMA_DEFAULT
@@ -517,7 +522,9 @@ int launch_wgrad8(const GemmParams& p, int splitk, hipStream_t stream) {
     constexpr int lds = opnd > strips ? opnd : strips;
     static_assert(strips <= WG8_RING_BYTES, "the epilogue strips reuse the dead ring");
     const int tiles = ((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN);
-    if (wgrad8_dma(p)) return ppf_launch<wgrad8_kernel<WMW, WNW, true, true>>(dim3(tiles * splitk), dim3(NTHR), WG8_RING_BYTES, stream, "wgrad8 (dma)", p);
+    const bool dma = wgrad8_dma(p);
+    g_last_kernel = (WMW == 4 ? ROUTE_WG8_42 : ROUTE_WG8_24) + (dma ? 1 : 0);
+    if (dma) return ppf_launch<wgrad8_kernel<WMW, WNW, true, true>>(dim3(tiles * splitk), dim3(NTHR), WG8_RING_BYTES, stream, "wgrad8 (dma)", p);
     return ppf_launch<wgrad8_kernel<WMW, WNW, true, false>>(dim3(tiles * splitk), dim3(NTHR), lds, stream, "wgrad8", p);
 }
 
@@ -806,6 +813,11 @@ int ppf_gemm_test_wgrad_path(int path) {
     return 0;
 }
 
+// Test hook: the kernel the last ppf_gemm_bf16 call launched (0 none yet, 1 gemm_kernel NT, 2 NN, 3 TT F32, 4 TT ATOMIC, 5 TT PARTIAL + reduce,
+// 6 gemm128g, 7 gemm224g, 8 / 9 wgrad8<4,2> register-staged / DMA, 10 / 11 wgrad8<2,4> register-staged / DMA); a refused call leaves it as it
+// was.  Not thread-safe; tests only.
+int ppf_gemm_test_last_kernel(void) { return g_last_kernel; }
+
 // Bytes of split-K workspace ppf_gemm_bf16 needs for an accumulating (epi = 6) problem of this shape.
 size_t ppf_gemm_workspace_bytes(int M, int N, int K) {
     return PPF_GEMM_COUNTER_BYTES + (size_t)pick_splitk(M, N, K) * ((size_t)M * N + M) * sizeof(float);
@@ -840,13 +852,13 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
     if (epi == EPI_DGELU) PPF_CHECK_ARG(aux_in != nullptr, PPF_ERR_ARG, "ppf_gemm_bf16: epi=5 needs aux_in");
     int rc;
     if (!trans_a && !trans_b) {
-        if (g224_eligible(p, epi)) return launch_g224(p, stream);
-        const auto g4 = [&](auto e) { return launch_g4<decltype(e)::value>(p, stream); };
-        const auto nt = [&](auto e) { return launch<false, false, decltype(e)::value, false>(p, 1, stream); };
+        if (g224_eligible(p, epi)) { g_last_kernel = ROUTE_G224; return launch_g224(p, stream); }
+        const auto g4 = [&](auto e) { g_last_kernel = ROUTE_G128; return launch_g4<decltype(e)::value>(p, stream); };
+        const auto nt = [&](auto e) { g_last_kernel = ROUTE_NT; return launch<false, false, decltype(e)::value, false>(p, 1, stream); };
         if (g4_eligible(p) && dispatch_epi<EPI_BF16, EPI_GELU, EPI_RESID, EPI_DGELU>(epi, rc, g4)) return rc;
         if (dispatch_epi<EPI_BF16, EPI_F32, EPI_GELU, EPI_SIGMOID_F32, EPI_RESID, EPI_DGELU>(epi, rc, nt)) return rc;
     } else if (!trans_a && trans_b) {
-        const auto nn = [&](auto e) { return launch<false, true, decltype(e)::value, false>(p, 1, stream); };
+        const auto nn = [&](auto e) { g_last_kernel = ROUTE_NN; return launch<false, true, decltype(e)::value, false>(p, 1, stream); };
         if (dispatch_epi<EPI_BF16, EPI_F32, EPI_DGELU>(epi, rc, nn)) return rc;
     } else if (epi == EPI_ATOMIC) {
         // split over the contraction: with a workspace the K slices leave fp32 partial tiles that splitk_reduce_kernel adds to C in
@@ -855,7 +867,7 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
         // in-kernel last-arriver reduce were measured slower IN THE STEP once more in round 4 and deleted: profiles/r4_wgrad_tiles.txt.)
         const int ns = pick_splitk(M, N, K);
         const size_t need = PPF_GEMM_COUNTER_BYTES + (size_t)ns * ((size_t)M * N + M) * sizeof(float);
-        if (workspace == nullptr || workspace_bytes < need || ns == 1) return launch<true, true, EPI_ATOMIC, true>(p, ns, stream);
+        if (workspace == nullptr || workspace_bytes < need || ns == 1) { g_last_kernel = ROUTE_TT_ATOMIC; return launch<true, true, EPI_ATOMIC, true>(p, ns, stream); }
         p.ws = (float*)((unsigned char*)workspace + PPF_GEMM_COUNTER_BYTES);
         p.cs_parts = 1;
         p.nsplit = ns;
@@ -872,7 +884,7 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
         const bool wide = (M < N ? M : N) >= 320;
         if (wide && M >= 512 && M >= N && (M % 256 == 0 || M >= 1024)) rc = launch_wgrad8<4, 2>(p, ns, stream);
         else if (wide && N >= 512 && (N % 256 == 0 || N >= 1024)) rc = launch_wgrad8<2, 4>(p, ns, stream);
-        else rc = launch<true, true, EPI_PARTIAL, true>(p, ns, stream);
+        else { g_last_kernel = ROUTE_TT_PARTIAL; rc = launch<true, true, EPI_PARTIAL, true>(p, ns, stream); }
         if (rc) return rc;
         if (e1) {
             (void)hipEventRecord(e1, stream);
@@ -883,6 +895,7 @@ int ppf_gemm_bf16(const void* A, const void* B, void* C, int M, int N, int K, in
         const int grid = (int)((work + 255) / 256);
         return ppf_launch<splitk_reduce_kernel>(dim3(grid), dim3(256), 0, stream, "ppf_gemm_bf16", p.ws, (float*)C, colsum, M, N, ldc, ns, p.cs_parts);
     } else if (epi == EPI_F32) {
+        g_last_kernel = ROUTE_TT_F32;
         return launch<true, true, EPI_F32, false>(p, 1, stream);
     }
     ppf_set_error("ppf_gemm_bf16: combination trans_a=%d trans_b=%d epi=%d not instantiated", trans_a, trans_b, epi);

@@ -108,6 +108,39 @@ def report(name, **values):
         pass
 
 
+# ---- fp64-reference gates in units of u (test_gpu_layernorm_paths.py, test_gpu_gemm_paths.py)
+U = 2.0 ** -24                          # fp32 unit roundoff
+SENT = float.fromhex("0x1.5p+100")      # sentinel for outputs that must stay untouched (compared bit for bit; exact in bf16 too)
+
+
+def bits(t):
+    t = t.detach().cpu().contiguous()
+    return t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int16) if t.element_size() == 2 else t
+
+
+def bf16_rne(v):
+    """fp64 -> nearest bf16 (ties to even), returned as fp64: one rounding, not fp64 -> fp32 -> bf16."""
+    # On the bit pattern (the device's ldexp goes through pow and is not exact there): keep 7 of the 52 fraction bits; a carry out of the
+    # fraction moves into the exponent field as it should.
+    b = v.contiguous().view(torch.int64)
+    b = (b + ((1 << 44) - 1) + ((b >> 45) & 1)) & ~((1 << 45) - 1)
+    return b.view(torch.float64)
+
+
+def half_ulp_bf16(v):
+    """Half a bf16 ulp of the fp64 value v: 2**-8 of its binade's lower edge."""
+    e = (v.contiguous().view(torch.int64) >> 52) & 0x7FF
+    return torch.where(v == 0, torch.zeros_like(v), ((e - 8) << 52).view(torch.float64))
+
+
+def maxu(err, scale):
+    """max err / (u * scale) over the elements whose scale is not zero; where it is zero the error must be zero too."""
+    err, scale = err.double(), scale.double()
+    z = scale == 0
+    assert not bool((err[z] != 0).any()), "non-zero error where the reference and its scale are exactly zero"
+    return float((err[~z] / (U * scale[~z])).max()) if bool((~z).any()) else 0.0
+
+
 # gelu'(x) as the fc1 epilogue saves it for backward: 8-bit linear codes (csrc/gemm_common.h gelu8_*)
 GELU8_ZERO, GELU8_STEP = 26.0, 1.0 / 196.0        # 0 -> code 26, 1 -> code 222: both exact
 

@@ -24,30 +24,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import report
+from helpers import SENT, U, bf16_rne, bits, half_ulp_bf16, maxu, report
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 EPS = float(np.float32(1e-6))           # the C entry point takes eps as a float
 K = 16.0                                # allowance factor of every fp32 gate, in u
-SENT = float.fromhex("0x1.5p+100")      # sentinel for outputs that must stay untouched (compared bit for bit)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int16)
-
-
-def bf16_rne(v):
-    """fp64 -> nearest bf16 (ties to even), returned as fp64: one rounding, not fp64 -> fp32 -> bf16."""
-    m, e = torch.frexp(v)
-    return torch.ldexp(torch.round(m * 256.0), e - 8)
-
-
-def half_ulp_bf16(v):
-    _, e = torch.frexp(v)
-    return torch.where(v == 0, torch.zeros_like(v), torch.ldexp(torch.ones_like(v), e - 9))
 
 
 def make_x(rows, D, g):
@@ -60,14 +42,6 @@ def make_x(rows, D, g):
 
 def make_wb(D, g):
     return 1 + 0.2 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
-
-
-def maxu(err, scale):
-    """max err / (u * scale) over the elements whose scale is not zero; where it is zero the error must be zero too."""
-    err, scale = err.double(), scale.double()
-    z = scale == 0
-    assert not bool((err[z] != 0).any()), "non-zero error where the reference and its scale are exactly zero"
-    return float((err[~z] / (U * scale[~z])).max()) if bool((~z).any()) else 0.0
 
 
 # ------------------------------------------------------------------------------------------------ forward

@@ -32,3 +32,5 @@ def test_wgrad_dma_layout(tmp_path):
     assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
     assert "wgrad DMA layout: ok" in run.stdout
     assert run.stdout.count("K tiles checked") == 4          # the K % 64 != 0 case has no DMA addresses to check
+    # pick_splitk / k_slice: non-empty, disjoint, 64-aligned slices that cover [0, K) for K = 8 .. 4096 and every (M, N) of test_gpu_gemm_paths.py
+    assert "K slicing:" in run.stdout and "FAIL" not in run.stdout

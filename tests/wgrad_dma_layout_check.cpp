@@ -86,7 +86,38 @@ static void check_shape(int M, int N, int K) {
     std::printf("shape %4d x %4d, K %4d: %d slices, %lld K tiles checked\n", M, N, K, ns, tiles_k);
 }
 
+// 3. The K slicing every split-K kernel relies on: for ns = pick_splitk(M, N, K) the slices k_slice(K, ns, z), z < ns, are non-empty, start on
+//    multiples of 64, follow each other without gap or overlap and end at K -- for the (M, N) of every split-K case of
+//    tests/test_gpu_gemm_paths.py and K = 8 .. 4096 in steps of 8 (a partial-tile slab that is never written would be read by the reduce).
+static void check_slices() {
+    static const int mn[][2] = {{192, 192}, {136, 72}, {136, 200}, {512, 320}, {1032, 328}, {320, 512}, {328, 1032},
+                                {1, 8}, {33, 132}, {130, 260}, {257, 128}, {16261, 520}, {16261, 516}, {16384, 512}, {225, 136}, {449, 392},
+                                {33, 136}, {130, 264}, {264, 136}};
+    long long slices = 0;
+    for (const auto& s : mn)
+        for (int K = 8; K <= 4096; K += 8) {
+            const int M = s[0], N = s[1], ns = pick_splitk(M, N, K);
+            CHECK(ns >= 1 && ns <= (K + BK - 1) / BK, "M %d N %d K %d: %d slices", M, N, K, ns);
+            int next = 0;
+            for (int z = 0; z < ns; ++z) {
+                const KSlice ks = k_slice(K, ns, z);
+                CHECK(ks.kbeg == next && ks.kbeg % BK == 0, "M %d N %d K %d slice %d of %d starts at %d, the one before ended at %d", M, N, K, z, ns, ks.kbeg, next);
+                CHECK(ks.kend > ks.kbeg && ks.kend <= K, "M %d N %d K %d slice %d of %d: [%d, %d) is empty or past K", M, N, K, z, ns, ks.kbeg, ks.kend);
+                next = ks.kend;
+                ++slices;
+            }
+            CHECK(next == K, "M %d N %d K %d: %d slices end at %d", M, N, K, ns, next);
+        }
+    // the slice counts the GPU tests' cases are built around
+    CHECK(pick_splitk(192, 192, 520) == 3 && pick_splitk(136, 72, 200) == 1 && pick_splitk(136, 200, 264) == 2, "slice counts of the 128 x 128 split-K cases");
+    CHECK(pick_splitk(512, 320, 512) == 2 && pick_splitk(1032, 328, 520) == 3 && pick_splitk(320, 512, 264) == 2, "slice counts of the eight-wave cases");
+    const KSlice last = k_slice(520, 3, 2);
+    CHECK(last.kbeg == 384 && last.kend == 520, "K = 520 in three slices: 192 / 192 / 136");
+    std::printf("K slicing: %lld slices checked\n", slices);
+}
+
 int main() {
+    check_slices();
     static_assert((256 + 128) * BK * 2 == WG8_SLOT_BYTES && 2 * WG8_SLOT_BYTES == 96 * 1024, "ring budget");
     check_image<256>();
     check_image<128>();
