@@ -416,6 +416,33 @@ int ppf_rise_apply(const float* x, const void* nodes_u8, const int* shift, int N
                    int B, int Cc, int H, int W, float* out, ppf_stream_t stream);
 int ppf_rise_accumulate(const void* nodes_u8, const int* shift, const float* prob, int B, int N, int M, int s, int thr, int H, int W, int G, float* sal,
                         float* cell, ppf_stream_t stream);
+/* Integrated gradients (csrc/ig.hip; Sundararajan et al., 2017): attribution = (x - baseline) * the gradient averaged along the straight
+ * path from the baseline to x; the attributions of an image sum to f(x) - f(baseline).  The forwards and backwards along the path are the
+ * caller's (interpret.input_gradient); these three streaming kernels are everything in between.  The reference has no such pass.
+ * Additions of ABI 10: no existing entry point changed.
+ * The arithmetic is the contract the numpy referees (interpret.ig_point, ig_accumulate, ig_finish with device=False) keep bit for bit:
+ * plain fp32, every operation rounded once to nearest (fsub_rn / fmul_rn / fadd_rn), nothing fused or reassociated, no transcendental
+ * function, no floating-point atomics.  16-byte accesses when the sizes named below are multiples of 4 and every pointer is 16-byte
+ * aligned, scalar ones otherwise: the values do not depend on it.  base[e] is baseline[e], or the constant baseline_const when baseline
+ * is NULL (as ppf_patch_perturb / ppf_rise_apply).
+ *   ppf_ig_point       out[e] = fadd_rn(base[e], fmul_rn(alpha, fsub_rn(x[e], base[e]))) over n >= 1 fp32 elements (vectors: n % 4 == 0).
+ *                      alpha = 0 gives the baseline exactly for finite inputs; a constant baseline of 0 and alpha = 1 give x.
+ *   ppf_ig_accumulate  g fp32 [R][n]; row r of the accumulator starts at acc + r * acc_stride, acc_stride >= n (so one class column of a
+ *                      [B][M][...] accumulator can be the target).  first = 1: acc = fmul_rn(w, g), the accumulator is not read (no
+ *                      zero fill before the first step); first = 0: acc = fadd_rn(acc, fmul_rn(w, g)).  Elements between the rows
+ *                      are not touched.  NaN propagates.  Vectors: n % 4 == 0 and acc_stride % 4 == 0.  first other than 0 / 1 is
+ *                      PPF_ERR_ARG.
+ *   ppf_ig_finish      acc, attr fp32 [B][M][C][H][W]; x, baseline fp32 [B][C][H][W] (shared by the M class columns):
+ *                      attr = fmul_rn(fsub_rn(x, base), acc).  cell64 fp64 [B][M][G], G = (H / patch) * (W / patch), cells row-major:
+ *                      the sum over the cell's C * patch^2 elements of (double)attr (every term exact).  The order of that sum is
+ *                      fixed but unspecified (within C * patch^2 * 2^-53 * sum |attr| of any other order); repeated runs are
+ *                      bit-identical; a NaN makes its own cell NaN and no other.  One pass: the attribution is written from the
+ *                      registers that feed the cell sums.  patch divides H and W, 1 <= M <= 8, G <= 1024 (ppf_cell_order's limits),
+ *                      else PPF_ERR_SHAPE before any device call.  Vectors: patch % 4 == 0. */
+int ppf_ig_point(const float* x, const float* baseline, float baseline_const, float alpha, int64_t n, float* out, ppf_stream_t stream);
+int ppf_ig_accumulate(const float* g, float w, int first, int R, int64_t n, float* acc, int64_t acc_stride, ppf_stream_t stream);
+int ppf_ig_finish(const float* acc, const float* x, const float* baseline, float baseline_const, int B, int M, int C, int H, int W, int patch,
+                  float* attr, double* cell64, ppf_stream_t stream);
 /* "This looks like that, because ..." (csrc/because.hip; Nauta et al., 2021): suppress one visual characteristic of an image -- hue,
  * saturation, contrast, texture or shape --, run the model again and read the prototype's similarity at the same grid cell; the forwards
  * in between are the caller's.  The reference has no such pass.  Additions of ABI 10: no existing entry point changed.

@@ -446,17 +446,21 @@ __device__ inline float block_max256(float v, float* red) {
     return r;
 }
 
-// Backward of th_attn_f32_kernel (cait:115-132): one workgroup per (sample, query), thread j = key.  With S = (q scale) K^T, M = wl S + bl,
+// Backward of th_attn_f32_kernel (cait:115-132): one workgroup per sample walks its queries in ascending order, thread j = key.  With
+// S = (q scale) K^T, M = wl S + bl,
 // P = softmax_j M, A = ww P + bw, out = A V:   dA = dO V^T, dV += A^T dO, dww += dA P^T, dbw += sum dA, dP = ww^T dA,
 // dM = P (dP - sum_j P dP), dwl += dM S^T, dbl += sum dM, dS = wl^T dM, dQ = scale dS K, dK += dS^T (q scale).
-// dK / dV (dqkv zero-filled by the caller) and the four mixer gradients are accumulated with fp32 atomics (verification only).
+// Row j of dK / dV (dqkv zero-filled by the caller) is added to by thread j alone, query after query: a fixed order, so the gradient with
+// respect to the tokens -- and with it the image gradient, which integrated gradients compares bit for bit -- repeats from run to run
+// (one workgroup per (sample, query) adding with fp32 atomics did not).  The four mixer gradients are still accumulated with fp32
+// atomics, in LDS and once per sample in memory (verification only).
 // lds: qrow [D] | S [H][N] | P [H][N] | T [H][N] (dS) | red [256] | acc [2 H H + 2 H]
 __global__ __launch_bounds__(256) void th_attn_bwd_f32_kernel(const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ wl,
                                                               const float* __restrict__ bl, const float* __restrict__ ww, const float* __restrict__ bw,
                                                               float* __restrict__ dqkv, float* __restrict__ dwl, float* __restrict__ dbl,
                                                               float* __restrict__ dww, float* __restrict__ dbw, int H, int N, int D) {
     extern __shared__ float lds[];
-    const int hd = D / H, b = blockIdx.x / N, q = blockIdx.x % N, j = threadIdx.x;
+    const int hd = D / H, b = blockIdx.x, j = threadIdx.x;
     float* qrow = lds;
     float* S = qrow + D;
     float* P = S + (size_t)H * N;
@@ -466,73 +470,76 @@ __global__ __launch_bounds__(256) void th_attn_bwd_f32_kernel(const float* __res
     const int nacc = 2 * H * H + 2 * H;
     const float scale = 1.0f / sqrtf((float)hd);
     const float* base = qkv + (size_t)b * N * 3 * D;
-    const float* dor = dout + ((size_t)b * N + q) * D;
     float* gb = dqkv + (size_t)b * N * 3 * D;
-    for (int d = threadIdx.x; d < D; d += 256) qrow[d] = base[(size_t)q * 3 * D + d] * scale;
     for (int i = threadIdx.x; i < nacc; i += 256) acc[i] = 0.f;
-    __syncthreads();
-    if (j < N)
-        for (int h = 0; h < H; ++h) {
-            float s = 0.f;
-            for (int d = 0; d < hd; ++d) s += qrow[h * hd + d] * base[(size_t)j * 3 * D + D + h * hd + d];
-            S[h * N + j] = s;
-        }
-    __syncthreads();
-    for (int g = 0; g < H; ++g) {
-        float m = -INFINITY;
-        if (j < N) {
-            m = bl[g];
-            for (int h = 0; h < H; ++h) m += wl[g * H + h] * S[h * N + j];
-        }
-        const float mx = block_max256(m, red);
-        const float e = j < N ? expf(m - mx) : 0.f;
-        const float sum = block_sum256(e, red);
-        if (j < N) P[g * N + j] = e / sum;
-    }
-    __syncthreads();
-    float dA[16], dP[16], dM[16];
-    for (int g = 0; g < H; ++g) { dA[g] = 0.f; dP[g] = 0.f; dM[g] = 0.f; }
-    if (j < N) {
-        for (int g = 0; g < H; ++g) {
-            float a = bw[g], da = 0.f;
-            for (int h = 0; h < H; ++h) a += ww[g * H + h] * P[h * N + j];
-            for (int d = 0; d < hd; ++d) {
-                const float o = dor[g * hd + d];
-                da += o * base[(size_t)j * 3 * D + 2 * D + g * hd + d];
-                atomicAdd(gb + (size_t)j * 3 * D + 2 * D + g * hd + d, a * o);                     // dV
+    for (int q = 0; q < N; ++q) {
+        const float* dor = dout + ((size_t)b * N + q) * D;
+        for (int d = threadIdx.x; d < D; d += 256) qrow[d] = base[(size_t)q * 3 * D + d] * scale;
+        __syncthreads();
+        if (j < N)
+            for (int h = 0; h < H; ++h) {
+                float s = 0.f;
+                for (int d = 0; d < hd; ++d) s += qrow[h * hd + d] * base[(size_t)j * 3 * D + D + h * hd + d];
+                S[h * N + j] = s;
             }
-            dA[g] = da;
-            atomicAdd(acc + 2 * H * H + H + g, da);                                                // dbw
-            for (int h = 0; h < H; ++h) atomicAdd(acc + H * H + g * H + h, da * P[h * N + j]);     // dww
-        }
-        for (int h = 0; h < H; ++h) {
-            float v = 0.f;
-            for (int g = 0; g < H; ++g) v += ww[g * H + h] * dA[g];
-            dP[h] = v;
-        }
-    }
-    for (int g = 0; g < H; ++g) {
-        const float dot = block_sum256(j < N ? P[g * N + j] * dP[g] : 0.f, red);
-        if (j < N) dM[g] = P[g * N + j] * (dP[g] - dot);
-    }
-    if (j < N) {
+        __syncthreads();
         for (int g = 0; g < H; ++g) {
-            atomicAdd(acc + 2 * H * H + g, dM[g]);                                                  // dbl
-            for (int h = 0; h < H; ++h) atomicAdd(acc + g * H + h, dM[g] * S[h * N + j]);          // dwl
+            float m = -INFINITY;
+            if (j < N) {
+                m = bl[g];
+                for (int h = 0; h < H; ++h) m += wl[g * H + h] * S[h * N + j];
+            }
+            const float mx = block_max256(m, red);
+            const float e = j < N ? expf(m - mx) : 0.f;
+            const float sum = block_sum256(e, red);
+            if (j < N) P[g * N + j] = e / sum;
         }
-        for (int h = 0; h < H; ++h) {
-            float ds = 0.f;
-            for (int g = 0; g < H; ++g) ds += wl[g * H + h] * dM[g];
-            T[h * N + j] = ds;
-            for (int d = 0; d < hd; ++d) atomicAdd(gb + (size_t)j * 3 * D + D + h * hd + d, ds * qrow[h * hd + d]);      // dK
+        __syncthreads();
+        float dA[16], dP[16], dM[16];
+        for (int g = 0; g < H; ++g) { dA[g] = 0.f; dP[g] = 0.f; dM[g] = 0.f; }
+        if (j < N) {
+            for (int g = 0; g < H; ++g) {
+                float a = bw[g], da = 0.f;
+                for (int h = 0; h < H; ++h) a += ww[g * H + h] * P[h * N + j];
+                for (int d = 0; d < hd; ++d) {
+                    const float o = dor[g * hd + d];
+                    da += o * base[(size_t)j * 3 * D + 2 * D + g * hd + d];
+                    gb[(size_t)j * 3 * D + 2 * D + g * hd + d] += a * o;                           // dV: thread j owns row j, q ascending
+                }
+                dA[g] = da;
+                atomicAdd(acc + 2 * H * H + H + g, da);                                                // dbw
+                for (int h = 0; h < H; ++h) atomicAdd(acc + H * H + g * H + h, da * P[h * N + j]);     // dww
+            }
+            for (int h = 0; h < H; ++h) {
+                float v = 0.f;
+                for (int g = 0; g < H; ++g) v += ww[g * H + h] * dA[g];
+                dP[h] = v;
+            }
         }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 256) {
-        const int h = c / hd;
-        float a = 0.f;
-        for (int k = 0; k < N; ++k) a += T[h * N + k] * base[(size_t)k * 3 * D + D + c];
-        gb[(size_t)q * 3 * D + c] = a * scale;                                                      // dQ (single writer)
+        for (int g = 0; g < H; ++g) {
+            const float dot = block_sum256(j < N ? P[g * N + j] * dP[g] : 0.f, red);
+            if (j < N) dM[g] = P[g * N + j] * (dP[g] - dot);
+        }
+        if (j < N) {
+            for (int g = 0; g < H; ++g) {
+                atomicAdd(acc + 2 * H * H + g, dM[g]);                                                  // dbl
+                for (int h = 0; h < H; ++h) atomicAdd(acc + g * H + h, dM[g] * S[h * N + j]);          // dwl
+            }
+            for (int h = 0; h < H; ++h) {
+                float ds = 0.f;
+                for (int g = 0; g < H; ++g) ds += wl[g * H + h] * dM[g];
+                T[h * N + j] = ds;
+                for (int d = 0; d < hd; ++d) gb[(size_t)j * 3 * D + D + h * hd + d] += ds * qrow[h * hd + d];       // dK: likewise
+            }
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < D; c += 256) {
+            const int h = c / hd;
+            float a = 0.f;
+            for (int k = 0; k < N; ++k) a += T[h * N + k] * base[(size_t)k * 3 * D + D + c];
+            gb[(size_t)q * 3 * D + c] = a * scale;                                                      // dQ (single writer)
+        }
+        __syncthreads();                                                                            // qrow, S, P and T are rewritten for the next query
     }
     for (int i = threadIdx.x; i < nacc; i += 256) {
         float* dst = i < H * H ? dwl + i : i < 2 * H * H ? dww + (i - H * H) : i < 2 * H * H + H ? dbl + (i - 2 * H * H) : dbw + (i - 2 * H * H - H);
@@ -621,7 +628,7 @@ int ppf_th_attn_bwd_f32(const float* qkv, const float* dout, const float* wl, co
     PPF_CHECK_ARG(qkv && dout && wl && bl && ww && bw && dqkv && dwl && dbl && dww && dbw && B > 0 && H > 0 && H <= 16 && N > 0 && N <= 256 && D % H == 0,
                   PPF_ERR_SHAPE, "ppf_th_attn_bwd_f32: bad shape B=%d H=%d N=%d D=%d", B, H, N, D);
     const size_t lds = ((size_t)D + 3 * (size_t)H * N + 256 + 2 * H * H + 2 * H) * sizeof(float);
-    return ppf_launch<th_attn_bwd_f32_kernel>(dim3(B * N), dim3(256), lds, stream, "ppf_th_attn_bwd_f32", qkv, dout, wl, bl, ww, bw, dqkv, dwl, dbl, dww, dbw, H, N, D);
+    return ppf_launch<th_attn_bwd_f32_kernel>(dim3(B), dim3(256), lds, stream, "ppf_th_attn_bwd_f32", qkv, dout, wl, bl, ww, bw, dqkv, dwl, dbl, dww, dbw, H, N, D);
 }
 
 int ppf_class_attn_bwd_f32(const float* q, const float* k, const float* v, const float* policy, const float* dout, float* dq, float* dk, float* dv,

@@ -3,14 +3,15 @@ explanation names are removed most important first (deletion: the class probabil
 come back), under three orders of the cells -- the class evidence of the prototypes ('evidence'), the rollout attention the token
 reservation looks at ('attention') and a random order, the control.  On request a fourth: 'rise', the cells ranked by the model-agnostic
 saliency the metric was published with (interpret.rise_saliency: forwards of randomly masked images alone), the black-box baseline an
-interpretable-by-design model is compared against.  The reference has no such pass.
+interpretable-by-design model is compared against; and 'ig', the cells ranked by the integrated gradients of the class logit
+(interpret.integrated_gradients: one forward and backward per path step), the gradient baseline.  The reference has no such pass.
 
 Per batch one eval forward, one `ppf_cell_order` launch per order, and per curve `ppf_patch_perturb`, the model's forwards and
 `ppf_class_prob` (interpret.faithfulness); the curves stay on the device until the split is done.
 
     python -m protopformer_amd.faithfulness --resume CKPT --data_set CUB2011U --data_path ... --output_dir OUT [--split test] [--steps 14]
-                                            [--orders evidence attention random [rise]] [--modes deletion insertion] [--against_label]
-                                            [--rise_masks 512] [--rise_cells 7] [--rise_p 0.5]
+                                            [--orders evidence attention random [rise] [ig]] [--modes deletion insertion] [--against_label]
+                                            [--rise_masks 512] [--rise_cells 7] [--rise_p 0.5] [--ig_steps 32] [--ig_rule midpoint]
                                             [--max_images N] [--seed 0] [--per-image]
                                             + the model flags of train.py
 
@@ -26,18 +27,20 @@ import torch
 
 
 def get_args_parser():
-    from .interpret import CURVE_MODES, EXTRA_ORDERS, ORDER_MODES, RISE_DEFAULTS
+    from .interpret import CURVE_MODES, EXTRA_ORDERS, GRADIENT_ORDERS, IG_DEFAULTS, IG_RULES, ORDER_MODES, RISE_DEFAULTS
     from .tooling import add_split_flags
     from .train import get_args_parser as train_parser
     p = argparse.ArgumentParser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", parents=[train_parser()])
     a = p.add_argument
     add_split_flags(p, "test", "evaluated")
     a("--steps", type=int, default=14, help="the curves have steps + 1 points: 0, G/steps, ... G cells removed / shown")
-    a("--orders", type=str, nargs="+", default=list(ORDER_MODES), choices=list(ORDER_MODES + EXTRA_ORDERS),
-      help="cell orders to evaluate (random is the control; rise, the black-box baseline, only on request)")
+    a("--orders", type=str, nargs="+", default=list(ORDER_MODES), choices=list(ORDER_MODES + EXTRA_ORDERS + GRADIENT_ORDERS),
+      help="cell orders to evaluate (random is the control; rise, the black-box baseline, and ig, the gradient baseline, only on request)")
     a("--rise_masks", type=int, default=RISE_DEFAULTS["masks"], help="masks per image of the rise order (one forward each)")
     a("--rise_cells", type=int, default=RISE_DEFAULTS["cells"], help="low-resolution cells per side of a rise mask")
     a("--rise_p", type=float, default=RISE_DEFAULTS["p"], help="probability that a node of a rise mask is on")
+    a("--ig_steps", type=int, default=IG_DEFAULTS["steps"], help="path steps of the ig order (one forward and backward each)")
+    a("--ig_rule", type=str, default=IG_DEFAULTS["rule"], choices=list(IG_RULES), help="quadrature of the ig order's path integral")
     a("--modes", type=str, nargs="+", default=list(CURVE_MODES), choices=list(CURVE_MODES))
     a("--against_label", action="store_true", default=False, help="follow the probability of the image's label instead of its top class")
     a("--per-image", dest="per_image", action="store_true", default=False, help="also write faithfulness.npz with every image's curves")
@@ -76,7 +79,7 @@ def main(args, model=None, loader=None):
     model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes), counts=default_counts(model.num_patches, args.steps),
                        against_label=args.against_label, seed=args.seed, max_images=args.max_images,
-                       rise=dict(masks=args.rise_masks, cells=args.rise_cells, p=args.rise_p))
+                       rise=dict(masks=args.rise_masks, cells=args.rise_cells, p=args.rise_p), ig=dict(steps=args.ig_steps, rule=args.ig_rule))
     os.makedirs(args.output_dir, exist_ok=True)
     path = os.path.join(args.output_dir, "faithfulness.json")
     with open(path, "w") as f:

@@ -963,12 +963,12 @@ class Faithfulness:
     """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
     class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
     order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G.  rise: the Rise the 'rise' order ranked by
-    (its cell scores are `score`), None for every other order."""
+    (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order."""
     FIELDS = ("counts", "classes", "order", "rank", "score")
 
-    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None):
+    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None, ig=None):
         self.curves, self.counts, self.classes, self.order, self.rank, self.score = dict(curves), counts, classes, order, rank, score
-        self.grid_cells, self.rise = int(grid_cells), rise
+        self.grid_cells, self.rise, self.ig = int(grid_cells), rise, ig
 
     @property
     def on_host(self):
@@ -980,7 +980,7 @@ class Faithfulness:
             return self
         out = read_once({**{k: getattr(self, k) for k in self.FIELDS}, **{("curve", k): v for k, v in self.curves.items()}})
         return Faithfulness({k: out["curve", k] for k in self.curves}, *(out[k] for k in self.FIELDS), self.grid_cells,
-                            rise=None if self.rise is None else self.rise.cpu())
+                            rise=None if self.rise is None else self.rise.cpu(), ig=None if self.ig is None else self.ig.cpu())
 
     def auc(self):
         """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
@@ -1022,13 +1022,20 @@ def _class_probs(ppnet, imgs, cols, batch_size):
     return [ops.class_prob(logits, c) for c in cols]
 
 
-def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None):
+def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None, ig=None):
     from . import ops
     B, G = x.shape[0], int(ppnet.num_patches)
     M, S = cls.shape[1], counts.shape[0]
     w_l = ppnet.last_layer.weight.detach().contiguous()
-    found = None
-    if order in EXTRA_ORDERS:
+    found = found_ig = None
+    if order in GRADIENT_ORDERS:
+        # the cells ranked by the integrated gradients of the class logit summed over each cell, along the path from the curve's own
+        # baseline; through ppf_cell_order's attention mode exactly as the rise order below
+        _refuse_pending_gradients("faithfulness_curves", ppnet)
+        found_ig = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
+        ordr, rank, score = (t.reshape(B, M, G) for t in ops.cell_order(cls.reshape(B * M, 1).contiguous(), G, "attention",
+                                                                        token_attn=found_ig.cell.reshape(B * M, G), weight=w_l))
+    elif order in EXTRA_ORDERS:
         # the cells ranked by their mean RISE saliency: ppf_cell_order's attention mode over the B * M (sample, class) rows, so the total
         # order, the NaN rule and the -1 rows of an invalid class are that kernel's
         found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
@@ -1054,7 +1061,7 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
                 imgs = imgs.reshape((n * B * M,) + tuple(x.shape[1:]))
                 prob[s0:s0 + n] = _class_probs(ppnet, imgs, [cls_flat[:n * B * M]], int(batch_size or B))[0].reshape(n, B, M)
             curves[mode] = prob.permute(1, 2, 0).contiguous()
-    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found)
+    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found, ig=found_ig)
 
 
 def _pick_classes(ppnet, outs, classes, top_classes, B):
@@ -1069,7 +1076,7 @@ def _pick_classes(ppnet, outs, classes, top_classes, B):
 
 @torch.no_grad()
 def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, modes=CURVE_MODES, order="evidence", baseline=0.0, seed=0, image_ids=None,
-                        batch_size=None, scratch_bytes=1 << 30, rise=None):
+                        batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
     """Deletion / insertion curves of a batch x [B, 3, H, W] (CUDA): one eval forward, one ppf_cell_order launch, then per mode
     ppf_patch_perturb in chunks of steps, the model's forward over each chunk in sub-batches of `batch_size` images (default B; the
     images of a chunk are ordered step, sample, class) and one ppf_class_prob per chunk.  The chunk's images are the one large scratch
@@ -1077,7 +1084,9 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     classes: as in explain (None: the top `top_classes` of the logits).  counts: the numbers of cells removed / shown (default
     default_counts(G)).  order: 'evidence', 'attention' or 'random' (seed, image_ids: the random order's key), or 'rise': the cells ranked
     by their RISE saliency for the class (rise_saliency with the same baseline, seed, image_ids, batch_size and scratch_bytes;
-    rise = dict(masks=, cells=, p=) overrides RISE_DEFAULTS; the result carries the Rise).  baseline: what a removed pixel becomes, a
+    rise = dict(masks=, cells=, p=) overrides RISE_DEFAULTS; the result carries the Rise), or 'ig': by the integrated gradients of the
+    class logit summed over each cell (integrated_gradients along the path from the same baseline, in the same sample groups;
+    ig = dict(steps=, rule=) overrides IG_DEFAULTS; the result carries the IntegratedGradients).  baseline: what a removed pixel becomes, a
     number in normalised space (0 = the data-set mean colour) or a tensor like x.  Returns a Faithfulness (device tensors; nothing is read
     back here)."""
     if not x.is_cuda:
@@ -1088,7 +1097,7 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     outs = _eval_outputs(ppnet, x)
     cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
     counts = _device_counts(counts, G, x.device)
-    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise)
+    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
 
 
 def _device_counts(counts, G, device):
@@ -1100,9 +1109,9 @@ def _device_counts(counts, G, device):
 
 @torch.no_grad()
 def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=None, top_classes=1, against_label=False, baseline=0.0, seed=0,
-                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None):
+                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
     """The curves over a data set.  loader yields (x, labels) or (x, labels, ids); without ids an image's id is its running index.  Per
-    batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
+    batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=), and 'ig', with ig = dict(steps=, rule=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
     The per-image curves stay on the device and are read back once at the end.  Returns dict(images, counts, grid_cells, orders:
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
     image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
@@ -1115,7 +1124,7 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
         if dev_counts is None:
             dev_counts = _device_counts(counts, G, x.device)
         for order in orders:
-            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise)
+            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise, ig)
             for mode in modes:
                 kept.setdefault((order, mode), []).append(f.curves[mode])
         cls_kept.append(cls); ids_kept.append(ids)
@@ -1327,6 +1336,19 @@ def rise_saliency(ppnet, x, classes=None, top_classes=1, masks=512, cells=7, p=0
 # the gradient with respect to the image, which the backbone's backward hands out when the image requires one (backbone.embed_bwd,
 # precise._embed_bwd: dcols = dtok W and ppf_col2im_patch_f32).  ppf_grad_box_mass and ppf_pgd_step_box (csrc/alignment.hip) do the
 # rest on the device; the numpy forms below (device=False) are the referees.  The reference has no such pass.
+def _refuse_pending_gradients(who, ppnet):
+    """Raises if a parameter holds a pending gradient: a .grad with a non-zero (or NaN) element.  The all-zero views the flat store
+    attaches when it is built (the first forward) hold nothing and do not count.  One fused norm over the attached gradients and one
+    read, only when gradients are attached at all."""
+    held = [(n, p.grad) for n, p in ppnet.named_parameters() if p.grad is not None]
+    if held:
+        pending = (torch.stack(torch._foreach_norm([g.detach().float().reshape(-1) for _, g in held])) != 0).cpu().numpy()
+        if pending.any():
+            first = held[int(np.nonzero(pending)[0][0])][0]
+            raise RuntimeError(f"{who}: {int(pending.sum())} parameters already hold a .grad ({first}, ...): its backward accumulates into "
+                               "the same buffers; finish the training step and drop the gradients (zero_grad(set_to_none=True)) first")
+
+
 def input_gradient(ppnet, x, target):
     """Gradient of a model output with respect to the image: (grad fp32 [B, 3, H, W], value fp32 [B]) of x [B, 3, H, W] (CUDA).
     target = ("logit", classes [B]): value = logits[b, classes[b]]; ("proto", "local" | "global", protos [B]): value = the prototype's
@@ -1337,16 +1359,7 @@ def input_gradient(ppnet, x, target):
     when it is built do not count -- since a training step in flight would be corrupted, and sets every .grad back to None on exit."""
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
         raise RuntimeError("input_gradient needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path)")
-    held = [(n, p.grad) for n, p in ppnet.named_parameters() if p.grad is not None]
-    if held:
-        # the flat store attaches zero-filled views when it is built (the first forward), and dropping an all-zero gradient loses nothing:
-        # a gradient is pending when it holds something.  One fused norm over the attached gradients and one read; only on a call that
-        # finds gradients attached (this function leaves none behind).
-        pending = (torch.stack(torch._foreach_norm([g.detach().float().reshape(-1) for _, g in held])) != 0).cpu().numpy()
-        if pending.any():
-            first = held[int(np.nonzero(pending)[0][0])][0]
-            raise RuntimeError(f"input_gradient: {int(pending.sum())} parameters already hold a .grad ({first}, ...): its backward accumulates into "
-                               "the same buffers; finish the training step and drop the gradients (zero_grad(set_to_none=True)) first")
+    _refuse_pending_gradients("input_gradient", ppnet)
     B = x.shape[0]
     kind = target[0] if isinstance(target, (tuple, list)) and target else None
     if kind == "logit" and len(target) == 2:
@@ -1614,6 +1627,188 @@ def spatial_alignment(ppnet, loader, protos_per_image=3, half_size=36, attack=Tr
     out = alignment_summary(torch.cat(ids), torch.cat(stats))
     out["images"] = images
     return out
+
+
+# ------------------------------------------------------------------------------------------------ integrated gradients: the gradient baseline of the faithfulness test
+# Integrated gradients (Sundararajan et al., "Axiomatic Attribution for Deep Networks", 2017): attribution = (x - baseline) times the
+# gradient averaged along the straight path from the baseline to x.  No noise level to pick, and a property that can be checked: the
+# attributions of an image sum to f(x) - f(baseline) (completeness) -- for a model that is continuous along the path; the token
+# reservation's top-k is not, so here the sum rule holds between its jumps and the gap (IntegratedGradients.delta) is reported, not
+# gated.  One step with the end-point rule is plain gradient x input.  The gradients are input_gradient's; between the model's passes
+# ppf_ig_point makes the path point, ppf_ig_accumulate adds the weighted gradient and ppf_ig_finish multiplies by (x - baseline) and sums
+# per grid cell (csrc/ig.hip): no image-sized tensor passes through the host.  The numpy forms below (device=False) are the referees,
+# bit for bit (the contract is in include/ppf_hip.h).  The reference has no such pass.
+GRADIENT_ORDERS = ("ig",)               # opt-in order of faithfulness_curves / faithfulness: the cells ranked by their integrated gradients
+IG_RULES = ("midpoint", "trapezoid", "endpoint")
+IG_DEFAULTS = dict(steps=32, rule="midpoint")
+
+
+def ig_rule(steps, rule="midpoint"):
+    """(alphas fp32 [n], weights fp32 [n]) of a quadrature of the path integral over [0, 1] with S = steps intervals, computed in fp64
+    and cast once.  'midpoint': alphas (s + 0.5) / S, weights 1 / S; 'trapezoid': alphas s / S for s = 0 .. S, weights 1 / (2 S) at both
+    ends and 1 / S inside; 'endpoint': alphas (s + 1) / S, weights 1 / S -- with S = 1 gradient x (x - baseline)."""
+    S = int(steps)
+    if S < 1 or S != steps:
+        raise ValueError(f"ig_rule: steps={steps!r} must be an integer >= 1")
+    if rule == "midpoint":
+        a, w = (np.arange(S, dtype=np.float64) + 0.5) / S, np.full(S, 1.0 / S)
+    elif rule == "trapezoid":
+        a, w = np.arange(S + 1, dtype=np.float64) / S, np.full(S + 1, 1.0 / S)
+        w[0] = w[-1] = 1.0 / (2 * S)
+    elif rule == "endpoint":
+        a, w = (np.arange(S, dtype=np.float64) + 1.0) / S, np.full(S, 1.0 / S)
+    else:
+        raise ValueError(f"ig_rule: rule must be one of {IG_RULES}, got {rule!r}")
+    return a.astype(np.float32), w.astype(np.float32)
+
+
+def ig_point(x, alpha, baseline=0.0, device=True, out=None):
+    """The path point baseline + alpha * (x - baseline), fp32, every operation rounded once.  baseline: a number or a tensor like x.
+    device=True: one ppf_ig_point launch (out: a buffer like x to write into); device=False: numpy."""
+    if device:
+        from . import ops
+        return ops.ig_point(x, alpha, baseline, out=out)
+    x = _host(x, np.float32)
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    with np.errstate(all="ignore"):
+        return (base + np.float32(alpha) * (x - base)).astype(np.float32)
+
+
+def ig_accumulate(g, w, acc, first=False, device=True):
+    """acc = w * g (first) or acc + w * g, fp32, every operation rounded once; acc has g's shape.  device=True: ppf_ig_accumulate in place
+    on the CUDA tensor acc (its rows may lie apart: ops.ig_accumulate), returns it; device=False: numpy, returns a new array (acc is
+    not read when first is set and may be None)."""
+    if device:
+        from . import ops
+        return ops.ig_accumulate(g, w, acc, first)
+    g = _host(g, np.float32)
+    with np.errstate(all="ignore"):
+        wg = (np.float32(w) * g).astype(np.float32)
+        return wg if first else (_host(acc, np.float32) + wg).astype(np.float32)
+
+
+def ig_finish(acc, x, baseline, patch, device=True):
+    """(attr fp32 [B, M, C, H, W], cell64 fp64 [B, M, G]) of acc fp32 [B, M, C, H, W] and x [B, C, H, W]: attr = (x - baseline) * acc in
+    fp32, each operation rounded once; cell64 = the fp64 sum of attr over the channels and the pixels of every patch x patch cell,
+    G = (H / patch) * (W / patch), cells row-major.  device=True: one ppf_ig_finish launch; device=False: numpy (np.sum in fp64)."""
+    if device:
+        from . import ops
+        return ops.ig_finish(acc, x, baseline, patch)
+    acc, x, patch = _host(acc, np.float32), _host(x, np.float32), int(patch)
+    B, M, C, H, W = acc.shape
+    if patch < 1 or H % patch or W % patch or not 1 <= M <= 8 or (H // patch) * (W // patch) > 1024:
+        raise ValueError(f"ig_finish: patch={patch} must divide H={H} and W={W}, M={M} lie in [1, 8] and the grid hold at most 1024 cells")
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    with np.errstate(all="ignore"):
+        attr = ((x - base)[:, None] * acc).astype(np.float32)
+        cells = attr.reshape(B, M, C, H // patch, patch, W // patch, patch).astype(np.float64)
+        return attr, np.sum(cells, axis=(2, 4, 6)).reshape(B, M, -1)
+
+
+class IntegratedGradients:
+    """What integrated_gradients returns, as device tensors (numpy arrays after cpu()): attribution fp32 [B, M, 3, H, W]; cell fp32
+    [B, M, G] = the attribution summed over each grid cell (the fp64 sums rounded once); total fp64 [B, M] = the fp64 cell sums added up,
+    the whole attribution of the image; value, value_base fp32 [B, M] = the target at x and at the baseline image; targets int32 [B, M];
+    alphas, weights fp32 [n] of the rule.  target = ("logit",) or ("proto", branch); steps, rule."""
+    FIELDS = ("attribution", "cell", "total", "value", "value_base", "targets", "alphas", "weights")      # the constructor's order
+
+    def __init__(self, attribution, cell, total, value, value_base, targets, alphas, weights, target, steps, rule):
+        self.attribution, self.cell, self.total, self.value, self.value_base = attribution, cell, total, value, value_base
+        self.targets, self.alphas, self.weights = targets, alphas, weights
+        self.target, self.steps, self.rule = tuple(target), int(steps), str(rule)
+
+    @property
+    def on_host(self):
+        return not isinstance(self.cell, torch.Tensor)
+
+    def delta(self):
+        """The completeness gap fp64 [B, M]: total - (value - value_base), the fp32 values widened first."""
+        if self.on_host:
+            return self.total - (self.value.astype(np.float64) - self.value_base.astype(np.float64))
+        return self.total - (self.value.double() - self.value_base.double())
+
+    def cpu(self):
+        """The same object with numpy arrays: every field in ONE host read."""
+        if self.on_host:
+            return self
+        return IntegratedGradients(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.target, self.steps, self.rule)
+
+
+def _ig_target(ppnet, target, B, device):
+    """(kind, branch, ids int32 [B, M] or None) of integrated_gradients' target; host ids are range-checked as input_gradient checks them."""
+    if target is None:
+        return "logit", None, None
+    kind = target[0] if isinstance(target, (tuple, list)) and target else None
+    if kind == "logit" and len(target) == 2:
+        branch, sel, n_out = None, target[1], ppnet.last_layer.weight.shape[0]
+    elif kind == "proto" and len(target) == 3 and target[1] in EXPLAIN_BRANCHES:
+        branch, sel = target[1], target[2]
+        n_out = ppnet.prototype_vectors.shape[0] if branch == "local" else ppnet.prototype_vectors_global.shape[0]
+    else:
+        raise ValueError('integrated_gradients: target must be None, ("logit", classes) or ("proto", "local" | "global", prototypes)')
+    return kind, branch, _explain_classes(sel, B, n_out, device)
+
+
+def _ig_pass(ppnet, x, outs, kind, branch, ids, steps, rule, baseline, batch_size):
+    """integrated_gradients after the forward of x (outs) and the pick of the targets ids int32 [B, M]."""
+    from . import ops
+    B, M = ids.shape
+    if not 1 <= M <= 8:
+        raise ValueError(f"integrated_gradients: M={M} targets per image outside [1, 8] (ppf_ig_finish's and ppf_cell_order's limit)")
+    G = int(ppnet.num_patches)
+    side = int(round(G ** 0.5))
+    if side * side != G or x.shape[2] % side or x.shape[2] != x.shape[3]:
+        raise ValueError(f"integrated_gradients: a square image and a square grid whose side divides it expected, got {tuple(x.shape)} and G={G}")
+    alphas, weights = ig_rule(steps, rule)
+    if isinstance(baseline, torch.Tensor):
+        baseline = baseline.to(device=x.device, dtype=torch.float32).expand_as(x).contiguous()
+    gather = ids.clamp(min=0).long()                                                              # a row whose class could not be picked (-1) follows class 0
+    out_of = {None: "logits", "local": "act_max", "global": "act_max_global"}[branch]
+    value = outs[out_of].float().gather(1, gather)
+    buf = ops.ig_point(x, 0.0, baseline)                                                          # the baseline image, by the kernel that makes every path point
+    value_base = _eval_outputs(ppnet, buf)[out_of].float().gather(1, gather)
+    acc = torch.empty((B, M) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    bs = int(batch_size or B)
+    cols = [gather[:, m].to(torch.int32) for m in range(M)]
+    for s, (a, w) in enumerate(zip(alphas.tolist(), weights.tolist())):                           # ascending: the order of the sum is the contract
+        ops.ig_point(x, a, baseline, out=buf)
+        for m in range(M):
+            for b0 in range(0, B, bs):
+                sel = cols[m][b0:b0 + bs]
+                g, _ = input_gradient(ppnet, buf[b0:b0 + bs], (kind, sel) if branch is None else (kind, branch, sel))
+                ops.ig_accumulate(g, w, acc[b0:b0 + bs, m], first=s == 0)
+    attr, cell64 = ops.ig_finish(acc, x, baseline, x.shape[2] // side)
+    dev = x.device
+    return IntegratedGradients(attr, cell64.float(), cell64.sum(-1), value, value_base, ids, torch.from_numpy(alphas).to(dev), torch.from_numpy(weights).to(dev),
+                               (kind,) if branch is None else (kind, branch), steps, rule)
+
+
+def integrated_gradients(ppnet, x, target=None, top_classes=1, steps=32, rule="midpoint", baseline=0.0, batch_size=None):
+    """Integrated gradients of a batch x [B, 3, H, W] (CUDA).  target None: the logits of the top `top_classes` classes, picked as
+    explain picks them; ("logit", classes) or ("proto", "local" | "global", prototypes): ids [B] or [B, M], M <= 8, validated as
+    input_gradient validates them.  baseline: the path's start, a number in normalised space (0 = the data-set mean colour) or a tensor
+    like x.  steps, rule: the quadrature (ig_rule); steps=1 with rule='endpoint' is gradient x (x - baseline).
+    One eval forward of x (the class pick and `value`), one of the baseline image (ppf_ig_point at alpha 0: `value_base`), then per step
+    in ascending order one ppf_ig_point launch into the one [B, 3, H, W] buffer and, per target column m and consecutive group of
+    batch_size samples (default B), one input_gradient call and one ppf_ig_accumulate into column m; one ppf_ig_finish at the end.  The
+    grouping depends on batch_size alone, so a result repeats bit for bit.  input_gradient's guard holds: pending parameter gradients
+    are refused and none are left behind; ppnet.precise is honoured; the training mode is left as found.
+    Returns an IntegratedGradients (device tensors; nothing is read back here)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError("integrated_gradients needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path; ig_point / ig_accumulate / ig_finish with "
+                           "device=False are the host referees)")
+    ig_rule(steps, rule)                                                                          # a bad rule is refused before anything runs
+    _refuse_pending_gradients("integrated_gradients", ppnet)
+    x = x.detach().float().contiguous()
+    kind, branch, ids = _ig_target(ppnet, target, x.shape[0], x.device)
+    M = int(top_classes) if ids is None else ids.shape[1]
+    if not 1 <= M <= 8:
+        raise ValueError(f"integrated_gradients: M={M} targets per image outside [1, 8] (ppf_ig_finish's and ppf_cell_order's limit)")
+    with torch.no_grad():
+        outs = _eval_outputs(ppnet, x)
+        if ids is None:
+            ids = _pick_classes(ppnet, outs, None, top_classes, x.shape[0])
+        return _ig_pass(ppnet, x, outs, kind, branch, ids, steps, rule, baseline, batch_size)
 
 
 # ------------------------------------------------------------------------------------------------ "this looks like that, because ...": colour, texture or shape?

@@ -819,6 +819,67 @@ def because_score(act_max, protos, grid_cells=0, *, act_full=None, idx=None, cel
     return same, best, lost
 
 
+# ---- integrated gradients (csrc/ig.hip): the path point, the weighted gradient sum, attribution and its cell sums
+def _ig_baseline(who, baseline, like):
+    if isinstance(baseline, torch.Tensor):
+        return _dev_tensor(who, "baseline", baseline, torch.float32, like.shape, like.device), 0.0
+    return None, float(baseline)
+
+
+def ig_point(x, alpha, baseline=0.0, out=None):
+    """out = baseline + alpha * (x - baseline), every operation rounded once (ppf_ig_point, include/ppf_hip.h); one launch.  x: an fp32
+    CUDA tensor of any shape; baseline: a number, or an fp32 tensor like x; out: an fp32 tensor like x to write into."""
+    who = "ig_point"
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    base_t, base_c = _ig_baseline(who, baseline, x)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _dev_tensor(who, "out", out, torch.float32, x.shape, x.device)
+    _lib.call("ppf_ig_point", x, base_t, base_c, float(alpha), x.numel(), out)
+    return out
+
+
+def ig_accumulate(g, w, acc, first=False):
+    """acc (+)= w * g IN PLACE (ppf_ig_accumulate, include/ppf_hip.h); one launch.  g fp32 [R, ...] contiguous; acc: an fp32 tensor of g's
+    shape whose rows acc[r] are contiguous and lie acc.stride(0) >= g[0].numel() elements apart -- a contiguous tensor, or one class
+    column acc_all[:, m] of a [B, M, ...] accumulator.  first=True writes w * g without reading acc.  Returns acc."""
+    who = "ig_accumulate"
+    if not isinstance(g, torch.Tensor) or g.dim() < 1:
+        raise ValueError(f"{who}: g must be an fp32 CUDA tensor [R, ...]")
+    _dev_tensor(who, "g", g, torch.float32, g.shape)
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.device != g.device or acc.dtype != torch.float32 or acc.shape != g.shape:
+        raise ValueError(f"{who}: acc must be an fp32 CUDA tensor {list(g.shape)} on {g.device}")
+    R = g.shape[0]
+    n = g.numel() // R if R else 0
+    stride = acc.stride(0) if R > 1 else n
+    if R and (not acc[0].is_contiguous() or stride < n):
+        raise ValueError(f"{who}: the rows of acc must be contiguous and at least {n} elements apart, got strides {tuple(acc.stride())}")
+    _lib.call("ppf_ig_accumulate", g, float(w), int(bool(first)), R, n, acc, stride)
+    return acc
+
+
+def ig_finish(acc, x, baseline, patch):
+    """(attr fp32 [B, M, C, H, W], cell64 fp64 [B, M, G]) from the averaged gradients acc fp32 [B, M, C, H, W] and x fp32 [B, C, H, W]:
+    attr = (x - baseline) * acc and its fp64 sum over every patch x patch cell and the channels, G = (H / patch) * (W / patch), cells
+    row-major (ppf_ig_finish, include/ppf_hip.h); one launch, one pass."""
+    who = "ig_finish"
+    if not isinstance(acc, torch.Tensor) or acc.dim() != 5:
+        raise ValueError(f"{who}: acc must be an fp32 CUDA tensor [B, M, C, H, W]")
+    _dev_tensor(who, "acc", acc, torch.float32, acc.shape)
+    B, M, C, H, W = acc.shape
+    _dev_tensor(who, "x", x, torch.float32, (B, C, H, W), acc.device)
+    base_t, base_c = _ig_baseline(who, baseline, x)
+    patch = int(patch)
+    G = (H // patch) * (W // patch) if patch > 0 else 0
+    attr = torch.empty_like(acc)
+    cell64 = torch.empty((B, M, G), dtype=torch.float64, device=acc.device)
+    _lib.call("ppf_ig_finish", acc, x, base_t, base_c, B, M, C, H, W, patch, attr, cell64)
+    return attr, cell64
+
+
 # ---- spatial alignment (csrc/alignment.hip): the image gradient's last step, gradient mass inside a box, the attack's step
 def col2im_patch(cols, B, C, H, W, patch):
     """img fp32 [B, C, H, W] from cols fp32 [B*(H/patch)*(W/patch), C*patch*patch]: the inverse of im2col_patch / im2col_patch_f32
