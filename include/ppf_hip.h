@@ -651,6 +651,91 @@ int ppf_copy_2d(void* dst, int64_t dst_pitch, const void* src, int64_t src_pitch
  * rects == NULL: no erasing); mean3 / std3 are HOST pointers; state_u64 (device, optional) = step counter mixed into the noise key. */
 int ppf_image_finish_u8(const void* in_u8_hwc, float* out_nchw, int B, int H, int W, const float* mean3, const float* std3,
                         const int* rects, uint64_t seed, const void* state_u64, ppf_stream_t stream);
+/* Device-resident data sets (protopformer_amd/csrc/device_data.hip): the decoded originals stay on the device as one flat uint8 buffer of HWC frames and
+ * every batch is cropped, flipped and augmented there, bit-equal to Pillow (the CPU path of data.build_transform: tools/datasets.py:280-336
+ * with timm's RandomResizedCropAndInterpolation, RandomHorizontalFlip and rand-m9-mstd0.5-inc1).  The host draws, the device applies.
+ * Additions of ABI 10: no existing entry point changed.  This file is compiled without floating-point contraction.
+ *
+ * ppf_resize_crop_u8: out uint8 [B][H][W][3] = PIL Image.resize((ow, oh), filter, box) of sample b's frame, cropped to the window
+ * rows [y0, y0 + H) x columns [x0, x0 + W) of that (oh, ow) result, then mirrored left-right when the flag is set.  Only the window is
+ * computed.  The plan is fp64 [B][PPF_RC_WORDS] = (frame offset in bytes into flat, frame h, w, box x0, y0, x1, y1, oh, ow, window y0,
+ * x0, mirror).  plan_host is a HOST copy read during the call only: every sample is validated on it (the frame inside flat_bytes, the box
+ * inside the frame and not empty, the window inside (oh, ow)) before anything is launched; plan_dev is the same table on the device.
+ * Arithmetic, per axis (x: in0 = box x0, in1 = box x1, size = w, out = ow; y likewise), all of it Pillow's 8-bit resample:
+ *   scale = (in1 - in0) / out, filterscale = max(1, scale), support = S * filterscale, ss = 1 / filterscale            (fp64)
+ *   filter 3 (BICUBIC): S = 2, the weight below; filter 2 (BILINEAR, the square view of interp_eval): S = 1, weight max(0, 1 - |x|)
+ *   for output coordinate xx: center = in0 + (xx + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)),
+ *     xmax = min(size, (int)(center + support + 0.5))  -- the taps clamp at the FRAME, not at the box
+ *   w_t = bicubic(((t + xmin) - center + 0.5) * ss) for t = 0 .. xmax - xmin - 1 with a = -0.5:
+ *     |x| < 1: ((a + 2) |x| - (a + 3)) |x| |x| + 1;  |x| < 2: (((|x| - 5) |x| + 8) |x| - 4) a;  else 0
+ *   ww = sum of w_t in tap order; w_t /= ww when ww != 0; k_t = (int)(w_t < 0 ? -0.5 + w_t * 2^22 : 0.5 + w_t * 2^22)
+ *   The fp64 part runs on the device, one thread per output coordinate, IEEE + - * / only, no contraction.
+ *   value = clip8((2^21 + sum_t p_t * k_t) >> 22) in int32, clip8 clamping to [0, 255].
+ * The horizontal pass comes first over the source rows the window's vertical taps need; its result is rounded to uint8 (in the
+ * workspace); the vertical pass runs over those rows.  workspace: ppf_resize_crop_workspace_bytes(plan_host, B, H, W, filter, flat_bytes) bytes,
+ * 16-byte aligned (0 and ppf_last_error() for an invalid plan).  Limits: B, H, W >= 1, H, W, oh, ow <= 16384, at most 1024 taps per axis.
+ *
+ * RandAugment on uint8 [B][H][W][3] frames.  The plan is fp64 [B][PPF_AUG_SLOTS][PPF_AUG_WORDS] = (op, resample, p0 .. p5) on the device;
+ * every entry point works on one slot, reads `in` and writes `out` (never in place) for the samples whose op is its own and leaves
+ * the other samples of `out` alone.  op = index into data.RandAugment.OPS (PPF_AUG_*), PPF_AUG_SKIP = copy.  An op out of range copies.
+ *   ppf_aug_hist       hist int32 [B][3][256] (zeroed by the call, integer atomics, exact at any launch shape): per-channel counts for
+ *                      AutoContrast and Equalize; for ContrastIncreasing the counts of L = (19595 R + 38470 G + 7471 B + 2^15) >> 16 in
+ *                      channel 0.  Other samples' counters stay zero.
+ *   ppf_aug_lut_build  lut uint8 [B][3][256] of the table ops (other samples' tables are not written):
+ *                      AutoContrast: lo / hi = first / last non-empty bin; hi <= lo: identity; else scale = 255.0 / (hi - lo),
+ *                        offset = -lo * scale, lut[i] = clamp((int)(i * scale + offset), 0, 255)                       (fp64)
+ *                      Equalize: with fewer than two non-empty bins or step = (H*W - hist[last non-empty]) / 255 == 0: identity; else
+ *                        lut[i] = min(255, (step / 2 + sum_{j < i} hist[j]) / step)                                     (integer)
+ *                      Invert 255 - i; Posterize i & ~(2^(8 - p0) - 1); Solarize i < p0 ? i : 255 - i; SolarizeAdd i < 128 ?
+ *                        min(255, i + p0) : i; Brightness blend(0, i, p0); Contrast blend(m, i, p0) with
+ *                        m = (int)(sum of L / (double)(H*W) + 0.5).
+ *   blend(a, b, f)     Image.blend: alpha = (float)f; t = (float)a + alpha * (float)(b - a) in fp32, two roundings; 0 <= alpha <= 1:
+ *                      (uint8)t (truncation); else t <= 0 -> 0, t >= 255 -> 255, else truncation.
+ *   ppf_aug_apply      table ops: out = lut[channel][in]; ColorIncreasing: out = blend(L, in, p0) with the pixel's own L; skip: copy.
+ *   ppf_aug_sharpness  SharpnessIncreasing: out = blend(s, in, p0), s = ImageFilter.SMOOTH: the one-pixel border (and every pixel when
+ *                      H < 3 or W < 3) is the input; inside t = 0.5f, then for rows y + 1, y, y - 1 in this order
+ *                      t += (in[x-1] * k0 + in[x] * k1 + in[x+1] * k2) in fp32 with k = 1.0f/13.0f, the centre 5.0f/13.0f;
+ *                      t <= 0 -> 0, t >= 255 -> 255, else truncation.
+ *   ppf_aug_affine     Rotate, ShearX, ShearY, TranslateXRel, TranslateYRel: Image.transform(AFFINE, (p0 .. p5), resample, fill).  The
+ *                      matrix comes from the host (the rotation's sine and cosine as Image.rotate rounds them); the device uses no
+ *                      transcendental.  Per output pixel, in fp64: xin = p0 * (x + 0.5) + p1 * (y + 0.5) + p2, yin = p3 * (x + 0.5) +
+ *                      p4 * (y + 0.5) + p5; outside [0, W) x [0, H): the fill colour; else xin -= 0.5, yin -= 0.5, xf = floor(xin),
+ *                      dx = xin - xf (y likewise); column and row indices clamp to the frame.
+ *                      resample 2 (BILINEAR): row value a + (b - a) * dx over columns xf, xf + 1; rows yf and yf + 1 (a row outside
+ *                        the frame repeats the previous row's value); v = v1 + (v2 - v1) * dy.
+ *                      resample 3 (BICUBIC): c(v1, v2, v3, v4, d) = v2 + d * ((-v1 + v3) + d * ((2 * (v1 - v2) + v3 - v4) + d *
+ *                        (-v1 + v2 - v3 + v4))) over columns xf - 1 .. xf + 2, then over rows yf - 1 .. yf + 2 (row yf - 1 clamps
+ *                        into the frame, each later row outside the frame repeats the previous row's value).
+ *                      Both filters: v <= 0 -> 0, v >= 255 -> 255, else truncation (no rounding). */
+#define PPF_RC_WORDS 12
+#define PPF_AUG_WORDS 8
+#define PPF_AUG_SLOTS 2
+#define PPF_AUG_SKIP (-1)
+#define PPF_AUG_AUTOCONTRAST 0
+#define PPF_AUG_EQUALIZE 1
+#define PPF_AUG_INVERT 2
+#define PPF_AUG_ROTATE 3
+#define PPF_AUG_POSTERIZE 4
+#define PPF_AUG_SOLARIZE 5
+#define PPF_AUG_SOLARIZE_ADD 6
+#define PPF_AUG_COLOR 7
+#define PPF_AUG_CONTRAST 8
+#define PPF_AUG_BRIGHTNESS 9
+#define PPF_AUG_SHARPNESS 10
+#define PPF_AUG_SHEAR_X 11
+#define PPF_AUG_SHEAR_Y 12
+#define PPF_AUG_TRANSLATE_X 13
+#define PPF_AUG_TRANSLATE_Y 14
+size_t ppf_resize_crop_workspace_bytes(const double* plan_host, int B, int H, int W, int filter, int64_t flat_bytes);
+int ppf_resize_crop_u8(const void* flat_u8, int64_t flat_bytes, const double* plan_host, const double* plan_dev, int B, int H, int W,
+                       int filter, void* workspace, size_t workspace_bytes, void* out_u8, ppf_stream_t stream);
+int ppf_aug_hist(const void* in_u8, const double* plan_dev, int slot, int B, int H, int W, int* hist, ppf_stream_t stream);
+int ppf_aug_lut_build(const int* hist, const double* plan_dev, int slot, int B, int H, int W, void* lut_u8, ppf_stream_t stream);
+int ppf_aug_apply(const void* in_u8, const double* plan_dev, int slot, const void* lut_u8, int B, int H, int W, void* out_u8,
+                  ppf_stream_t stream);
+int ppf_aug_sharpness(const void* in_u8, const double* plan_dev, int slot, int B, int H, int W, void* out_u8, ppf_stream_t stream);
+int ppf_aug_affine(const void* in_u8, const double* plan_dev, int slot, int B, int H, int W, int fill_r, int fill_g, int fill_b,
+                   void* out_u8, ppf_stream_t stream);
 /* Mixup / CutMix of the device batch (timm 0.5.4 Mixup, tools/engine_proto.py:47-48, main.py:325-335).  The per-sample parameter
  * table is int32 [B][PPF_MIX_WORDS]: kind (0 untouched, 1 blend, 2 box paste), the box rows [yl, yh) and columns [xl, xh), and two
  * fp32 weights stored as their bits.  Sample i is mixed with sample j = B-1-i as it was before the call:

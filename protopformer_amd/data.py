@@ -249,9 +249,29 @@ class RandAugment:
     def _neg(self, v):
         return -v if self.rng.random() > 0.5 else v
 
-    def _apply(self, name, img, mag):
+    def _draw_op(self, name, mag):
+        """(name, signed parameter, resample filter) of one op at magnitude `mag`: the resample choice is drawn first, then the sign."""
         lv = mag / 10.0
         resample = self.rng.choice((Image.BILINEAR, Image.BICUBIC))
+        if name in ("AutoContrast", "Equalize", "Invert"):
+            return name, 0.0, resample
+        if name == "Rotate":
+            return name, self._neg(lv * 30.0), resample
+        if name == "PosterizeIncreasing":
+            return name, max(1, 4 - int(lv * 4)), resample
+        if name == "SolarizeIncreasing":
+            return name, 256 - int(lv * 256), resample
+        if name == "SolarizeAdd":
+            return name, int(lv * 110), resample
+        if name in ("ColorIncreasing", "ContrastIncreasing", "BrightnessIncreasing", "SharpnessIncreasing"):
+            return name, max(0.1, 1.0 + self._neg(lv * 0.9)), resample
+        if name in ("ShearX", "ShearY"):
+            return name, self._neg(lv * 0.3), resample
+        if name in ("TranslateXRel", "TranslateYRel"):
+            return name, self._neg(lv * self.translate_pct), resample
+        raise KeyError(name)
+
+    def _apply_drawn(self, name, param, resample, img):
         if name == "AutoContrast":
             return ImageOps.autocontrast(img)
         if name == "Equalize":
@@ -259,37 +279,51 @@ class RandAugment:
         if name == "Invert":
             return ImageOps.invert(img)
         if name == "Rotate":
-            return img.rotate(self._neg(lv * 30.0), resample=resample, fillcolor=self.fill)
+            return img.rotate(param, resample=resample, fillcolor=self.fill)
         if name == "PosterizeIncreasing":
-            return ImageOps.posterize(img, max(1, 4 - int(lv * 4))) if 4 - int(lv * 4) < 8 else img
+            return ImageOps.posterize(img, param)
         if name == "SolarizeIncreasing":
-            return ImageOps.solarize(img, 256 - int(lv * 256))
+            return ImageOps.solarize(img, param)
         if name == "SolarizeAdd":
-            add, thresh = int(lv * 110), 128
-            lut = [min(255, i + add) if i < thresh else i for i in range(256)]
+            lut = [min(255, i + param) if i < 128 else i for i in range(256)]
             return img.point(lut * 3)
         if name in ("ColorIncreasing", "ContrastIncreasing", "BrightnessIncreasing", "SharpnessIncreasing"):
-            f = max(0.1, 1.0 + self._neg(lv * 0.9))
             enh = {"Color": ImageEnhance.Color, "Contrast": ImageEnhance.Contrast, "Brightness": ImageEnhance.Brightness,
                    "Sharpness": ImageEnhance.Sharpness}[name[:-len("Increasing")]]
-            return enh(img).enhance(f)
+            return enh(img).enhance(param)
         if name == "ShearX":
-            return img.transform(img.size, Image.AFFINE, (1, self._neg(lv * 0.3), 0, 0, 1, 0), resample=resample, fillcolor=self.fill)
+            return img.transform(img.size, Image.AFFINE, (1, param, 0, 0, 1, 0), resample=resample, fillcolor=self.fill)
         if name == "ShearY":
-            return img.transform(img.size, Image.AFFINE, (1, 0, 0, self._neg(lv * 0.3), 1, 0), resample=resample, fillcolor=self.fill)
+            return img.transform(img.size, Image.AFFINE, (1, 0, 0, param, 1, 0), resample=resample, fillcolor=self.fill)
         if name == "TranslateXRel":
-            return img.transform(img.size, Image.AFFINE, (1, 0, self._neg(lv * self.translate_pct) * img.size[0], 0, 1, 0), resample=resample, fillcolor=self.fill)
+            return img.transform(img.size, Image.AFFINE, (1, 0, param * img.size[0], 0, 1, 0), resample=resample, fillcolor=self.fill)
         if name == "TranslateYRel":
-            return img.transform(img.size, Image.AFFINE, (1, 0, 0, 0, 1, self._neg(lv * self.translate_pct) * img.size[1]), resample=resample, fillcolor=self.fill)
+            return img.transform(img.size, Image.AFFINE, (1, 0, 0, 0, 1, param * img.size[1]), resample=resample, fillcolor=self.fill)
         raise KeyError(name)
 
-    def __call__(self, img):
+    def _apply(self, name, img, mag):
+        return self._apply_drawn(*self._draw_op(name, mag), img)
+
+    def draw(self):
+        """The plan of one image: per slot (op name or None when the slot is skipped, signed parameter, resample filter).  The calls on
+        `rng` are those __call__ always made, in its order: the names, then per op the skip draw, the magnitude, the resample choice, the sign."""
+        plan = []
         for name in [self.rng.choice(self.OPS) for _ in range(self.n)]:
             if self.rng.random() > 0.5:
+                plan.append((None, 0.0, Image.BILINEAR))
                 continue
             mag = self.m if self.mstd <= 0 else self.rng.gauss(self.m, self.mstd)
-            img = self._apply(name, img, min(10.0, max(0.0, mag)))
+            plan.append(self._draw_op(name, min(10.0, max(0.0, mag))))
+        return plan
+
+    def apply(self, plan, img):
+        for name, param, resample in plan:
+            if name is not None:
+                img = self._apply_drawn(name, param, resample, img)
         return img
+
+    def __call__(self, img):
+        return self.apply(self.draw(), img)
 
 
 class ToUint8HWC:
@@ -377,7 +411,8 @@ class GpuFinisher:
         self.seed = torch.initial_seed() if seed is None else int(seed)
         self.step = 0
 
-    def __call__(self, frames_u8, out=None):
+    def __call__(self, frames_u8, out=None, rects=None):
+        """rects: int32 [B, 4] erase rectangles drawn by the caller (DeviceAugLoader draws them per sample); None: drawn here."""
         from . import _lib
         if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8:
             raise RuntimeError("GpuFinisher needs a uint8 CUDA tensor [B, H, W, 3] (no CPU fallback path)")
@@ -385,9 +420,10 @@ class GpuFinisher:
         assert C == 3 and frames_u8.is_contiguous()
         if out is None:
             out = torch.empty((B, 3, H, W), dtype=torch.float32, device=frames_u8.device)
-        rects = state = None
+        state = None
         if self.re_prob > 0:
-            rects = torch.from_numpy(random_erasing_rects(B, H, W, self.re_prob, rng=self.rng)).to(frames_u8.device, non_blocking=True)
+            rects = random_erasing_rects(B, H, W, self.re_prob, rng=self.rng) if rects is None else np.ascontiguousarray(rects, dtype=np.int32).reshape(B, 4)
+            rects = torch.from_numpy(rects).to(frames_u8.device, non_blocking=True)
             state = torch.tensor([self.step], dtype=torch.int64, device=frames_u8.device)
             self.step += 1
         _lib.call("ppf_image_finish_u8", frames_u8, out, B, H, W, self.mean.ctypes.data, self.std.ctypes.data, rects, self.seed & 0xFFFFFFFFFFFFFFFF, state)
@@ -408,7 +444,7 @@ class DeviceLoader:
         self.loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle if sampler is None else False, sampler=sampler,
                                                   num_workers=num_workers, drop_last=drop_last, pin_memory=pin_memory and torch.cuda.is_available(),
                                                   collate_fn=_collate_u8)
-        self.device, self.finisher, self.sampler = device, finisher, sampler
+        self.device, self.finisher, self.sampler, self.dataset = device, finisher, sampler, dataset
 
     def __len__(self):
         return len(self.loader)
@@ -419,6 +455,166 @@ class DeviceLoader:
             yield (x, target.to(self.device, non_blocking=True).long(), *rest)
 
 
+def _collate_list(batch):
+    return batch
+
+
+def device_data_enabled(args):
+    """The switch of the device-resident path: args.device_data when it is set, else the environment variable PPF_DEVICE_DATA (set to
+    something other than 0).  Off by default."""
+    v = getattr(args, "device_data", None)
+    if v is None:
+        return os.environ.get("PPF_DEVICE_DATA", "0") not in ("", "0")
+    return bool(v)
+
+
+class DeviceDataset:
+    """The decoded originals of a Cub2011 / StanfordCars / Dogs on the device: one pass with ToUint8HWC as the only transform (CPU workers
+    decode, nothing is decoded again), then one flat uint8 buffer of HWC frames, an int64 offset table, an int32 (h, w) table, the labels
+    and, for a data set with return_id, the image ids.  Every rank holds the whole set; samplers keep working on the indices."""
+
+    def __init__(self, dataset, device, num_workers=0, max_bytes=64 << 30):
+        import copy
+        import time
+        t0 = time.perf_counter()
+        ds = copy.copy(dataset)
+        ds.transform = ToUint8HWC()
+        with_ids = bool(getattr(ds, "return_id", False))
+        frames, labels, ids, total = [], [], [], 0
+        loader = torch.utils.data.DataLoader(ds, batch_size=16, shuffle=False, num_workers=num_workers, collate_fn=_collate_list)
+        for batch in loader:
+            for item in batch:
+                a = np.asarray(item[0])
+                total += a.size
+                if total > max_bytes:
+                    est = int(total / (len(frames) + 1) * len(ds))
+                    raise RuntimeError(f"DeviceDataset: the decoded frames need about {est} bytes ({total} after {len(frames) + 1} of {len(ds)} images), "
+                                       f"max_bytes is {max_bytes}; there is no fallback: raise max_bytes or use the CPU loader")
+                frames.append(a)
+                labels.append(int(item[1]))
+                if with_ids:
+                    ids.append(int(item[2]))
+        if not frames:
+            raise RuntimeError("DeviceDataset: the data set is empty")
+        self.sizes_host = np.array([f.shape[:2] for f in frames], dtype=np.int32)
+        nbytes = self.sizes_host[:, 0].astype(np.int64) * self.sizes_host[:, 1] * 3
+        self.offsets_host = np.concatenate(([0], np.cumsum(nbytes)[:-1])).astype(np.int64)
+        self.device = torch.device(device)
+        self.flat = torch.empty(int(nbytes.sum()), dtype=torch.uint8, device=self.device)
+        for k in range(0, len(frames), 256):                  # uploaded in runs of 256 frames
+            run = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames[k:k + 256]]))
+            self.flat[int(self.offsets_host[k]):int(self.offsets_host[k]) + run.numel()].copy_(run)
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.sizes = torch.from_numpy(self.sizes_host).to(self.device)
+        self.labels_host = np.array(labels, dtype=np.int64)
+        self.labels = torch.from_numpy(self.labels_host).to(self.device)
+        self.ids_host = np.array(ids, dtype=np.int64) if with_ids else None
+        self.ids = torch.from_numpy(self.ids_host).to(self.device) if with_ids else None
+        self.dataset = dataset
+        self.decode_seconds = time.perf_counter() - t0
+
+    def __len__(self):
+        return len(self.labels_host)
+
+
+class DeviceAugLoader:
+    """Batches from a DeviceDataset, produced on the device: yields what DeviceLoader yields.  train: RandomResizedCrop + flip (one
+    ppf_resize_crop_u8 launch chain), RandAugment (ppf_aug_*), then the finisher with its RandomErasing; eval: Resize(256/224 * size) +
+    CenterCrop (`square`: the plain bilinear (size, size) resize of build_view_transform).  The host draws, once per sample in sampler order,
+    RandomResizedCrop.get_params, the flip, RandAugment.draw and random_erasing_rects from one random.Random seeded from (seed, epoch,
+    rank): an epoch is a function of those three and the sampler's order, whatever the batch size.  The plan of the next batch is drawn
+    while the current one runs; host_seconds holds the draw time per batch."""
+
+    def __init__(self, device_dataset, batch_size, finisher, train, args, shuffle=False, sampler=None, drop_last=False, seed=0, square=False,
+                 keep_plans=False):
+        self.dd, self.batch_size, self.finisher, self.train, self.sampler = device_dataset, int(batch_size), finisher, bool(train), sampler
+        self.shuffle, self.drop_last, self.seed, self.square, self.keep_plans = shuffle and sampler is None, drop_last, int(seed), square, keep_plans
+        self.dataset, self.device, self.size = device_dataset.dataset, device_dataset.device, int(args.input_size)
+        self.epoch, self.rank = 0, int(getattr(sampler, "rank", 0))
+        self.host_seconds, self.plans, self._ws = [], [], None
+        self.aa = None
+        if self.train:
+            if getattr(args, "train_interpolation", "bicubic") != "bicubic":
+                raise NotImplementedError("DeviceAugLoader: the train crop is bicubic (train_interpolation of the reference's scripts)")
+            aa = getattr(args, "aa", "rand-m9-mstd0.5-inc1")
+            self.aa = aa if aa and aa != "none" else None
+        if self.size <= 32:
+            raise NotImplementedError("the CIFAR-sized (input_size <= 32) branch is not on the ProtoPFormer path")
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+        if hasattr(self.sampler, "set_epoch"):
+            self.sampler.set_epoch(epoch)
+
+    def __len__(self):
+        n = len(self.sampler) if self.sampler is not None else len(self.dd)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _order(self):
+        if self.sampler is not None:
+            return [int(i) for i in self.sampler]
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch)
+            return torch.randperm(len(self.dd), generator=g).tolist()
+        return list(range(len(self.dd)))
+
+    def _plan(self, idx, rrc, ra, rng):
+        """The host's share of one batch: the resize table, the RandAugment draws and the erase rectangles of samples idx."""
+        import time
+        t0 = time.perf_counter()
+        S, dd = self.size, self.dd
+        boxes, outs, wins, mirror, draws = [], [], [], [], []
+        rects = np.zeros((len(idx), 4), dtype=np.int32)
+        for j, i in enumerate(idx):
+            h, w = (int(v) for v in dd.sizes_host[i])
+            if self.train:
+                top, left, ch, cw = rrc.get_params(w, h)
+                boxes.append((left, top, left + cw, top + ch))
+                outs.append((S, S))
+                wins.append((0, 0))
+                mirror.append(1 if rng.random() < 0.5 else 0)
+                draws.append(ra.draw() if ra is not None else [])
+                if self.finisher.re_prob > 0:
+                    rects[j] = random_erasing_rects(1, S, S, self.finisher.re_prob, rng=rng)[0]
+            else:
+                oh, ow, y0, x0 = (S, S, 0, 0) if self.square else eval_geometry(h, w, int((256 / 224) * S), S)
+                boxes.append((0, 0, w, h))
+                outs.append((oh, ow))
+                wins.append((y0, x0))
+                mirror.append(0)
+        plan = {"idx": np.asarray(idx, dtype=np.int64), "resize": resize_plan(dd.offsets_host[idx], dd.sizes_host[idx], boxes, outs, wins, mirror),
+                "draws": draws, "aug": aug_plan(draws, S, S) if self.aa and self.train else None, "rects": rects}
+        self.host_seconds.append(time.perf_counter() - t0)
+        return plan
+
+    def __iter__(self):
+        order = self._order()
+        nb = len(order) // self.batch_size if self.drop_last else -(-len(order) // self.batch_size)
+        rng = random.Random(f"{self.seed}:{self.epoch}:{self.rank}")
+        rrc = RandomResizedCrop(self.size, rng=rng) if self.train else None
+        ra = RandAugment(self.aa, img_size=self.size, rng=rng) if self.aa else None
+        fill = ra.fill if ra is not None else (0, 0, 0)
+        filt = Image.BILINEAR if self.square and not self.train else Image.BICUBIC
+        chunk = lambda k: order[k * self.batch_size:(k + 1) * self.batch_size]
+        plan = self._plan(chunk(0), rrc, ra, rng) if nb else None
+        for k in range(nb):
+            S = self.size
+            need = int(resize_workspace_bytes(plan["resize"], S, S, filt, self.dd.flat.numel()))
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            frames = resize_crop(self.dd.flat, plan["resize"], S, S, device=True, workspace=self._ws, filter=filt)
+            if plan["aug"] is not None:
+                frames = randaugment_apply(frames, plan["aug"], fill, device=True)
+            x = self.finisher(frames, rects=plan["rects"] if self.train else None)
+            idx = torch.from_numpy(plan["idx"]).to(self.device)
+            rest = (torch.from_numpy(self.dd.ids_host[plan["idx"]]),) if self.dd.ids_host is not None else ()
+            batch = (x, self.dd.labels[idx], *rest)
+            if self.keep_plans:
+                self.plans.append(plan)
+            plan = self._plan(chunk(k + 1), rrc, ra, rng) if k + 1 < nb else None      # drawn while the device works on batch k
+            yield batch
+
+
 def build_loaders(args, device):
     """main.py:281-316: train loader (shuffled / DistributedSampler, drop_last) and validation loader (batch 1.5x, sequential)."""
     import torch.distributed as dist
@@ -427,10 +623,338 @@ def build_loaders(args, device):
     sampler = None
     if dist.is_initialized() and dist.get_world_size() > 1:
         sampler = torch.utils.data.DistributedSampler(ds_train, num_replicas=dist.get_world_size(), rank=dist.get_rank(), shuffle=True)
+    if device_data_enabled(args):                       # opt-in: the originals resident on the device, every batch produced there
+        workers, seed = getattr(args, "num_workers", 10), getattr(args, "seed", 0)
+        train = DeviceAugLoader(DeviceDataset(ds_train, device, num_workers=workers), args.batch_size, GpuFinisher(re_prob=getattr(args, "reprob", 0.25)),
+                                True, args, shuffle=sampler is None, sampler=sampler, drop_last=True, seed=seed)
+        val = DeviceAugLoader(DeviceDataset(ds_val, device, num_workers=workers), int(1.5 * args.batch_size), GpuFinisher(re_prob=0.0), False, args, seed=seed)
+        return train, val, nb
     train = DeviceLoader(ds_train, args.batch_size, device, GpuFinisher(re_prob=getattr(args, "reprob", 0.25)), shuffle=sampler is None, sampler=sampler,
                          num_workers=getattr(args, "num_workers", 10), drop_last=True)
     val = DeviceLoader(ds_val, int(1.5 * args.batch_size), device, GpuFinisher(re_prob=0.0), num_workers=getattr(args, "num_workers", 10))
     return train, val, nb
+
+
+# ------------------------------------------------------------------------------------------------ device-resident data sets
+# The originals are decoded once and stay on the device; every batch is cropped, flipped and augmented there by csrc/device_data.hip.
+# The host only draws (the transform classes above, so the distribution is theirs by construction) and packs the draws into two small
+# fp64 tables.  Every function below has a numpy referee (device=False) that is bit-equal to Pillow; the kernels are bit-equal to the
+# referee.  The arithmetic contract is written out in include/ppf_hip.h.
+RC_WORDS, AUG_WORDS, AUG_SLOTS = 12, 8, 2             # PPF_RC_WORDS / PPF_AUG_WORDS / PPF_AUG_SLOTS of the header
+AUG_SKIP = -1
+_AFFINE_OPS = ("Rotate", "ShearX", "ShearY", "TranslateXRel", "TranslateYRel")
+
+
+def resize_plan(offsets, sizes, boxes, out_sizes, windows, mirror):
+    """fp64 [B][RC_WORDS] = (frame offset in bytes, h, w, box x0, y0, x1, y1, full output oh, ow, window y0, x0, mirror) per sample."""
+    B = len(offsets)
+    plan = np.zeros((B, RC_WORDS), dtype=np.float64)
+    plan[:, 0] = np.asarray(offsets, dtype=np.float64)
+    plan[:, 1:3] = np.asarray(sizes, dtype=np.float64).reshape(B, 2)
+    plan[:, 3:7] = np.asarray(boxes, dtype=np.float64).reshape(B, 4)
+    plan[:, 7:9] = np.asarray(out_sizes, dtype=np.float64).reshape(B, 2)
+    plan[:, 9:11] = np.asarray(windows, dtype=np.float64).reshape(B, 2)
+    plan[:, 11] = np.asarray(mirror, dtype=np.float64)
+    return plan
+
+
+def eval_geometry(h, w, size, crop):
+    """(oh, ow, y0, x0): Resize(size)'s output size for an h x w frame and CenterCrop(crop)'s window in it."""
+    if w < h:
+        oh, ow = int(size * h / w), size
+    elif (w <= h and w == size) or (h <= w and h == size):
+        oh, ow = h, w
+    else:
+        oh, ow = size, int(size * w / h)
+    return oh, ow, int(round((oh - crop) / 2.0)), int(round((ow - crop) / 2.0))
+
+
+def _bicubic_weight(x):
+    x = np.abs(x)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+def _bilinear_weight(x):
+    x = np.abs(x)
+    return np.where(x < 1.0, 1.0 - x, 0.0)
+
+
+_RESAMPLE = {Image.BICUBIC: (2.0, _bicubic_weight), Image.BILINEAR: (1.0, _bilinear_weight)}
+
+
+def resample_taps(in_size, in0, in1, out_size, first, count, filter=Image.BICUBIC):
+    """Pillow's 8-bit taps of output coordinates first .. first + count - 1 of one axis: [(xmin, int32 weights)]."""
+    fsupport, weight = _RESAMPLE[filter]
+    scale = filterscale = (in1 - in0) / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support, ss = fsupport * filterscale, 1.0 / filterscale
+    taps = []
+    for xx in range(first, first + count):
+        center = in0 + (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        w = weight((np.arange(xmin, xmax) - center + 0.5) * ss)
+        ww = 0.0
+        for v in w:                                     # summed in tap order
+            ww += v
+        if ww != 0.0:
+            w = w / ww
+        taps.append((xmin, np.where(w < 0, -0.5 + w * 4194304.0, 0.5 + w * 4194304.0).astype(np.int32)))
+    return taps
+
+
+def _resize_crop_np(flat, plan, H, W, filter):
+    out = np.empty((len(plan), H, W, 3), dtype=np.uint8)
+    for b, p in enumerate(plan):
+        off, h, w = int(p[0]), int(p[1]), int(p[2])
+        oh, ow, y0, x0 = (int(v) for v in p[7:11])
+        if not (0 <= y0 and y0 + H <= oh and 0 <= x0 and x0 + W <= ow):
+            raise ValueError(f"sample {b}: window ({y0}, {x0}, {H}, {W}) leaves the output size ({oh}, {ow})")
+        src = flat[off:off + h * w * 3].reshape(h, w, 3).astype(np.int64)
+        tx, ty = resample_taps(w, p[3], p[5], ow, x0, W, filter), resample_taps(h, p[4], p[6], oh, y0, H, filter)
+        r0, r1 = ty[0][0], ty[-1][0] + len(ty[-1][1])
+        tmp = np.empty((r1 - r0, W, 3), dtype=np.int64)
+        for x, (xmin, k) in enumerate(tx):                  # horizontal pass, rounded to uint8
+            acc = (1 << 21) + np.tensordot(src[r0:r1, xmin:xmin + len(k)], k.astype(np.int64), axes=([1], [0]))
+            tmp[:, x] = np.clip(acc >> 22, 0, 255)
+        for y, (ymin, k) in enumerate(ty):                  # vertical pass over those rows
+            acc = (1 << 21) + np.tensordot(k.astype(np.int64), tmp[ymin - r0:ymin - r0 + len(k)], axes=([0], [0]))
+            out[b, y] = np.clip(acc >> 22, 0, 255)
+        if p[11]:
+            out[b] = out[b, :, ::-1]
+    return out
+
+
+def resize_crop(flat, plan, H, W, device=False, workspace=None, filter=Image.BICUBIC):
+    """uint8 [B][H][W][3]: per sample PIL's Image.resize((ow, oh), filter, box=box) of its frame in `flat`, cropped to the window
+    (y0, x0, H, W) and mirrored, bit for bit.  plan = resize_plan(...).  device=False: the numpy referee (flat a numpy uint8 array);
+    device=True: ppf_resize_crop_u8 (flat a uint8 CUDA tensor; no fallback)."""
+    plan = np.ascontiguousarray(plan, dtype=np.float64).reshape(-1, RC_WORDS)
+    if not device:
+        return _resize_crop_np(np.asarray(flat, dtype=np.uint8).reshape(-1), plan, H, W, filter)
+    from . import _lib
+    if not (isinstance(flat, torch.Tensor) and flat.is_cuda and flat.dtype == torch.uint8 and flat.is_contiguous()):
+        raise RuntimeError("resize_crop(device=True) needs a contiguous uint8 CUDA tensor of frames (no CPU fallback path)")
+    B = len(plan)
+    need = resize_workspace_bytes(plan, H, W, filter, flat.numel())
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=flat.device)
+    plan_dev = torch.from_numpy(plan).to(flat.device)
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=flat.device)
+    _lib.call("ppf_resize_crop_u8", flat, flat.numel(), plan.ctypes.data, plan_dev, B, H, W, int(filter), workspace, workspace.numel(), out)
+    return out
+
+
+def resize_workspace_bytes(plan, H, W, filter, flat_bytes):
+    """Bytes of device workspace ppf_resize_crop_u8 needs for this plan; an invalid plan raises with the library's message."""
+    from . import _lib
+    plan = np.ascontiguousarray(plan, dtype=np.float64).reshape(-1, RC_WORDS)
+    need = _lib.lib().ppf_resize_crop_workspace_bytes(plan.ctypes.data, len(plan), H, W, int(filter), int(flat_bytes))
+    if need == 0:
+        raise RuntimeError("ppf_resize_crop_workspace_bytes: " + _lib.lib().ppf_last_error().decode())
+    return need
+
+
+def aug_plan(draws, H, W):
+    """fp64 [B][AUG_SLOTS][AUG_WORDS] = (op index in RandAugment.OPS or AUG_SKIP, resample filter, p0 .. p5) from RandAugment.draw()
+    plans of B samples of H x W frames: p0 is the op's parameter, or p0 .. p5 the affine matrix PIL would build (the rotation's sine and
+    cosine are taken here, as Image.rotate takes them)."""
+    plan = np.zeros((len(draws), AUG_SLOTS, AUG_WORDS), dtype=np.float64)
+    plan[:, :, 0] = AUG_SKIP
+    for b, slots in enumerate(draws):
+        if len(slots) > AUG_SLOTS:
+            raise ValueError(f"{len(slots)} RandAugment ops per image: the device path takes {AUG_SLOTS}")
+        for s, (name, param, resample) in enumerate(slots):
+            if name is None:
+                continue
+            if resample not in (Image.BILINEAR, Image.BICUBIC):
+                raise ValueError(f"resample filter {resample}: the device path takes BILINEAR and BICUBIC")
+            m = (float(param), 0.0, 0.0, 0.0, 0.0, 0.0)
+            if name == "Rotate":
+                angle = param % 360.0
+                if angle == 0:
+                    continue                            # Image.rotate returns a copy
+                angle = -math.radians(angle)
+                m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+                cx, cy = W / 2, H / 2
+                m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+                m[2] += cx
+                m[5] += cy
+            elif name == "ShearX":
+                m = (1.0, param, 0.0, 0.0, 1.0, 0.0)
+            elif name == "ShearY":
+                m = (1.0, 0.0, 0.0, param, 1.0, 0.0)
+            elif name == "TranslateXRel":
+                m = (1.0, 0.0, param * W, 0.0, 1.0, 0.0)
+            elif name == "TranslateYRel":
+                m = (1.0, 0.0, 0.0, 0.0, 1.0, param * H)
+            plan[b, s, 0], plan[b, s, 1] = RandAugment.OPS.index(name), resample
+            plan[b, s, 2:] = m
+    return plan
+
+
+def _luma(img):
+    i = img.astype(np.int64)
+    return ((i[..., 0] * 19595 + i[..., 1] * 38470 + i[..., 2] * 7471 + 0x8000) >> 16).astype(np.uint8)
+
+
+def _blend(a, b, factor):
+    """Image.blend(a, b, factor) on uint8 arrays: C float arithmetic and a truncation, clamped only when the factor leaves [0, 1]."""
+    f = np.float32(factor)
+    a = a.astype(np.int32)
+    t = a.astype(np.float32) + f * (b.astype(np.int32) - a).astype(np.float32)
+    if not 0.0 <= factor <= 1.0:
+        t = np.clip(t, np.float32(0), np.float32(255))
+    return t.astype(np.uint8)
+
+
+def _smooth(img):
+    """ImageFilter.SMOOTH: fp32 3 x 3 sums with 0.5 added first, truncated; the one-pixel border is copied."""
+    out = img.copy()
+    k = (np.array([1, 1, 1, 1, 5, 1, 1, 1, 1], dtype=np.float32) / np.float32(13)).reshape(3, 3)
+    f = img.astype(np.float32)
+    H, W = img.shape[:2]
+    if H < 3 or W < 3:
+        return out
+    ss = np.full((H - 2, W - 2, 3), 0.5, dtype=np.float32)
+    for r in (2, 1, 0):                                   # row y + 1 first, as the C loop
+        row = f[r:r + H - 2]
+        ss = ss + (row[:, 0:W - 2] * k[r, 0] + row[:, 1:W - 1] * k[r, 1] + row[:, 2:W] * k[r, 2])
+    out[1:-1, 1:-1] = np.clip(ss, np.float32(0), np.float32(255)).astype(np.uint8)
+    return out
+
+
+def _cubic(v1, v2, v3, v4, d):
+    p2 = -v1 + v3
+    p3 = 2 * (v1 - v2) + v3 - v4
+    p4 = -v1 + v2 - v3 + v4
+    return v2 + d * (p2 + d * (p3 + d * p4))
+
+
+def _affine_np(img, m, resample, fill):
+    """Image.transform(size, AFFINE, m, resample, fillcolor=fill): every output pixel's centre is mapped in closed form in double."""
+    H, W = img.shape[:2]
+    xs, ys = (np.arange(W) + 0.5)[None, :], (np.arange(H) + 0.5)[:, None]
+    xin, yin = m[0] * xs + m[1] * ys + m[2], m[3] * xs + m[4] * ys + m[5]
+    inside = (xin >= 0.0) & (xin < W) & (yin >= 0.0) & (yin < H)
+    xin, yin = xin - 0.5, yin - 0.5
+    x, y = np.floor(xin), np.floor(yin)
+    dx, dy = (xin - x)[..., None], (yin - y)[..., None]
+    x, y = x.astype(np.int64), y.astype(np.int64)
+    src = img.astype(np.int64)
+
+    def row(yy, fn):
+        cols = [src[np.clip(yy, 0, H - 1), np.clip(x + j, 0, W - 1)] for j in range(fn[0], fn[1])]
+        return fn[2](*cols)
+    if resample == Image.BILINEAR:
+        fn = (0, 2, lambda a, b: a + (b - a) * dx)
+        v1 = row(y, fn)
+        ok = ((y + 1 >= 0) & (y + 1 < H))[..., None]
+        v2 = np.where(ok, row(y + 1, fn), v1)
+        v = v1 + (v2 - v1) * dy
+    else:
+        fn = (-1, 3, lambda a, b, c, d: _cubic(a, b, c, d, dx))
+        v1 = row(y - 1, fn)
+        v2 = np.where(((y >= 0) & (y < H))[..., None], row(y, fn), v1)
+        v3 = np.where(((y + 1 >= 0) & (y + 1 < H))[..., None], row(y + 1, fn), v2)
+        v4 = np.where(((y + 2 >= 0) & (y + 2 < H))[..., None], row(y + 2, fn), v3)
+        v = _cubic(v1, v2, v3, v4, dy)
+    v = _AFFINE_ROUND[resample](v)
+    return np.where(inside[..., None], v, np.asarray(fill, dtype=np.uint8)).astype(np.uint8)
+
+
+_AFFINE_ROUND = {Image.BILINEAR: lambda v: np.clip(v, 0, 255).astype(np.uint8),
+                 Image.BICUBIC: lambda v: np.where(v <= 0.0, 0, np.where(v >= 255.0, 255, v.astype(np.int64)))}
+
+
+def _table_lut(op, p0, img):
+    """uint8 [3][256]: the per-channel table of one table op on one frame."""
+    name = RandAugment.OPS[op]
+    i = np.arange(256, dtype=np.int64)
+    if name == "Invert":
+        lut = 255 - i
+    elif name == "PosterizeIncreasing":
+        lut = i & ~((1 << (8 - int(p0))) - 1)
+    elif name == "SolarizeIncreasing":
+        lut = np.where(i < int(p0), i, 255 - i)
+    elif name == "SolarizeAdd":
+        lut = np.where(i < 128, np.minimum(255, i + int(p0)), i)
+    elif name == "BrightnessIncreasing":
+        lut = _blend(np.zeros(256, dtype=np.uint8), i.astype(np.uint8), p0)
+    elif name == "ContrastIncreasing":
+        mean = int(_luma(img).astype(np.int64).sum() / (img.shape[0] * img.shape[1]) + 0.5)
+        lut = _blend(np.full(256, mean, dtype=np.uint8), i.astype(np.uint8), p0)
+    else:
+        luts = []
+        for c in range(3):
+            h = np.bincount(img[..., c].reshape(-1), minlength=256).astype(np.int64)
+            nz = np.nonzero(h)[0]
+            lut = i.copy()
+            if name == "AutoContrast":
+                lo, hi = int(nz[0]), int(nz[-1])
+                if hi > lo:
+                    scale = 255.0 / (hi - lo)
+                    offset = -lo * scale
+                    lut = np.clip((i * scale + offset).astype(np.int64), 0, 255)
+            else:
+                step = (int(h.sum()) - int(h[nz[-1]])) // 255
+                if len(nz) > 1 and step:
+                    lut = np.minimum((step // 2 + np.concatenate(([0], np.cumsum(h)[:-1]))) // step, 255)
+            luts.append(lut)
+        return np.stack(luts).astype(np.uint8)
+    return np.broadcast_to(lut.astype(np.uint8), (3, 256))
+
+
+def _aug_np(img, op, resample, p, fill):
+    name = RandAugment.OPS[op]
+    if name in _AFFINE_OPS:
+        return _affine_np(img, p, resample, fill)
+    if name == "ColorIncreasing":
+        return _blend(np.repeat(_luma(img)[..., None], 3, axis=2), img, p[0])
+    if name == "SharpnessIncreasing":
+        return _blend(_smooth(img), img, p[0])
+    lut = _table_lut(op, p[0], img)
+    return np.stack([lut[c][img[..., c]] for c in range(3)], axis=2)
+
+
+def randaugment_apply(frames, plan, fill, device=False):
+    """uint8 [B][H][W][3] frames after the ops of plan = aug_plan(...), each bit-equal to RandAugment._apply_drawn under Pillow.
+    device=False: the numpy referee; device=True: the ppf_aug_* kernels (uint8 CUDA tensor; no fallback)."""
+    plan = np.ascontiguousarray(plan, dtype=np.float64).reshape(-1, AUG_SLOTS, AUG_WORDS)
+    fill = tuple(int(v) for v in fill)
+    if not device:
+        out = np.array(frames, dtype=np.uint8)
+        for b in range(len(plan)):
+            for s in range(AUG_SLOTS):
+                if int(plan[b, s, 0]) != AUG_SKIP:
+                    out[b] = _aug_np(out[b], int(plan[b, s, 0]), int(plan[b, s, 1]), plan[b, s, 2:], fill)
+        return out
+    from . import _lib
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4):
+        raise RuntimeError("randaugment_apply(device=True) needs a contiguous uint8 CUDA tensor [B, H, W, 3] (no CPU fallback path)")
+    B, H, W, _ = frames.shape
+    if len(plan) != B:
+        raise ValueError(f"plan of {len(plan)} samples for a batch of {B}")
+    plan_dev = torch.from_numpy(plan).to(frames.device)
+    hist = torch.empty((B, 3, 256), dtype=torch.int32, device=frames.device)
+    lut = torch.empty((B, 3, 256), dtype=torch.uint8, device=frames.device)
+    cur, nxt = frames, None
+    for s in range(AUG_SLOTS):
+        ops = plan[:, s, 0].astype(np.int64)
+        if (ops == AUG_SKIP).all():
+            continue
+        nxt = torch.empty_like(frames) if nxt is None else nxt
+        _lib.call("ppf_aug_hist", cur, plan_dev, s, B, H, W, hist)
+        _lib.call("ppf_aug_lut_build", hist, plan_dev, s, B, H, W, lut)
+        _lib.call("ppf_aug_apply", cur, plan_dev, s, lut, B, H, W, nxt)
+        if (ops == RandAugment.OPS.index("SharpnessIncreasing")).any():
+            _lib.call("ppf_aug_sharpness", cur, plan_dev, s, B, H, W, nxt)
+        if np.isin(ops, [RandAugment.OPS.index(n) for n in _AFFINE_OPS]).any():
+            _lib.call("ppf_aug_affine", cur, plan_dev, s, B, H, W, fill[0], fill[1], fill[2], nxt)
+        cur, nxt = nxt, (cur if cur is not frames else None)
+    return cur
 
 
 # ------------------------------------------------------------------------------------------------ tools/preprocess.py

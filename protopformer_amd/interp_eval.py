@@ -91,7 +91,10 @@ def main(args, model=None):
     root, meta = cub_dirs(args.data_path)
     view = D.build_view_transform(args, square=True)          # the reference's Resize((size, size)); GpuFinisher normalises
     ds = D.Cub2011(root, train=False, transform=view, return_id=True)
-    loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=10)
+    if D.device_data_enabled(args):                     # the same square bilinear view produced on the device from resident originals
+        loader = D.DeviceAugLoader(D.DeviceDataset(ds, device, num_workers=10), args.batch_size, D.GpuFinisher(re_prob=0.0), False, args, square=True)
+    else:
+        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=10)
     if args.check_test:
         acc = E.evaluate_epoch(loader, model, device)
         print(f"test accuracy: {acc['acc1']:.2f}%", flush=True)

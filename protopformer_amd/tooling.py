@@ -31,6 +31,9 @@ def eval_loader(args, device, *, with_ids=True):
     ds, num_classes = D.build_dataset(args.split == "train", args, transform=D.build_view_transform(args))
     if with_ids and hasattr(ds, "return_id"):
         ds.return_id = True
+    if D.device_data_enabled(args):                     # the same geometry produced on the device from resident originals
+        return ds, num_classes, D.DeviceAugLoader(D.DeviceDataset(ds, device, num_workers=args.num_workers), args.batch_size,
+                                                  D.GpuFinisher(re_prob=0.0), False, args)
     return ds, num_classes, D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
 
 

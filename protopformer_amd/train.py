@@ -287,14 +287,18 @@ def main(args, model=None):
 
     loader_train, loader_val, args.nb_classes = D.build_loaders(args, device)
     if args.distributed and args.dist_eval:
-        ds_val = loader_val.loader.dataset
+        ds_val = loader_val.dataset
         if len(ds_val) % args.world_size != 0:
             logger.warning("Warning: Enabling distributed evaluation with an eval dataset not divisible by process number. This will slightly "
                            "alter validation results as extra duplicate entries are added to achieve equal num of samples per-process.")
         sampler_val = torch.utils.data.DistributedSampler(ds_val, num_replicas=args.world_size, rank=args.rank, shuffle=False)
-        loader_val = D.DeviceLoader(ds_val, int(1.5 * args.batch_size), device, D.GpuFinisher(re_prob=0.0), sampler=sampler_val,
-                                    num_workers=args.num_workers)
-    n_train, n_val = len(loader_train.loader.dataset), len(loader_val.loader.dataset)
+        if isinstance(loader_val, D.DeviceAugLoader):                # the resident path (PPF_DEVICE_DATA): every rank holds the whole set
+            loader_val = D.DeviceAugLoader(loader_val.dd, int(1.5 * args.batch_size), D.GpuFinisher(re_prob=0.0), False, args, sampler=sampler_val,
+                                           seed=args.seed)
+        else:
+            loader_val = D.DeviceLoader(ds_val, int(1.5 * args.batch_size), device, D.GpuFinisher(re_prob=0.0), sampler=sampler_val,
+                                        num_workers=args.num_workers)
+    n_train, n_val = len(loader_train.dataset), len(loader_val.dataset)
     logger.info(f"Dataset num_classes: {args.nb_classes}")
     logger.info(f"train {n_train} test: {n_val}")
 
@@ -336,7 +340,9 @@ def main(args, model=None):
     logger.info(f"Start training for {args.epochs} epochs ({step_kind} step)")
 
     def train_epoch(epoch):
-        if loader_train.sampler is not None:
+        if hasattr(loader_train, "set_epoch"):
+            loader_train.set_epoch(epoch)                            # the resident loader: its draws and its sampler follow the epoch
+        elif loader_train.sampler is not None:
             loader_train.sampler.set_epoch(epoch)
         return E.train_one_epoch(model, criterion, loader_train, optimizer, device, epoch, args=args, grad_sync=grad_sync, logger=logger.info,
                                  max_norm=args.clip_grad, step_fn=phases.get(epoch) if phases is not None else None, mixup_fn=mixup_fn)
