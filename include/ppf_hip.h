@@ -383,6 +383,43 @@ int ppf_cell_order(const float* act_full, const int* idx, const float* token_att
 int ppf_patch_perturb(const float* x, const int* rank, const int* counts, int S, int insertion, const float* baseline, float baseline_const, int B,
                       int M, int Cc, int H, int W, int G, float* out, ppf_stream_t stream);
 int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* prob, ppf_stream_t stream);
+/* The same curves per PIXEL, from a blurred canvas (csrc/pixel_faithful.hip): the metric as published removes pixels in saliency order and
+ * starts the insertion curve from a blurred image.  n = H * W pixels per row, pixel i = y * W + x.  Additions of ABI 10: no existing entry
+ * point changed.
+ *   ppf_pixel_order    rank int32 [R][n] from score fp32 [R][n] and classes int32 [R]: rank[r][i] = the number of pixels j of row r that
+ *                      come before i -- a larger score_key(score) (order_keys.h: NaN lowest, -0 == +0), or the same key and j < i.  Every
+ *                      row is a permutation of 0 .. n-1; a row with classes[r] < 0 is all -1.  1 <= n <= 65536, R >= 1.  The composite key
+ *                      pixel_order_key(score, i) = (~score_key << 32) | i (order_keys.h) is unique per row and ascending in this order, so
+ *                      any correct sort gives these bits.  Built: a workgroup per row runs a stable LSD radix sort, 8 bits per pass, over
+ *                      the 32-bit word ~score_key, with (key, pixel) pairs ping-ponging through `scratch` (stable passes from pixel order
+ *                      keep equal keys in pixel order); the four digit histograms come from one read of the row and a pass whose digit is
+ *                      constant over the row is skipped (up-sampled maps have few distinct values).  Not the bitonic network on 64-bit
+ *                      keys: a row does not fit LDS (50 176 x 8 B against 160 KiB) and the network is 136 stages over 65 536 padded keys
+ *                      against at most four passes.  scratch: ppf_pixel_order_scratch_bytes(R, n) = min(R, 256) * 16 * n bytes, 4-byte
+ *                      aligned, used by this launch only (0 for sizes outside the limits).  Integer LDS atomics only: deterministic.
+ *   ppf_pixel_random   score fp32 [B][n] = (word >> 8) * 2^-24, word = the first word of Philox4x32-10, key = seed, counter = (pixel,
+ *                      0x80000000, image id low, image id high): a function of (seed, image id, pixel) alone.  Counter word 1 across the
+ *                      library: 0 the random cell order, 1 + n < 2^31 the RISE masks, e/4 high (0 below 2^34 elements) the input noise of
+ *                      ppf_add_gauss_noise, 0x80000000 ppf_warp_nodes -- so this draw is disjoint from the cell order and the RISE masks
+ *                      but NOT from ppf_warp_nodes: pixel q and warp node q < (s + 1)^2 <= 289 of the same image under the same seed share
+ *                      a Philox block (this draw reads word .x, the node's dy).  The two never meet in one computation (a pixel order and
+ *                      a shape perturbation of 'because'); a caller who needs them independent gives them different seeds.
+ *   ppf_pixel_perturb  ppf_patch_perturb's contract with rank int32 [B][M][n], n = H * W, in place of the cell's rank: out fp32
+ *                      [S][B][M][Cc][H][W]; deletion: the pixel is the baseline when rank < counts[s]; insertion: the pixel is x when
+ *                      rank < counts[s]; a negative rank keeps x (a row of -1 copies x).  H >= 1, W a multiple of 4, 1 <= M <= 8; x,
+ *                      baseline, rank and out 16-byte aligned.  x, the baseline and the rank are read once per launch, all S * M copies
+ *                      written from registers.
+ *   ppf_gauss_blur     out fp32 [R][H][W] = a separable blur of every plane of x with a zero border and taps fp32 [2r + 1] on the DEVICE.
+ *                      Horizontal: t[y][x] = the fp32 sum, started from +0, over d = -r .. r in that order of fl(taps[d + r] * x[y][x + d]),
+ *                      one rounding per multiply and per add, nothing contracted; a tap with x + d outside [0, W) is skipped, not added
+ *                      as zero.  Vertical: the same over t (rounded to fp32) along y.  1 <= r <= 16, H, W >= 1, R <= 65535 planes,
+ *                      H <= 65535 * 16, out != x.  One launch, the intermediate in LDS. */
+size_t ppf_pixel_order_scratch_bytes(int R, int n);
+int ppf_pixel_order(const float* score, const int* classes, int R, int n, int* rank, void* scratch, size_t scratch_bytes, ppf_stream_t stream);
+int ppf_pixel_random(const void* image_id_i64, uint64_t seed, int B, int n, float* score, ppf_stream_t stream);
+int ppf_pixel_perturb(const float* x, const int* rank, const int* counts, int S, int insertion, const float* baseline, float baseline_const, int B,
+                      int M, int Cc, int H, int W, float* out, ppf_stream_t stream);
+int ppf_gauss_blur(const float* x, const float* taps, int r, int R, int H, int W, float* out, ppf_stream_t stream);
 /* RISE saliency (csrc/rise.hip): the model-agnostic baseline the deletion / insertion metric was published with (Petsiuk et al., 2018):
  * N random masks per image, the class probability of each masked image (the forwards and ppf_class_prob are the caller's), saliency =
  * the probability-weighted mean mask.  The reference has no such pass.  Additions of ABI 10: no existing entry point changed.

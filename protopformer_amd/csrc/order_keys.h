@@ -25,6 +25,11 @@ PPF_HD uint32_t score_key(float v) {
     return order_key(v);                                                      // -inf -> 0x007fffff, above the NaN key
 }
 
+// one ascending 64-bit key per (score, index) of a row: a < b  <=>  (score a, index a) comes before (score b, index b) under score_key
+// descending, then the smaller index.  Unique per row, so any correct sort of these keys gives the same order (ppf_pixel_order;
+// tests/pixel_key_check.cpp).
+PPF_HD uint64_t pixel_order_key(float score, uint32_t index) { return ((uint64_t)(~score_key(score)) << 32) | index; }
+
 // does (v, id) come before (w, jd)?  Larger value first, equal values by smaller id; V: float, or an integer key.  A NaN never compares
 // greater or equal: with a NaN on either side neither comes before the other.
 template <typename V>

@@ -12,12 +12,19 @@ Per batch one eval forward, one `ppf_cell_order` launch per order, and per curve
     python -m protopformer_amd.faithfulness --resume CKPT --data_set CUB2011U --data_path ... --output_dir OUT [--split test] [--steps 14]
                                             [--orders evidence attention random [rise] [ig]] [--modes deletion insertion] [--against_label]
                                             [--rise_masks 512] [--rise_cells 7] [--rise_p 0.5] [--ig_steps 32] [--ig_rule midpoint]
+                                            [--resolution cell|pixel] [--baseline mean|blur] [--blur_sigma 5] [--blur_radius 5]
                                             [--max_images N] [--seed 0] [--per-image]
                                             + the model flags of train.py
 
 writes OUT/faithfulness.json: the image count, the cell counts, per order and mode the mean curve and its area, and per order the
 difference of both areas to the random order's (an explanation is informative when its deletion area lies below and its insertion area
-above); with --per-image also OUT/faithfulness.npz (the curves, classes and ids of every image)."""
+above); with --per-image also OUT/faithfulness.npz (the curves, classes and ids of every image).
+
+--resolution pixel is the metric as published: every order becomes a pixel map (the evidence and attention grids up-sampled as the
+overlays are, the RISE saliency and the integrated gradients at their own resolution), the pixels are ranked by `ppf_pixel_order` and
+removed by `ppf_pixel_perturb`; the counts are pixels.  --baseline blur replaces a removed pixel by the Gaussian-blurred image
+(`ppf_gauss_blur`, --blur_sigma, --blur_radius) instead of the mean colour, at either resolution.  faithfulness.json carries the keys
+`resolution`, `baseline` and `blur` only when one of these flags departs from its default."""
 import argparse
 import json
 import os
@@ -27,7 +34,7 @@ import torch
 
 
 def get_args_parser():
-    from .interpret import CURVE_MODES, EXTRA_ORDERS, GRADIENT_ORDERS, IG_DEFAULTS, IG_RULES, ORDER_MODES, RISE_DEFAULTS
+    from .interpret import BLUR_DEFAULTS, CURVE_MODES, EXTRA_ORDERS, GRADIENT_ORDERS, IG_DEFAULTS, IG_RULES, ORDER_MODES, RESOLUTIONS, RISE_DEFAULTS
     from .tooling import add_split_flags
     from .train import get_args_parser as train_parser
     p = argparse.ArgumentParser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", parents=[train_parser()])
@@ -42,15 +49,20 @@ def get_args_parser():
     a("--ig_steps", type=int, default=IG_DEFAULTS["steps"], help="path steps of the ig order (one forward and backward each)")
     a("--ig_rule", type=str, default=IG_DEFAULTS["rule"], choices=list(IG_RULES), help="quadrature of the ig order's path integral")
     a("--modes", type=str, nargs="+", default=list(CURVE_MODES), choices=list(CURVE_MODES))
+    a("--resolution", type=str, default=RESOLUTIONS[0], choices=list(RESOLUTIONS), help="remove grid cells, or pixels as the published metric does")
+    a("--baseline", type=str, default="mean", choices=["mean", "blur"], help="what a removed pixel becomes: the mean colour or the blurred image")
+    a("--blur_sigma", type=float, default=BLUR_DEFAULTS["sigma"], help="standard deviation of the blur baseline, in pixels")
+    a("--blur_radius", type=int, default=BLUR_DEFAULTS["radius"], help="radius of the blur baseline's kernel (2 r + 1 taps), at most 16")
     a("--against_label", action="store_true", default=False, help="follow the probability of the image's label instead of its top class")
     a("--per-image", dest="per_image", action="store_true", default=False, help="also write faithfulness.npz with every image's curves")
     p.set_defaults(seed=0)                                 # keys the random order (train.py's --seed, with this tool's default)
     return p
 
 
-def summarize(result):
+def summarize(result, extra=None):
     """The JSON record of interpret.faithfulness's result: images, counts, grid_cells, orders (mean curve and area per order and mode) and
-    vs_random: per other order the two area differences to the random order and whether both have the informative sign."""
+    vs_random: per other order the two area differences to the random order and whether both have the informative sign.  extra: keys
+    appended behind them (main: resolution, baseline, blur when a flag departs from its default)."""
     out = dict(images=int(result["images"]), counts=[int(c) for c in result["counts"]], grid_cells=int(result["grid_cells"]), orders=result["orders"],
                vs_random={})
     rnd = result["orders"].get("random")
@@ -61,13 +73,14 @@ def summarize(result):
         if len(d) == 2:
             d["informative"] = bool(d["deletion_auc_minus_random"] < 0 < d["insertion_auc_minus_random"])
         out["vs_random"][order] = d
+    out.update(extra or {})
     return out
 
 
 def main(args, model=None, loader=None):
     """loader: a ready iterable of (x, labels[, ids]) CUDA batches with its model (tests, notebooks); by default both are built from the
     data flags as the explain tool builds them."""
-    from .interpret import default_counts, faithfulness
+    from .interpret import BLUR_DEFAULTS, default_counts, faithfulness
     from .tooling import eval_loader, load_for_eval, model_from_args
     from .train import set_seed
     set_seed(args.seed)
@@ -77,13 +90,19 @@ def main(args, model=None, loader=None):
     if loader is None:
         _, nb_classes, loader = eval_loader(args, device)
     model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
-    res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes), counts=default_counts(model.num_patches, args.steps),
+    pixel, blur = args.resolution == "pixel", dict(sigma=args.blur_sigma, radius=args.blur_radius)
+    res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes),
+                       counts=default_counts(int(model.img_size) ** 2 if pixel else model.num_patches, args.steps),
                        against_label=args.against_label, seed=args.seed, max_images=args.max_images,
-                       rise=dict(masks=args.rise_masks, cells=args.rise_cells, p=args.rise_p), ig=dict(steps=args.ig_steps, rule=args.ig_rule))
+                       rise=dict(masks=args.rise_masks, cells=args.rise_cells, p=args.rise_p), ig=dict(steps=args.ig_steps, rule=args.ig_rule),
+                       resolution=args.resolution, baseline="blur" if args.baseline == "blur" else 0.0, blur=blur)
+    extra = {}
+    if pixel or args.baseline != "mean" or blur != BLUR_DEFAULTS:
+        extra = dict(resolution=args.resolution, baseline=args.baseline, blur=blur)
     os.makedirs(args.output_dir, exist_ok=True)
     path = os.path.join(args.output_dir, "faithfulness.json")
     with open(path, "w") as f:
-        json.dump(summarize(res), f, indent=1)
+        json.dump(summarize(res, extra), f, indent=1)
     if args.per_image:
         arrays = {f"{order}_{mode}": c for order, modes in res["per_image"].items() for mode, c in modes.items()}
         np.savez(os.path.join(args.output_dir, "faithfulness.npz"), counts=np.asarray(res["counts"]), classes=res["classes"], image_ids=res["image_ids"],

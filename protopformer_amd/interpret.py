@@ -959,16 +959,178 @@ def perturb_patches(x, rank, counts, insertion=False, baseline=0.0, device=True)
     return np.where(keep[:, :, :, None], x[None, :, None], base[None, :, None]).astype(np.float32)
 
 
+# ---- the same test per pixel, from a blurred canvas (csrc/pixel_faithful.hip).  The metric as published removes PIXELS in saliency order,
+# and its insertion curve starts from a blurred image: sharp islands on a flat canvas are out of distribution for every order alike.  The
+# patch grid suits the model's own explanation and discards the resolution of the pixel maps (RISE, integrated gradients); here every
+# order is a [B, M, H, W] score map, ranked by ppf_pixel_order and perturbed by ppf_pixel_perturb.  Opt-in: resolution="pixel" and
+# baseline="blur" of faithfulness_curves / faithfulness.  The numpy forms (device=False) are the referees, bit for bit.
+RESOLUTIONS = ("cell", "pixel")
+BLUR_DEFAULTS = dict(sigma=5.0, radius=5)   # klen = 11, sigma = 5
+
+
+def gauss_taps(sigma=5.0, radius=5):
+    """fp32 [2 * radius + 1]: exp(-d^2 / (2 sigma^2)) for d = -radius .. radius, normalised in fp64 and cast once."""
+    r, sigma = int(radius), float(sigma)
+    if not 1 <= r <= 16 or not sigma > 0.0:
+        raise ValueError(f"gauss_taps: radius={radius} outside [1, 16] (ppf_gauss_blur's limit) or sigma={sigma} not positive")
+    d = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-(d * d) / (2.0 * sigma * sigma))
+    return (w / w.sum()).astype(np.float32)
+
+
+def _blur_axis(a, taps, axis):
+    """One pass of the blur's contract along `axis` of an fp32 array: from +0, ascending d, one rounding per multiply and per add; a tap
+    that falls outside the plane is skipped."""
+    r, n = (taps.shape[0] - 1) // 2, a.shape[axis]
+    a = np.moveaxis(a, axis, -1)
+    acc = np.zeros(a.shape, dtype=np.float32)
+    for d in range(-r, r + 1):
+        lo, hi = max(0, -d), min(n, n - d)                                         # the outputs whose tap d lies inside
+        if lo < hi:
+            acc[..., lo:hi] = acc[..., lo:hi] + (taps[d + r] * a[..., lo + d:hi + d]).astype(np.float32)
+    return np.moveaxis(acc, -1, axis)
+
+
+def gauss_blur(x, sigma=5.0, radius=5, device=True):
+    """Every [H, W] plane of x fp32 [..., H, W] blurred separably (horizontal, then vertical) with gauss_taps(sigma, radius) and a zero
+    border -- in normalised space a border of the data-set mean colour; the contract is ppf_gauss_blur's (include/ppf_hip.h).
+    device=True: one launch on a CUDA tensor; device=False: numpy, a loop of rounded fp32 operations."""
+    taps = gauss_taps(sigma, radius)
+    if device:
+        from . import ops
+        return ops.gauss_blur(x, torch.from_numpy(taps).to(x.device))
+    a = _host(x, np.float32)
+    with np.errstate(all="ignore"):
+        return _blur_axis(_blur_axis(a, taps, a.ndim - 1), taps, a.ndim - 2)
+
+
+def pixel_order_from_scores(score, classes, device=True):
+    """rank int32 classes.shape + (n,) of score fp32 classes.shape + (n,) (or + (H, W)): the number of pixels of the row that come before
+    pixel i -- larger score first, ties by the smaller pixel index, NaN lowest, -0 == +0; a row whose class is negative is all -1.  The
+    contract is ppf_pixel_order's (include/ppf_hip.h).  device=True: one launch; device=False: np.lexsort, NaN handled as
+    cell_order_from_outputs handles it."""
+    lead = tuple(classes.shape)
+    R = int(np.prod(lead, dtype=np.int64))
+    n = int(score.numel() if isinstance(score, torch.Tensor) else np.asarray(score).size) // max(R, 1)
+    if device:
+        from . import ops
+        return ops.pixel_order(score.reshape(R, n), classes.reshape(R).contiguous()).reshape(lead + (n,))
+    s, cls = _host(score, np.float32).reshape(R, n), _host(classes, np.int32).reshape(R)
+    if not 1 <= n <= 65536:
+        raise ValueError(f"pixel_order_from_scores: n={n} pixels outside ppf_pixel_order's limits [1, 65536]")
+    rank, pixels = np.full((R, n), -1, dtype=np.int32), np.arange(n)
+    with np.errstate(all="ignore"):
+        for r in range(R):
+            if cls[r] < 0:
+                continue
+            nan = np.isnan(s[r])
+            rank[r, np.lexsort((pixels, np.where(nan, np.float32(0), -s[r]), nan))] = pixels     # NaN last, score descending, smaller pixel
+    return rank.reshape(lead + (n,))
+
+
+def pixel_random_scores(image_ids, pixels, seed=0, device=True):
+    """fp32 [B, pixels]: (word >> 8) * 2^-24 of Philox4x32-10 keyed by seed at counter (pixel, 0x80000000, image id low, image id high)
+    (ppf_pixel_random); a function of (seed, image id, pixel) alone.  device=False: the numpy Philox."""
+    if device:
+        from . import ops
+        return ops.pixel_random(image_ids, pixels, seed)
+    ids, n, sd = _host(image_ids, np.int64).reshape(-1).astype(np.uint64), int(pixels), int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((ids.shape[0], n, 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1] = np.arange(n, dtype=np.uint64), 0x80000000
+    ctr[..., 2], ctr[..., 3] = (ids & np.uint64(0xFFFFFFFF))[:, None], (ids >> np.uint64(32))[:, None]
+    word = philox4x32_10(ctr, np.array([sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint64))[..., 0]
+    return (word >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def perturb_pixels(x, rank, counts, insertion=False, baseline=0.0, device=True):
+    """The perturbed images [S, B, M, Cc, H, W] of x [B, Cc, H, W]: with rank [B, M, H * W] from pixel_order_from_scores and counts [S],
+    deletion replaces the pixels with rank < counts[s] by the baseline, insertion keeps x at those pixels only; a row of ranks -1 copies
+    x.  baseline: a number or a tensor like x.  device=True: one ppf_pixel_perturb launch (counts may be a host list; W a multiple of 4);
+    device=False: numpy."""
+    if device:
+        from . import ops
+        counts = counts if isinstance(counts, torch.Tensor) else torch.from_numpy(np.asarray(counts, dtype=np.int32))
+        return ops.pixel_perturb(x, rank, counts.to(device=x.device, dtype=torch.int32).contiguous(), insertion, baseline)
+    x, rank, counts = _host(x, np.float32), _host(rank, np.int64), _host(counts, np.int64).reshape(-1)
+    (B, Cc, H, W), M = x.shape, rank.shape[1]
+    if rank.shape != (B, M, H * W):
+        raise ValueError(f"perturb_pixels: rank must be [{B}, M, {H * W}], got {list(rank.shape)}")
+    pix = rank.reshape(B, M, H, W)
+    keep = (pix[None] < 0) | ((pix[None] < counts[:, None, None, None, None]) == bool(insertion))   # [S, B, M, H, W]
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    return np.where(keep[:, :, :, None], x[None, :, None], base[None, :, None]).astype(np.float32)
+
+
+def _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig):
+    """(score fp32 [B, M, H, W], the Rise or None, the IntegratedGradients or None) of pixel_scores."""
+    from . import ops
+    (B, _, H, W), M, G = x.shape, cls.shape[1], int(ppnet.num_patches)
+    side = int(round(G ** 0.5))
+    if order in ORDER_MODES[:2] and (H != W or side * side != G):
+        raise ValueError(f"pixel_scores: the {order} map is up-sampled from a square grid to a square image, got G={G} and {H} x {W}")
+    if order == "evidence":
+        _, _, cell = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], ppnet.last_layer.weight.detach().contiguous(),
+                                             1.0 - float(ppnet.global_coe), cls, G, mode="evidence")
+        idx = outs["idx"].long()
+        reserved = torch.zeros((B, G + 1), dtype=torch.bool, device=x.device)
+        reserved.scatter_(1, torch.where((idx >= 0) & (idx < G), idx, torch.full_like(idx, G)), True)      # entries outside the grid: the spare column
+        grid = torch.where(reserved[:, None, :G], cell, torch.zeros_like(cell))
+        return upsample_cubic_device(grid.reshape(B, M, side, side).contiguous(), H), None, None
+    if order == "attention":
+        up = upsample_cubic_device(outs["token_attn"].reshape(B, side, side).contiguous(), H)
+        return up[:, None].expand(B, M, H, W).contiguous(), None, None
+    if order == "random":
+        s = ops.pixel_random(_image_ids(image_ids, B, x.device), H * W, seed)
+        return s.reshape(B, 1, H, W).expand(B, M, H, W).contiguous(), None, None
+    if order in EXTRA_ORDERS:
+        found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
+                                   **{**RISE_DEFAULTS, **(rise or {})})
+        return found.saliency.contiguous(), found, None
+    if order in GRADIENT_ORDERS:
+        _refuse_pending_gradients("faithfulness_curves", ppnet)
+        found = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
+        a = found.attribution
+        return ((a[:, :, 0] + a[:, :, 1]) + a[:, :, 2]).contiguous(), None, found                  # two rounded adds, in this order
+    raise ValueError(f"pixel_scores: order must be one of {ORDER_MODES + EXTRA_ORDERS + GRADIENT_ORDERS}, got {order!r}")
+
+
+def pixel_scores(ppnet, x, outs, cls, order, baseline=0.0, seed=0, image_ids=None, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
+    """The map fp32 [B, M, H, W] (device) whose pixels the order `order` removes largest first, for x [B, 3, H, W], the eval outputs of its
+    forward (outs) and the classes cls int32 [B, M]:
+      'evidence'   the g x g grid that holds, on the reserved cells, the class evidence ppf_cell_order's mode 0 returns and 0 elsewhere,
+                   up-sampled to H by upsample_cubic_device -- the map a person is shown.  The two-tier rule of the cell order (reserved
+                   cells first, then the others by attention) is NOT carried over: an unreserved cell has no evidence, and the cubic
+                   kernel mixes neighbouring cells anyway;
+      'attention'  the rollout grid, up-sampled the same way (the same for every class);
+      'random'     ppf_pixel_random of (seed, image id, pixel), the same for every class;
+      'rise'       Rise.saliency of rise_saliency with this baseline, seed, image_ids (rise = dict(masks=, cells=, p=));
+      'ig'         (a[:, :, 0] + a[:, :, 1]) + a[:, :, 2] of the attribution of integrated_gradients from this baseline, two rounded fp32
+                   adds in that order (ig = dict(steps=, rule=)).
+    The caller holds no_grad."""
+    return _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)[0]
+
+
+def _resolve_baseline(baseline, x, blur):
+    """The baseline of a curve: a number or a tensor as given; the string 'blur': gauss_blur(x) with BLUR_DEFAULTS overridden by `blur`."""
+    if isinstance(baseline, str):
+        if baseline != "blur":
+            raise ValueError(f"faithfulness: baseline must be a number, a tensor like x or 'blur', got {baseline!r}")
+        return gauss_blur(x, **{**BLUR_DEFAULTS, **(blur or {})})
+    return baseline
+
+
 class Faithfulness:
     """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
     class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
     order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G.  rise: the Rise the 'rise' order ranked by
-    (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order."""
+    (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order.
+    resolution 'pixel': counts are pixels, grid_cells = H * W, rank int32 and score fp32 are [B, M, H * W] as ppf_pixel_order ranked them,
+    and order is None (51 MB per class column at 224^2 that nobody reads)."""
     FIELDS = ("counts", "classes", "order", "rank", "score")
 
-    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None, ig=None):
+    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None, ig=None, resolution="cell"):
         self.curves, self.counts, self.classes, self.order, self.rank, self.score = dict(curves), counts, classes, order, rank, score
-        self.grid_cells, self.rise, self.ig = int(grid_cells), rise, ig
+        self.grid_cells, self.rise, self.ig, self.resolution = int(grid_cells), rise, ig, str(resolution)
 
     @property
     def on_host(self):
@@ -980,7 +1142,8 @@ class Faithfulness:
             return self
         out = read_once({**{k: getattr(self, k) for k in self.FIELDS}, **{("curve", k): v for k, v in self.curves.items()}})
         return Faithfulness({k: out["curve", k] for k in self.curves}, *(out[k] for k in self.FIELDS), self.grid_cells,
-                            rise=None if self.rise is None else self.rise.cpu(), ig=None if self.ig is None else self.ig.cpu())
+                            rise=None if self.rise is None else self.rise.cpu(), ig=None if self.ig is None else self.ig.cpu(),
+                            resolution=self.resolution)
 
     def auc(self):
         """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
@@ -1022,13 +1185,22 @@ def _class_probs(ppnet, imgs, cols, batch_size):
     return [ops.class_prob(logits, c) for c in cols]
 
 
-def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None, ig=None):
+def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None, ig=None,
+                         resolution="cell"):
     from . import ops
     B, G = x.shape[0], int(ppnet.num_patches)
     M, S = cls.shape[1], counts.shape[0]
     w_l = ppnet.last_layer.weight.detach().contiguous()
-    found = found_ig = None
-    if order in GRADIENT_ORDERS:
+    found = found_ig = ordr = None
+    perturb = ops.patch_perturb
+    if resolution == "pixel":
+        # every order is a [B, M, H, W] map (pixel_scores); one ppf_pixel_order launch ranks the B * M rows, ppf_pixel_perturb takes
+        # ppf_patch_perturb's place below.  The chunking, the forwards and ppf_class_prob are the cell path's.
+        G, perturb = x.shape[2] * x.shape[3], ops.pixel_perturb
+        score, found, found_ig = _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
+        score = score.reshape(B, M, G)
+        rank = pixel_order_from_scores(score, cls)
+    elif order in GRADIENT_ORDERS:
         # the cells ranked by the integrated gradients of the class logit summed over each cell, along the path from the curve's own
         # baseline; through ppf_cell_order's attention mode exactly as the rise order below
         _refuse_pending_gradients("faithfulness_curves", ppnet)
@@ -1057,11 +1229,11 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
             prob = torch.empty((S, B, M), dtype=torch.float32, device=x.device)
             for s0 in range(0, S, chunk):
                 n = min(chunk, S - s0)
-                imgs = ops.patch_perturb(x, rank, counts[s0:s0 + n].contiguous(), mode == "insertion", baseline, out=buf[:n])
+                imgs = perturb(x, rank, counts[s0:s0 + n].contiguous(), mode == "insertion", baseline, out=buf[:n])
                 imgs = imgs.reshape((n * B * M,) + tuple(x.shape[1:]))
                 prob[s0:s0 + n] = _class_probs(ppnet, imgs, [cls_flat[:n * B * M]], int(batch_size or B))[0].reshape(n, B, M)
             curves[mode] = prob.permute(1, 2, 0).contiguous()
-    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found, ig=found_ig)
+    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found, ig=found_ig, resolution=resolution)
 
 
 def _pick_classes(ppnet, outs, classes, top_classes, B):
@@ -1076,7 +1248,7 @@ def _pick_classes(ppnet, outs, classes, top_classes, B):
 
 @torch.no_grad()
 def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, modes=CURVE_MODES, order="evidence", baseline=0.0, seed=0, image_ids=None,
-                        batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
+                        batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None):
     """Deletion / insertion curves of a batch x [B, 3, H, W] (CUDA): one eval forward, one ppf_cell_order launch, then per mode
     ppf_patch_perturb in chunks of steps, the model's forward over each chunk in sub-batches of `batch_size` images (default B; the
     images of a chunk are ordered step, sample, class) and one ppf_class_prob per chunk.  The chunk's images are the one large scratch
@@ -1087,17 +1259,24 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     rise = dict(masks=, cells=, p=) overrides RISE_DEFAULTS; the result carries the Rise), or 'ig': by the integrated gradients of the
     class logit summed over each cell (integrated_gradients along the path from the same baseline, in the same sample groups;
     ig = dict(steps=, rule=) overrides IG_DEFAULTS; the result carries the IntegratedGradients).  baseline: what a removed pixel becomes, a
-    number in normalised space (0 = the data-set mean colour) or a tensor like x.  Returns a Faithfulness (device tensors; nothing is read
-    back here)."""
+    number in normalised space (0 = the data-set mean colour), a tensor like x, or 'blur': gauss_blur(x) with blur = dict(sigma=, radius=)
+    over BLUR_DEFAULTS, computed once and used wherever the baseline is (the rise and ig passes included).  resolution 'pixel': the
+    metric as published -- the order's [B, M, H, W] map (pixel_scores) is ranked by one ppf_pixel_order launch, counts are pixels (default
+    default_counts(H * W)) and ppf_pixel_perturb builds the images; everything else is the same.  Returns a Faithfulness (device
+    tensors; nothing is read back here)."""
+    if resolution not in RESOLUTIONS:
+        raise ValueError(f"faithfulness_curves: resolution must be one of {RESOLUTIONS}, got {resolution!r}")
     if not x.is_cuda:
         raise RuntimeError("faithfulness_curves needs a CUDA/HIP batch (no CPU fallback path; cell_order_from_outputs / perturb_patches with "
                            "device=False are the host referees)")
     x = x.float().contiguous()
-    G = int(ppnet.num_patches)
+    G = int(ppnet.num_patches) if resolution == "cell" else x.shape[2] * x.shape[3]
+    baseline = _resolve_baseline(baseline, x, blur)
     outs = _eval_outputs(ppnet, x)
     cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
     counts = _device_counts(counts, G, x.device)
-    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
+    return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig,
+                                resolution)
 
 
 def _device_counts(counts, G, device):
@@ -1109,22 +1288,31 @@ def _device_counts(counts, G, device):
 
 @torch.no_grad()
 def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=None, top_classes=1, against_label=False, baseline=0.0, seed=0,
-                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
+                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None):
     """The curves over a data set.  loader yields (x, labels) or (x, labels, ids); without ids an image's id is its running index.  Per
     batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=), and 'ig', with ig = dict(steps=, rule=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
     The per-image curves stay on the device and are read back once at the end.  Returns dict(images, counts, grid_cells, orders:
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
-    image_ids [N]); rows whose class could not be picked (-1) are left out of the means."""
+    image_ids [N]); rows whose class could not be picked (-1) are left out of the means.  resolution, baseline = 'blur' and blur: as in
+    faithfulness_curves (the blurred batch is computed once per batch and serves every order); at pixel resolution counts are pixels
+    and grid_cells = H * W."""
+    if resolution not in RESOLUTIONS:
+        raise ValueError(f"faithfulness: resolution must be one of {RESOLUTIONS}, got {resolution!r}")
     G, kept, cls_kept, ids_kept, seen, dev_counts = int(ppnet.num_patches), {}, [], [], 0, None
+    given = baseline
     for x, y, ids in batches_with_ids(loader, max_images):
         x = (x if x.is_cuda else x.cuda()).float().contiguous()
         B, ids = x.shape[0], ids.to(x.device)               # on the device once: the random / rise orders key by them, the closing read takes them
+        if resolution == "pixel":
+            G = x.shape[2] * x.shape[3]
+        baseline = _resolve_baseline(given, x, blur)
         outs = _eval_outputs(ppnet, x)
         cls = _pick_classes(ppnet, outs, torch.as_tensor(y).to(x.device) if against_label else None, top_classes, B)
         if dev_counts is None:
             dev_counts = _device_counts(counts, G, x.device)
         for order in orders:
-            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise, ig)
+            f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise, ig,
+                                     resolution)
             for mode in modes:
                 kept.setdefault((order, mode), []).append(f.curves[mode])
         cls_kept.append(cls); ids_kept.append(ids)

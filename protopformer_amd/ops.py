@@ -636,6 +636,82 @@ def class_prob(logits, cls):
     return prob
 
 
+# ---- the same curves per pixel (csrc/pixel_faithful.hip): pixel order, random pixel scores, perturbed images, Gaussian blur
+def pixel_order(score, classes):
+    """rank int32 [R, n]: the number of pixels of row r that come before pixel i, larger score first, ties by the smaller pixel, NaN lowest,
+    -0 == +0; a row with classes[r] < 0 is all -1 (ppf_pixel_order, include/ppf_hip.h); one launch.  score fp32 [R, n], classes int32 [R];
+    the sort's ping-pong buffers come from the stream's workspace."""
+    who = "pixel_order"
+    if not isinstance(score, torch.Tensor) or score.dim() != 2:
+        raise ValueError(f"{who}: score must be an fp32 CUDA tensor [R, n]")
+    _dev_tensor(who, "score", score, torch.float32, score.shape)
+    R, n = score.shape
+    _dev_tensor(who, "classes", classes, torch.int32, (R,), score.device)
+    rank = torch.empty((R, n), dtype=torch.int32, device=score.device)
+    nbytes = _lib.lib().ppf_pixel_order_scratch_bytes(R, n)
+    ws = _workspace(score.device, max(nbytes, 16))
+    _lib.call("ppf_pixel_order", score, classes, R, n, rank, ws, ws.numel())
+    return rank
+
+
+def pixel_random(image_ids, pixels, seed=0):
+    """score fp32 [B, pixels]: the Philox draw of (seed, image id, pixel) in [0, 1) (ppf_pixel_random); image_ids int64 [B]."""
+    who = "pixel_random"
+    if not isinstance(image_ids, torch.Tensor) or image_ids.dim() != 1:
+        raise ValueError(f"{who}: image_ids must be an int64 CUDA tensor [B]")
+    _dev_tensor(who, "image_ids", image_ids, torch.int64, image_ids.shape)
+    B, n = image_ids.shape[0], int(pixels)
+    score = torch.empty((B, max(n, 0)), dtype=torch.float32, device=image_ids.device)
+    _lib.call("ppf_pixel_random", image_ids, int(seed) & 0xFFFFFFFFFFFFFFFF, B, n, score)
+    return score
+
+
+def pixel_perturb(x, rank, counts, insertion=False, baseline=0.0, out=None):
+    """The perturbed images out fp32 [S, B, M, Cc, H, W] of x fp32 [B, Cc, H, W] for rank int32 [B, M, H * W] and counts int32 [S] on the
+    device (ppf_pixel_perturb, include/ppf_hip.h); one launch.  baseline: a number, or an fp32 tensor like x."""
+    who = "pixel_perturb"
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [B, Cc, H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    B, Cc, H, W = x.shape
+    if not isinstance(rank, torch.Tensor) or rank.dim() != 3 or rank.shape[0] != B or rank.shape[2] != H * W:
+        raise ValueError(f"{who}: rank must be an int32 CUDA tensor [{B}, M, {H * W}]")
+    _dev_tensor(who, "rank", rank, torch.int32, rank.shape, x.device)
+    M = rank.shape[1]
+    if not isinstance(counts, torch.Tensor) or counts.dim() != 1:
+        raise ValueError(f"{who}: counts must be an int32 CUDA tensor [S]")
+    _dev_tensor(who, "counts", counts, torch.int32, counts.shape, x.device)
+    S = counts.shape[0]
+    base_t, base_c = None, 0.0
+    if isinstance(baseline, torch.Tensor):
+        base_t = _dev_tensor(who, "baseline", baseline, torch.float32, x.shape, x.device)
+    else:
+        base_c = float(baseline)
+    shape = (S, B, M, Cc, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_tensor(who, "out", out, torch.float32, shape, x.device)
+    _lib.call("ppf_pixel_perturb", x, rank, counts, S, 1 if insertion else 0, base_t, base_c, B, M, Cc, H, W, out)
+    return out
+
+
+def gauss_blur(x, taps):
+    """out like x fp32 [..., H, W]: every plane blurred separably with taps fp32 [2r + 1] (a CUDA tensor) and a zero border
+    (ppf_gauss_blur, include/ppf_hip.h); one launch."""
+    who = "gauss_blur"
+    if not isinstance(x, torch.Tensor) or x.dim() < 2:
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [..., H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    if not isinstance(taps, torch.Tensor) or taps.dim() != 1 or taps.shape[0] % 2 != 1:
+        raise ValueError(f"{who}: taps must be an fp32 CUDA tensor [2r + 1]")
+    _dev_tensor(who, "taps", taps, torch.float32, taps.shape, x.device)
+    H, W = x.shape[-2:]
+    out = torch.empty_like(x)
+    _lib.call("ppf_gauss_blur", x, taps, (taps.shape[0] - 1) // 2, x.numel() // max(H * W, 1), H, W, out)
+    return out
+
+
 # ---- RISE saliency (csrc/rise.hip): node tables, masked images, the probability-weighted mean mask
 def _rise_tables(who, nodes, shift, cells):
     LL = (int(cells) + 2) ** 2
