@@ -609,6 +609,47 @@ int ppf_act_part_table(const int* peak_yx, int M, int S, const int* parts, int m
                        ppf_stream_t stream);
 int ppf_act_order_stats(const float* grids, int M, int g, int S, int k_lo, int k_hi, float* stats, ppf_stream_t stream);
 int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int* box, ppf_stream_t stream);
+/* Foreground focus (csrc/interp.hip, csrc/explain.hip; interpret.foreground_focus): does the model look at the object?  The reserved
+ * tokens, the peaks and the positive mass of the prototype maps, and the class evidence, each against an annotated object box per image
+ * (the energy-based pointing game of Wang et al., Score-CAM, 2020, on the positive part of the up-sampled map).  The reference has no
+ * such pass.  Additions of ABI 10: no existing entry point changed.
+ * An object box is int32 (y0, y1, x0, x1), half-open, in pixels of the S x S model input (the layout ppf_act_box writes and
+ * ppf_grad_box_mass reads).  Every entry point clips it to [0, S] per coordinate; a box whose upper end is not above its lower end is
+ * empty, and an empty box is accepted.
+ *   ppf_act_focus        grids [M][g][g] as above (the same limits on g, S and LDS as ppf_act_peak), obj [M / maps_per_img][4]: map m
+ *                        belongs to image m / maps_per_img (M a multiple of maps_per_img >= 1).  One workgroup per map, the map never
+ *                        written.  peak_val [M], peak_yx [M][2]: bit-identical to ppf_act_peak on the same maps (first occurrence in
+ *                        row-major order, NaN never wins, a map of NaNs gives (0, 0) with value -inf).  hit [M] int32 = 1 iff
+ *                        y0 <= peak_y < y1 and x0 <= peak_x < x1.  inside [M], total [M] fp64 = the sum of max(v, 0) over the finite fp32
+ *                        values v of the up-sampled map inside the box and over the whole map, every term exact; the summation order is
+ *                        fixed by the thread mapping and otherwise unspecified.  nonfinite [M] int32 (may be NULL) = how many values were
+ *                        NaN or +-inf; they add 0 to both sums.  No floating-point atomics: repeated runs are bit-identical.
+ *   ppf_focus_box_terms  box [M][4] (as ppf_act_box writes it), obj [M / maps_per_img][4] -> terms [M][4] int32 = (intersection area, box
+ *                        area, object area, union area) of the two boxes, both clipped to [0, S]^2.  Integers only.  1 <= S <= 32768.
+ *   ppf_reserve_focus    idx [B][T] int32 = the grid cells of the reserved tokens on the g x g grid of patch x patch pixel cells
+ *                        (S = g * patch <= 32768), obj [B][4] -> out [B][4] int32 = (pixels of the reserved cells inside the box: the sum
+ *                        of the exact rectangle overlaps; reserved cells whose centre pixel (cy * patch + patch / 2, cx * patch + patch / 2)
+ *                        is inside; all g*g cells whose centre is inside; idx entries inside [0, g*g)).  An idx entry outside [0, g*g) is
+ *                        skipped everywhere; a cell listed twice counts twice.  token_attn [B][g*g] fp32 not NULL: also attn [B][2] fp64
+ *                        = the rollout score summed over the cells with centre inside and over all cells, non-finite scores counting
+ *                        0 (fixed order).  token_attn and attn are both given or both NULL.  T * patch^2 <= 2^31 - 1.
+ *   ppf_evidence_focus   the local branch's evidence for classes [B][M] int32 (1 <= M <= 8), one wave per (sample, class) row: the
+ *                        contribution of prototype p is fl(act_max[b][p] * fl(scale * weight[c][p])), ppf_explain_topk's two roundings;
+ *                        its cell is idx[b][argmax[b][p]] and it is "located" when that argmax lies in [0, T) and the cell in [0, g*g)
+ *                        (argmax == NULL, the k = 1 model: the cell is idx[b][0]).  ev [B][M][4] fp64 = the sums over (own class and
+ *                        centre inside obj[b], own class and not inside, other classes and inside, other classes and not inside), own
+ *                        class meaning p / ppc == c; a prototype that is not located counts as not inside.  The four sums together are
+ *                        the branch's share of logits[b][c], so non-finite terms are included, as in ppf_explain_topk's evidence.
+ *                        cnt [B][M][4] int32 = the number of terms of each sum.  A class outside [0, C): zeros, nothing read out of
+ *                        range.  act_max [B][P], argmax [B][P], idx [B][T], weight [C][P], obj [B][4]; P % ppc == 0, T >= 1. */
+int ppf_act_focus(const float* grids, const int* obj, int M, int g, int S, int maps_per_img, float* peak_val, int* peak_yx, int* hit,
+                  double* inside, double* total, int* nonfinite, ppf_stream_t stream);
+int ppf_focus_box_terms(const int* box, const int* obj, int M, int maps_per_img, int S, int* terms, ppf_stream_t stream);
+int ppf_reserve_focus(const int* idx, const int* obj, const float* token_attn, int B, int T, int g, int patch, int* out, double* attn,
+                      ppf_stream_t stream);
+int ppf_evidence_focus(const float* act_max, const int* argmax, const int* idx, int T, const float* weight, float scale, int ppc,
+                       const int* classes, const int* obj, int g, int patch, int B, int P, int C, int M, double* ev, int* cnt,
+                       ppf_stream_t stream);
 /* Stability score (Huang et al., ICCV 2023: does a prototype point at the same parts when the input is perturbed?) next to the
  * consistency score, both accumulated on the device.  Additions of ABI 10: no existing entry point changed.
  *   ppf_add_gauss_noise    out[b][e] = fmaf(sigma, n(seed, image_id[b], e), x[b][e]) on fp32 [B][n_per_img]; out may be x.  n is a standard

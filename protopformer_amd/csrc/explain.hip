@@ -18,6 +18,8 @@
 //   * Evidence: per-lane fp64 partial sums over the chunks, one shuffle reduction at the end, one rounding to fp32.
 //   * Maps: written by the wave after the list is final.  The inverse of idx[b] (grid cell -> reserved token, -1 elsewhere) is built once
 //     in LDS, so every cell of every map is written exactly once, coalesced: zero, or act_full[b][p][t] at cell idx[b][t].
+//   * evidence_focus_kernel: the same walk over P without a list; the evidence of a class split four ways, by own / other class and by
+//     whether the prototype's cell has its centre pixel inside the image's object box (interpret.foreground_focus).
 #include <limits.h>
 #include <math.h>
 
@@ -154,6 +156,76 @@ __global__ __launch_bounds__(64) void explain_topk_kernel(const float* __restric
     }
 }
 
+// Foreground focus of the evidence: the contributions of explain_topk_kernel (the same two roundings), split by whose class the prototype
+// is and by whether its cell's centre pixel lies in the image's object box.  One wave per (sample, class) row, per-lane fp64 partial sums
+// over the chunks, one shuffle reduction: no atomics.  grid: B * M workgroups of one wave.
+__global__ __launch_bounds__(64) void evidence_focus_kernel(const float* __restrict__ act_max, const int* __restrict__ argmax, const int* __restrict__ idx,
+                                                            int T, const float* __restrict__ weight, float scale, int ppc, const int* __restrict__ classes,
+                                                            const int* __restrict__ obj, int g, int patch, int P, int C, int M, double* __restrict__ ev,
+                                                            int* __restrict__ cnt) {
+    const int lane = threadIdx.x;
+    const int list = blockIdx.x, b = list / M;
+    int c = classes[list];
+    if (c < 0 || c >= C) c = -1;
+    c = __builtin_amdgcn_readfirstlane(c);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                                       // own & inside, own & not, other & inside, other & not
+    int n[4] = {0, 0, 0, 0};
+    if (c >= 0) {
+        const int S = g * patch, G = g * g;
+        const int* o = obj + 4 * (size_t)b;
+        const int y0 = min(max(o[0], 0), S), y1 = min(max(o[1], 0), S), x0 = min(max(o[2], 0), S), x1 = min(max(o[3], 0), S);
+        const float* __restrict__ arow = act_max + (size_t)b * P;
+        const float* __restrict__ wrow = weight + (size_t)c * P;
+        const int own_lo = c * ppc, own_hi = own_lo + ppc;
+        for (int p0 = 0; p0 < P; p0 += 64 * UNR) {
+            float av[UNR], wv[UNR];
+            int tv[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int p = p0 + u * 64 + lane;
+                av[u] = p < P ? arow[p] : 0.0f;
+                wv[u] = p < P ? wrow[p] : 0.0f;
+                tv[u] = (p < P && argmax) ? argmax[(size_t)b * P + p] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                const int p = p0 + u * 64 + lane;
+                if (p >= P) continue;
+                const float ctr = __fmul_rn(av[u], __fmul_rn(scale, wv[u]));
+                bool in = false;
+                if (tv[u] >= 0 && tv[u] < T) {
+                    const int cell = idx[(size_t)b * T + tv[u]];
+                    if (cell >= 0 && cell < G) {
+                        const int cy = cell / g, cx = cell - cy * g;
+                        const int py = cy * patch + patch / 2, px = cx * patch + patch / 2;
+                        in = py >= y0 && py < y1 && px >= x0 && px < x1;
+                    }
+                }
+                const int k = ((p >= own_lo && p < own_hi) ? 0 : 2) + (in ? 0 : 1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {                                 // (no dynamic register index)
+                    s[j] += j == k ? (double)ctr : 0.0;
+                    n[j] += j == k ? 1 : 0;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s[j] = wave_sum_f64(s[j]);
+        n[j] = wave_sum_i32(n[j]);
+    }
+    if (lane < 4) {
+        double sv = s[0];
+        int nv = n[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j)
+            if (lane == j) { sv = s[j]; nv = n[j]; }
+        ev[4 * (size_t)list + lane] = sv;
+        cnt[4 * (size_t)list + lane] = nv;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,6 +252,20 @@ int ppf_explain_topk(const float* act_max, const int* argmax, const int* idx, in
     return ppf_launch<explain_topk_kernel>(dim3((unsigned)(B * M)), dim3(64), maps ? (size_t)G * sizeof(int) : 0, stream, "ppf_explain_topk", act_max,
                                            argmax, idx, T, act_full, weight, scale, ppc, logits, cls_in, sign, P, C, M, K, G, cls_out, cls_logit, proto,
                                            contrib, act, cell, evidence, maps);
+}
+
+int ppf_evidence_focus(const float* act_max, const int* argmax, const int* idx, int T, const float* weight, float scale, int ppc, const int* classes,
+                       const int* obj, int g, int patch, int B, int P, int C, int M, double* ev, int* cnt, hipStream_t stream) {
+    PPF_CHECK_ARG(M >= 1 && M <= 8, PPF_ERR_SHAPE, "ppf_evidence_focus: M=%d outside [1, 8] (classes per sample)", M);
+    PPF_CHECK_ARG(B >= 1 && P >= 1 && C >= 1 && T >= 1, PPF_ERR_SHAPE, "ppf_evidence_focus: bad shape B=%d P=%d C=%d T=%d (all >= 1)", B, P, C, T);
+    PPF_CHECK_ARG((long long)B * M <= INT_MAX, PPF_ERR_SHAPE, "ppf_evidence_focus: B=%d x M=%d rows exceed the grid", B, M);
+    PPF_CHECK_ARG(ppc >= 1 && P % ppc == 0 && (long long)C * ppc <= INT_MAX, PPF_ERR_SHAPE, "ppf_evidence_focus: ppc=%d must be >= 1 and divide P=%d (C=%d)",
+                  ppc, P, C);
+    PPF_CHECK_ARG(g >= 1 && patch >= 1 && (long long)g * patch <= 32768, PPF_ERR_SHAPE, "ppf_evidence_focus: bad grid g=%d patch=%d (both >= 1, g * patch <= 32768)",
+                  g, patch);
+    PPF_CHECK_ARG(act_max && idx && weight && classes && obj && ev && cnt, PPF_ERR_ARG, "ppf_evidence_focus: null pointer (only argmax may be NULL)");
+    return ppf_launch<evidence_focus_kernel>(dim3((unsigned)(B * M)), dim3(64), 0, stream, "ppf_evidence_focus", act_max, argmax, idx, T, weight, scale, ppc,
+                                             classes, obj, g, patch, P, C, M, ev, cnt);
 }
 
 }  // extern "C"

@@ -19,6 +19,9 @@
 //     act_box_kernel reduces the row / column extent of up >= thr; act_order_stats_kernel selects order statistics of the S*S fp32
 //     values exactly -- the 4-pass 8-bit radix select over order-preserving keys of rollout.hip (pass steps: ppf_select.h), the map
 //     recomputed in every pass instead of being held (S*S values do not fit the registers), integer LDS atomics only.
+//   * Foreground focus (interpret.foreground_focus): act_focus_kernel is act_peak_kernel's walk with an object box per image: the same
+//     peak, whether it lies in the box, and the fp64 sums of max(v, 0) over the box and over the map; focus_box_terms_kernel and
+//     reserve_focus_kernel are the integer kernels around it (box overlap areas; the reserved cells and the rollout scores against the box).
 //   * The stability score's two kernels live here too: gauss_noise_kernel adds N(0, sigma^2) noise that is a function of (seed, image id,
 //     element) alone (Philox4x32-10 + Box-Muller, accurate logf / sincospif), and part_meter_kernel adds a batch's part tables, and the
 //     row equality of a clean and a noisy table, into per-class int32 accumulators (interpret.PartMeter).
@@ -272,6 +275,146 @@ __global__ __launch_bounds__(NT) void act_box_kernel(const float* __restrict__ g
     }
 }
 
+// ---- 5. foreground focus: the peak, and the positive mass of the map inside / outside an object box
+// an object box (y0, y1, x0, x1), half-open, clipped to [0, S]; empty: the upper end is not above the lower one
+struct ObjBox { int y0, y1, x0, x1; };
+__device__ __forceinline__ ObjBox obj_clip(const int* __restrict__ o, int S) {
+    return ObjBox{clampi(o[0], S), clampi(o[1], S), clampi(o[2], S), clampi(o[3], S)};
+}
+
+// act_peak_kernel's walk and its peak, element for element, plus two fp64 sums per thread: max(v, 0) of the finite values over the map and
+// over the box.  A thread's columns never change, so their box test is made once; the row's is uniform over a call.  The sums are
+// reduced by wavefront shuffles and then over the four waves in index order: a fixed order, no atomics.
+__global__ __launch_bounds__(NT) void act_focus_kernel(const float* __restrict__ grids, const int* __restrict__ obj, int g, int S, double ratio,
+                                                       int maps_per_img, float* __restrict__ peak_val, int* __restrict__ peak_yx, int* __restrict__ hit,
+                                                       double* __restrict__ inside, double* __restrict__ total, int* __restrict__ nonfinite) {
+    extern __shared__ __align__(16) unsigned char act_smem[];
+    __shared__ float red_v[NT / 64];
+    __shared__ int red_i[NT / 64], red_n[NT / 64];
+    __shared__ double red_in[NT / 64], red_tot[NT / 64];
+    const int m = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const Lds L = act_carve(act_smem, g, S);
+    act_stage(grids + (size_t)m * g * g, L, g, S, ratio);
+    ColTaps T;
+    act_taps(T, L, g, S);
+    const ObjBox ob = obj_clip(obj + 4 * (size_t)(m / maps_per_img), S);
+    bool cin[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cin[q] = T.col0 + q >= ob.x0 && T.col0 + q < ob.x1;
+    float bv = -INFINITY;
+    int bi = INT_MAX, nf = 0;
+    double s_in = 0.0, s_tot = 0.0;
+    for (int r0 = 0; r0 < S; r0 += BAND)
+        act_band(L, T, g, S, r0, min(BAND, S - r0), [&](int row, int col0, const float (&v)[4], int n) {
+            const bool rin = row >= ob.y0 && row < ob.y1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int i = row * S + col0 + q;
+                if (q < n && comes_before(v[q], i, bv, bi)) { bv = v[q]; bi = i; }
+                const bool fin = fabsf(v[q]) < INFINITY;                      // false for NaN and +-inf
+                const double pos = (q < n && fin && v[q] > 0.0f) ? (double)v[q] : 0.0;
+                nf += (q < n && !fin) ? 1 : 0;
+                s_tot += pos;
+                s_in += (rin && cin[q]) ? pos : 0.0;
+            }
+        });
+    wave_first(bv, bi);
+    s_in = wave_sum_f64(s_in);
+    s_tot = wave_sum_f64(s_tot);
+    nf = wave_sum_i32(nf);
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; red_in[wave] = s_in; red_tot[wave] = s_tot; red_n[wave] = nf; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) {
+            if (comes_before(red_v[w], red_i[w], bv, bi)) { bv = red_v[w]; bi = red_i[w]; }
+            s_in += red_in[w];
+            s_tot += red_tot[w];
+            nf += red_n[w];
+        }
+        if (bi == INT_MAX) bi = 0;                        // nothing compared (NaNs only)
+        const int y = bi / S, x = bi - y * S;
+        peak_val[m] = bv;
+        peak_yx[2 * (size_t)m] = y;
+        peak_yx[2 * (size_t)m + 1] = x;
+        hit[m] = (y >= ob.y0 && y < ob.y1 && x >= ob.x0 && x < ob.x1) ? 1 : 0;
+        inside[m] = s_in;
+        total[m] = s_tot;
+        if (nonfinite) nonfinite[m] = nf;
+    }
+}
+
+// (intersection, box, object, union) areas of the clipped boxes: integers only, one thread per map
+__global__ __launch_bounds__(NT) void focus_box_terms_kernel(const int* __restrict__ box, const int* __restrict__ obj, int M, int maps_per_img, int S,
+                                                             int* __restrict__ terms) {
+    const int m = blockIdx.x * NT + threadIdx.x;
+    if (m >= M) return;
+    const ObjBox a = obj_clip(box + 4 * (size_t)m, S), o = obj_clip(obj + 4 * (size_t)(m / maps_per_img), S);
+    const int abox = max(a.y1 - a.y0, 0) * max(a.x1 - a.x0, 0), aobj = max(o.y1 - o.y0, 0) * max(o.x1 - o.x0, 0);
+    const int inter = (abox > 0 && aobj > 0) ? max(min(a.y1, o.y1) - max(a.y0, o.y0), 0) * max(min(a.x1, o.x1) - max(a.x0, o.x0), 0) : 0;
+    int* t = terms + 4 * (size_t)m;
+    t[0] = inter; t[1] = abox; t[2] = aobj; t[3] = abox + aobj - inter;
+}
+
+// is the centre pixel of grid cell c inside the (clipped) box?
+__device__ __forceinline__ bool cell_centre_in(int c, int g, int patch, const ObjBox& ob) {
+    const int cy = c / g, cx = c - cy * g;
+    const int py = cy * patch + patch / 2, px = cx * patch + patch / 2;
+    return py >= ob.y0 && py < ob.y1 && px >= ob.x0 && px < ob.x1;
+}
+
+// One workgroup per image: the reserved cells against the box (integers), and the rollout scores over the cells whose centre is inside
+// (fp64, a thread's cells in ascending order, then shuffles, then the waves in index order).
+__global__ __launch_bounds__(NT) void reserve_focus_kernel(const int* __restrict__ idx, const int* __restrict__ obj, const float* __restrict__ token_attn,
+                                                           int T, int g, int patch, int* __restrict__ out, double* __restrict__ attn) {
+    __shared__ int red_i[NT / 64][4];
+    __shared__ double red_d[NT / 64][2];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, G = g * g;
+    const ObjBox ob = obj_clip(obj + 4 * (size_t)b, g * patch);
+    int e[4] = {0, 0, 0, 0};
+    for (int t = threadIdx.x; t < T; t += NT) {
+        const int c = idx[(size_t)b * T + t];
+        if (c < 0 || c >= G) continue;
+        const int cy = c / g, cx = c - cy * g;
+        const int oy = max(min((cy + 1) * patch, ob.y1) - max(cy * patch, ob.y0), 0), ox = max(min((cx + 1) * patch, ob.x1) - max(cx * patch, ob.x0), 0);
+        e[0] += oy * ox;
+        e[1] += cell_centre_in(c, g, patch, ob) ? 1 : 0;
+        e[3] += 1;
+    }
+    double a_in = 0.0, a_all = 0.0;
+    for (int c = threadIdx.x; c < G; c += NT) {
+        const bool in = cell_centre_in(c, g, patch, ob);
+        e[2] += in ? 1 : 0;
+        if (token_attn) {
+            const float v = token_attn[(size_t)b * G + c];
+            const double d = fabsf(v) < INFINITY ? (double)v : 0.0;
+            a_all += d;
+            a_in += in ? d : 0.0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = wave_sum_i32(e[k]);
+    a_in = wave_sum_f64(a_in);
+    a_all = wave_sum_f64(a_all);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red_i[wave][k] = e[k];
+        red_d[wave][0] = a_in; red_d[wave][1] = a_all;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e[k] += red_i[w][k];
+            a_in += red_d[w][0]; a_all += red_d[w][1];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[4 * (size_t)b + k] = e[k];
+        if (token_attn) { attn[2 * (size_t)b] = a_in; attn[2 * (size_t)b + 1] = a_all; }
+    }
+}
+
 // ---- order statistics of the S*S fp32 values
 // ranks are 0-based in ascending order, k_lo <= k_hi <= k_lo + 1
 __global__ __launch_bounds__(NT) void act_order_stats_kernel(const float* __restrict__ grids, int g, int S, double ratio, int k_lo, int k_hi,
@@ -519,6 +662,35 @@ int ppf_act_box(const float* grids, const double* thr, int M, int g, int S, int*
     if (int rc = act_check("ppf_act_box", grids, M, g, S)) return rc;
     PPF_CHECK_ARG(thr != nullptr && box != nullptr, PPF_ERR_ARG, "ppf_act_box: null pointer");
     return ppf_launch<act_box_kernel>(dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_box", grids, thr, g, S, (double)g / (double)S, box);
+}
+
+int ppf_act_focus(const float* grids, const int* obj, int M, int g, int S, int maps_per_img, float* peak_val, int* peak_yx, int* hit, double* inside,
+                  double* total, int* nonfinite, hipStream_t stream) {
+    if (int rc = act_check("ppf_act_focus", grids, M, g, S)) return rc;
+    PPF_CHECK_ARG(maps_per_img >= 1 && M % maps_per_img == 0, PPF_ERR_SHAPE, "ppf_act_focus: M=%d maps are no multiple of maps_per_img=%d (>= 1)", M,
+                  maps_per_img);
+    PPF_CHECK_ARG(obj != nullptr && peak_val != nullptr && peak_yx != nullptr && hit != nullptr && inside != nullptr && total != nullptr, PPF_ERR_ARG,
+                  "ppf_act_focus: null pointer (only nonfinite may be NULL)");
+    return ppf_launch<act_focus_kernel>(dim3((unsigned)M), dim3(NT), act_lds_bytes(g, S), stream, "ppf_act_focus", grids, obj, g, S, (double)g / (double)S,
+                                        maps_per_img, peak_val, peak_yx, hit, inside, total, nonfinite);
+}
+
+int ppf_focus_box_terms(const int* box, const int* obj, int M, int maps_per_img, int S, int* terms, hipStream_t stream) {
+    PPF_CHECK_ARG(M >= 1 && S >= 1 && S <= 32768, PPF_ERR_SHAPE, "ppf_focus_box_terms: bad shape M=%d S=%d (M >= 1, 1 <= S <= 32768)", M, S);
+    PPF_CHECK_ARG(maps_per_img >= 1 && M % maps_per_img == 0, PPF_ERR_SHAPE, "ppf_focus_box_terms: M=%d boxes are no multiple of maps_per_img=%d (>= 1)", M,
+                  maps_per_img);
+    PPF_CHECK_ARG(box != nullptr && obj != nullptr && terms != nullptr, PPF_ERR_ARG, "ppf_focus_box_terms: null pointer");
+    return ppf_launch<focus_box_terms_kernel>(dim3((unsigned)((M + NT - 1) / NT)), dim3(NT), 0, stream, "ppf_focus_box_terms", box, obj, M, maps_per_img, S,
+                                              terms);
+}
+
+int ppf_reserve_focus(const int* idx, const int* obj, const float* token_attn, int B, int T, int g, int patch, int* out, double* attn, hipStream_t stream) {
+    PPF_CHECK_ARG(B >= 1 && T >= 1 && g >= 1 && patch >= 1 && (long long)g * patch <= 32768, PPF_ERR_SHAPE,
+                  "ppf_reserve_focus: bad shape B=%d T=%d g=%d patch=%d (all >= 1, g * patch <= 32768)", B, T, g, patch);
+    PPF_CHECK_ARG((long long)T * patch * patch <= INT_MAX, PPF_ERR_SHAPE, "ppf_reserve_focus: T=%d cells of patch=%d pixels squared overflow int32", T, patch);
+    PPF_CHECK_ARG(idx != nullptr && obj != nullptr && out != nullptr, PPF_ERR_ARG, "ppf_reserve_focus: null pointer");
+    PPF_CHECK_ARG((token_attn == nullptr) == (attn == nullptr), PPF_ERR_ARG, "ppf_reserve_focus: token_attn and attn must both be given or both be NULL");
+    return ppf_launch<reserve_focus_kernel>(dim3((unsigned)B), dim3(NT), 0, stream, "ppf_reserve_focus", idx, obj, token_attn, T, g, patch, out, attn);
 }
 
 int ppf_add_gauss_noise(const float* x, float* out, int B, int64_t n_per_img, const void* image_id_i64, float sigma, uint64_t seed, hipStream_t stream) {

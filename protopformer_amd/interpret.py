@@ -1159,10 +1159,11 @@ def curve_auc(curves, counts, grid_cells):
 
 
 def _eval_outputs(ppnet, x):
-    """One eval forward: what the cell orders and the class pick need, all on the device."""
+    """One eval forward: what the cell orders, the class pick and the focus pass need, all on the device."""
     r = ppnet.eval_branches(x)
     return dict(token_attn=r.cls_attn.reshape(x.shape[0], -1).float().contiguous(), idx=r.idx.contiguous(), act_full=r.act_full.contiguous(),
-                logits=r.logits.contiguous(), act_max=r.act_max_local, act_max_global=r.act_max_global, argmax=r.argmax)
+                logits=r.logits.contiguous(), act_max=r.act_max_local, act_max_global=r.act_max_global, argmax=r.argmax,
+                logits_global=r.logits_global)
 
 
 def _image_ids(image_ids, B, device):
@@ -2483,4 +2484,352 @@ def characteristic_importance(ppnet, loader, protos="own", branch="local", chara
     out.update(images=images, characteristics=list(names), branch=branch)
     if per_image:
         out["rows"] = rows
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ foreground focus: does the model look at the object?
+# ProtoPFormer's argument is about where the model looks: the rollout reservation is to keep the object's tokens, the local prototypes
+# are to fire on its parts.  With an annotated object box per image (CUB's bounding_boxes.txt) three questions have numbers: are the
+# reserved tokens on the object, do the prototype maps peak and carry their positive mass there (the pointing game and its energy-based
+# form, Wang et al., Score-CAM, 2020), and how much of the class evidence comes from cells on the object.  Each is reported next to
+# `chance`, the object's share of the image area: what a spatially blind map, reservation or evidence would score.  The kernels:
+# ppf_act_focus, ppf_focus_box_terms, ppf_reserve_focus (csrc/interp.hip) and ppf_evidence_focus (csrc/explain.hip); the numpy forms
+# below (device=False) are the referees (the contract is in include/ppf_hip.h).  The reference has no such pass.
+FOCUS_PROTOS = ("own", "top")
+FOCUS_FIELDS = ("protos", "classes", "peak_val", "peak_yx", "hit", "inside", "total", "nonfinite", "box", "terms", "reserve", "attn", "ev", "cnt",
+                "global_ev", "obj", "labels")
+
+
+def scaled_boxes(ids, boxes, image_sizes, img_size):
+    """The object boxes of a batch in pixels of the square img_size x img_size view (Resize((S, S)): a linear map per axis): int32
+    [B, 4] rows (Y0, Y1, X0, X1), half-open.  boxes {img_id: (x0, y0, x1, y1)} in pixels of the original file, image_sizes {img_id:
+    (width, height)}.  In integers: X0 = (S * x0) // w, X1 = min(S, max(X0 + 1, ceil(S * x1 / w))), likewise in y: the scaled box covers
+    every view pixel the source box touches and is never empty for a non-empty source box.  The host referee and the device path both
+    take their boxes from here (as scaled_parts for the parts)."""
+    S = int(img_size)
+    out = np.zeros((len(ids), 4), dtype=np.int32)
+    for j, i in enumerate(ids):
+        x0, y0, x1, y1 = (int(v) for v in boxes[int(i)])
+        w, h = (int(v) for v in image_sizes[int(i)])
+        X0, Y0 = (S * x0) // w, (S * y0) // h
+        X1, Y1 = min(S, max(X0 + 1, -((-S * x1) // w))), min(S, max(Y0 + 1, -((-S * y1) // h)))
+        out[j] = (Y0, Y1, X0, X1)
+    return out
+
+
+def _clipped(box, size):
+    return np.clip(np.asarray(box, dtype=np.int64).reshape(-1, 4), 0, int(size))
+
+
+def act_focus(grids, size, obj, device=True):
+    """Peak and positive mass of every up-sampled map against its image's object box: dict(peak_val [M] fp32, peak_yx [M, 2] int32, hit
+    [M] int32, inside / total [M] fp64, nonfinite [M] int32); grids [M, g, g] fp32, obj int32 [M_img, 4] (y0, y1, x0, x1), half-open, map m
+    belonging to image m // (M / M_img).  device=True: one ppf_act_focus launch, device tensors.  device=False: the numpy referee:
+    resize_cubic per map, then np.where / np.sum in fp64."""
+    if device:
+        from . import ops
+        return ops.act_focus(grids, size, obj)
+    grids, S = _host(grids, np.float32), int(size)
+    M = grids.shape[0]
+    ob = _clipped(_host(obj, np.int32), S)
+    if M and (ob.shape[0] == 0 or M % ob.shape[0]):
+        raise ValueError(f"act_focus: {M} maps do not divide over {ob.shape[0]} object boxes")
+    per = M // ob.shape[0] if M else 1
+    out = dict(peak_val=np.zeros(M, dtype=np.float32), peak_yx=np.zeros((M, 2), dtype=np.int32), hit=np.zeros(M, dtype=np.int32),
+               inside=np.zeros(M), total=np.zeros(M), nonfinite=np.zeros(M, dtype=np.int32))
+    for m in range(M):
+        with np.errstate(invalid="ignore"):                                         # inf - inf of a map with non-finite entries
+            up = resize_cubic(grids[m], S)
+        y0, y1, x0, x1 = ob[m // per]
+        seen = ~np.isnan(up)
+        top = up[seen].max() if seen.any() else np.float32(-np.inf)                # a NaN never wins; only NaNs: (0, 0), -inf
+        ys, xs = np.where(up == top)
+        y, x = (int(ys[0]), int(xs[0])) if ys.size else (0, 0)
+        fin = np.isfinite(up)
+        with np.errstate(invalid="ignore"):
+            pos = np.where(fin & (up > 0), up, np.float32(0)).astype(np.float64)
+        out["peak_val"][m], out["peak_yx"][m], out["hit"][m] = top, (y, x), int(y0 <= y < y1 and x0 <= x < x1)
+        out["inside"][m], out["total"][m], out["nonfinite"][m] = np.sum(pos[y0:max(y1, y0), x0:max(x1, x0)]), np.sum(pos), int((~fin).sum())
+    return out
+
+
+def focus_box_terms(box, obj, size, device=True):
+    """int32 [M, 4] = (intersection, box, object, union) areas of box [M, 4] (high_activation_boxes) against obj [M_img, 4], both clipped
+    to the size x size image.  device=True: one ppf_focus_box_terms launch; device=False: integer numpy."""
+    if device:
+        from . import ops
+        return ops.focus_box_terms(box, obj, size)
+    a, o = _clipped(_host(box, np.int32), size), _clipped(_host(obj, np.int32), size)
+    M = a.shape[0]
+    if M and (o.shape[0] == 0 or M % o.shape[0]):
+        raise ValueError(f"focus_box_terms: {M} boxes do not divide over {o.shape[0]} object boxes")
+    o = np.repeat(o, M // o.shape[0], axis=0) if M else o[:0]
+    area = lambda b: np.maximum(b[:, 1] - b[:, 0], 0) * np.maximum(b[:, 3] - b[:, 2], 0)
+    inter = (np.maximum(np.minimum(a[:, 1], o[:, 1]) - np.maximum(a[:, 0], o[:, 0]), 0)
+             * np.maximum(np.minimum(a[:, 3], o[:, 3]) - np.maximum(a[:, 2], o[:, 2]), 0))
+    inter = np.where((area(a) > 0) & (area(o) > 0), inter, 0)
+    return np.stack([inter, area(a), area(o), area(a) + area(o) - inter], axis=1).astype(np.int32)
+
+
+def _centre_inside(cells, grid_side, patch, ob):
+    """Is the centre pixel (cy * patch + patch // 2, cx * patch + patch // 2) of each grid cell inside the clipped box ob?"""
+    cy, cx = cells // grid_side, cells % grid_side
+    py, px = cy * patch + patch // 2, cx * patch + patch // 2
+    return (py >= ob[0]) & (py < ob[1]) & (px >= ob[2]) & (px < ob[3])
+
+
+def reserve_focus(idx, obj, grid_side, patch, token_attn=None, device=True):
+    """The reserved tokens against the object box: (out int32 [B, 4], attn fp64 [B, 2] or None).  idx int32 [B, T] the grid cells of the
+    reserved tokens on the grid_side x grid_side grid of patch x patch pixel cells; out = (pixels of the reserved cells inside the box,
+    reserved cells whose centre pixel is inside, all cells whose centre is inside, idx entries inside [0, grid_side^2): the others are
+    skipped); attn, with token_attn [B, grid_side^2]: the rollout score over the cells with centre inside and over all cells, non-finite
+    scores counting 0.  device=True: one ppf_reserve_focus launch; device=False: the numpy referee."""
+    if device:
+        from . import ops
+        return ops.reserve_focus(idx, obj, grid_side, patch, token_attn)
+    idx, g, patch = _host(idx, np.int64), int(grid_side), int(patch)
+    B, G = idx.shape[0], g * g
+    ob = _clipped(_host(obj, np.int32), g * patch)
+    ta = None if token_attn is None else _host(token_attn, np.float32).reshape(B, G)
+    out, attn = np.zeros((B, 4), dtype=np.int32), None if ta is None else np.zeros((B, 2))
+    cells = np.arange(G)
+    for b in range(B):
+        c = idx[b][(idx[b] >= 0) & (idx[b] < G)]
+        cy, cx = c // g, c % g
+        oy = np.maximum(np.minimum((cy + 1) * patch, ob[b, 1]) - np.maximum(cy * patch, ob[b, 0]), 0)
+        ox = np.maximum(np.minimum((cx + 1) * patch, ob[b, 3]) - np.maximum(cx * patch, ob[b, 2]), 0)
+        on = _centre_inside(cells, g, patch, ob[b])
+        out[b] = (int((oy * ox).sum()), int(_centre_inside(c, g, patch, ob[b]).sum()), int(on.sum()), c.size)
+        if ta is not None:
+            v = np.where(np.isfinite(ta[b]), ta[b], np.float32(0)).astype(np.float64)
+            attn[b] = (np.sum(v[on]), np.sum(v))
+    return out, attn
+
+
+def evidence_focus(act_max, weight, scale, ppc, classes, obj, grid_side, patch, idx, argmax=None, device=True):
+    """The local branch's class evidence against the object box: (ev fp64 [B, M, 4], cnt int32 [B, M, 4]) for classes int32 [B, M]: the
+    sums and the term counts of the contributions fl(act_max[b][p] * fl(scale * weight[c][p])) over (own class and cell centre inside,
+    own class and not inside, other classes and inside, other classes and not inside); the cell of p is idx[b][argmax[b][p]] (argmax
+    None: idx[b][0]), and a prototype without a valid cell counts as not inside.  A class outside [0, C): zeros.  device=True: one
+    ppf_evidence_focus launch; device=False: the numpy referee (the same fp32 products, np.sum in fp64)."""
+    if device:
+        from . import ops
+        return ops.evidence_focus(act_max, weight, scale, ppc, classes, obj, grid_side, patch, idx=idx, argmax=argmax)
+    act_max, weight, idx = _host(act_max, np.float32), _host(weight, np.float32), _host(idx, np.int64)
+    argmax, cls = _host(argmax, np.int64), _host(classes, np.int32)
+    (B, P), C, T, g, patch = act_max.shape, weight.shape[0], idx.shape[1], int(grid_side), int(patch)
+    cls = cls.reshape(B, -1)
+    M = cls.shape[1]
+    ob = _clipped(_host(obj, np.int32), g * patch)
+    ev, cnt = np.zeros((B, M, 4)), np.zeros((B, M, 4), dtype=np.int32)
+    proto_class = np.arange(P) // int(ppc)
+    with np.errstate(all="ignore"):
+        w = np.float32(scale) * weight                                               # fp32: the first rounding
+        for b in range(B):
+            t = np.zeros(P, dtype=np.int64) if argmax is None else argmax[b]
+            ok = (t >= 0) & (t < T)
+            cell = np.where(ok, idx[b, np.clip(t, 0, T - 1)], -1)
+            ok &= (cell >= 0) & (cell < g * g)
+            inside = ok & _centre_inside(np.where(ok, cell, 0), g, patch, ob[b])
+            for m in range(M):
+                c = int(cls[b, m])
+                if c < 0 or c >= C:
+                    continue
+                ctr = (act_max[b] * w[c]).astype(np.float64)                         # fp32: the second rounding; then exact in fp64
+                own = proto_class == c
+                for j, sel in enumerate((own & inside, own & ~inside, ~own & inside, ~own & ~inside)):
+                    ev[b, m, j], cnt[b, m, j] = np.sum(ctr[sel]), int(sel.sum())
+    return ev, cnt
+
+
+class Focus:
+    """What focus_rows returns, as device tensors (numpy arrays after cpu()), K prototypes per image: protos int32 [B, K]; classes int32
+    [B] the predicted class; peak_val fp32, hit / nonfinite int32, inside / total fp64 [B, K], peak_yx int32 [B, K, 2] (ppf_act_focus);
+    box int32 [B, K, 4] the top-percentile box and terms int32 [B, K, 4] its (intersection, box, object, union) areas; reserve int32
+    [B, 4] and attn fp64 [B, 2] (ppf_reserve_focus); ev fp64 [B, 4] and cnt int32 [B, 4] the predicted class's local evidence
+    (ppf_evidence_focus); global_ev fp64 [B] the global branch's share of the predicted logit (it has no cells: unlocated), or None;
+    obj int32 [B, 4]; labels int64 [B] or None.  img_size, grid_side, patch, mode, percentile: the settings."""
+
+    def __init__(self, fields, img_size, grid_side, patch, mode, percentile):
+        for k in FOCUS_FIELDS:
+            setattr(self, k, fields.get(k))
+        self.img_size, self.grid_side, self.patch, self.mode, self.percentile = int(img_size), int(grid_side), int(patch), mode, percentile
+
+    def fields(self):
+        return {k: getattr(self, k) for k in FOCUS_FIELDS}
+
+    @property
+    def on_host(self):
+        return not isinstance(self.protos, torch.Tensor)
+
+    def cpu(self):
+        """The same object with numpy arrays: every field in ONE host read."""
+        if self.on_host:
+            return self
+        return Focus(read_once(self.fields()), self.img_size, self.grid_side, self.patch, self.mode, self.percentile)
+
+
+def focus_from_outputs(outs, obj, weight, scale, ppc, k, img_size, labels=None, protos="own", protos_per_image=3, percentile=95, global_coe=None,
+                       device=True):
+    """focus_rows on what one eval forward left (outs: token_attn [B, G], idx [B, T], act_full [B, P, T], logits [B, C], act_max [B, P],
+    argmax [B, P] or None, optionally logits_global [B, C]: _eval_outputs); weight [C, P] and scale: the local last layer and its share of the logit; k:
+    the reserved tokens per image.  device=True: CUDA tensors in, the kernels, a Focus of device tensors.  device=False: the referee
+    pipeline on host copies -- the same selection, expand_to_grid, then the numpy referees with find_high_activation_crop of
+    resize_cubic for the boxes -- and a Focus of numpy arrays."""
+    if protos not in FOCUS_PROTOS:
+        raise ValueError(f"focus: protos must be 'own' or 'top', got {protos!r}")
+    if protos == "own" and labels is None:
+        raise ValueError("focus: protos='own' takes the prototypes of labels[b]: labels are needed")
+    place = (lambda t: t) if device else (lambda t: None if t is None else torch.as_tensor(t).detach().cpu())
+    o = {n: place(v) for n, v in outs.items()}
+    obj_t, weight = place(obj), place(weight)
+    B, P = o["act_max"].shape
+    C, ppc, S, dev = weight.shape[0], int(ppc), int(img_size), o["act_max"].device
+    G = o["token_attn"].shape[1]
+    g = int(round(G ** 0.5))
+    patch = S // g
+    pred = o["logits"].argmax(1)
+    if protos == "own":
+        lab = torch.as_tensor(labels).to(dev, torch.int64)
+        pr = lab.clamp(0, C - 1)[:, None] * ppc + torch.arange(ppc, device=dev)[None, :]
+    else:
+        lab = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
+        own = pred[:, None] * ppc + torch.arange(ppc, device=dev)[None, :]
+        pr = own.gather(1, torch.sort(o["act_max"].gather(1, own), dim=1, descending=True, stable=True)[1][:, :max(1, min(int(protos_per_image), ppc))])
+    K, s = pr.shape[1], int(round(int(k) ** 0.5))
+    sel = torch.gather(o["act_full"].reshape(B, P, -1), 1, pr[:, :, None].expand(B, K, int(k))).reshape(B, K, s, s)
+    grid = patch_grid(o["token_attn"], sel, int(k)).contiguous()                         # expand_to_grid of the selected prototypes only
+    maps = grid.reshape(B * K, g, g)
+    cls = pred.to(torch.int32)[:, None].contiguous()
+    if device:
+        f = act_focus(maps, S, obj_t)
+        box = high_activation_boxes(grid, S, percentile).reshape(B * K, 4)
+    else:
+        f = act_focus(maps.numpy(), S, obj_t.numpy(), device=False)
+        box = np.array([find_high_activation_crop(resize_cubic(a, S), percentile) for a in maps.numpy()], dtype=np.int32).reshape(B * K, 4)
+    terms = focus_box_terms(box, obj_t, S, device=device)
+    reserve, attn = reserve_focus(o["idx"], obj_t, g, patch, o["token_attn"], device=device)
+    ev, cnt = evidence_focus(o["act_max"], weight, scale, ppc, cls, obj_t, g, patch, o["idx"], o["argmax"], device=device)
+    glob = None
+    if o.get("logits_global") is not None and global_coe is not None:
+        glob = float(global_coe) * o["logits_global"].double().gather(1, pred[:, None]).reshape(B)
+    host = (lambda t: t) if device else (lambda t: None if t is None else (t.numpy() if isinstance(t, torch.Tensor) else t))
+    shape = lambda t, *tail: t.reshape((B, K) + tail)
+    fields = dict(protos=host(pr.to(torch.int32)), classes=host(cls.reshape(B)), peak_val=shape(f["peak_val"]), peak_yx=shape(f["peak_yx"], 2),
+                  hit=shape(f["hit"]), inside=shape(f["inside"]), total=shape(f["total"]), nonfinite=shape(f["nonfinite"]), box=shape(box, 4),
+                  terms=shape(terms, 4), reserve=reserve, attn=attn, ev=ev.reshape(B, 4), cnt=cnt.reshape(B, 4), global_ev=host(glob),
+                  obj=host(obj_t), labels=host(lab))
+    return Focus(fields, S, g, patch, protos, percentile)
+
+
+@torch.no_grad()
+def focus_rows(ppnet, x, obj, labels=None, protos="own", protos_per_image=3, percentile=95):
+    """The foreground-focus measurements of one batch x [B, 3, S, S] against obj int32 [B, 4] = (y0, y1, x0, x1), half-open, in pixels of
+    the model input (scaled_boxes).  One eval forward, expand_to_grid of the selected local prototypes only, one ppf_act_focus, the
+    order-statistics and box launches of high_activation_boxes (which reads its two order statistics per map back), ppf_focus_box_terms,
+    ppf_reserve_focus, and ppf_evidence_focus for the predicted class.  protos 'own': the prototypes of labels[b]; 'top': the
+    protos_per_image strongest local prototypes of the predicted class by pooled activation (equal ones by smaller id).  Returns a Focus
+    of device tensors; .cpu() is one host read."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError("focus_rows needs a CUDA/HIP batch [B, 3, S, S] (no CPU fallback path; focus_from_outputs(device=False) is the host referee)")
+    obj = obj if isinstance(obj, torch.Tensor) and obj.is_cuda else torch.as_tensor(np.asarray(obj)).to(x.device)
+    obj = obj.to(torch.int32).contiguous()
+    coe = float(ppnet.global_coe)
+    return focus_from_outputs(_eval_outputs(ppnet, x.float().contiguous()), obj, ppnet.last_layer.weight.detach().contiguous(), 1.0 - coe,
+                              ppnet.num_prototypes_per_class, ppnet.reserve_token_nums[0], ppnet.img_size, labels, protos, protos_per_image,
+                              percentile, coe)
+
+
+def _ordered_mean(v):
+    """(fp64 mean of v in index order, or None for no value; how many values)."""
+    v = np.asarray(v, dtype=np.float64)
+    return (_ordered_sum(v) / v.size if v.size else None), int(v.size)
+
+
+def _ratio_mean(num, den):
+    """_ordered_mean of num / den over the entries with den > 0."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        live = den > 0
+    return _ordered_mean(num[live] / den[live])
+
+
+def focus_summary(rows, img_size, patch, per_prototype=True):
+    """The report of foreground_focus from all rows, on the host: rows = dict of numpy arrays, image_ids [N] and the fields of Focus
+    (protos, hit, inside, total, nonfinite, terms [N, K, ...]; reserve, attn, ev, cnt, global_ev, obj, classes, labels [N, ...]).  The
+    rows are put into image-id order first (equal ids keep their order) and every mean is an fp64 sum in that order, or a ratio of
+    integer sums: the result does not depend on how the images were batched or on the order they arrived in.
+    Prototype maps: pointing = hits / rows; energy = the mean of inside / total over the rows with total > 0 (energy_rows of them;
+    zero_total_rows and nonfinite_rows are counted, not hidden); iou, box_inside = intersection / union and intersection / box area of
+    the top-percentile box; chance = the mean object area / S^2, what a spatially blind map scores in pointing and energy.
+    Reservation: reserved_on_object = reserved pixels inside / (valid reserved cells * patch^2) against the same chance; object_recall =
+    reserved cells with centre inside / grid cells with centre inside (images_without_object_cells counted separately);
+    attention_on_object = the rollout score on cells with centre inside / over all cells.  Evidence of the predicted class:
+    own_inside = own-class evidence located inside / own-class evidence, over the images where the latter is > 0 (own_images);
+    other_inside likewise for the other classes' prototypes; global_branch_share = the global branch's part of (global + local)
+    evidence, unlocated since that branch has no cells.  Returns dict(images, rows, overall, per_class {class: ...}, per_prototype
+    {prototype: the prototype-map measures} or None); a class is the image's label when labels are given, else the predicted class."""
+    S, patch = int(img_size), int(patch)
+    ids = np.asarray(rows["image_ids"]).reshape(-1)
+    order = np.argsort(ids, kind="stable")
+    r = {k: (None if v is None else np.asarray(v)[order]) for k, v in rows.items()}
+    N = ids.size
+    K = r["protos"].shape[1] if N else 0
+    cls_img = r["labels"] if r.get("labels") is not None else r["classes"]
+    cls_row = np.repeat(cls_img, K)
+    flat = {k: r[k].reshape((N * K,) + r[k].shape[2:]) for k in ("protos", "hit", "inside", "total", "nonfinite", "terms")}
+
+    def maps(sel):
+        hit, ins, tot, nf, t = (flat[k][sel] for k in ("hit", "inside", "total", "nonfinite", "terms"))
+        n = int(hit.shape[0])
+        energy, energy_rows = _ratio_mean(ins, tot)
+        return dict(rows=n, pointing=(int(hit.astype(np.int64).sum()) / n if n else None), energy=energy, energy_rows=energy_rows,
+                    zero_total_rows=int((tot == 0).sum()), nonfinite_rows=int((nf > 0).sum()), iou=_ratio_mean(t[:, 0], t[:, 3])[0],
+                    box_inside=_ratio_mean(t[:, 0], t[:, 1])[0], chance=_ordered_mean(t[:, 2].astype(np.float64) / float(S * S))[0])
+
+    def images(sel):
+        res, ob, ev = r["reserve"][sel].astype(np.int64), _clipped(r["obj"][sel], S), r["ev"][sel]
+        n = int(res.shape[0])
+        recall, with_cells = _ratio_mean(res[:, 1], res[:, 2])
+        out = dict(images=n, reserved_on_object=_ratio_mean(res[:, 0], res[:, 3] * patch * patch)[0], object_recall=recall,
+                   images_without_object_cells=n - with_cells,
+                   attention_on_object=None if r.get("attn") is None else _ratio_mean(r["attn"][sel][:, 0], r["attn"][sel][:, 1])[0],
+                   chance=_ordered_mean((ob[:, 1] - ob[:, 0]).clip(0) * (ob[:, 3] - ob[:, 2]).clip(0) / float(S * S))[0])
+        own, own_images = _ratio_mean(ev[:, 0], ev[:, 0] + ev[:, 1])
+        other, other_images = _ratio_mean(ev[:, 2], ev[:, 2] + ev[:, 3])
+        ge = None
+        if r.get("global_ev") is not None:
+            ge = _ratio_mean(r["global_ev"][sel], r["global_ev"][sel] + ev.sum(1))[0]
+        return out, dict(own_inside=own, own_images=own_images, other_inside=other, other_images=other_images, global_branch_share=ge)
+
+    def group(sel_rows, sel_img):
+        reservation, evidence = images(sel_img)
+        return dict(prototype_maps=maps(sel_rows), reservation=reservation, evidence=evidence)
+    all_rows, all_img = np.ones(N * K, dtype=bool), np.ones(N, dtype=bool)
+    return dict(images=int(N), rows=int(N * K), overall=group(all_rows, all_img),
+                per_class={int(c): group(cls_row == c, cls_img == c) for c in np.unique(cls_img)} if N else {},
+                per_prototype={int(p): maps(flat["protos"] == p) for p in np.unique(flat["protos"])} if per_prototype and N else None)
+
+
+def foreground_focus(ppnet, loader, boxes, image_sizes, protos="own", protos_per_image=3, percentile=95, max_images=0, per_image=False):
+    """Foreground focus over a data set.  loader yields (x, targets, img_ids) in the square view (Resize((S, S))); boxes {img_id: (x0, y0,
+    x1, y1)} in pixels of the original file, image_sizes {img_id: (width, height)} (scaled_boxes maps them into the view).  Per batch one
+    focus_rows; the rows stay on the device and are read once at the end; the summaries are focus_summary's, taken in image-id order.
+    Returns its dict plus settings and, with per_image, per_image = the rows as numpy arrays (image_ids and the fields of Focus)."""
+    if protos not in FOCUS_PROTOS:
+        raise ValueError(f"foreground_focus: protos must be 'own' or 'top', got {protos!r}")
+    keep, meta = [], None
+    for x, y, ids in batches_with_ids(loader, max_images):
+        x = x if x.is_cuda else x.cuda()
+        obj = torch.from_numpy(scaled_boxes(ids.cpu().tolist(), boxes, image_sizes, ppnet.img_size)).to(x.device)
+        f = focus_rows(ppnet, x, obj, torch.as_tensor(y).to(x.device, torch.int64), protos, protos_per_image, percentile)
+        keep.append(dict(f.fields(), image_ids=ids.to(x.device)))
+        meta = f
+    if not keep:
+        raise ValueError("foreground_focus: the loader gave no image")
+    rows = read_once({k: (None if keep[0][k] is None else torch.cat([d[k] for d in keep])) for k in keep[0]})            # the one read
+    out = focus_summary(rows, meta.img_size, meta.patch, per_prototype=protos == "own")
+    out["settings"] = dict(protos=protos, protos_per_image=int(protos_per_image), percentile=percentile, img_size=meta.img_size, patch=meta.patch)
+    if per_image:
+        out["per_image"] = rows
     return out

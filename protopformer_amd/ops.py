@@ -1089,6 +1089,99 @@ def act_box(grids, size, thr):
     return box
 
 
+# ---- foreground focus (csrc/interp.hip, csrc/explain.hip): maps, boxes, reserved tokens and evidence against an object box per image
+def _obj_boxes(who, obj, rows, device):
+    """obj int32 [B, 4] on `device` with `rows` a multiple of B >= 1: returns rows per image."""
+    if not isinstance(obj, torch.Tensor) or obj.dim() != 2:
+        raise ValueError(f"{who}: obj must be an int32 CUDA tensor [B, 4] of (y0, y1, x0, x1)")
+    _dev_tensor(who, "obj", obj, torch.int32, (obj.shape[0], 4), device)
+    if obj.shape[0] == 0 or rows % obj.shape[0] != 0:
+        raise ValueError(f"{who}: {rows} rows do not divide over {obj.shape[0]} object boxes")
+    return rows // obj.shape[0]
+
+
+def act_focus(grids, size, obj, want_nonfinite=True):
+    """Peak and positive mass of every up-sampled map against its image's object box, without writing the map (ppf_act_focus): dict of
+    peak_val [M] fp32, peak_yx [M, 2] int32 (both as act_peak), hit [M] int32, inside / total [M] fp64, nonfinite [M] int32 or None.
+    grids [M, g, g] fp32; obj [M_img, 4] int32 (y0, y1, x0, x1), half-open, with M a multiple of M_img.  One launch."""
+    M, g, S = _act_maps("ppf_act_focus", grids, size)
+    dev = grids.device
+    out = dict(peak_val=torch.empty(M, dtype=torch.float32, device=dev), peak_yx=torch.empty((M, 2), dtype=torch.int32, device=dev),
+               hit=torch.empty(M, dtype=torch.int32, device=dev), inside=torch.empty(M, dtype=torch.float64, device=dev),
+               total=torch.empty(M, dtype=torch.float64, device=dev),
+               nonfinite=torch.empty(M, dtype=torch.int32, device=dev) if want_nonfinite else None)
+    if M > 0:
+        per = _obj_boxes("act_focus", obj, M, dev)
+        _lib.call("ppf_act_focus", grids, obj, M, g, S, per, out["peak_val"], out["peak_yx"], out["hit"], out["inside"], out["total"], out["nonfinite"])
+    return out
+
+
+def focus_box_terms(box, obj, size):
+    """terms int32 [M, 4] = (intersection, box, object, union) areas of box [M, 4] (as act_box returns it) against obj [M_img, 4], both
+    clipped to the size x size image (ppf_focus_box_terms)."""
+    who = "focus_box_terms"
+    if not isinstance(box, torch.Tensor) or box.dim() != 2:
+        raise ValueError(f"{who}: box must be an int32 CUDA tensor [M, 4]")
+    _dev_tensor(who, "box", box, torch.int32, (box.shape[0], 4))
+    M = box.shape[0]
+    terms = torch.empty((M, 4), dtype=torch.int32, device=box.device)
+    if M > 0:
+        per = _obj_boxes(who, obj, M, box.device)
+        _lib.call("ppf_focus_box_terms", box, obj, M, per, int(size), terms)
+    return terms
+
+
+def reserve_focus(idx, obj, grid_side, patch, token_attn=None):
+    """(out int32 [B, 4], attn fp64 [B, 2] or None) of the reserved cells idx int32 [B, T] against obj int32 [B, 4] on the grid_side x
+    grid_side grid of patch x patch pixel cells (ppf_reserve_focus): out = (reserved pixels inside, reserved cells with centre inside, all
+    cells with centre inside, valid idx entries); with token_attn fp32 [B, grid_side^2] also the rollout score over the cells with centre
+    inside and over all cells."""
+    who = "reserve_focus"
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be an int32 CUDA tensor [B, T]")
+    B, T = idx.shape
+    g, patch = int(grid_side), int(patch)
+    _dev_tensor(who, "idx", idx, torch.int32, (B, T))
+    _dev_tensor(who, "obj", obj, torch.int32, (B, 4), idx.device)
+    out = torch.empty((B, 4), dtype=torch.int32, device=idx.device)
+    attn = None
+    if token_attn is not None:
+        _dev_tensor(who, "token_attn", token_attn, torch.float32, (B, g * g), idx.device)
+        attn = torch.empty((B, 2), dtype=torch.float64, device=idx.device)
+    if B > 0:
+        _lib.call("ppf_reserve_focus", idx, obj, token_attn, B, T, g, patch, out, attn)
+    return out, attn
+
+
+def evidence_focus(act_max, weight, scale, ppc, classes, obj, grid_side, patch, *, idx, argmax=None):
+    """(ev fp64 [B, M, 4], cnt int32 [B, M, 4]) of the local branch's evidence for classes int32 [B, M] against obj int32 [B, 4]
+    (ppf_evidence_focus): the sums and term counts over (own class & cell centre inside, own & not, other classes & inside, other & not).
+    act_max [B, P] fp32, argmax [B, P] int32 or None (k = 1: every cell is idx[b][0]), idx [B, T] int32, weight [C, P] fp32."""
+    who = "evidence_focus"
+    if not isinstance(act_max, torch.Tensor) or act_max.dim() != 2 or not isinstance(weight, torch.Tensor) or weight.dim() != 2:
+        raise ValueError(f"{who}: act_max must be [B, P] and weight [C, P]")
+    B, P = act_max.shape
+    C, dev = weight.shape[0], act_max.device
+    _dev_tensor(who, "act_max", act_max, torch.float32, (B, P))
+    _dev_tensor(who, "weight", weight, torch.float32, (C, P), dev)
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+        raise ValueError(f"{who}: idx must be an int32 CUDA tensor [B, T]")
+    T = idx.shape[1]
+    _dev_tensor(who, "idx", idx, torch.int32, (B, T), dev)
+    if argmax is not None:
+        _dev_tensor(who, "argmax", argmax, torch.int32, (B, P), dev)
+    if not isinstance(classes, torch.Tensor) or classes.dim() != 2:
+        raise ValueError(f"{who}: classes must be an int32 CUDA tensor [B, M]")
+    M = classes.shape[1]
+    _dev_tensor(who, "classes", classes, torch.int32, (B, M), dev)
+    _dev_tensor(who, "obj", obj, torch.int32, (B, 4), dev)
+    ev = torch.empty((B, M, 4), dtype=torch.float64, device=dev)
+    cnt = torch.empty((B, M, 4), dtype=torch.int32, device=dev)
+    if B > 0:
+        _lib.call("ppf_evidence_focus", act_max, argmax, idx, T, weight, float(scale), int(ppc), classes, obj, int(grid_side), int(patch), B, P, C, M, ev, cnt)
+    return ev, cnt
+
+
 # ---- stability score (csrc/interp.hip): per-image Gaussian input noise and the per-class accumulators of interpret.PartMeter
 def add_gauss_noise(x, image_ids, sigma, seed=0, out=None):
     """x + sigma * N(0, 1) on an fp32 CUDA batch [B, ...] (ppf_add_gauss_noise): the noise of an image is a function of (seed, its id in
