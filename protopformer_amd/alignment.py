@@ -15,19 +15,12 @@ stay on the device until the split is done.
 
 writes OUT/alignment.json: the image and row counts, the settings, and overall and per prototype the mean share, the mean area
 baseline, their ratio, the mean PAC, the mean PLC and the fraction of peaks that left the box."""
-import argparse
-import json
-import os
-
-import torch
 
 
 def get_args_parser():
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer spatial alignment: gradient locality and the misalignment attack", parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer spatial alignment: gradient locality and the misalignment attack", "test", "evaluated")
     a = p.add_argument
-    add_split_flags(p, "test", "evaluated")
     a("--protos_per_image", type=int, default=3, help="the strongest local prototypes of the predicted class kept per image")
     a("--half_size", type=int, default=36, help="the box reaches this many pixels to each side of the activation peak")
     a("--attack_steps", type=int, default=10, help="signed-gradient steps of the attack (a forward and a backward each)")
@@ -40,39 +33,26 @@ def get_args_parser():
 
 def summarize(result, args):
     """The JSON record: counts, settings, the overall means and the per-prototype table (keys as strings, NaN as null)."""
-    def clean(d):
-        return {k: (None if isinstance(v, float) and v != v else v) for k, v in d.items()}
-    return dict(images=int(result["images"]), rows=int(result["rows"]),
+    from .tooling import json_clean
+    return json_clean(dict(images=int(result["images"]), rows=int(result["rows"]),
                 settings=dict(protos_per_image=args.protos_per_image, half_size=args.half_size, attack=bool(args.attack), attack_steps=args.attack_steps,
                               eps_255=args.eps, precise=bool(args.precise), split=args.split),
-                overall=clean(result["overall"]), per_prototype={str(p): clean(v) for p, v in sorted(result["per_prototype"].items())})
+                overall=result["overall"], per_prototype=dict(sorted(result["per_prototype"].items()))))
 
 
 def main(args, model=None, loader=None):
-    """loader: a ready iterable of (x, ...) batches with its model (tests, notebooks); by default both are built from the data flags as
-    the faithfulness tool builds them."""
+    """model / loader: a ready model and iterable of (x, ...) CUDA batches (tests, notebooks); by default tooling.tool_setup builds both."""
     from .interpret import spatial_alignment
-    from .tooling import eval_loader, load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    if loader is not None and model is None:
-        raise ValueError("alignment.main: a ready loader comes with a ready model (the class count is the data set's)")
-    if loader is None:
-        _, nb_classes, loader = eval_loader(args, device, with_ids=False)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
+    from .tooling import tool_setup, write_json
+    model, loader, _, _ = tool_setup(args, "alignment", model, loader, with_ids=False)
     if args.precise:
         model.precise = True
     res = spatial_alignment(model, loader, protos_per_image=args.protos_per_image, half_size=args.half_size, attack=args.attack,
                             attack_steps=args.attack_steps, eps=args.eps / 255.0, max_images=args.max_images, pass_images=args.batch_size)
-    os.makedirs(args.output_dir, exist_ok=True)
-    path = os.path.join(args.output_dir, "alignment.json")
-    with open(path, "w") as f:
-        json.dump(summarize(res, args), f, indent=1)
+    path = write_json(args, "alignment.json", summarize(res, args))
     print(f"spatial alignment of {res['images']} {args.split} images ({res['rows']} image-prototype pairs): {path}", flush=True)
     return path
 
 
 if __name__ == "__main__":
-    cli_args = get_args_parser().parse_args()
-    main(cli_args)
+    main(get_args_parser().parse_args())

@@ -15,8 +15,6 @@ writes OUT/attributions.json: the settings, per image and class the logit at the
 the summed attribution (`total`), their gap (`delta`) and the ten cells with the largest attribution with their pixel boxes; overall
 the mean of |delta| / |value - value_base|.  With --save-maps also OUT/attributions.npz: the cell scores [N, M, G] and the
 channel-summed pixel maps [N, M, H, W] with the image ids and classes.  No rendering."""
-import argparse
-import json
 import os
 
 import numpy as np
@@ -27,11 +25,9 @@ TOP_CELLS = 10
 
 def get_args_parser():
     from .interpret import IG_DEFAULTS, IG_RULES
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer attribution: integrated gradients of the class logit", parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer attribution: integrated gradients of the class logit", "test", "attributed")
     a = p.add_argument
-    add_split_flags(p, "test", "attributed")
     a("--steps", type=int, default=IG_DEFAULTS["steps"], help="path steps (one forward and backward each, per class column)")
     a("--rule", type=str, default=IG_DEFAULTS["rule"], choices=list(IG_RULES), help="quadrature of the path integral")
     a("--top_classes", type=int, default=1, help="attribute the top M classes of every image")
@@ -67,18 +63,10 @@ def relative_gaps(recs):
 
 
 def main(args, model=None, loader=None):
-    """loader: a ready iterable of (x, labels[, ids]) batches with its model (tests, notebooks); by default both are built from the data
-    flags as the faithfulness tool builds them."""
+    """model / loader: a ready model and iterable of (x, labels[, ids]) CUDA batches (tests, notebooks); by default tooling.tool_setup builds both."""
     from .interpret import integrated_gradients
-    from .tooling import batches_with_ids, eval_loader, load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    if loader is not None and model is None:
-        raise ValueError("attribute.main: a ready loader comes with a ready model (the class count is the data set's)")
-    if loader is None:
-        _, nb_classes, loader = eval_loader(args, device)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
+    from .tooling import batches_with_ids, tool_setup, write_json
+    model, loader, _, _ = tool_setup(args, "attribute", model, loader)
     G = int(model.num_patches)
     side = int(round(G ** 0.5))
     patch = int(model.img_size) // side
@@ -102,10 +90,7 @@ def main(args, model=None, loader=None):
                              baseline=0.0),
                mean_relative_gap=float(gaps.mean()) if gaps.size else None, worst_relative_gap=float(gaps.max()) if gaps.size else None,
                per_image=recs)
-    os.makedirs(args.output_dir, exist_ok=True)
-    path = os.path.join(args.output_dir, "attributions.json")
-    with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
+    path = write_json(args, "attributions.json", doc)
     if args.save_maps:
         np.savez(os.path.join(args.output_dir, "attributions.npz"), **{k: np.concatenate(v) for k, v in kept.items()})
     print(f"integrated gradients of {len(recs)} {args.split} images: {path}", flush=True)
@@ -113,5 +98,4 @@ def main(args, model=None, loader=None):
 
 
 if __name__ == "__main__":
-    cli_args = get_args_parser().parse_args()
-    main(cli_args)
+    main(get_args_parser().parse_args())

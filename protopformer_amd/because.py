@@ -21,8 +21,6 @@ The default strengths are choices, not tuned values: nobody has run this on a tr
 writes OUT/because.json: the parameters, per prototype and overall the importance of every characteristic (the paper's weighted form, the
 unweighted mean and the location-free variant), the share of lost cells, the dominant characteristic and the image counts; with
 --per-image also OUT/because.npz (the rows); with --save-images N the perturbed views of the first N images as OUT/views/<id>_<name>.jpg."""
-import argparse
-import json
 import os
 
 import numpy as np
@@ -31,12 +29,9 @@ import torch
 
 def get_args_parser():
     from .interpret import BECAUSE_DEFAULTS as D, CHARACTERISTICS, EXPLAIN_BRANCHES
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer: this looks like that, because ... (importance of hue, saturation, contrast, texture, shape)",
-                                parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer: this looks like that, because ... (importance of hue, saturation, contrast, texture, shape)", "train", "analysed")
     a = p.add_argument
-    add_split_flags(p, "train", "analysed")
     a("--characteristics", type=str, nargs="+", default=list(CHARACTERISTICS), choices=list(CHARACTERISTICS))
     a("--protos", type=str, default="own", choices=["own", "top"],
       help="own: every prototype of the image's label class; top: the strongest prototypes of the predicted class")
@@ -90,26 +85,15 @@ def save_views(x, ids, names, params, seed, out_dir):
 
 
 def main(args, model=None, loader=None):
-    """loader: a ready iterable of (x, labels[, ids]) CUDA batches with its model (tests, notebooks); by default both are built from the
-    data flags as the faithfulness tool builds them."""
+    """model / loader: a ready model and iterable of (x, labels[, ids]) CUDA batches (tests, notebooks); by default tooling.tool_setup builds both."""
     from .interpret import characteristic_importance
-    from .tooling import batches_with_ids, eval_loader, load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    if loader is not None and model is None:
-        raise ValueError("because.main: a ready loader comes with a ready model (the class count is the data set's)")
-    if loader is None:
-        _, nb_classes, loader = eval_loader(args, device)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
+    from .tooling import batches_with_ids, tool_setup, write_json
+    model, loader, _, _ = tool_setup(args, "because", model, loader)
     params, names = params_from_args(args), tuple(args.characteristics)
     res = characteristic_importance(model, loader, protos=args.protos, branch=args.branch, characteristics=names, params=params, seed=args.seed,
                                     max_images=args.max_images, pass_images=args.pass_images, protos_per_image=args.protos_per_image,
                                     per_image=args.per_image)
-    os.makedirs(args.output_dir, exist_ok=True)
-    path = os.path.join(args.output_dir, "because.json")
-    with open(path, "w") as f:
-        json.dump(summarize(res, args), f, indent=1)
+    path = write_json(args, "because.json", summarize(res, args))
     if args.per_image:
         np.savez(os.path.join(args.output_dir, "because.npz"), characteristics=np.asarray(names), **{k: v for k, v in res["rows"].items() if v is not None})
     if args.save_images > 0:
@@ -120,5 +104,4 @@ def main(args, model=None, loader=None):
 
 
 if __name__ == "__main__":
-    cli_args = get_args_parser().parse_args()
-    main(cli_args)
+    main(get_args_parser().parse_args())

@@ -13,7 +13,6 @@ writes OUT/explanations.jsonl, one line per image (Explanation.report's record p
 --stats its activation's percentile among all and among the own-class images of the prototype statistics (python -m
 protopformer_amd.protostats); with
 --render also img_<id>/class<c>_rank<r>.jpg: the activation overlay of the rank-r local prototype with its high-activation box."""
-import argparse
 import json
 import os
 
@@ -22,11 +21,9 @@ import torch
 
 
 def get_args_parser():
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer local analysis: the prototypes behind each image's top classes", parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer local analysis: the prototypes behind each image's top classes", "train", "explained")
     a = p.add_argument
-    add_split_flags(p, "train", "explained")
     a("--topk", type=int, default=10, help="prototypes listed per (image, class) and branch (1..64)")
     a("--top_classes", type=int, default=1, help="classes explained per image, by logit (1..8)")
     a("--against", action="store_true", default=False, help="rank the strongest evidence against each class instead of for it")
@@ -69,21 +66,14 @@ def render_overlays(out_dir, host, views_bgr, image_ids):
 
 
 def main(args, model=None, loader=None, index=None):
-    """loader / index: a ready iterable of (x, labels[, ids]) CUDA batches and its {image id: (path, label)} (tests, notebooks); by
-    default both are built from the data flags as the bank tool builds them."""
+    """model / loader / index: ready ones, the index {image id: (path, label)} (tests, notebooks); by default tooling.tool_setup builds them."""
     from . import data as D
     from .bank import image_index
     from .interpret import explain
-    from .tooling import batches_with_ids, eval_loader, load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    if loader is not None and model is None:
-        raise ValueError("explain.main: a ready loader comes with a ready model (the class count is the data set's)")
-    if loader is None:
-        ds, nb_classes, loader = eval_loader(args, device)
+    from .tooling import batches_with_ids, tool_setup
+    model, loader, ds, device = tool_setup(args, "explain", model, loader)
+    if ds is not None:
         index = image_index(ds)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     bank = dict(np.load(args.bank)) if args.bank else None
     stats = None
     if args.stats:
@@ -111,5 +101,4 @@ def main(args, model=None, loader=None, index=None):
 
 
 if __name__ == "__main__":
-    cli_args = get_args_parser().parse_args()
-    main(cli_args)
+    main(get_args_parser().parse_args())

@@ -25,21 +25,16 @@ overlays are, the RISE saliency and the integrated gradients at their own resolu
 removed by `ppf_pixel_perturb`; the counts are pixels.  --baseline blur replaces a removed pixel by the Gaussian-blurred image
 (`ppf_gauss_blur`, --blur_sigma, --blur_radius) instead of the mean colour, at either resolution.  faithfulness.json carries the keys
 `resolution`, `baseline` and `blur` only when one of these flags departs from its default."""
-import argparse
-import json
 import os
 
 import numpy as np
-import torch
 
 
 def get_args_parser():
     from .interpret import BLUR_DEFAULTS, CURVE_MODES, EXTRA_ORDERS, GRADIENT_ORDERS, IG_DEFAULTS, IG_RULES, ORDER_MODES, RESOLUTIONS, RISE_DEFAULTS
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer faithfulness: deletion / insertion curves of the explanations", "test", "evaluated")
     a = p.add_argument
-    add_split_flags(p, "test", "evaluated")
     a("--steps", type=int, default=14, help="the curves have steps + 1 points: 0, G/steps, ... G cells removed / shown")
     a("--orders", type=str, nargs="+", default=list(ORDER_MODES), choices=list(ORDER_MODES + EXTRA_ORDERS + GRADIENT_ORDERS),
       help="cell orders to evaluate (random is the control; rise, the black-box baseline, and ig, the gradient baseline, only on request)")
@@ -78,18 +73,10 @@ def summarize(result, extra=None):
 
 
 def main(args, model=None, loader=None):
-    """loader: a ready iterable of (x, labels[, ids]) CUDA batches with its model (tests, notebooks); by default both are built from the
-    data flags as the explain tool builds them."""
+    """model / loader: a ready model and iterable of (x, labels[, ids]) CUDA batches (tests, notebooks); by default tooling.tool_setup builds both."""
     from .interpret import BLUR_DEFAULTS, default_counts, faithfulness
-    from .tooling import eval_loader, load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    if loader is not None and model is None:
-        raise ValueError("faithfulness.main: a ready loader comes with a ready model (the class count is the data set's)")
-    if loader is None:
-        _, nb_classes, loader = eval_loader(args, device)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
+    from .tooling import tool_setup, write_json
+    model, loader, _, _ = tool_setup(args, "faithfulness", model, loader)
     pixel, blur = args.resolution == "pixel", dict(sigma=args.blur_sigma, radius=args.blur_radius)
     res = faithfulness(model, loader, orders=tuple(args.orders), modes=tuple(args.modes),
                        counts=default_counts(int(model.img_size) ** 2 if pixel else model.num_patches, args.steps),
@@ -99,10 +86,7 @@ def main(args, model=None, loader=None):
     extra = {}
     if pixel or args.baseline != "mean" or blur != BLUR_DEFAULTS:
         extra = dict(resolution=args.resolution, baseline=args.baseline, blur=blur)
-    os.makedirs(args.output_dir, exist_ok=True)
-    path = os.path.join(args.output_dir, "faithfulness.json")
-    with open(path, "w") as f:
-        json.dump(summarize(res, extra), f, indent=1)
+    path = write_json(args, "faithfulness.json", summarize(res, extra))
     if args.per_image:
         arrays = {f"{order}_{mode}": c for order, modes in res["per_image"].items() for mode, c in modes.items()}
         np.savez(os.path.join(args.output_dir, "faithfulness.npz"), counts=np.asarray(res["counts"]), classes=res["classes"], image_ids=res["image_ids"],
@@ -112,5 +96,4 @@ def main(args, model=None, loader=None):
 
 
 if __name__ == "__main__":
-    cli_args = get_args_parser().parse_args()
-    main(cli_args)
+    main(get_args_parser().parse_args())

@@ -18,18 +18,14 @@ interpret.focus_summary; with --per-image also OUT/focus.npz, the rows.  For CUB
 (interpret.CubParts.id_to_bbox); for any other set --boxes names a JSON {image id: [x0, y0, x1, y1]} in pixels of the original files,
 the image id being the image's index in the split's file order.  Nothing GPU-related is imported with the module: the parser works
 anywhere."""
-import argparse
 import json
 import os
 
 
 def get_args_parser():
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer foreground focus: reserved tokens, prototype maps and evidence against object boxes",
-                                parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer foreground focus: reserved tokens, prototype maps and evidence against object boxes", "test", "evaluated")
     a = p.add_argument
-    add_split_flags(p, "test", "evaluated")
     a("--protos", type=str, default="own", choices=["own", "top"],
       help="own: the prototypes of the image's label class; top: the strongest prototypes of the predicted class")
     a("--protos_per_image", type=int, default=3, help="with --protos top: the strongest local prototypes of the predicted class kept per image")
@@ -71,30 +67,20 @@ def cub_boxes(data_path):
 
 def summarize(result, args):
     """The JSON record: counts, settings and the measures (keys as strings, NaN as null)."""
-    def clean(v):
-        if isinstance(v, dict):
-            return {str(k): clean(x) for k, x in v.items()}
-        return None if isinstance(v, float) and v != v else v
+    from .tooling import json_clean
     settings = dict(result.get("settings", {}), split=args.split, data_set=args.data_set, boxes=args.boxes or "bounding_boxes.txt")
-    return dict(images=int(result["images"]), rows=int(result["rows"]), settings=settings, overall=clean(result["overall"]),
-                per_class=clean(dict(sorted(result["per_class"].items()))),
-                per_prototype=None if result.get("per_prototype") is None else clean(dict(sorted(result["per_prototype"].items()))))
+    return json_clean(dict(images=int(result["images"]), rows=int(result["rows"]), settings=settings, overall=result["overall"],
+                           per_class=dict(sorted(result["per_class"].items())),
+                           per_prototype=None if result.get("per_prototype") is None else dict(sorted(result["per_prototype"].items()))))
 
 
 def main(args, model=None):
     import numpy as np
-    import torch
     from PIL import Image
 
-    from . import data as D
     from .interpret import foreground_focus
-    from .tooling import load_for_eval, model_from_args
-    from .train import set_seed
-    set_seed(args.seed)
-    device = torch.device(args.device)
-    ds, nb_classes = D.build_dataset(args.split == "train", args, transform=D.build_view_transform(args, square=True))
-    if hasattr(ds, "return_id"):
-        ds.return_id = True
+    from .tooling import tool_setup, write_json
+    model, loader, ds, _ = tool_setup(args, "focus", model, square=True)       # the square view, resident on the device where PPF_DEVICE_DATA says so
     if args.boxes:
         boxes = read_boxes(args.boxes)
     elif args.data_set == "CUB2011U":
@@ -105,19 +91,10 @@ def main(args, model=None):
     for i, path in image_files(ds).items():
         with Image.open(path) as im:
             sizes[i] = im.size                                  # (width, height) of the original file
-    if D.device_data_enabled(args):                             # the same square bilinear view produced on the device from resident originals
-        loader = D.DeviceAugLoader(D.DeviceDataset(ds, device, num_workers=args.num_workers), args.batch_size, D.GpuFinisher(re_prob=0.0), False, args,
-                                   square=True)
-    else:
-        loader = D.DeviceLoader(ds, args.batch_size, device, D.GpuFinisher(re_prob=0.0), shuffle=False, num_workers=args.num_workers)
-    model = load_for_eval(model_from_args(args, nb_classes) if model is None else model, args, device)
     model.eval()
     res = foreground_focus(model, loader, boxes, sizes, protos=args.protos, protos_per_image=args.protos_per_image, percentile=args.percentile,
                            max_images=args.max_images, per_image=args.per_image)
-    os.makedirs(args.output_dir, exist_ok=True)
-    path = os.path.join(args.output_dir, "focus.json")
-    with open(path, "w") as f:
-        json.dump(summarize(res, args), f, indent=1)
+    path = write_json(args, "focus.json", summarize(res, args))
     if args.per_image:
         np.savez(os.path.join(args.output_dir, "focus.npz"), **{k: v for k, v in res["per_image"].items() if v is not None})
     print(f"foreground focus of {res['images']} {args.split} images ({res['rows']} image-prototype pairs): {path}", flush=True)

@@ -11,7 +11,65 @@ import os
 import numpy as np
 import torch
 
-from .tooling import batches_with_ids, read_once, take_images
+from .tooling import batches_with_ids, read_once, read_rows, regroup, take_images
+
+
+# ------------------------------------------------------------------------------------------------ what the passes below share
+class Record:
+    """Base of the result records of the passes.  A subclass declares FIELDS, the names of its tensor-valued attributes (device tensors,
+    numpy arrays after cpu(); any of them may be None, and one may be a dict of tensors), and META, {name: conversion or None} of its
+    plain settings (DEFAULTS: the trailing ones that may be left out).  Construction takes FIELDS then META, by position or by name."""
+    FIELDS, META, DEFAULTS = (), {}, {}
+
+    def __init__(self, *args, **kw):
+        names = tuple(self.FIELDS) + tuple(self.META)
+        given = {**self.DEFAULTS, **dict(zip(names, args)), **kw}
+        if len(args) > len(names) or set(kw) - set(names[len(args):]) or set(names) - set(given):
+            raise TypeError(f"{type(self).__name__} takes {names}, got {len(args)} positional values and {sorted(kw)}")
+        for k in names:
+            conv = self.META.get(k)
+            setattr(self, k, given[k] if conv is None else conv(given[k]))
+
+    def fields(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    @property
+    def on_host(self):
+        return not any(isinstance(t, torch.Tensor) for v in self.fields().values() for t in (v.values() if isinstance(v, dict) else (v,)))
+
+    def cpu(self):
+        """The same record with numpy arrays: every field in ONE host read (a record among the settings: one more read for it).  A record
+        on the host already is returned as it is."""
+        if self.on_host:
+            return self
+        f = self.fields()
+        host = read_once({(k, j): t for k, v in f.items() for j, t in (v.items() if isinstance(v, dict) else ((None, v),))})
+        return type(self)(**{k: ({j: host[k, j] for j in v} if isinstance(v, dict) else host[k, None]) for k, v in f.items()},
+                          **{k: (v.cpu() if isinstance(v, Record) else v) for k, v in ((k, getattr(self, k)) for k in self.META)})
+
+
+def select_prototypes(mode, ppc, classes, act_max=None, k=None, num_classes=None):
+    """int64 [B, K] prototype ids of one class per image, on the device classes [B] (integers) is on; prototype j of class c is c * ppc + j.
+      'own'        every prototype of the label classes[b], clamped into [0, num_classes), in id order (K = ppc);
+      'predicted'  every prototype of classes[b] = the predicted class (logits.argmax(1), which the caller holds), in id order;
+      'top'        the first k of the predicted class's by act_max [B, P]: a stable descending sort, so equal activations go to the
+                   smaller id and a NaN sorts as torch.sort sorts it.  The slice [:, :k] is all that is done with k: each caller clamps
+                   it by its own rule.
+    Plain torch: it runs where its inputs are, the host included."""
+    if mode not in ("own", "predicted", "top"):
+        raise ValueError(f"select_prototypes: mode must be 'own', 'predicted' or 'top', got {mode!r}")
+    ppc = int(ppc)
+    cls = classes.clamp(0, int(num_classes) - 1) if mode == "own" else classes
+    own = cls[:, None] * ppc + torch.arange(ppc, device=classes.device)[None, :]
+    if mode != "top":
+        return own
+    return own.gather(1, torch.sort(act_max.gather(1, own), dim=1, descending=True, stable=True)[1][:, :k])
+
+
+def forward_groups(ppnet, imgs, batch_size):
+    """The model's forward over imgs [R, C, H, W] in consecutive groups of batch_size images: the list of the groups' output records
+    (PPNet._branches without the distances).  The caller holds eval mode and no_grad."""
+    return [ppnet._branches(imgs[i:i + batch_size], want_dist=False) for i in range(0, imgs.shape[0], batch_size)]
 
 
 # ------------------------------------------------------------------------------------------------ activation maps
@@ -698,7 +756,7 @@ def explain_from_outputs(act_max, weight, scale, ppc, logits, topk, classes=None
     return out
 
 
-class Explanation:
+class Explanation(Record):
     """What explain() returns: per branch ('local' / 'global') the fields of EXPLAIN_FIELDS, as device tensors (or numpy arrays after
     cpu()).  classes / class_logits [B, M]: the explained classes and the model's logits for them; prototypes / contributions /
     activations / cells / weights [B, M, K]: the ranked prototypes (-1 / -inf in unfilled slots), their share of the logit, pooled
@@ -707,33 +765,22 @@ class Explanation:
     branch with maps=True, else None.  ex.local / ex.global_ are the two field sets; a field name on the object itself is the local one.
     meta: ppc and scale per branch, side (cells per grid side), patch_size, img_size, against."""
 
-    def __init__(self, local, global_, ppc, scale, side, patch_size, img_size, against=False):
-        for br in (local, global_):
+    FIELDS = ("local", "global_")                           # each a dict of the EXPLAIN_FIELDS
+    META = dict(ppc=dict, scale=lambda s: {k: float(v) for k, v in s.items()}, side=int, patch_size=int, img_size=int, against=bool)
+    DEFAULTS = dict(against=False)
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        for br in (self.local, self.global_):
             for k in EXPLAIN_FIELDS:
                 br.setdefault(k, None)
-        self.branches = {"local": local, "global": global_}
-        self.ppc, self.scale = dict(ppc), {k: float(v) for k, v in scale.items()}
-        self.side, self.patch_size, self.img_size, self.against = int(side), int(patch_size), int(img_size), bool(against)
 
-    local = property(lambda self: self.branches["local"])
-    global_ = property(lambda self: self.branches["global"])
+    branches = property(lambda self: {"local": self.local, "global": self.global_})
 
     def __getattr__(self, name):
         if name in EXPLAIN_FIELDS:
-            return self.__dict__["branches"]["local"][name]
+            return self.__dict__["local"][name]
         raise AttributeError(name)
-
-    @property
-    def on_host(self):
-        return not isinstance(self.branches["local"]["classes"], torch.Tensor)
-
-    def cpu(self):
-        """The same explanation with numpy arrays: every field of both branches in ONE host read."""
-        if self.on_host:
-            return self
-        host = read_once({(br, k): v for br in EXPLAIN_BRANCHES for k, v in self.branches[br].items()})
-        out = {br: {k: host[br, k] for k in self.branches[br]} for br in EXPLAIN_BRANCHES}
-        return Explanation(out["local"], out["global"], self.ppc, self.scale, self.side, self.patch_size, self.img_size, self.against)
 
     def report(self, index=None, bank=None, stats=None):
         """JSON-able records, one per image (index: None = every image of the batch, or one batch position, or a sequence of them):
@@ -1061,10 +1108,24 @@ def perturb_pixels(x, rank, counts, insertion=False, baseline=0.0, device=True):
     return np.where(keep[:, :, :, None], x[None, :, None], base[None, :, None]).astype(np.float32)
 
 
-def _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig):
-    """(score fp32 [B, M, H, W], the Rise or None, the IntegratedGradients or None) of pixel_scores."""
+def _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig):
+    """(score, the Rise or None, the IntegratedGradients or None) of an order at a resolution.  'pixel': score fp32 [B, M, H, W], the map
+    of pixel_scores.  'cell': the 'rise' and 'ig' orders give their cell score fp32 [B, M, G] (_rank_cell_scores ranks it); 'evidence',
+    'attention' and 'random' give None: ppf_cell_order scores and ranks those in one launch (cell_order_from_outputs)."""
     from . import ops
     (B, _, H, W), M, G = x.shape, cls.shape[1], int(ppnet.num_patches)
+    pixel = resolution == "pixel"
+    if order in EXTRA_ORDERS + GRADIENT_ORDERS:
+        if order in EXTRA_ORDERS:       # the one place the faithfulness code runs the RISE pass, from the curve's own baseline ...
+            found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
+                                       **{**RISE_DEFAULTS, **(rise or {})})
+            return (found.saliency.contiguous() if pixel else found.cell), found, None
+        _refuse_pending_gradients("faithfulness_curves", ppnet)                                      # ... and integrated gradients
+        found = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
+        a = found.attribution
+        return (((a[:, :, 0] + a[:, :, 1]) + a[:, :, 2]).contiguous() if pixel else found.cell), None, found      # two rounded adds, in this order
+    if not pixel:
+        return None, None, None
     side = int(round(G ** 0.5))
     if order in ORDER_MODES[:2] and (H != W or side * side != G):
         raise ValueError(f"pixel_scores: the {order} map is up-sampled from a square grid to a square image, got G={G} and {H} x {W}")
@@ -1082,16 +1143,16 @@ def _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_s
     if order == "random":
         s = ops.pixel_random(_image_ids(image_ids, B, x.device), H * W, seed)
         return s.reshape(B, 1, H, W).expand(B, M, H, W).contiguous(), None, None
-    if order in EXTRA_ORDERS:
-        found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
-                                   **{**RISE_DEFAULTS, **(rise or {})})
-        return found.saliency.contiguous(), found, None
-    if order in GRADIENT_ORDERS:
-        _refuse_pending_gradients("faithfulness_curves", ppnet)
-        found = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
-        a = found.attribution
-        return ((a[:, :, 0] + a[:, :, 1]) + a[:, :, 2]).contiguous(), None, found                  # two rounded adds, in this order
     raise ValueError(f"pixel_scores: order must be one of {ORDER_MODES + EXTRA_ORDERS + GRADIENT_ORDERS}, got {order!r}")
+
+
+def _rank_cell_scores(cell, cls, G, weight):
+    """(order, rank int32, score fp32 [B, M, G]) of a cell score [B, M, G]: ppf_cell_order's attention mode over the B * M (sample, class)
+    rows, so the total order, the NaN rule and the -1 rows of an invalid class are that kernel's."""
+    from . import ops
+    B, M = cls.shape
+    return tuple(t.reshape(B, M, G) for t in ops.cell_order(cls.reshape(B * M, 1).contiguous(), G, "attention", token_attn=cell.reshape(B * M, G),
+                                                            weight=weight))
 
 
 def pixel_scores(ppnet, x, outs, cls, order, baseline=0.0, seed=0, image_ids=None, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None):
@@ -1107,7 +1168,7 @@ def pixel_scores(ppnet, x, outs, cls, order, baseline=0.0, seed=0, image_ids=Non
       'ig'         (a[:, :, 0] + a[:, :, 1]) + a[:, :, 2] of the attribution of integrated_gradients from this baseline, two rounded fp32
                    adds in that order (ig = dict(steps=, rule=)).
     The caller holds no_grad."""
-    return _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)[0]
+    return _order_scores(ppnet, x, outs, cls, order, "pixel", baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)[0]
 
 
 def _resolve_baseline(baseline, x, blur):
@@ -1119,31 +1180,16 @@ def _resolve_baseline(baseline, x, blur):
     return baseline
 
 
-class Faithfulness:
+class Faithfulness(Record):
     """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
     class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
     order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G.  rise: the Rise the 'rise' order ranked by
     (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order.
     resolution 'pixel': counts are pixels, grid_cells = H * W, rank int32 and score fp32 are [B, M, H * W] as ppf_pixel_order ranked them,
     and order is None (51 MB per class column at 224^2 that nobody reads)."""
-    FIELDS = ("counts", "classes", "order", "rank", "score")
-
-    def __init__(self, curves, counts, classes, order, rank, score, grid_cells, rise=None, ig=None, resolution="cell"):
-        self.curves, self.counts, self.classes, self.order, self.rank, self.score = dict(curves), counts, classes, order, rank, score
-        self.grid_cells, self.rise, self.ig, self.resolution = int(grid_cells), rise, ig, str(resolution)
-
-    @property
-    def on_host(self):
-        return not isinstance(self.counts, torch.Tensor)
-
-    def cpu(self):
-        """The same object with numpy arrays: every field in ONE host read."""
-        if self.on_host:
-            return self
-        out = read_once({**{k: getattr(self, k) for k in self.FIELDS}, **{("curve", k): v for k, v in self.curves.items()}})
-        return Faithfulness({k: out["curve", k] for k in self.curves}, *(out[k] for k in self.FIELDS), self.grid_cells,
-                            rise=None if self.rise is None else self.rise.cpu(), ig=None if self.ig is None else self.ig.cpu(),
-                            resolution=self.resolution)
+    FIELDS = ("curves", "counts", "classes", "order", "rank", "score")
+    META = dict(grid_cells=int, rise=None, ig=None, resolution=str)
+    DEFAULTS = dict(rise=None, ig=None, resolution="cell")
 
     def auc(self):
         """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
@@ -1182,7 +1228,7 @@ def _class_probs(ppnet, imgs, cols, batch_size):
     """The probabilities fp32 [R] of the classes cols[j] int32 [R] of the images imgs [R, C, H, W], per column: the model's forward in
     sub-batches of batch_size images, then one ppf_class_prob per column.  The caller holds eval mode and no_grad."""
     from . import ops
-    logits = torch.cat([ppnet._branches(imgs[i:i + batch_size], want_dist=False).logits for i in range(0, imgs.shape[0], batch_size)]).contiguous()
+    logits = torch.cat([r.logits for r in forward_groups(ppnet, imgs, batch_size)]).contiguous()
     return [ops.class_prob(logits, c) for c in cols]
 
 
@@ -1192,29 +1238,18 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
     B, G = x.shape[0], int(ppnet.num_patches)
     M, S = cls.shape[1], counts.shape[0]
     w_l = ppnet.last_layer.weight.detach().contiguous()
-    found = found_ig = ordr = None
-    perturb = ops.patch_perturb
+    ordr, perturb = None, ops.patch_perturb
+    score, found, found_ig = _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
     if resolution == "pixel":
         # every order is a [B, M, H, W] map (pixel_scores); one ppf_pixel_order launch ranks the B * M rows, ppf_pixel_perturb takes
         # ppf_patch_perturb's place below.  The chunking, the forwards and ppf_class_prob are the cell path's.
         G, perturb = x.shape[2] * x.shape[3], ops.pixel_perturb
-        score, found, found_ig = _pixel_scores(ppnet, x, outs, cls, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
         score = score.reshape(B, M, G)
         rank = pixel_order_from_scores(score, cls)
-    elif order in GRADIENT_ORDERS:
-        # the cells ranked by the integrated gradients of the class logit summed over each cell, along the path from the curve's own
-        # baseline; through ppf_cell_order's attention mode exactly as the rise order below
-        _refuse_pending_gradients("faithfulness_curves", ppnet)
-        found_ig = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
-        ordr, rank, score = (t.reshape(B, M, G) for t in ops.cell_order(cls.reshape(B * M, 1).contiguous(), G, "attention",
-                                                                        token_attn=found_ig.cell.reshape(B * M, G), weight=w_l))
-    elif order in EXTRA_ORDERS:
-        # the cells ranked by their mean RISE saliency: ppf_cell_order's attention mode over the B * M (sample, class) rows, so the total
-        # order, the NaN rule and the -1 rows of an invalid class are that kernel's
-        found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
-                                   **{**RISE_DEFAULTS, **(rise or {})})
-        ordr, rank, score = (t.reshape(B, M, G) for t in ops.cell_order(cls.reshape(B * M, 1).contiguous(), G, "attention",
-                                                                        token_attn=found.cell.reshape(B * M, G), weight=w_l))
+    elif score is not None:
+        # 'rise': the cells ranked by their mean RISE saliency; 'ig': by the integrated gradients of the class logit summed over each
+        # cell, along the path from the curve's own baseline
+        ordr, rank, score = _rank_cell_scores(score, cls, G, w_l)
     else:
         ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G,
                                                     mode=order, seed=seed, image_ids=image_ids)
@@ -1456,25 +1491,12 @@ def rise_accumulate(nodes, shift, prob, size, cells, grid_cells, p=0.5, device=T
         return (acc / norm).astype(np.float32), (acc_w / (norm * float(patch * patch))).astype(np.float32)
 
 
-class Rise:
+class Rise(Record):
     """What rise_saliency returns, as device tensors (numpy arrays after cpu()): saliency fp32 [B, M, H, W], cell fp32 [B, M, G] (the mean
     saliency of each grid cell), prob fp32 [N, B, M] (the class probabilities of the masked images), nodes uint8 [B, N, L*L], shift int32
     [B, N, 2], classes int32 [B, M]; cells, p: the mask parameters."""
-    FIELDS = ("saliency", "cell", "prob", "shift", "classes", "nodes")                            # the constructor's order
-
-    def __init__(self, saliency, cell, prob, shift, classes, nodes, cells, p):
-        self.saliency, self.cell, self.prob, self.shift, self.classes, self.nodes = saliency, cell, prob, shift, classes, nodes
-        self.cells, self.p = int(cells), float(p)
-
-    @property
-    def on_host(self):
-        return not isinstance(self.nodes, torch.Tensor)
-
-    def cpu(self):
-        """The same object with numpy arrays: every field in ONE host read."""
-        if self.on_host:
-            return self
-        return Rise(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.cells, self.p)
+    FIELDS = ("saliency", "cell", "prob", "shift", "classes", "nodes")
+    META = dict(cells=int, p=float)
 
 
 def _rise_from_classes(ppnet, x, cls, masks, cells, p, baseline, seed, image_ids, batch_size, scratch_bytes):
@@ -1538,6 +1560,23 @@ def _refuse_pending_gradients(who, ppnet):
                                "the same buffers; finish the training step and drop the gradients (zero_grad(set_to_none=True)) first")
 
 
+def _parse_target(who, ppnet, target, B, device, or_none=False):
+    """(kind, branch, ids int32 [B, M]) of a target ("logit", classes) or ("proto", "local" | "global", prototypes): branch None for a
+    logit; ids [B] or [B, M], host values range-checked against the output's width (_explain_classes), device tensors not read back.
+    or_none: None stands for the logits of classes still to be picked, ("logit", None, None)."""
+    if target is None and or_none:
+        return "logit", None, None
+    kind = target[0] if isinstance(target, (tuple, list)) and target else None
+    if kind == "logit" and len(target) == 2:
+        branch, sel, n_out = None, target[1], ppnet.last_layer.weight.shape[0]
+    elif kind == "proto" and len(target) == 3 and target[1] in EXPLAIN_BRANCHES:
+        branch, sel = target[1], target[2]
+        n_out = ppnet.prototype_vectors.shape[0] if branch == "local" else ppnet.prototype_vectors_global.shape[0]
+    else:
+        raise ValueError(f'{who}: target must be {"None, " if or_none else ""}("logit", classes) or ("proto", "local" | "global", prototypes)')
+    return kind, branch, _explain_classes(sel, B, n_out, device)
+
+
 def input_gradient(ppnet, x, target):
     """Gradient of a model output with respect to the image: (grad fp32 [B, 3, H, W], value fp32 [B]) of x [B, 3, H, W] (CUDA).
     target = ("logit", classes [B]): value = logits[b, classes[b]]; ("proto", "local" | "global", protos [B]): value = the prototype's
@@ -1550,15 +1589,7 @@ def input_gradient(ppnet, x, target):
         raise RuntimeError("input_gradient needs a CUDA/HIP batch [B, 3, H, W] (no CPU fallback path)")
     _refuse_pending_gradients("input_gradient", ppnet)
     B = x.shape[0]
-    kind = target[0] if isinstance(target, (tuple, list)) and target else None
-    if kind == "logit" and len(target) == 2:
-        branch, sel, n_out = None, target[1], ppnet.last_layer.weight.shape[0]
-    elif kind == "proto" and len(target) == 3 and target[1] in EXPLAIN_BRANCHES:
-        branch, sel = target[1], target[2]
-        n_out = ppnet.prototype_vectors.shape[0] if branch == "local" else ppnet.prototype_vectors_global.shape[0]
-    else:
-        raise ValueError('input_gradient: target must be ("logit", classes) or ("proto", "local" | "global", prototypes)')
-    sel = _explain_classes(sel, B, n_out, x.device)                       # [B, 1] int32, host values range-checked
+    _, branch, sel = _parse_target("input_gradient", ppnet, target, B, x.device)
     if sel.shape[1] != 1:
         raise ValueError(f"input_gradient: one target per sample expected, got {tuple(sel.shape)}")
     xg = x.detach().float().contiguous().requires_grad_(True)
@@ -1730,20 +1761,6 @@ def misalignment_attack(ppnet, x, protos, boxes, steps=10, eps=8 / 255, alpha=No
 ALIGNMENT_STATS = ("share", "area", "pac", "plc", "left_box")
 
 
-def _regroup(loader, n, max_images):
-    """The loader's images in consecutive passes of exactly n images (the last may be shorter), whatever its own batch size: what
-    spatial_alignment computes then depends on the image sequence alone.  Yields fp32 batches on the device the loader's are on."""
-    held, have = [], 0
-    for x, in take_images(((b[0],) for b in loader), max_images):
-        held.append(x.float()); have += x.shape[0]
-        while have >= n:
-            full = torch.cat(held) if len(held) > 1 else held[0]
-            yield full[:n].contiguous()
-            held, have = ([full[n:]] if full.shape[0] > n else []), full.shape[0] - n
-    if have:
-        yield torch.cat(held).contiguous()
-
-
 def alignment_rows(ppnet, x, protos_per_image=3, half_size=36, attack=True, attack_steps=10, eps=8 / 255, alpha=None):
     """The spatial-alignment measurements of one batch x [B, 3, H, W]: per image the predicted class's local prototypes ranked by
     pooled activation (larger first, equal ones by smaller id), the first protos_per_image of them; one row per (image, prototype)
@@ -1753,10 +1770,8 @@ def alignment_rows(ppnet, x, protos_per_image=3, half_size=36, attack=True, atta
     with torch.no_grad():
         outs = _eval_outputs(ppnet, x)
     B, ppc = x.shape[0], int(ppnet.num_prototypes_per_class)
-    K = min(int(protos_per_image), ppc)
-    own = outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
-    rank = torch.sort(outs["act_max"].gather(1, own), dim=1, descending=True, stable=True)[1][:, :K]
-    protos = own.gather(1, rank).to(torch.int32).contiguous()
+    K = min(int(protos_per_image), ppc)                    # this pass's clamp: min(k, ppc), at most ppc and no lower bound
+    protos = select_prototypes("top", ppc, outs["logits"].argmax(1), outs["act_max"], K).to(torch.int32).contiguous()
     boxes = prototype_boxes(ppnet, outs, protos, half_size)
     rows = protos.reshape(-1)
     grad, _ = input_gradient(ppnet, x.repeat_interleave(K, dim=0).contiguous(), ("proto", "local", rows))
@@ -1801,12 +1816,12 @@ def alignment_summary(protos, stats):
 def spatial_alignment(ppnet, loader, protos_per_image=3, half_size=36, attack=True, attack_steps=10, eps=8 / 255, alpha=None, max_images=0,
                       pass_images=16):
     """The spatial-alignment test over a data set.  loader yields (x, ...); its images are regrouped into passes of pass_images images
-    (_regroup), so the result does not depend on the loader's batch size, and each pass is measured by alignment_rows.  The rows
+    (tooling.regroup), so the result does not depend on the loader's batch size, and each pass is measured by alignment_rows.  The rows
     stay on the device; their fp64 means are taken once at the end (alignment_summary) and read back once.  Returns dict(images, rows,
     overall: mean_share, mean_area (box area / image area, the share a spatially blind gradient would reach), share_over_area, mean_pac,
     mean_plc, mean_left_box; per_prototype: the same per prototype id that occurred, with its row count)."""
     ids, stats, images = [], [], 0
-    for x in _regroup(loader, int(pass_images), int(max_images)):
+    for x, in regroup(((x.float(),) for x, in take_images(((b[0],) for b in loader), int(max_images))), int(pass_images)):
         x = x if x.is_cuda else x.cuda()
         p, s = alignment_rows(ppnet, x, protos_per_image, half_size, attack, attack_steps, eps, alpha)
         ids.append(p); stats.append(s)
@@ -1894,48 +1909,19 @@ def ig_finish(acc, x, baseline, patch, device=True):
         return attr, np.sum(cells, axis=(2, 4, 6)).reshape(B, M, -1)
 
 
-class IntegratedGradients:
+class IntegratedGradients(Record):
     """What integrated_gradients returns, as device tensors (numpy arrays after cpu()): attribution fp32 [B, M, 3, H, W]; cell fp32
     [B, M, G] = the attribution summed over each grid cell (the fp64 sums rounded once); total fp64 [B, M] = the fp64 cell sums added up,
     the whole attribution of the image; value, value_base fp32 [B, M] = the target at x and at the baseline image; targets int32 [B, M];
     alphas, weights fp32 [n] of the rule.  target = ("logit",) or ("proto", branch); steps, rule."""
-    FIELDS = ("attribution", "cell", "total", "value", "value_base", "targets", "alphas", "weights")      # the constructor's order
-
-    def __init__(self, attribution, cell, total, value, value_base, targets, alphas, weights, target, steps, rule):
-        self.attribution, self.cell, self.total, self.value, self.value_base = attribution, cell, total, value, value_base
-        self.targets, self.alphas, self.weights = targets, alphas, weights
-        self.target, self.steps, self.rule = tuple(target), int(steps), str(rule)
-
-    @property
-    def on_host(self):
-        return not isinstance(self.cell, torch.Tensor)
+    FIELDS = ("attribution", "cell", "total", "value", "value_base", "targets", "alphas", "weights")
+    META = dict(target=tuple, steps=int, rule=str)
 
     def delta(self):
         """The completeness gap fp64 [B, M]: total - (value - value_base), the fp32 values widened first."""
         if self.on_host:
             return self.total - (self.value.astype(np.float64) - self.value_base.astype(np.float64))
         return self.total - (self.value.double() - self.value_base.double())
-
-    def cpu(self):
-        """The same object with numpy arrays: every field in ONE host read."""
-        if self.on_host:
-            return self
-        return IntegratedGradients(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.target, self.steps, self.rule)
-
-
-def _ig_target(ppnet, target, B, device):
-    """(kind, branch, ids int32 [B, M] or None) of integrated_gradients' target; host ids are range-checked as input_gradient checks them."""
-    if target is None:
-        return "logit", None, None
-    kind = target[0] if isinstance(target, (tuple, list)) and target else None
-    if kind == "logit" and len(target) == 2:
-        branch, sel, n_out = None, target[1], ppnet.last_layer.weight.shape[0]
-    elif kind == "proto" and len(target) == 3 and target[1] in EXPLAIN_BRANCHES:
-        branch, sel = target[1], target[2]
-        n_out = ppnet.prototype_vectors.shape[0] if branch == "local" else ppnet.prototype_vectors_global.shape[0]
-    else:
-        raise ValueError('integrated_gradients: target must be None, ("logit", classes) or ("proto", "local" | "global", prototypes)')
-    return kind, branch, _explain_classes(sel, B, n_out, device)
 
 
 def _ig_pass(ppnet, x, outs, kind, branch, ids, steps, rule, baseline, batch_size):
@@ -1989,7 +1975,7 @@ def integrated_gradients(ppnet, x, target=None, top_classes=1, steps=32, rule="m
     ig_rule(steps, rule)                                                                          # a bad rule is refused before anything runs
     _refuse_pending_gradients("integrated_gradients", ppnet)
     x = x.detach().float().contiguous()
-    kind, branch, ids = _ig_target(ppnet, target, x.shape[0], x.device)
+    kind, branch, ids = _parse_target("integrated_gradients", ppnet, target, x.shape[0], x.device, or_none=True)
     M = int(top_classes) if ids is None else ids.shape[1]
     if not 1 <= M <= 8:
         raise ValueError(f"integrated_gradients: M={M} targets per image outside [1, 8] (ppf_ig_finish's and ppf_cell_order's limit)")
@@ -2274,31 +2260,18 @@ def because_perturb(x, characteristic, params=None, seed=0, image_ids=None, devi
     raise ValueError(f"because: characteristics must come from {CHARACTERISTICS}, got {characteristic!r}")
 
 
-class Because:
+class Because(Record):
     """What because returns, as device tensors (numpy arrays after cpu()): protos int32 [B, K]; base fp32 [B, K] the clean pooled
     activation of each prototype; cell int32 [B, K] the grid cell it was found at (-1 on the global branch); per characteristic n:
     same fp32 [n, B, K] its activation at that cell after the perturbation (0 where lost), best fp32 [n, B, K] its pooled activation
     wherever it is, lost int32 [n, B, K] = 1 where the perturbed image no longer reserves the cell.  On the global branch same and lost
     are None."""
     FIELDS = ("base", "cell", "same", "best", "lost", "protos")
-
-    def __init__(self, base, cell, same, best, lost, protos, characteristics, branch):
-        self.base, self.cell, self.same, self.best, self.lost, self.protos = base, cell, same, best, lost, protos
-        self.characteristics, self.branch = tuple(characteristics), branch
-
-    @property
-    def on_host(self):
-        return not isinstance(self.base, torch.Tensor)
+    META = dict(characteristics=tuple, branch=None)
 
     def local(self):
         """The local importance [n, B, K] = base - same: how far the similarity at the same patch fell (best on the global branch)."""
         return self.base[None] - (self.best if self.same is None else self.same)
-
-    def cpu(self):
-        """The same object with numpy arrays: every field in ONE host read."""
-        if self.on_host:
-            return self
-        return Because(*read_once({k: getattr(self, k) for k in self.FIELDS}).values(), self.characteristics, self.branch)
 
     def report(self, index):
         """The JSON records of image `index`: per prototype its id, cell, clean activation and per characteristic the local importance,
@@ -2318,7 +2291,7 @@ class Because:
 def _because_forward(ppnet, imgs, batch_size):
     """The model's eval forward over imgs in sub-batches of batch_size images: (act_full [R, P, T], idx [R, T], act_max local [R, P],
     act_max global [R, Pg]) on the device.  The caller holds eval mode and no_grad."""
-    rs = [ppnet._branches(imgs[i:i + batch_size], want_dist=False) for i in range(0, imgs.shape[0], batch_size)]
+    rs = forward_groups(ppnet, imgs, batch_size)
     cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
     return (cat([r.act_full.reshape(r.act_max_local.shape[0], r.act_max_local.shape[1], -1) for r in rs]).contiguous(),
             cat([r.idx for r in rs]).contiguous(), cat([r.act_max_local for r in rs]).contiguous(), cat([r.act_max_global for r in rs]).contiguous())
@@ -2330,7 +2303,7 @@ def _because_rows(ppnet, outs, protos, branch, B, device):
     act = outs["act_max"] if local else outs["act_max_global"]
     ppc = int(ppnet.num_prototypes_per_class) if local else act.shape[1] // outs["logits"].shape[1]
     if protos is None:
-        protos = (outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=device)[None, :]).to(torch.int32).contiguous()
+        protos = select_prototypes("predicted", ppc, outs["logits"].argmax(1)).to(torch.int32).contiguous()
     else:
         t = protos if isinstance(protos, torch.Tensor) and protos.is_cuda else torch.as_tensor(np.asarray(protos)).to(device)
         if t.is_floating_point() or t.dim() not in (1, 2) or t.shape[0] != B:
@@ -2435,20 +2408,6 @@ def importance_from_rows(image_ids, protos, base, same, best, lost, characterist
     return dict(per_prototype={int(p): summary(pf == p) for p in np.unique(pf)}, overall=summary(np.ones(pf.shape, dtype=bool)))
 
 
-def _regroup_fields(loader, n, max_images):
-    """_regroup for (x, labels, ids) batches: consecutive passes of exactly n images (the last may be shorter), whatever the loader's
-    batch size; x fp32, labels and ids int64, all on the device of the loader's images."""
-    held, have = [], 0
-    for x, y, ids in batches_with_ids(loader, max_images):
-        held.append((x.float(), torch.as_tensor(y).to(x.device, torch.int64), ids.to(x.device))); have += x.shape[0]
-        while have >= n:
-            full = tuple(torch.cat(f) if len(held) > 1 else f[0] for f in zip(*held))
-            yield tuple(f[:n].contiguous() for f in full)
-            held, have = ([tuple(f[n:] for f in full)] if have > n else []), have - n
-    if have:
-        yield tuple(torch.cat(f).contiguous() for f in zip(*held))
-
-
 def characteristic_importance(ppnet, loader, protos="own", branch="local", characteristics=CHARACTERISTICS, params=None, seed=0, max_images=0,
                               pass_images=16, protos_per_image=3, scratch_bytes=1 << 30, per_image=False):
     """The importance of every characteristic for every prototype over a data set.  loader yields (x, labels) or (x, labels, ids); its
@@ -2460,28 +2419,24 @@ def characteristic_importance(ppnet, loader, protos="own", branch="local", chara
     if protos not in ("own", "top"):
         raise ValueError(f"characteristic_importance: protos must be 'own' or 'top', got {protos!r}")
     names, local = tuple(characteristics), branch == "local"
-    keep, images = [], 0
-    for x, y, ids in _regroup_fields(loader, int(pass_images), int(max_images)):
+    keep = []
+    fields = ((x.float(), torch.as_tensor(y).to(x.device, torch.int64), ids.to(x.device)) for x, y, ids in batches_with_ids(loader, int(max_images)))
+    for x, y, ids in regroup(fields, int(pass_images)):
         x = x if x.is_cuda else x.cuda()
         y, ids = y.to(x.device), ids.to(x.device)
         C = ppnet.last_layer.weight.shape[0]
         ppc = int(ppnet.num_prototypes_per_class) if local else ppnet.prototype_vectors_global.shape[0] // C
         if protos == "own":
-            pr = y.clamp(0, C - 1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
+            pr = select_prototypes("own", ppc, y, num_classes=C)
         else:
-            outs = _eval_outputs(ppnet, x.float().contiguous())
-            own = outs["logits"].argmax(1)[:, None] * ppc + torch.arange(ppc, device=x.device)[None, :]
-            act = outs["act_max"] if local else outs["act_max_global"]
-            pr = own.gather(1, torch.sort(act.gather(1, own), dim=1, descending=True, stable=True)[1][:, :min(int(protos_per_image), ppc)])
+            outs = _eval_outputs(ppnet, x.float().contiguous())                            # the pick's own forward; because runs another
+            K = min(int(protos_per_image), ppc)            # this pass's clamp: min(k, ppc), at most ppc and no lower bound
+            pr = select_prototypes("top", ppc, outs["logits"].argmax(1), outs["act_max"] if local else outs["act_max_global"], K)
         r = because(ppnet, x, pr.to(torch.int32), branch, names, params, seed, ids, None, scratch_bytes)
         keep.append(dict(image_ids=ids, labels=y, protos=r.protos, cell=r.cell, base=r.base, same=r.same, best=r.best, lost=r.lost))
-        images += x.shape[0]
-    if not images:
-        raise ValueError("characteristic_importance: the loader gave no image")
-    cat = lambda k, dim: None if keep[0][k] is None else torch.cat([d[k] for d in keep], dim=dim)
-    rows = read_once({k: cat(k, 1 if k in ("same", "best", "lost") else 0) for k in keep[0]})            # the one read
+    rows = read_rows(keep, "characteristic_importance", dict(same=1, best=1, lost=1))                      # the one read; [n, N, K]: images on dim 1
     out = importance_from_rows(rows["image_ids"], rows["protos"], rows["base"], rows["same"], rows["best"], rows["lost"], names)
-    out.update(images=images, characteristics=list(names), branch=branch)
+    out.update(images=int(rows["image_ids"].shape[0]), characteristics=list(names), branch=branch)
     if per_image:
         out["rows"] = rows
     return out
@@ -2642,7 +2597,7 @@ def evidence_focus(act_max, weight, scale, ppc, classes, obj, grid_side, patch, 
     return ev, cnt
 
 
-class Focus:
+class Focus(Record):
     """What focus_rows returns, as device tensors (numpy arrays after cpu()), K prototypes per image: protos int32 [B, K]; classes int32
     [B] the predicted class; peak_val fp32, hit / nonfinite int32, inside / total fp64 [B, K], peak_yx int32 [B, K, 2] (ppf_act_focus);
     box int32 [B, K, 4] the top-percentile box and terms int32 [B, K, 4] its (intersection, box, object, union) areas; reserve int32
@@ -2650,23 +2605,8 @@ class Focus:
     (ppf_evidence_focus); global_ev fp64 [B] the global branch's share of the predicted logit (it has no cells: unlocated), or None;
     obj int32 [B, 4]; labels int64 [B] or None.  img_size, grid_side, patch, mode, percentile: the settings."""
 
-    def __init__(self, fields, img_size, grid_side, patch, mode, percentile):
-        for k in FOCUS_FIELDS:
-            setattr(self, k, fields.get(k))
-        self.img_size, self.grid_side, self.patch, self.mode, self.percentile = int(img_size), int(grid_side), int(patch), mode, percentile
-
-    def fields(self):
-        return {k: getattr(self, k) for k in FOCUS_FIELDS}
-
-    @property
-    def on_host(self):
-        return not isinstance(self.protos, torch.Tensor)
-
-    def cpu(self):
-        """The same object with numpy arrays: every field in ONE host read."""
-        if self.on_host:
-            return self
-        return Focus(read_once(self.fields()), self.img_size, self.grid_side, self.patch, self.mode, self.percentile)
+    FIELDS = FOCUS_FIELDS
+    META = dict(img_size=int, grid_side=int, patch=int, mode=None, percentile=None)
 
 
 def focus_from_outputs(outs, obj, weight, scale, ppc, k, img_size, labels=None, protos="own", protos_per_image=3, percentile=95, global_coe=None,
@@ -2691,11 +2631,11 @@ def focus_from_outputs(outs, obj, weight, scale, ppc, k, img_size, labels=None, 
     pred = o["logits"].argmax(1)
     if protos == "own":
         lab = torch.as_tensor(labels).to(dev, torch.int64)
-        pr = lab.clamp(0, C - 1)[:, None] * ppc + torch.arange(ppc, device=dev)[None, :]
+        pr = select_prototypes("own", ppc, lab, num_classes=C)
     else:
         lab = None if labels is None else torch.as_tensor(labels).to(dev, torch.int64)
-        own = pred[:, None] * ppc + torch.arange(ppc, device=dev)[None, :]
-        pr = own.gather(1, torch.sort(o["act_max"].gather(1, own), dim=1, descending=True, stable=True)[1][:, :max(1, min(int(protos_per_image), ppc))])
+        K = max(1, min(int(protos_per_image), ppc))        # this pass's clamp: max(1, min(k, ppc)), at most ppc and at least one
+        pr = select_prototypes("top", ppc, pred, o["act_max"], K)
     K, s = pr.shape[1], int(round(int(k) ** 0.5))
     sel = torch.gather(o["act_full"].reshape(B, P, -1), 1, pr[:, :, None].expand(B, K, int(k))).reshape(B, K, s, s)
     grid = patch_grid(o["token_attn"], sel, int(k)).contiguous()                         # expand_to_grid of the selected prototypes only
@@ -2719,7 +2659,7 @@ def focus_from_outputs(outs, obj, weight, scale, ppc, k, img_size, labels=None, 
                   hit=shape(f["hit"]), inside=shape(f["inside"]), total=shape(f["total"]), nonfinite=shape(f["nonfinite"]), box=shape(box, 4),
                   terms=shape(terms, 4), reserve=reserve, attn=attn, ev=ev.reshape(B, 4), cnt=cnt.reshape(B, 4), global_ev=host(glob),
                   obj=host(obj_t), labels=host(lab))
-    return Focus(fields, S, g, patch, protos, percentile)
+    return Focus(**fields, img_size=S, grid_side=g, patch=patch, mode=protos, percentile=percentile)
 
 
 @torch.no_grad()
@@ -2825,9 +2765,7 @@ def foreground_focus(ppnet, loader, boxes, image_sizes, protos="own", protos_per
         f = focus_rows(ppnet, x, obj, torch.as_tensor(y).to(x.device, torch.int64), protos, protos_per_image, percentile)
         keep.append(dict(f.fields(), image_ids=ids.to(x.device)))
         meta = f
-    if not keep:
-        raise ValueError("foreground_focus: the loader gave no image")
-    rows = read_once({k: (None if keep[0][k] is None else torch.cat([d[k] for d in keep])) for k in keep[0]})            # the one read
+    rows = read_rows(keep, "foreground_focus")                                                             # the one read
     out = focus_summary(rows, meta.img_size, meta.patch, per_prototype=protos == "own")
     out["settings"] = dict(protos=protos, protos_per_image=int(protos_per_image), percentile=percentile, img_size=meta.img_size, patch=meta.patch)
     if per_image:

@@ -16,7 +16,6 @@ writes OUT/prototype_stats.npz (the tables of PrototypeStats.result, the range a
 (stats_report: per prototype branch, class, counts, AUROC, mean and median activation, the overlaps above 0.5 with their partners; with
 --prune also the keep decision with the reason for every dropped prototype, acc@1 on the test split before and after, and the path of
 the pruned checkpoint)."""
-import argparse
 import json
 import math
 import os
@@ -378,11 +377,9 @@ def stats_report(result, overlap_above=0.5):
 
 # ------------------------------------------------------------------------------------------------ the tool
 def get_args_parser():
-    from .tooling import add_split_flags
-    from .train import get_args_parser as train_parser
-    p = argparse.ArgumentParser("ProtoPFormer prototype statistics: selectivity, overlap and pruning of the prototypes", parents=[train_parser()])
+    from .tooling import tool_parser
+    p = tool_parser("ProtoPFormer prototype statistics: selectivity, overlap and pruning of the prototypes", "train", "measured")
     a = p.add_argument
-    add_split_flags(p, "train", "measured")
     a("--bins", type=int, default=64, help=f"histogram bins per prototype ({MIN_BINS}..{MAX_BINS})")
     a("--range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="activation range of the histograms (default: [0, log(1 / epsilon)] "
       "of the 'log' activation; required for 'linear')")

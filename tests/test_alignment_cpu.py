@@ -170,10 +170,11 @@ def test_summary_leaves_nan_rows_out_of_their_mean():
 
 def test_regroup_gives_the_same_passes_for_every_loader_batch_size():
     import torch
-    from protopformer_amd.interpret import _regroup
+    from protopformer_amd.tooling import regroup, take_images
     x = torch.arange(7.0).reshape(7, 1)
-    for bs in (1, 2, 3, 7):
-        passes = [p.cpu().reshape(-1).tolist() for p in _regroup([(x[i:i + bs], None) for i in range(0, 7, bs)], 4, 0)]
+    for bs in (1, 2, 3, 7):                                # composed as spatial_alignment composes it
+        loader = [(x[i:i + bs], None) for i in range(0, 7, bs)]
+        passes = [p.cpu().reshape(-1).tolist() for p, in regroup(((v.float(),) for v, in take_images(((b[0],) for b in loader), 0)), 4)]
         assert passes == [[0, 1, 2, 3], [4, 5, 6]]
 
 

@@ -37,9 +37,9 @@ def test_take_images_counts_truncates_every_element_and_stops(width, max_images,
 
 
 def test_regroup_over_take_images():
-    from protopformer_amd.interpret import _regroup
     x = torch.arange(14.0).reshape(14, 1)
-    passes = list(_regroup([(x[i:i + 4], None) for i in range(0, 14, 4)], 3, 10))
+    loader = [(x[i:i + 4], None) for i in range(0, 14, 4)]                 # composed as spatial_alignment composes it
+    passes = [p for p, in T.regroup(((v.float(),) for v, in T.take_images(((b[0],) for b in loader), 10)), 3)]
     assert [p.shape[0] for p in passes] == [3, 3, 3, 1]
     assert torch.equal(torch.cat(passes), x[:10]) and all(p.dtype == torch.float32 and p.is_contiguous() for p in passes)
 
@@ -175,3 +175,68 @@ def test_model_from_args_overrides(monkeypatch):
     del args.img_size, args.no_pretrained
     T.model_from_args(args, 7, img_size=64, pretrained=True)
     assert seen["img_size"] == 64
+
+
+def test_regroup_carries_every_field_across_batch_borders():
+    """Three fields, 7 images in loader batches of 2, passes of 3: the batch size does not divide the pass, a pass takes rows of two
+    batches, the last one is short."""
+    x, y, ids = torch.arange(21.0).reshape(7, 3), torch.arange(7) * 10, torch.arange(7) + 100
+    loader = [(x[i:i + 2], y[i:i + 2], ids[i:i + 2]) for i in range(0, 7, 2)]
+    passes = list(T.regroup(loader, 3))
+    assert [tuple(f.shape[0] for f in p) for p in passes] == [(3, 3, 3), (3, 3, 3), (1, 1, 1)]
+    for j, whole in enumerate((x, y, ids)):
+        assert torch.equal(torch.cat([p[j] for p in passes]), whole) and all(p[j].dtype == whole.dtype and p[j].is_contiguous() for p in passes)
+    assert passes[0][2].tolist() == [100, 101, 102] and passes[1][1].tolist() == [30, 40, 50]      # image 2 crossed a batch border with its fields
+    assert list(T.regroup([], 3)) == []
+
+
+def test_read_rows_concatenates_per_field_in_one_read(monkeypatch):
+    import numpy as np
+    kept = [dict(ids=torch.tensor([3, 1]), same=torch.arange(12.0).reshape(2, 2, 3), lost=None, base=torch.ones(2, 3, dtype=torch.float64)),
+            dict(ids=torch.tensor([7]), same=100 + torch.arange(6.0).reshape(2, 1, 3), lost=None, base=torch.zeros(1, 3, dtype=torch.float64))]
+    calls, real = [], torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **k: calls.append(1) or real(self, *a, **k))
+    rows = T.read_rows(kept, "somebody", dict(same=1))
+    monkeypatch.undo()
+    assert len(calls) == 1 and list(rows) == ["ids", "same", "lost", "base"] and rows["lost"] is None
+    assert rows["ids"].tolist() == [3, 1, 7] and rows["ids"].dtype == np.int64
+    assert rows["same"].shape == (2, 3, 3) and rows["same"].dtype == np.float32                   # [n, N, K]: the images on dim 1
+    assert rows["same"][:, :2].tobytes() == kept[0]["same"].numpy().tobytes() and rows["same"][:, 2].tolist() == [[100, 101, 102], [103, 104, 105]]
+    assert rows["base"].shape == (3, 3) and rows["base"].dtype == np.float64 and rows["base"][:, 0].tolist() == [1, 1, 0]
+    with pytest.raises(ValueError, match="somebody: the loader gave no image"):
+        T.read_rows([], "somebody")
+
+
+def test_write_json_cleans_nan_and_keys_at_every_depth(tmp_path):
+    import json
+    import types
+    nan = float("nan")
+    doc = dict(images=3, overall=dict(mean=nan, rows=2), per_prototype={4: dict(share=nan, deep={7: [1.5, nan, (nan, 2)]}), 11: dict(share=0.25)}, none=None)
+    args = types.SimpleNamespace(output_dir=str(tmp_path / "made" / "here"))
+    path = T.write_json(args, "doc.json", doc)
+    assert path == str(tmp_path / "made" / "here" / "doc.json")
+    text = open(path).read()
+    assert "NaN" not in text and json.loads(text) == dict(images=3, overall=dict(mean=None, rows=2), none=None,
+                                                          per_prototype={"4": dict(share=None, deep={"7": [1.5, None, [None, 2]]}), "11": dict(share=0.25)})
+    # what the tools wrote before: a shallow clean of the values, prototype ids as strings, indent 1
+    shallow = dict(overall={k: (None if isinstance(v, float) and v != v else v) for k, v in doc["overall"].items()}, per={str(p): v for p, v in {4: 1, 11: 2}.items()})
+    assert open(T.write_json(args, "same.json", dict(overall=doc["overall"], per={4: 1, 11: 2}))).read() == json.dumps(shallow, indent=1)
+
+
+@pytest.mark.parametrize("device_data", [False, True])
+def test_eval_loader_passes_square_to_the_view_and_the_device_loader(monkeypatch, device_data):
+    import types
+    from protopformer_amd import data as D
+    seen = {}
+    monkeypatch.setattr(D, "build_view_transform", lambda args, square=False: seen.update(view=square) or "view")
+    monkeypatch.setattr(D, "build_dataset", lambda train, args, transform=None: (types.SimpleNamespace(return_id=False, transform=transform), 7))
+    monkeypatch.setattr(D, "device_data_enabled", lambda args: device_data)
+    monkeypatch.setattr(D, "DeviceDataset", lambda ds, device, num_workers=0: ("resident", ds))
+    monkeypatch.setattr(D, "DeviceAugLoader", lambda dds, bs, fin, train, args, square=False: seen.update(loader=square) or "device loader")
+    monkeypatch.setattr(D, "DeviceLoader", lambda ds, bs, device, fin, shuffle=False, num_workers=0: "host loader")
+    args = types.SimpleNamespace(split="test", num_workers=0, batch_size=4)
+    for square in (True, False):
+        seen.clear()
+        ds, classes, loader = T.eval_loader(args, "cpu", square=square)
+        assert seen["view"] is square and ds.transform == "view" and ds.return_id is True and classes == 7
+        assert (loader, seen.get("loader")) == (("device loader", square) if device_data else ("host loader", None))
