@@ -992,6 +992,8 @@ extern "C" {
 // tokens: fp32 rows of Dp values; sample b's token i is at tok + b*stride_b + (t0+i)*Dp, T tokens per sample
 // (T == 1: the global/cls branch, no pooling).  protos [P][Dp].  act_kind 0 = 'log', 1 = 'linear'.
 // Outputs: act_max [B][P], argmax [B][P] (T > 1), optional dist_full / act_full [B][P][T].
+// Ties of the arg-max: the smallest token index among equal activations (`a > best` keeps the first of a lane's ascending rows, the
+// two half-waves are merged with `ob == best && oi < besti`); bit-identical token rows, as padded images produce them, resolve to the first.
 // workspace (optional, ppf_proto_fwd_workspace(P, Dp) bytes, any content): the pre-split prototype planes of the pooled branch; NULL or too
 // small: every workgroup splits its prototype rows itself (same results: the pieces are the same numbers, |p|^2 is summed in another order).
 size_t ppf_proto_fwd_workspace(int P, int Dp) {
@@ -1043,18 +1045,17 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
 
 // Backward of ppf_proto_fwd given upstream grads of act_max (g_max) and act_full (g_full and / or its block form g_rows), any may be null.
 // dtok rows are overwritten; dprotos [P][Dp] is accumulated (+=).
-static int proto_bwd_launch(ProtoBwdParams p, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+static int proto_bwd_launch(ProtoBwdParams p, void* workspace, size_t workspace_bytes, hipStream_t stream, const char* who) {
     const int B = p.B, P = p.P, Dp = p.Dp, T = p.T;
     const int W = (P + 31) / 32;
     const size_t need = p.dtok ? (((size_t)B * T * W * sizeof(uint32_t) + 255) & ~(size_t)255) : 0;
     PPF_CHECK_ARG(p.dtok == nullptr || (workspace != nullptr && workspace_bytes >= (size_t)B * T * W * sizeof(uint32_t)), PPF_ERR_ARG,
-                  "ppf_proto_bwd: needs a ZEROED workspace of B*T*ceil(P/32)*4 = %zu bytes", (size_t)B * T * W * sizeof(uint32_t));
+                  "%s: needs a ZEROED workspace of B*T*ceil(P/32)*4 = %zu bytes", who, (size_t)B * T * W * sizeof(uint32_t));
     // prototype gradients: the tiled form when there is no dense g_full and the caller's workspace has room for its partial sums
     ProtoTiled tg = (p.dprotos && !p.g_full && (!p.g_max || p.argmax)) ? proto_tiled_geometry(B, T, P, Dp, p.stride_b, p.t0) : ProtoTiled{};
     if (tg.ok && p.g_rows && p.ppc > PT_NW) tg.ok = false;
     if (tg.ok && !(workspace && workspace_bytes >= need + tg.ws_bytes && ((uintptr_t)p.tok & 15) == 0)) tg.ok = false;
     const int nj = (Dp + 63) / 64;
-    const char* who = "ppf_proto_bwd";
     auto run = [&](auto njc) -> int {                 // every launch is checked on its own: the first failure is the one reported
         constexpr int NJ = decltype(njc)::value;
         int rc = 0;
@@ -1105,7 +1106,7 @@ int ppf_proto_bwd(const float* tok, int64_t stride_b, int t0, int T, const float
     p.tok = tok; p.stride_b = stride_b; p.t0 = t0; p.T = T; p.protos = protos; p.B = B; p.P = P; p.Dp = Dp; p.act_kind = act_kind; p.eps = eps;
     p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_full = g_full; p.g_rows = nullptr; p.row_label = nullptr; p.ppc = 0; p.g_max = g_max;
     p.argmax = (T == 1) ? nullptr : argmax; p.dtok = dtok; p.dstride_b = dstride_b; p.dprotos = dprotos;
-    return proto_bwd_launch(p, workspace, workspace_bytes, stream);
+    return proto_bwd_launch(p, workspace, workspace_bytes, stream, "ppf_proto_bwd");
 }
 
 // The same backward with the activation-map gradient in the block form the PPC loss produces (protopformer.py:259-288: only the ppc
@@ -1121,7 +1122,7 @@ int ppf_proto_bwd_rows(const float* tok, int64_t stride_b, int t0, int T, const 
     p.tok = tok; p.stride_b = stride_b; p.t0 = t0; p.T = T; p.protos = protos; p.B = B; p.P = P; p.Dp = Dp; p.act_kind = act_kind; p.eps = eps;
     p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_full = nullptr; p.g_rows = g_rows; p.row_label = (const long long*)label_i64; p.ppc = ppc; p.g_max = g_max;
     p.argmax = argmax; p.dtok = dtok; p.dstride_b = dstride_b; p.dprotos = dprotos;
-    return proto_bwd_launch(p, workspace, workspace_bytes, stream);
+    return proto_bwd_launch(p, workspace, workspace_bytes, stream, "ppf_proto_bwd_rows");
 }
 
 // Bytes of workspace ppf_proto_bwd wants: the zeroed bitmap (when token gradients are asked for) followed by the scratch of the tiled
