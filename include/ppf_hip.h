@@ -162,6 +162,11 @@ int ppf_layernorm_bwd(const void* dy, const float* x, const int* row_map, const 
 int ppf_layernorm_bwd_blocks(int rows);
 int ppf_layernorm_bwd_reduce(const float* partial, int rows, int D, float* dw, float* db, float* dbias_next, float* dcolscale,
                              ppf_stream_t stream);
+/* Test hook (tests/test_gpu_ln_bwd_lean.py): form of the half-wave-per-row backward kernel behind ppf_layernorm_bwd.  path = 0 the dispatch
+ * as shipped, 1 the parent form (111 VGPRs at D = 384) for every width, 2 the register-lean form (at most 96 VGPRs: two waves per SIMD beside
+ * a resident weight-gradient workgroup) wherever it is instantiated: D = 384 without LayerScale operands; every other case keeps the parent
+ * form.  Both forms produce the same bits. */
+int ppf_layernorm_test_bwd_path(int path);
 
 /* ---- attention with the policy softmax (deit:29-60; class attention cait:50-90 with self_keep = 0) -------------
  * qkv bf16 [B*N][3D] packed q|k|v, head h at columns h*hd.  policy [B][N] in {0,1} or NULL.

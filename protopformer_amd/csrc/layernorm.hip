@@ -162,15 +162,164 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdParams p) {
     if (p.cast_out) { flush(anb, p.dbias_next, 2); if (p.branch) flush(acs, p.dcolscale, 3); }
 }
 
+// Workgroup reduction of one set of ln_bwd2_kernel column accumulators for its lean form: the two rows of each wave, then the four waves in
+// order through LDS, into this workgroup's row of `partial` (or by one atomic per column without it).  The same operations in the same order
+// as the `flush` of the parent form, which keeps its own copy: called from here instead, the parent form no longer compiles to the code it had.
+template <int V, int NJ>
+__device__ __forceinline__ void ln_bwd2_flush(const LnBwdParams& p, float (&red)[WAVES][NJ * V * 32], float (&a)[NJ][V], float* dst, int which,
+                                              int wave, int l32, int half) {
+    if (!dst) return;
+    float* part = p.partial ? p.partial + ((size_t)blockIdx.x * 4 + which) * p.D : nullptr;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float v = a[j][e] + __shfl_xor(a[j][e], 32, 64);       // the two rows a wave works on
+            if (half == 0) red[wave][(j * 32 + l32) * V + e] = v;
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < NJ * V * 32; i += 256) {
+        float s = 0.f;
+#pragma unroll
+        for (int w_ = 0; w_ < WAVES; ++w_) s += red[w_][i];
+        const int j = i / (32 * V), rem = i % (32 * V);
+        if (part) part[32 * V * j + rem] = s;                            // column = V*l32 + e + 32*V*j
+        else unsafeAtomicAdd(dst + 32 * V * j + rem, s);
+    }
+}
+
+// A value the optimiser has to take as new: what is computed from it after this point is computed again, not kept from before.
+#define PPF_LN_FORGET(v) asm volatile("" : "+v"(v))
+
+// The register-lean body of ln_bwd2_kernel<4, NJ, false, true> (described there).
+template <int NJ>
+__device__ __forceinline__ void ln_bwd2_lean(const LnBwdParams& p, float (&red)[WAVES][NJ * 128], int wave, int l32, int half) {
+#pragma clang fp contract(off)                                            // every fused multiply-add below is written as one
+    const int D = p.D;
+    float adw[NJ][4], adb[NJ][4], anb[NJ][4];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) adw[j][e] = adb[j][e] = anb[j][e] = 0.f;
+    float* wl = &red[0][0];                                               // the weights, column c at wl[c]; red is not written before the flush
+    if (p.dy)
+        for (int i = threadIdx.x; i < NJ * 128; i += 256) wl[i] = p.w[i];
+    __syncthreads();
+    const float invD = 1.0f / (float)D;
+    for (int r0 = (blockIdx.x * WAVES + wave) * 2; r0 < p.rows; r0 += gridDim.x * WAVES * 2) {
+        const int r = r0 + half;
+        const bool ok = r < p.rows;
+        const size_t src = ok ? (p.row_map ? (size_t)p.row_map[r] : (size_t)r) : 0;
+        // element offsets of this lane's first column in the streams indexed by the source row and in dy: with the lane's part folded in and
+        // forgotten, each address is a kernel argument plus one of these, and no per-lane address of any stream lives across the loop
+        size_t es = src * D + 4 * l32, er = (size_t)r * D + 4 * l32;
+        PPF_LN_FORGET(es); PPF_LN_FORGET(er);
+        int wo = 4 * l32;                                                 // this lane's four columns of a 128-column group
+        PPF_LN_FORGET(wo);                                                // keeps the LDS reads of the weights inside the loop
+        float dx[NJ][4];                                                  // dres_in, then dx
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (p.dres_in && ok) {
+                const float4 t = *reinterpret_cast<const float4*>(p.dres_in + es + 128 * j);
+                dx[j][0] = t.x; dx[j][1] = t.y; dx[j][2] = t.z; dx[j][3] = t.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dx[j][e] = 0.f;
+            }
+        }
+        if (p.dy) {
+            const float mu = ok ? p.mean[r] : 0.f, rs = ok ? p.rstd[r] : 0.f;
+            float xh[NJ][4];                                              // x, then xhat
+            uint32_t dyp[NJ][2];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (ok) {
+                    const float4 t = *reinterpret_cast<const float4*>(p.x + es + 128 * j);
+                    xh[j][0] = t.x; xh[j][1] = t.y; xh[j][2] = t.z; xh[j][3] = t.w;
+                    const uint2 u = *reinterpret_cast<const uint2*>(p.dy + er + 128 * j);
+                    dyp[j][0] = u.x; dyp[j][1] = u.y;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) xh[j][e] = 0.f;
+                    dyp[j][0] = dyp[j][1] = 0u;
+                }
+            }
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const float4 w4 = *reinterpret_cast<const float4*>(wl + wo + 128 * j);
+                const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+                const float2 a = unpack_bf16x2(dyp[j][0]), b = unpack_bf16x2(dyp[j][1]);
+                const float dyv[4] = {a.x, a.y, b.x, b.y};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    xh[j][e] = (xh[j][e] - mu) * rs;
+                    const float g = dyv[e] * wv[e];
+                    s1 = s1 + g;
+                    const float gx = g * xh[j][e];                       // product and sum rounded separately, as the parent form compiles
+                    s2 = s2 + gx;
+                    adw[j][e] = __builtin_fmaf(dyv[e], xh[j][e], adw[j][e]);
+                    adb[j][e] = adb[j][e] + dyv[e];
+                }
+            }
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+            const float c1 = s1 * invD, c2 = s2 * invD;
+            __builtin_amdgcn_sched_barrier(0);                            // the first phase has retired its temporaries before the second starts
+            PPF_LN_FORGET(wo);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                PPF_LN_FORGET(dyp[j][0]); PPF_LN_FORGET(dyp[j][1]);      // dy is unpacked again, not kept unpacked across the row reduction
+                const float4 w4 = *reinterpret_cast<const float4*>(wl + wo + 128 * j);
+                const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+                const float2 a = unpack_bf16x2(dyp[j][0]), b = unpack_bf16x2(dyp[j][1]);
+                const float dyv[4] = {a.x, a.y, b.x, b.y};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)                               // dx += rs * (g - c1 - xhat * c2), g - c1 in one fma as in the parent form
+                    dx[j][e] = __builtin_fmaf(rs, __builtin_fmaf(-c2, xh[j][e], __builtin_fmaf(dyv[e], wv[e], -c1)), dx[j][e]);
+            }
+        }
+        if (!ok) continue;
+        const float rsc = p.rowscale ? p.rowscale[(uint32_t)src / (uint32_t)p.rows_per_group] : 1.0f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (p.dx_out) *reinterpret_cast<float4*>(p.dx_out + es + 128 * j) = make_float4(dx[j][0], dx[j][1], dx[j][2], dx[j][3]);
+            if (p.cast_out) {
+                uint32_t pk[2];
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    pk[e / 2] = pack_bf16x2(dx[j][e] * rsc, dx[j][e + 1] * rsc);
+                    const float2 rt = unpack_bf16x2(pk[e / 2]);
+                    anb[j][e] += rt.x; anb[j][e + 1] += rt.y;
+                }
+                *reinterpret_cast<uint2*>(p.cast_out + es + 128 * j) = make_uint2(pk[0], pk[1]);
+            }
+        }
+    }
+    if (p.dy) { ln_bwd2_flush<4, NJ>(p, red, adw, p.dw, 0, wave, l32, half); ln_bwd2_flush<4, NJ>(p, red, adb, p.db, 1, wave, l32, half); }
+    if (p.cast_out) ln_bwd2_flush<4, NJ>(p, red, anb, p.dbias_next, 2, wave, l32, half);
+}
+
 // Bandwidth-oriented variant for D = 32*V*NJ (V = 4: D % 128 == 0, V = 2: D % 64 == 0): half a wavefront per row, so a
 // wave streams two independent rows at a time with 16-/8-byte accesses (twice the loads in flight of the generic kernel).
 // (round 6: non-temporal loads / stores of any of the five streams change nothing, stand-alone or in the step: profiles/r6_ln_bwd_nt.txt)
 // LS = false: no LayerScale operands (colscale / branch / dcolscale all null, the DeiT case): 24 fewer live registers -> 4 waves/SIMD.
-template <int V, int NJ, bool LS>
-__global__ __launch_bounds__(256) void ln_bwd2_kernel(const LnBwdParams p) {
+//
+// LEAN = true (V = 4, no LayerScale): the same arithmetic, operation for operation, in at most 96 VGPRs, so that two waves per SIMD fit in the
+// 192 registers a resident wgrad8_kernel workgroup leaves (the parent form's 111 allow one).  What differs is where values live: the LayerNorm
+// weights sit in LDS (in `red`, which is idle until the flush) and are read at each use; dy stays packed and is unpacked again after the row
+// reduction; xhat overwrites x and dx overwrites the dres_in registers; g = dy * w is not kept (the parent form, as compiled, forms
+// dy * w - c1 in one fma as well).  The lean body is compiled without floating-point contraction and writes a fused multiply-add exactly
+// where the compiler contracts the parent form (adw, and the three of dx), which keeps the two forms equal bit for bit
+// (tests/test_gpu_ln_bwd_lean.py).
+template <int V, int NJ, bool LS, bool LEAN>
+__global__ __launch_bounds__(256, LEAN ? 5 : 1) void ln_bwd2_kernel(const LnBwdParams p) {
     __shared__ float red[WAVES][NJ * V * 32];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l32 = lane & 31, half = lane >> 5;
     const int D = p.D;
+    static_assert(!LEAN || (V == 4 && !LS), "the lean form has 16-byte lanes and no LayerScale operands");
+    if constexpr (LEAN) { ln_bwd2_lean<NJ>(p, red, wave, l32, half); return; }
     float wv[NJ][V], cs[NJ][V], adw[NJ][V], adb[NJ][V], anb[NJ][V], acs[NJ][V];
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
@@ -332,6 +481,15 @@ int ln_bwd_grid(int rows) {
     return g < cap ? g : cap;
 }
 
+// The register-lean ln_bwd2_kernel exists for D = 384 (V = 4, NJ = 3) without LayerScale.  At D = 128 and 256 the parent form is within 96
+// VGPRs as it stands (63 and 83); D = 512 carries 48 accumulators and does not fit.
+constexpr int LN_LEAN_NJ = 3;
+// Test hook (ppf_layernorm_test_bwd_path): 0 = dispatch as shipped, 1 = the parent form everywhere, 2 = the lean form wherever it exists.
+int g_bwd_path = 0;
+#ifndef PPF_LN_LEAN_DEFAULT
+#define PPF_LN_LEAN_DEFAULT 1        // what path 0 means where the lean form exists (a measurement build can flip it for a same-box A/B)
+#endif
+
 template <int I> using Int = std::integral_constant<int, I>;
 
 template <typename F>
@@ -380,8 +538,11 @@ int ppf_layernorm_bwd(const void* dy, const float* x, const int* row_map, const 
     const bool ls = colscale != nullptr || branch != nullptr || dcolscale != nullptr;
     auto ln2 = [&](auto v, auto nj) {                                      // the ln_bwd2_kernel of V values per lane and NJ of them per row, with or without LayerScale
         constexpr int V = decltype(v)::value, NJ = decltype(nj)::value;
-        if (ls) return ppf_launch<ln_bwd2_kernel<V, NJ, true>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
-        return ppf_launch<ln_bwd2_kernel<V, NJ, false>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
+        if (ls) return ppf_launch<ln_bwd2_kernel<V, NJ, true, false>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
+        if constexpr (V == 4 && NJ == LN_LEAN_NJ)                          // the register-lean form, unless the test hook forces the parent form
+            if (g_bwd_path == 2 || (g_bwd_path == 0 && PPF_LN_LEAN_DEFAULT))
+                return ppf_launch<ln_bwd2_kernel<4, NJ, false, true>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd (lean)", p);
+        return ppf_launch<ln_bwd2_kernel<V, NJ, false, false>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
     };
     if (D % 128 == 0 && D <= 512) switch (D / 128) {
         case 1: return ln2(Int<4>(), Int<1>()); case 2: return ln2(Int<4>(), Int<2>()); case 3: return ln2(Int<4>(), Int<3>()); case 4: return ln2(Int<4>(), Int<4>());
@@ -392,6 +553,15 @@ int ppf_layernorm_bwd(const void* dy, const float* x, const int* row_map, const 
     return dispatch_nj(D, [&](auto nj) {
         return ppf_launch<ln_bwd_kernel<decltype(nj)::value>>(dim3(grid), dim3(256), 0, stream, "ppf_layernorm_bwd", p);
     });
+}
+
+// Test hook: form of ln_bwd2_kernel behind ppf_layernorm_bwd.  0 = dispatch as shipped, 1 = the parent form for every width, 2 = the
+// register-lean form wherever it is instantiated (D = 384 without LayerScale; every other case keeps the parent form).  Not thread-safe;
+// never set on the product path.
+int ppf_layernorm_test_bwd_path(int path) {
+    PPF_CHECK_ARG(path >= 0 && path <= 2, PPF_ERR_ARG, "ppf_layernorm_test_bwd_path: path must be 0, 1 or 2 (got %d)", path);
+    g_bwd_path = path;
+    return 0;
 }
 
 // Rows of the partial-sum workspace for `rows` rows (workgroups + second-level slices): it holds blocks * 4 * D floats.

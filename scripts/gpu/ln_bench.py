@@ -23,3 +23,16 @@ t_nocol = timeit(lambda: ops.layernorm_bwd(dy, x, w, mean, rstd, None, None, dre
 y = torch.empty(M, D, dtype=torch.bfloat16, device=dev)
 t_fwd = timeit(lambda: ops.layernorm_fwd(x, w, w, 1e-6))
 print(f"ln_bwd full {t_full:.1f} us | without column sums {t_nocol:.1f} us | ln_fwd {t_fwd:.1f} us   (bytes bwd: {(M*D*(2+4+4+4+2))/1e6:.0f} MB)")
+# the two forms of ln_bwd2_kernel alone, alternating (test hook ppf_layernorm_test_bwd_path: 1 parent, 2 lean): python ln_bench.py [ROUNDS]
+from protopformer_amd import _lib
+full = lambda: ops.layernorm_bwd(dy, x, w, mean, rstd, dw, db, dres_in=dres, dx_out=dx, cast_out=cast, rowscale=rs, rows_per_group=197, dbias_next=dnb)
+nocol = lambda: ops.layernorm_bwd(dy, x, w, mean, rstd, None, None, dres_in=dres, dx_out=dx, cast_out=cast, rowscale=rs, rows_per_group=197)
+try:
+    for i in range(int(sys.argv[1]) if len(sys.argv) > 1 else 5):
+        t = {}
+        for path in (1, 2):
+            _lib.call("ppf_layernorm_test_bwd_path", path)
+            t[path] = (timeit(full, 50), timeit(nocol, 50))
+        print(f"round {i}: full (with the reduce launch) parent {t[1][0]:.1f} us lean {t[2][0]:.1f} us | without column sums parent {t[1][1]:.1f} us lean {t[2][1]:.1f} us")
+finally:
+    _lib.call("ppf_layernorm_test_bwd_path", 0)
