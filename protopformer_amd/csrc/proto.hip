@@ -25,8 +25,9 @@ constexpr int PB = 128;           // prototypes per workgroup (4 waves x 32)
 constexpr int BKF = 32;           // contraction chunk (floats)
 constexpr int LDP = BKF + 1;      // padded LDS pitch: conflict-free ds_read_b32 for the MFMA operands
 
-struct ProtoFwdParams {
-    const float* tok;      // token rows: row(b, i) = tok + b*stride_b + (t0 + i)*Dp      (POOL)
+// What the forward and the backward are told about the problem alike (proto_shape fills it for every entry point).
+struct ProtoShape {
+    const float* tok;      // token rows: row(b, i) = tok + b*stride_b + (t0 + i)*Dp      (POOL, and the backward)
                            //            row(g, i) = tok + (g*rows + i)*stride_b + t0*Dp  (!POOL: one token per sample)
     int64_t stride_b;
     int t0, T;             // POOL: tokens per sample
@@ -34,6 +35,12 @@ struct ProtoFwdParams {
     int B, P, Dp;
     int act_kind;          // 0: log((d+1)/(d+eps))   1: -d
     float eps;
+};
+ProtoShape proto_shape(const float* tok, int64_t stride_b, int t0, int T, const float* protos, int B, int P, int Dp, int act_kind, float eps) {
+    return ProtoShape{tok, stride_b, t0, T, protos, B, P, Dp, act_kind, eps};
+}
+
+struct ProtoFwdParams : ProtoShape {
     float* act_max;        // [B][P]
     int* argmax;           // [B][P] (POOL only)
     float* dist_full;      // [B][P][T] or null
@@ -48,6 +55,15 @@ __device__ __forceinline__ float activation(float d, int kind, float eps) {
     return kind == 0 ? __logf((d + 1.0f) / (d + eps)) : -d;
 }
 
+// Row `row` of workgroup `grp`'s ROWS-row token tile (see ProtoShape::tok).
+template <bool POOL, int ROWS>
+__device__ __forceinline__ const float* fwd_tok_row(const ProtoFwdParams& p, int grp, int row) {
+    return POOL ? p.tok + (size_t)grp * p.stride_b + (size_t)(p.t0 + row) * p.Dp
+                : p.tok + (size_t)(grp * ROWS + row) * p.stride_b + (size_t)p.t0 * p.Dp;
+}
+// Token row of accumulator register r of tile t in half-wave hh (the 32x32 MFMA's D layout)
+__device__ __forceinline__ int acc_row(int t, int r, int hh) { return t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh; }
+
 // Everything after the contraction: distances (protopformer.py:213-216 association order), activations, max-pool + arg-max over the
 // tokens, the (B,P) outputs and the full (B,P,T) maps.  acc[t][r] = <token row, prototype of this lane>; lx2 holds |x|^2 per row.
 template <int TT, bool POOL>
@@ -61,7 +77,7 @@ __device__ __forceinline__ void proto_fwd_epilogue(const ProtoFwdParams& p, f32x
     for (int t = 0; t < TT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int row = acc_row(t, r, hh);
             const float d = fmaxf(lx2[row] + (-2.0f * acc[t][r] + p2), 0.0f);      // protopformer.py:213-216 association order
             acc[t][r] = d;
             if (POOL && row < p.T) {
@@ -83,7 +99,7 @@ __device__ __forceinline__ void proto_fwd_epilogue(const ProtoFwdParams& p, f32x
         for (int t = 0; t < TT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                const int row = acc_row(t, r, hh);
                 const int smp = grp * ROWS + row;
                 if (row < nrows && pidx < p.P) {
                     p.act_max[(size_t)smp * p.P + pidx] = activation(acc[t][r], p.act_kind, p.eps);
@@ -110,7 +126,7 @@ __device__ __forceinline__ void proto_fwd_epilogue(const ProtoFwdParams& p, f32x
                 for (int t = 0; t < TT; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                        const int row = acc_row(t, r, hh);
                         xp[(lane & 15) * (ROWS + 1) + row] = pass == 0 ? acc[t][r] : activation(acc[t][r], p.act_kind, p.eps);
                     }
             }
@@ -193,11 +209,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? 3 : 2) void proto_fwd6_kernel(const 
     const int p0 = blockIdx.x * PB, grp = blockIdx.y;
     const int nrows = POOL ? p.T : min(ROWS, p.B - grp * ROWS);
 
-    f32x16 acc[TT];
-#pragma unroll
-    for (int t = 0; t < TT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    f32x16 acc[TT] = {};
 
     // token rows: global -> registers (next chunk in flight while this one is multiplied) -> three bf16 piece images in LDS
     constexpr int NLD = ROWS * (BK6 / 4) / 256;                    // float4 per thread and chunk (ROWS is a multiple of 32)
@@ -211,8 +223,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? 3 : 2) void proto_fwd6_kernel(const 
         for (int j = 0; j < NLD; ++j) {
             const int i = tid + j * 256, row = i >> 4, c4 = i & 15;
             const int rr = min(row, nrows - 1);                    // rows past the end repeat the last one (never written out)
-            const float* src = POOL ? p.tok + (size_t)grp * p.stride_b + (size_t)(p.t0 + rr) * p.Dp
-                                    : p.tok + (size_t)(grp * ROWS + rr) * p.stride_b + (size_t)p.t0 * p.Dp;
+            const float* src = fwd_tok_row<POOL, ROWS>(p, grp, rr);
             const int kk = min(k0 + c4 * 4, p.Dp - 4);
             float4 v = *reinterpret_cast<const float4*>(src + kk);
             if (k0 + c4 * 4 >= p.Dp) v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -322,11 +333,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? PROTO_OCC : 2) void proto_fwd_kernel
     const int p0 = blockIdx.x * PB, grp = blockIdx.y;
     const int nrows = POOL ? p.T : min(ROWS, p.B - grp * ROWS);
 
-    f32x16 acc[TT];
-#pragma unroll
-    for (int t = 0; t < TT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    f32x16 acc[TT] = {};
     float x2p[TT], p2p = 0.f;
 #pragma unroll
     for (int t = 0; t < TT; ++t) x2p[t] = 0.f;
@@ -342,11 +349,7 @@ __global__ __launch_bounds__(256, TT <= 3 ? PROTO_OCC : 2) void proto_fwd_kernel
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i < (ROWS + PB) * (BKF / 4) && k0 + c4 * 4 < p.Dp) {
                 if (row < ROWS) {
-                    if (row < nrows) {
-                        const float* src = POOL ? p.tok + (size_t)grp * p.stride_b + (size_t)(p.t0 + row) * p.Dp
-                                                : p.tok + (size_t)(grp * ROWS + row) * p.stride_b + (size_t)p.t0 * p.Dp;
-                        v = *reinterpret_cast<const float4*>(src + k0 + c4 * 4);
-                    }
+                    if (row < nrows) v = *reinterpret_cast<const float4*>(fwd_tok_row<POOL, ROWS>(p, grp, row) + k0 + c4 * 4);
                 } else if (p0 + row - ROWS < p.P) {
                     v = *reinterpret_cast<const float4*>(p.protos + (size_t)(p0 + row - ROWS) * p.Dp + k0 + c4 * 4);
                 }
@@ -398,11 +401,8 @@ __global__ __launch_bounds__(256, TT <= 3 ? PROTO_OCC : 2) void proto_fwd_kernel
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-struct ProtoBwdParams {
-    const float* tok; int64_t stride_b; int t0, T;
-    const float* protos; int B, P, Dp;
-    int act_kind; float eps;
-    const float* dist_full;    // [B][P][T]: the distances (map_is_act == 0) or the ACTIVATIONS the forward wrote (map_is_act == 1)
+struct ProtoBwdParams : ProtoShape {
+    const float* dist_full;   // [B][P][T]: the distances (map_is_act == 0) or the ACTIVATIONS the forward wrote (map_is_act == 1)
     int map_is_act;
     const float* g_full;       // [B][P][T] upstream grad of act_full, or null
     const float* g_rows;       // [B][ppc][T] or null: the same gradient in block form -- sample b's rows are the prototypes
@@ -429,23 +429,94 @@ __device__ __forceinline__ float dact_from_act(float a, int kind, float eps) {
     const float em1 = expm1f(a);
     return -(em1 * em1) / ((1.0f - eps) * (em1 + 1.0f));
 }
-__device__ __forceinline__ float dact_map(const ProtoBwdParams& p, size_t o);
-
-// G[b,p,t] = dL/dd
-__device__ __forceinline__ float grad_d(const ProtoBwdParams& p, int b, int pi, int t, int amax, float gmax) {
-    const size_t o = ((size_t)b * p.P + pi) * p.T + t;
-    float g = p.g_full ? p.g_full[o] : 0.f;
-    if (p.g_rows) {
-        const int k = pi - (int)p.row_label[b] * p.ppc;
-        if (k >= 0 && k < p.ppc) g += p.g_rows[((size_t)b * p.ppc + k) * p.T + t];
-    }
-    if (t == amax) g += gmax;
-    if (g == 0.f) return 0.f;
-    return g * dact_map(p, o);
-}
 __device__ __forceinline__ float dact_map(const ProtoBwdParams& p, size_t o) {
     const float v = p.dist_full[o];
     return p.map_is_act ? dact_from_act(v, p.act_kind, p.eps) : dact_dd(v, p.act_kind, p.eps);
+}
+
+// Sample b's own class block: its first prototype, and the block row (row of g_rows) of prototype pi -- -1 when pi lies outside the
+// block or there is no g_rows.
+__device__ __forceinline__ int own_first(const ProtoBwdParams& p, int b) { return (int)p.row_label[b] * p.ppc; }
+__device__ __forceinline__ int own_row(const ProtoBwdParams& p, int b, int pi) {
+    if (!p.g_rows) return -1;
+    const int k = pi - own_first(p, b);
+    return (k >= 0 && k < p.ppc) ? k : -1;
+}
+// Upstream gradient of act[b, pi, t]: the sources named in SRC that are given, added in the order g_full, g_rows, g_max.
+//   k: own_row(b, pi);  am, gm: arg-max token and g_max of (b, pi) -- gm is looked at only where t == am, a caller may load it only there
+enum { G_FULL = 1, G_ROWS = 2, G_MAX = 4, G_ALL = 7 };
+template <int SRC>
+__device__ __forceinline__ float upstream(const ProtoBwdParams& p, int b, int pi, int t, int k, int am, float gm) {
+    float g = 0.f;
+    if ((SRC & G_FULL) && p.g_full) g = p.g_full[((size_t)b * p.P + pi) * p.T + t];
+    if ((SRC & G_ROWS) && k >= 0) g += p.g_rows[((size_t)b * p.ppc + k) * p.T + t];
+    if ((SRC & G_MAX) && t == am) g += gm;
+    return g;
+}
+// G = dL/dd at element o of the map = g * d act / d dist; the map is read only where g != 0
+__device__ __forceinline__ float coeff(const ProtoBwdParams& p, size_t o, float g) { return g != 0.f ? g * dact_map(p, o) : 0.f; }
+
+// (row, t) with f = row * T + t from the float reciprocal invT = 1 / T: exact for f < 2^20
+__device__ __forceinline__ void split_flat(int f, int T, float invT, int& row, int& t) {
+    row = __float2int_rz(((float)f + 0.5f) * invT);
+    t = f - row * T;
+    if (t < 0) { --row; t += T; } else if (t >= T) { ++row; t -= T; }
+}
+
+// ---- a row of Dp <= 64 NJ floats held by one wave: lane holds element lane + 64 j in register j, zero past Dp
+template <int NJ>
+__device__ __forceinline__ void row_zero(float (&r)[NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) r[j] = 0.f;
+}
+template <int NJ>
+__device__ __forceinline__ void row_load(float (&r)[NJ], const float* row, int Dp, int lane) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; r[j] = d < Dp ? row[d] : 0.f; }
+}
+template <int NJ>
+__device__ __forceinline__ void row_store(float* row, const float (&r)[NJ], int Dp, int lane) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; if (d < Dp) row[d] = r[j]; }
+}
+// acc += g * (own - v)
+template <int NJ>
+__device__ __forceinline__ void row_axmy(float (&acc)[NJ], float g, const float (&own)[NJ], const float (&v)[NJ]) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] += g * (own[j] - v[j]);
+}
+// The gather of both gradients: n <= 64 list entries, one per lane (coefficient g2; row_of(l) = the row lane l names, broadcast by the
+// caller's own shuffle), four rows in flight per step: acc += g2[l] * (own - row_of(l)) for l = e .. e + 3, ascending.
+template <int NJ, class RowOf>
+__device__ __forceinline__ void gather4_step(float (&acc)[NJ], const float (&own)[NJ], float g2, int e, int n, int Dp, int lane, RowOf&& row_of) {
+    float gs[4], v[4][NJ];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int src = min(e + u, n - 1);
+        gs[u] = (e + u < n) ? __shfl(g2, src, 64) : 0.f;
+        row_load(v[u], row_of(src), Dp, lane);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) row_axmy(acc, gs[u], own, v[u]);
+}
+// ... and the whole list.  (proto_bwd_tokens_kernel writes this loop out around gather4_step and proto_bwd_protos_kernel calls it here: which
+// of the multiply-adds the compiler fuses depends on where the loop stands, and either kernel written the other way moves its last bit.)
+template <int NJ, class RowOf>
+__device__ __forceinline__ void gather4(float (&acc)[NJ], const float (&own)[NJ], float g2, int n, int Dp, int lane, RowOf&& row_of) {
+    for (int e = 0; e < n; e += 4) gather4_step(acc, own, g2, e, n, Dp, lane, row_of);
+}
+// The workgroup's NW per-wave partial rows -> one row, added in wave order through LDS (part: [NW][NJ * 64] floats): out = or += the sum.
+template <int NJ, int NW, bool ADD>
+__device__ __forceinline__ void reduce_rows(float* part, const float (&acc)[NJ], float* out, int Dp, int wave, int lane) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) part[wave * (NJ * 64) + j * 64 + lane] = acc[j];
+    __syncthreads();
+    for (int d = threadIdx.x; d < min(Dp, NJ * 64); d += 64 * NW) {
+        float s = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) s += part[w * (NJ * 64) + d];
+        if (ADD) out[d] += s; else out[d] = s;            // single writer per element
+    }
 }
 
 // Token gradients in two fully parallel passes (deterministic, no float atomics):
@@ -473,9 +544,8 @@ __global__ __launch_bounds__(256) void proto_bwd_mark_kernel(const ProtoBwdParam
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (v[e] != 0.f) {
-                        int pl = (int)(((float)(f + e) + 0.5f) * invT);                  // exact for f < 2^20
-                        int t = f + e - pl * T;
-                        if (t < 0) { --pl; t += T; } else if (t >= T) { ++pl; t -= T; }
+                        int pl, t;
+                        split_flat(f + e, T, invT, pl, t);
                         atomicOr(&bm[((size_t)b * T + t) * W + w], 1u << pl);
                     }
             }
@@ -484,14 +554,11 @@ __global__ __launch_bounds__(256) void proto_bwd_mark_kernel(const ProtoBwdParam
                 if (src[f] != 0.f) { const int pl = f / T, t = f - pl * T; atomicOr(&bm[((size_t)b * T + t) * W + w], 1u << pl); }
         }
     }
-    if (p.g_rows) {
-        const int k0 = 32 * w - (int)p.row_label[b] * p.ppc;                    // block row of this word's first prototype
-        if (k0 + np > 0 && k0 < p.ppc)
+    if (p.g_rows)
         for (int i = threadIdx.x; i < np * T; i += 256) {
-            const int pl = i / T, t = i - pl * T, k = k0 + pl;
-            if (k >= 0 && k < p.ppc && p.g_rows[((size_t)b * p.ppc + k) * T + t] != 0.f) atomicOr(&bm[((size_t)b * T + t) * W + w], 1u << pl);
+            const int pl = i / T, t = i - pl * T, k = own_row(p, b, 32 * w + pl);
+            if (k >= 0 && p.g_rows[((size_t)b * p.ppc + k) * T + t] != 0.f) atomicOr(&bm[((size_t)b * T + t) * W + w], 1u << pl);
         }
-    }
     if (p.g_max && threadIdx.x < np) {
         const size_t bp = (size_t)b * p.P + 32 * w + threadIdx.x;
         if (p.g_max[bp] != 0.f) {
@@ -510,7 +577,7 @@ __global__ __launch_bounds__(256) void proto_bwd_mark_sparse_kernel(const ProtoB
             if (p.g_max[bp] != 0.f) atomicOr(&bm[((size_t)b * T + (p.argmax ? p.argmax[bp] : 0)) * W + (pi >> 5)], 1u << (pi & 31));
         }
     if (p.g_rows) {
-        const int p0 = (int)p.row_label[b] * p.ppc;
+        const int p0 = own_first(p, b);
         for (int i = threadIdx.x; i < p.ppc * T; i += 256) {
             const int k = i / T, t = i - k * T, pi = p0 + k;
             if (pi >= 0 && pi < p.P && p.g_rows[((size_t)b * p.ppc + k) * T + t] != 0.f) atomicOr(&bm[((size_t)b * T + t) * W + (pi >> 5)], 1u << (pi & 31));
@@ -530,8 +597,8 @@ __global__ __launch_bounds__(64 * NW) void proto_bwd_tokens_kernel(const ProtoBw
     const int b = row / p.T, t = row % p.T;
     const float* xrow = p.tok + (size_t)b * p.stride_b + (size_t)(p.t0 + t) * p.Dp;
     float x[NJ], acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; x[j] = d < p.Dp ? xrow[d] : 0.f; acc[j] = 0.f; }
+    row_load(x, xrow, p.Dp, lane);
+    row_zero(acc);
     const int wpw = (W + NW - 1) / NW;                     // words per wave (<= 64)
     const int w_begin = wave * wpw, w_end = min(W, w_begin + wpw);
     // (1) ascending list of this wave's prototypes with a non-zero gradient for this token
@@ -554,45 +621,14 @@ __global__ __launch_bounds__(64 * NW) void proto_bwd_tokens_kernel(const ProtoBw
             pi = w_begin * 32 + plist[wave][base + lane];
             const int am = p.argmax ? p.argmax[(size_t)b * p.P + pi] : 0;
             const float gm = p.g_max ? p.g_max[(size_t)b * p.P + pi] : 0.f;
-            g2 = 2.0f * grad_d(p, b, pi, t, am, gm);
+            g2 = 2.0f * coeff(p, ((size_t)b * p.P + pi) * p.T + t, upstream<G_ALL>(p, b, pi, t, own_row(p, b, pi), am, gm));
         }
-        for (int e = 0; e < n; e += 4) {
-            float gs[4]; const float* pr[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int src = min(e + u, n - 1);
-                gs[u] = (e + u < n) ? __shfl(g2, src, 64) : 0.f;
-                pr[u] = p.protos + (size_t)__shfl(pi, src, 64) * p.Dp;
-            }
-            float v[4][NJ];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; v[u][j] = d < p.Dp ? pr[u][d] : 0.f; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[j] += gs[u] * (x[j] - v[u][j]);
-        }
+        for (int e = 0; e < n; e += 4)
+            gather4_step(acc, x, g2, e, n, p.Dp, lane, [&](int src) { return p.protos + (size_t)__shfl(pi, src, 64) * p.Dp; });
     }
     float* drow = p.dtok + (size_t)b * p.dstride_b + (size_t)(p.t0 + t) * p.Dp;
-    if constexpr (NW == 1) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; if (d < p.Dp) drow[d] = acc[j]; }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) part[wave][j * 64 + lane] = acc[j];
-    __syncthreads();
-    for (int i = threadIdx.x; i < NJ * 64; i += 64 * NW) {
-        const int d = (i & 63) + 64 * (i >> 6);
-        if (d < p.Dp) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) sacc += part[w][i];
-            drow[d] = sacc;
-        }
-    }
+    if constexpr (NW == 1) row_store(drow, acc, p.Dp, lane);
+    else reduce_rows<NJ, NW, false>(&part[0][0], acc, drow, p.Dp, wave, lane);
 }
 
 // Prototype gradients: one 16-wave workgroup per prototype, two passes over blocks of 16 x 1024 (sample, token) elements.
@@ -615,11 +651,10 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_kernel(const ProtoBwdPa
     const int pi = blockIdx.x;
     const float* prow = p.protos + (size_t)pi * p.Dp;
     float pv[NJ], acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; pv[j] = d < p.Dp ? prow[d] : 0.f; acc[j] = 0.f; }
+    row_load(pv, prow, p.Dp, lane);
+    row_zero(acc);
     const int E = p.B * p.T;
     const float invT = 1.0f / (float)p.T;
-    const size_t PT = (size_t)p.P * p.T;
     for (int blk0 = 0; blk0 < E; blk0 += PB_NW * PB_CHUNK) {
         // ---- scan + compact
         const int w0 = blk0 + wave * PB_CHUNK;
@@ -629,25 +664,17 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_kernel(const ProtoBwdPa
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int e = w0 + s0 + u * 64 + lane;
-                int b = __float2int_rz(((float)e + 0.5f) * invT);
-                int t = e - b * p.T;
-                if (t < 0) { --b; t += p.T; } else if (t >= p.T) { ++b; t -= p.T; }
-                bb[u] = b; tt[u] = t;
+                split_flat(e, p.T, invT, bb[u], tt[u]);
                 g[u] = 0.f;
                 if (e < E) {
-                    const size_t bp = (size_t)b * p.P + pi;
-                    if (p.g_full) g[u] = p.g_full[bp * p.T + t];
-                    if (p.g_rows) {
-                        const int k = pi - (int)p.row_label[b] * p.ppc;
-                        if (k >= 0 && k < p.ppc) g[u] += p.g_rows[((size_t)b * p.ppc + k) * p.T + t];
-                    }
-                    if (p.g_max) { const int am = p.argmax ? p.argmax[bp] : 0; if (t == am) g[u] += p.g_max[bp]; }
+                    const size_t bp = (size_t)bb[u] * p.P + pi;
+                    const int am = p.g_max ? (p.argmax ? p.argmax[bp] : 0) : -1;
+                    g[u] = upstream<G_ALL>(p, bb[u], pi, tt[u], own_row(p, bb[u], pi), am, tt[u] == am ? p.g_max[bp] : 0.f);
                 }
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                float G = 0.f;
-                if (g[u] != 0.f) G = g[u] * dact_map(p, (size_t)bb[u] * PT + (size_t)pi * p.T + tt[u]);
+                const float G = coeff(p, ((size_t)bb[u] * p.P + pi) * p.T + tt[u], g[u]);
                 const unsigned long long m = __ballot(G != 0.f);
                 if (G != 0.f) {
                     const int pos = n + __popcll(m & ((1ull << lane) - 1ull));
@@ -674,46 +701,18 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_kernel(const ProtoBwdPa
                 for (int w = 1; w < PB_NW; ++w) sw += (k >= cnt[w]) ? 1 : 0;
                 const int li = k - cnt[sw];
                 g2 = 2.0f * gl[sw * PB_CHUNK + li];
-                const int e = blk0 + sw * PB_CHUNK + il[sw * PB_CHUNK + li];
-                int b = __float2int_rz(((float)e + 0.5f) * invT);
-                int t = e - b * p.T;
-                if (t < 0) { --b; t += p.T; } else if (t >= p.T) { ++b; t -= p.T; }
+                int b, t;
+                split_flat(blk0 + sw * PB_CHUNK + il[sw * PB_CHUNK + li], p.T, invT, b, t);
                 roff = (long long)b * p.stride_b + (long long)(p.t0 + t) * p.Dp;
             }
-            for (int e4 = 0; e4 < nn; e4 += 4) {
-                float gs[4]; const float* xr[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int src = min(e4 + u, nn - 1);
-                    gs[u] = (e4 + u < nn) ? __shfl(g2, src, 64) : 0.f;
-                    const int lo = __shfl((int)(roff & 0xffffffffll), src, 64), hi = __shfl((int)(roff >> 32), src, 64);
-                    xr[u] = p.tok + (((long long)hi << 32) | (unsigned int)lo);
-                }
-                float v[4][NJ];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; v[u][j] = d < p.Dp ? xr[u][d] : 0.f; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) acc[j] += gs[u] * (pv[j] - v[u][j]);
-            }
+            gather4(acc, pv, g2, nn, p.Dp, lane, [&](int src) {
+                const int lo = __shfl((int)(roff & 0xffffffffll), src, 64), hi = __shfl((int)(roff >> 32), src, 64);
+                return p.tok + (((long long)hi << 32) | (unsigned int)lo);
+            });
         }
         __syncthreads();                                     // lists are rewritten by the next block
     }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) red[wave * (NJ * 64) + j * 64 + lane] = acc[j];
-    __syncthreads();
-    for (int i = threadIdx.x; i < NJ * 64; i += 1024) {
-        const int d = (i & 63) + 64 * (i >> 6);
-        if (d < p.Dp) {
-            float s = 0.f;
-#pragma unroll
-            for (int w = 0; w < PB_NW; ++w) s += red[w * (NJ * 64) + i];
-            p.dprotos[(size_t)pi * p.Dp + d] += s;           // single writer per (prototype, d)
-        }
-    }
+    reduce_rows<NJ, PB_NW, true>(red, acc, p.dprotos + (size_t)pi * p.Dp, p.Dp, wave, lane);
 }
 
 // ---- prototype gradients, tiled form (round 4).  The per-prototype kernel above gathers one 1.5 KiB token row per non-zero dL/dd
@@ -731,15 +730,31 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_kernel(const ProtoBwdPa
 typedef __attribute__((address_space(3))) void pt_lds_void;
 typedef const __attribute__((address_space(1))) void pt_gbl_void;
 constexpr int PT_NW = 16;
-// LDS-DMA copy of rows [r0, r0 + rows) of sample b's token block into image `dst` (1 KiB per wave instruction).
-__device__ __forceinline__ void pt_issue_chunk(const ProtoBwdParams& p, int b, int r0, int rows, unsigned char* dst, int wave, int lane) {
-    const int bytes = rows * p.Dp * 4;
-    const unsigned char* src = reinterpret_cast<const unsigned char*>(p.tok + (size_t)b * p.stride_b + (size_t)(p.t0 + r0) * p.Dp);
-    for (int i = wave; i * 1024 < bytes; i += PT_NW) {
-        const int off = min(i * 1024 + lane * 16, bytes - 16);                 // the last wave-row re-reads the final 16 bytes
-        __builtin_amdgcn_global_load_lds((pt_gbl_void*)(src + off), (pt_lds_void*)(dst + i * 1024), 16, 0, 0);
+// A sample's token block goes through LDS in chunks of R rows (chunk c = rows [c R, min(T, c R + R))), two images of chunk_pad bytes.
+struct PtStage {
+    const ProtoBwdParams& p;
+    unsigned char* smem;
+    int R, chunk_pad, wave, lane;
+    __device__ __forceinline__ int rows(int c) const { return min(R, p.T - c * R); }
+    // LDS-DMA copy of chunk c of sample b into image `img` (1 KiB per wave instruction).
+    __device__ __forceinline__ void issue(int b, int c, int img) const {
+        const int bytes = rows(c) * p.Dp * 4;
+        const unsigned char* src = reinterpret_cast<const unsigned char*>(p.tok + (size_t)b * p.stride_b + (size_t)(p.t0 + c * R) * p.Dp);
+        unsigned char* dst = smem + img * chunk_pad;
+        for (int i = wave; i * 1024 < bytes; i += PT_NW) {
+            const int off = min(i * 1024 + lane * 16, bytes - 16);             // the last wave-row re-reads the final 16 bytes
+            __builtin_amdgcn_global_load_lds((pt_gbl_void*)(src + off), (pt_lds_void*)(dst + i * 1024), 16, 0, 0);
+        }
     }
-}
+    // Step s of the walk: wait for its chunk (issued one step earlier), start the next one -- chunk nc of sample nb, if `more` -- and
+    // return the image of step s.
+    __device__ __forceinline__ const float* step(int s, bool more, int nb, int nc) const {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // this wave's share of chunk s has landed ...
+        __syncthreads();                                                       // ... everyone's has, and image (s+1)&1 is no longer read
+        if (more) issue(nb, nc, (s + 1) & 1);
+        return reinterpret_cast<const float*>(smem + (s & 1) * chunk_pad);
+    }
+};
 template <int NJ, int SLOTS>
 __global__ __launch_bounds__(1024) void proto_bwd_protos_tiled_kernel(const ProtoBwdParams p, float* __restrict__ part, float* __restrict__ psum,
                                                                        int pt, int nsg, int spg, int R, int nchunks, int chunk_pad) {
@@ -757,49 +772,41 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_tiled_kernel(const Prot
     const int nvalid = min(SLOTS, p.P - pw0);                              // <= 0: this wave only helps with the copies
     const int b0 = grp * spg, b1 = min(p.B, b0 + spg);
     const int T = p.T, Dp = p.Dp;
+    const PtStage stage{p, pt_smem, R, chunk_pad, wave, lane};
     float acc[SLOTS][NJ];
 #pragma unroll
-    for (int s = 0; s < SLOTS; ++s)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[s][j] = 0.f;
+    for (int s = 0; s < SLOTS; ++s) row_zero(acc[s]);
     float sg = 0.f;                                                        // lane s < SLOTS: sum of G for prototype pw0 + s
     const int nsteps = (b1 - b0) * nchunks;
-    if (nsteps > 0) pt_issue_chunk(p, b0, 0, min(R, T), pt_smem, wave, lane);
+    if (nsteps > 0) stage.issue(b0, 0, 0);
     int am = 0; float G = 0.f;
     for (int s = 0; s < nsteps; ++s) {
         const int bi = s / nchunks, c = s - bi * nchunks, b = b0 + bi;
-        const int r0 = c * R, rows = min(R, T - r0);
         if (c == 0) {                                                      // new sample: coefficients of this wave's prototypes
             am = 0; G = 0.f;
             if (lane < nvalid) {
                 const int pi = pw0 + lane;
                 const size_t bp = (size_t)b * p.P + pi;
                 const float gm = p.g_max[bp];
-                bool mine = gm != 0.f;
-                if (p.g_rows) { const int k = pi - (int)p.row_label[b] * p.ppc; mine = mine && !(k >= 0 && k < p.ppc); }
-                if (mine) {
+                if (gm != 0.f && own_row(p, b, pi) < 0) {                  // (own-class pairs: the rows kernel has them)
                     am = p.argmax[bp];
-                    G = gm * dact_map(p, bp * T + am);
+                    G = coeff(p, bp * T + am, upstream<G_MAX>(p, b, pi, am, -1, am, gm));
                     sg += G;
                 }
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // this wave's share of chunk s has landed ...
-        __syncthreads();                                                   // ... everyone's has, and image (s+1)&1 is no longer read
-        if (s + 1 < nsteps) {
-            const int bi2 = (s + 1) / nchunks, c2 = s + 1 - bi2 * nchunks;
-            pt_issue_chunk(p, b0 + bi2, c2 * R, min(R, T - c2 * R), pt_smem + ((s + 1) & 1) * chunk_pad, wave, lane);
-        }
-        const float* X = reinterpret_cast<const float*>(pt_smem + (s & 1) * chunk_pad);
+        const int bi2 = (s + 1) / nchunks;
+        const float* X = stage.step(s, s + 1 < nsteps, b0 + bi2, s + 1 - bi2 * nchunks);
         if (nvalid > 0) {
 #pragma unroll
             for (int sl = 0; sl < SLOTS; ++sl) {
-                const int t = __builtin_amdgcn_readlane(am, sl) - r0;
+                const int t = __builtin_amdgcn_readlane(am, sl) - c * R;
                 const float Gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(G), sl));
-                if (Gs != 0.f && t >= 0 && t < rows) {
-                    const float* xr = X + t * Dp;
+                if (Gs != 0.f && t >= 0 && t < stage.rows(c)) {
+                    float v[NJ];
+                    row_load(v, X + t * Dp, Dp, lane);
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; acc[sl][j] += Gs * (d < Dp ? xr[d] : 0.f); }
+                    for (int j = 0; j < NJ; ++j) acc[sl][j] += Gs * v[j];
                 }
             }
         }
@@ -808,10 +815,7 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_tiled_kernel(const Prot
         float* out = part + ((size_t)grp * p.P + pw0) * Dp;
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl)
-            if (sl < nvalid) {
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; if (d < Dp) out[(size_t)sl * Dp + d] = acc[sl][j]; }
-            }
+            if (sl < nvalid) row_store(out + (size_t)sl * Dp, acc[sl], Dp, lane);
         if (lane < nvalid) psum[(size_t)grp * p.P + pw0 + lane] = sg;
     }
 }
@@ -822,17 +826,19 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_rows_kernel(const Proto
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x, T = p.T, Dp = p.Dp;
-    const int pi = (int)p.row_label[b] * p.ppc + wave;
+    const int pi = own_first(p, b) + wave;
     const bool owner = wave < p.ppc && pi >= 0 && pi < p.P;
-    pt_issue_chunk(p, b, 0, min(R, T), pt_smem, wave, lane);
+    const PtStage stage{p, pt_smem, R, chunk_pad, wave, lane};
+    stage.issue(b, 0, 0);
     float pv[NJ], acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; pv[j] = (owner && d < Dp) ? p.protos[(size_t)pi * Dp + d] : 0.f; acc[j] = 0.f; }
+    row_zero(pv);
+    if (owner) row_load(pv, p.protos + (size_t)pi * Dp, Dp, lane);
+    row_zero(acc);
     const size_t bp = (size_t)b * p.P + (owner ? pi : 0);
     const int am = (owner && p.argmax && p.g_max) ? p.argmax[bp] : -1;
     const float gm = (owner && p.g_max) ? p.g_max[bp] : 0.f;
     for (int c = 0; c < nchunks; ++c) {
-        const int r0 = c * R, rows = min(R, T - r0);
+        const int r0 = c * R, rows = stage.rows(c);
         // coefficients of this chunk's tokens (R <= 128 rows starting anywhere in a 64-block: three per lane), loaded ahead of the
         // wait so they travel with the chunk
         float Gt[3] = {0.f, 0.f, 0.f};
@@ -842,33 +848,25 @@ __global__ __launch_bounds__(1024) void proto_bwd_protos_rows_kernel(const Proto
             for (int h = 0; h < 3; ++h) {
                 const int t = th0 + 64 * h + lane;
                 const bool in = t >= r0 && t < r0 + rows;
-                float g = in ? p.g_rows[((size_t)b * p.ppc + wave) * T + t] : 0.f;
-                if (in && t == am) g += gm;
-                Gt[h] = (g != 0.f) ? 2.0f * g * dact_map(p, bp * T + t) : 0.f;
+                const float g = in ? upstream<G_ROWS | G_MAX>(p, b, pi, t, wave, am, gm) : 0.f;
+                Gt[h] = coeff(p, bp * T + t, 2.0f * g);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (c + 1 < nchunks) pt_issue_chunk(p, b, (c + 1) * R, min(R, T - (c + 1) * R), pt_smem + ((c + 1) & 1) * chunk_pad, wave, lane);
+        const float* X = stage.step(c, c + 1 < nchunks, b, c + 1);
         if (!owner) continue;
-        const float* X = reinterpret_cast<const float*>(pt_smem + (c & 1) * chunk_pad);
 #pragma unroll
         for (int h = 0; h < 3; ++h) {
             unsigned long long m = __ballot(Gt[h] != 0.f);
             while (m) {
                 const int l = __builtin_ctzll(m); m &= m - 1;
                 const float Gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Gt[h]), l));
-                const float* xr = X + (th0 + 64 * h + l - r0) * Dp;
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; acc[j] += Gs * (pv[j] - (d < Dp ? xr[d] : 0.f)); }
+                float v[NJ];
+                row_load(v, X + (th0 + 64 * h + l - r0) * Dp, Dp, lane);
+                row_axmy(acc, Gs, pv, v);
             }
         }
     }
-    if (owner) {
-        float* out = rpart + ((size_t)b * p.ppc + wave) * Dp;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { const int d = lane + 64 * j; if (d < Dp) out[d] = acc[j]; }
-    }
+    if (owner) row_store(rpart + ((size_t)b * p.ppc + wave) * Dp, acc, Dp, lane);
 }
 // dprotos[p][:] += 2 ((sum_g psum[g][p]) protos[p][:] - sum_g part[g][p][:])  (sample groups ascending; skipped when part == null)
 //               +  sum over the samples b of class p / ppc, ascending, of rpart[b][p % ppc][:]   (skipped when rpart == null)
@@ -984,6 +982,9 @@ ProtoTiled proto_tiled_geometry(int B, int T, int P, int Dp, int64_t stride_b, i
     g.ok = true;
     return g;
 }
+// The token kernels' bitmap [B][T][ceil(P / 32)] words; the scratch of the tiled form starts behind it at the next multiple of 256 bytes.
+size_t proto_bitmap_bytes(int B, int T, int P) { return (size_t)B * T * ((P + 31) / 32) * sizeof(uint32_t); }
+size_t proto_bitmap_span(int B, int T, int P) { return (proto_bitmap_bytes(B, T, P) + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -1005,8 +1006,7 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
                   float* act_max, int* argmax, float* dist_full, float* act_full, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && P > 0 && Dp > 0 && Dp % 4 == 0 && T >= 1 && T <= 128, PPF_ERR_SHAPE, "ppf_proto_fwd: bad shape B=%d P=%d Dp=%d T=%d", B, P, Dp, T);
     PPF_CHECK_ARG(tok && protos && act_max && (T == 1 || argmax), PPF_ERR_ARG, "ppf_proto_fwd: null pointer");
-    ProtoFwdParams p;
-    p.tok = tok; p.stride_b = stride_b; p.t0 = t0; p.T = T; p.protos = protos; p.B = B; p.P = P; p.Dp = Dp; p.act_kind = act_kind; p.eps = eps;
+    ProtoFwdParams p{proto_shape(tok, stride_b, t0, T, protos, B, P, Dp, act_kind, eps)};       // (every other field zero)
     p.act_max = act_max; p.argmax = argmax; p.dist_full = dist_full; p.act_full = act_full;
     p.t_magic = T >= 2 ? (uint32_t)((0x100000000ull + (uint64_t)T - 1) / (uint64_t)T) : 0u;
     const int gx = (P + PB - 1) / PB;
@@ -1022,7 +1022,7 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
         float* p2 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + (size_t)gx * PB * Dp * 6);
         p.pre_p2 = p2;
         if (int rc = ppf_launch<proto_presplit_kernel>(dim3(gx * (PB / 32)), dim3(256), 0, stream, who, protos, P, Dp, reinterpret_cast<uint4*>(workspace), p2)) return rc;
-    } else { p.pre = nullptr; p.pre_p2 = nullptr; }
+    }
     if (T == 1) {
         if (x6) return ppf_launch<proto_fwd6_kernel<2, false, false>>(dim3(gx, (B + 63) / 64), dim3(256), 0, stream, who, p);
         return ppf_launch<proto_fwd_kernel<2, false>>(dim3(gx, (B + 63) / 64), dim3(256), 0, stream, who, p);
@@ -1048,9 +1048,9 @@ int ppf_proto_fwd(const float* tok, int64_t stride_b, int t0, int T, const float
 static int proto_bwd_launch(ProtoBwdParams p, void* workspace, size_t workspace_bytes, hipStream_t stream, const char* who) {
     const int B = p.B, P = p.P, Dp = p.Dp, T = p.T;
     const int W = (P + 31) / 32;
-    const size_t need = p.dtok ? (((size_t)B * T * W * sizeof(uint32_t) + 255) & ~(size_t)255) : 0;
-    PPF_CHECK_ARG(p.dtok == nullptr || (workspace != nullptr && workspace_bytes >= (size_t)B * T * W * sizeof(uint32_t)), PPF_ERR_ARG,
-                  "%s: needs a ZEROED workspace of B*T*ceil(P/32)*4 = %zu bytes", who, (size_t)B * T * W * sizeof(uint32_t));
+    const size_t need = p.dtok ? proto_bitmap_span(B, T, P) : 0;
+    PPF_CHECK_ARG(p.dtok == nullptr || (workspace != nullptr && workspace_bytes >= proto_bitmap_bytes(B, T, P)), PPF_ERR_ARG,
+                  "%s: needs a ZEROED workspace of B*T*ceil(P/32)*4 = %zu bytes", who, proto_bitmap_bytes(B, T, P));
     // prototype gradients: the tiled form when there is no dense g_full and the caller's workspace has room for its partial sums
     ProtoTiled tg = (p.dprotos && !p.g_full && (!p.g_max || p.argmax)) ? proto_tiled_geometry(B, T, P, Dp, p.stride_b, p.t0) : ProtoTiled{};
     if (tg.ok && p.g_rows && p.ppc > PT_NW) tg.ok = false;
@@ -1102,9 +1102,8 @@ int ppf_proto_bwd(const float* tok, int64_t stride_b, int t0, int T, const float
                   float* dprotos, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && P > 0 && P <= 8192 && Dp > 0 && T >= 1 && Dp <= 512, PPF_ERR_SHAPE, "ppf_proto_bwd: bad shape B=%d P=%d Dp=%d T=%d", B, P, Dp, T);
     PPF_CHECK_ARG(tok && protos && dist_full && (g_full || g_max) && (T == 1 || argmax || !g_max), PPF_ERR_ARG, "ppf_proto_bwd: null pointer");
-    ProtoBwdParams p;
-    p.tok = tok; p.stride_b = stride_b; p.t0 = t0; p.T = T; p.protos = protos; p.B = B; p.P = P; p.Dp = Dp; p.act_kind = act_kind; p.eps = eps;
-    p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_full = g_full; p.g_rows = nullptr; p.row_label = nullptr; p.ppc = 0; p.g_max = g_max;
+    ProtoBwdParams p{proto_shape(tok, stride_b, t0, T, protos, B, P, Dp, act_kind, eps)};       // (every other field zero: no g_rows)
+    p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_full = g_full; p.g_max = g_max;
     p.argmax = (T == 1) ? nullptr : argmax; p.dtok = dtok; p.dstride_b = dstride_b; p.dprotos = dprotos;
     return proto_bwd_launch(p, workspace, workspace_bytes, stream, "ppf_proto_bwd");
 }
@@ -1118,9 +1117,8 @@ int ppf_proto_bwd_rows(const float* tok, int64_t stride_b, int t0, int T, const 
     PPF_CHECK_ARG(B > 0 && P > 0 && P <= 8192 && Dp > 0 && T >= 2 && Dp <= 512 && ppc >= 1 && ppc <= P, PPF_ERR_SHAPE,
                   "ppf_proto_bwd_rows: bad shape B=%d P=%d Dp=%d T=%d ppc=%d", B, P, Dp, T, ppc);
     PPF_CHECK_ARG(tok && protos && dist_full && g_rows && label_i64 && (argmax || !g_max), PPF_ERR_ARG, "ppf_proto_bwd_rows: null pointer");
-    ProtoBwdParams p;
-    p.tok = tok; p.stride_b = stride_b; p.t0 = t0; p.T = T; p.protos = protos; p.B = B; p.P = P; p.Dp = Dp; p.act_kind = act_kind; p.eps = eps;
-    p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_full = nullptr; p.g_rows = g_rows; p.row_label = (const long long*)label_i64; p.ppc = ppc; p.g_max = g_max;
+    ProtoBwdParams p{proto_shape(tok, stride_b, t0, T, protos, B, P, Dp, act_kind, eps)};       // (every other field zero: no g_full)
+    p.dist_full = dist_full; p.map_is_act = map_is_act != 0; p.g_rows = g_rows; p.row_label = (const long long*)label_i64; p.ppc = ppc; p.g_max = g_max;
     p.argmax = argmax; p.dtok = dtok; p.dstride_b = dstride_b; p.dprotos = dprotos;
     return proto_bwd_launch(p, workspace, workspace_bytes, stream, "ppf_proto_bwd_rows");
 }
@@ -1128,7 +1126,7 @@ int ppf_proto_bwd_rows(const float* tok, int64_t stride_b, int t0, int T, const 
 // Bytes of workspace ppf_proto_bwd wants: the zeroed bitmap (when token gradients are asked for) followed by the scratch of the tiled
 // prototype-gradient form (need not be initialised; a smaller workspace selects the per-prototype gather kernel instead).
 size_t ppf_proto_bwd_workspace(int B, int T, int P, int Dp, int want_dtok, int want_dprotos) {
-    const size_t bm = want_dtok ? (((size_t)B * T * ((P + 31) / 32) * sizeof(uint32_t) + 255) & ~(size_t)255) : 0;
+    const size_t bm = want_dtok ? proto_bitmap_span(B, T, P) : 0;
     const ProtoTiled tg = want_dprotos ? proto_tiled_geometry(B, T, P, Dp, 0, 0) : ProtoTiled{};
     return bm + (tg.ok ? tg.ws_bytes : 0);
 }
@@ -1154,22 +1152,23 @@ int ppf_proto_bwd_single(const float* tok, int64_t stride_b, int t0, const float
     float* gemm_ws = sums + (B > P ? B : P);
     const float* tok0 = tok + (size_t)t0 * Dp;
     const char* who = "ppf_proto_bwd_single";
+    auto fixup = [&](float* out, int64_t ostride, const float* x, int64_t xstride, int R) {      // out[r][:] += 2 * sums[r] * x[r][:]
+        const int64_t blocks = ((int64_t)R * Dp + 255) / 256;
+        return ppf_launch<proto_single_fixup_kernel>(dim3((int)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, stream, who, out, ostride, x, xstride,
+                                                     (const float*)sums, R, Dp);
+    };
     if (dtok) {
         float* out = dtok + (size_t)t0 * Dp;
         if (int rc = ppf_launch<proto_single_gd_rows_kernel>(dim3(B), dim3(256), 0, stream, who, dist, g, P, act_kind, eps, G, sums)) return rc;
         // out[b][d] = -2 sum_p G[b][p] protos[p][d]
         if (int rc = ppf_sgemm(G, protos, out, B, Dp, P, P, 1, 1, Dp, (int)dstride_b, -2.0f, 0.0f, gemm_ws, (int64_t)16 * B * Dp, stream)) return rc;
-        const int64_t n = (int64_t)B * Dp;
-        if (int rc = ppf_launch<proto_single_fixup_kernel>(dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, who, out, dstride_b,
-                                                           tok0, stride_b, sums, B, Dp)) return rc;
+        if (int rc = fixup(out, dstride_b, tok0, stride_b, B)) return rc;
     }
     if (dprotos) {
         if (int rc = ppf_launch<proto_single_gd_cols_kernel>(dim3((P + 63) / 64), dim3(256), 0, stream, who, dist, g, B, P, act_kind, eps, G, sums)) return rc;
         // dprotos[p][d] += -2 sum_b G[b][p] tok[b][d]
         if (int rc = ppf_sgemm(G, tok0, dprotos, P, Dp, B, 1, P, 1, stride_b, Dp, -2.0f, 1.0f, gemm_ws, (int64_t)16 * P * Dp, stream)) return rc;
-        const int64_t n = (int64_t)P * Dp;
-        if (int rc = ppf_launch<proto_single_fixup_kernel>(dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, stream, who, dprotos, (int64_t)Dp,
-                                                           protos, (int64_t)Dp, sums, P, Dp)) return rc;
+        if (int rc = fixup(dprotos, (int64_t)Dp, protos, (int64_t)Dp, P)) return rc;
     }
     return 0;
 }

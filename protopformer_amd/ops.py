@@ -320,10 +320,12 @@ def proto_bwd(tokens, t0, T, protos, dist, g_full, g_max, argmax, dtok, dprotos,
         _lib.call("ppf_proto_bwd_single", tokens, Ttot * Dp, t0, protos, B, P, Dp, act_kind, float(eps), dist, g_max if g_max is not None else g_full,
                   dtok, Ttot * Dp, dprotos, ws, ws.numel())
         return
-    need = _lib.lib().ppf_proto_bwd_workspace(B, T, P, Dp, int(dtok is not None), int(dprotos is not None))
+    # the zeroed bitmap of the token gradients, then the scratch of the tiled prototype gradients: the two sizes add up
+    bitmap = _lib.lib().ppf_proto_bwd_workspace(B, T, P, Dp, 1, 0) if dtok is not None else 0
+    need = bitmap + (_lib.lib().ppf_proto_bwd_workspace(B, T, P, Dp, 0, 1) if dprotos is not None else 0)
     if dtok is not None:
         ws = torch.empty(need, dtype=torch.uint8, device=tokens.device)
-        _lib.call("ppf_memset_zero", ws, _lib.lib().ppf_proto_bwd_workspace(B, T, P, Dp, 1, 0))     # the bitmap; the scratch behind it is write-first
+        _lib.call("ppf_memset_zero", ws, bitmap)                  # the scratch behind the bitmap is write-first
     else:
         ws = _workspace(tokens.device, need) if need else None    # prototype gradients only: per-stream scratch, any content
     if rows is not None:

@@ -57,7 +57,6 @@ def build_features(base_architecture, pretrained=False, img_size=224, drop_path=
 
 
 # ------------------------------------------------------------------------------------------------ autograd nodes
-_SIDE_FIRST = True           # the side stream starts on the prototype gradients before the main stream's token-gradient kernels (+1.4 % in round 2, +0.6 % again in round 6: profiles/r6_proto_order.txt)
 _KEEP_DIST = os.environ.get("PPF_PROTO_KEEP_DIST", "0") != "0"      # A/B: write and save the (B,P,k) distance map in training as before round 5
 
 
@@ -164,30 +163,24 @@ class ProtoLayerFn(torch.autograd.Function):
         lane = wgrad_lane(store)      # prototype gradients feed only the optimizer: side stream, under the backbone backward
         torch.autograd.Variable._execution_engine.queue_callback(lane.join)     # ... joined when this backward pass ends
         rows, g_full = _rows_for(g_full)
-        if g_l is not None or g_full is not None or rows is not None:
-            gf = g_full.contiguous() if g_full is not None else None
-            gl = g_l.contiguous() if g_l is not None else None
-            pl = protos_local.reshape(-1, Dp)
+
+        def branch(t0, T, protos, dmap, gf, gm, am, rows=None, from_act=False):
+            """One branch's backward: prototype gradients on the side stream, token gradients (into df) on the main stream."""
+            pv = protos.reshape(-1, Dp)
+            kw = dict(rows=rows, from_act=from_act)
+            side = lambda: ops.proto_bwd(f, t0, T, pv, dmap, gf, gm, am, None, store.grad_view(protos).reshape(-1, Dp), act_kind, ppnet.epsilon, **kw)
+            reads = [t for t in (f, dmap, gf, gm, am) + (rows[:2] if rows is not None else ()) if t is not None]
             # the side stream starts on the prototype gradients BEFORE the main stream's token-gradient kernels are enqueued: the two
             # only share inputs, and the lane orders itself behind whatever the main stream has enqueued at submit time
-            side_l = lambda: ops.proto_bwd(f, 1, T1 - 1, pl, dist, gf, gl, argmax, None, store.grad_view(protos_local).reshape(-1, Dp),
-                                           act_kind, ppnet.epsilon, rows=rows, from_act=from_act)
-            reads_l = [t for t in (f, dist, gf, gl, argmax) + (rows[:2] if rows is not None else ()) if t is not None]
-            if _SIDE_FIRST:
-                lane.submit(side_l, reads_l, tag="PROTO")
-            ops.proto_bwd(f, 1, T1 - 1, pl, dist, gf, gl, argmax, df, None, act_kind, ppnet.epsilon, rows=rows, from_act=from_act)
-            if not _SIDE_FIRST:
-                lane.submit(side_l, reads_l, tag="PROTO")
+            # (+1.4 % in round 2, +0.6 % again in round 6 against the other order: profiles/r6_proto_order.txt)
+            lane.submit(side, reads, tag="PROTO")
+            ops.proto_bwd(f, t0, T, pv, dmap, gf, gm, am, df, None, act_kind, ppnet.epsilon, **kw)
+
+        if g_l is not None or g_full is not None or rows is not None:
+            branch(1, T1 - 1, protos_local, dist, g_full.contiguous() if g_full is not None else None, g_l.contiguous() if g_l is not None else None,
+                   argmax, rows=rows, from_act=from_act)
         if g_g is not None:
-            gg = g_g.contiguous()
-            pg = protos_global.reshape(-1, Dp)
-            side_g = lambda: ops.proto_bwd(f, 0, 1, pg, dist_g, None, gg, None, None, store.grad_view(protos_global).reshape(-1, Dp),
-                                           act_kind, ppnet.epsilon)
-            if _SIDE_FIRST:
-                lane.submit(side_g, (f, dist_g, gg), tag="PROTO")
-            ops.proto_bwd(f, 0, 1, pg, dist_g, None, gg, None, df, None, act_kind, ppnet.epsilon)
-            if not _SIDE_FIRST:
-                lane.submit(side_g, (f, dist_g, gg), tag="PROTO")
+            branch(0, 1, protos_global, dist_g, None, g_g.contiguous(), None)
         return df, None, None, None, None
 
 
