@@ -405,7 +405,8 @@ int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* pro
  *   ppf_pixel_random   score fp32 [B][n] = (word >> 8) * 2^-24, word = the first word of Philox4x32-10, key = seed, counter = (pixel,
  *                      0x80000000, image id low, image id high): a function of (seed, image id, pixel) alone.  Counter word 1 across the
  *                      library: 0 the random cell order, 1 + n < 2^31 the RISE masks, e/4 high (0 below 2^34 elements) the input noise of
- *                      ppf_add_gauss_noise, 0x80000000 ppf_warp_nodes -- so this draw is disjoint from the cell order and the RISE masks
+ *                      ppf_add_gauss_noise, 0x80000000 ppf_warp_nodes, 0x80000001 + (n >> 1) in [0x80000001, 0xC0000000] the KernelSHAP
+ *                      coalitions (ppf_shap_coalitions) -- so this draw is disjoint from the cell order, the RISE masks and the coalitions
  *                      but NOT from ppf_warp_nodes: pixel q and warp node q < (s + 1)^2 <= 289 of the same image under the same seed share
  *                      a Philox block (this draw reads word .x, the node's dy).  The two never meet in one computation (a pixel order and
  *                      a shape perturbation of 'because'); a caller who needs them independent gives them different seeds.
@@ -458,6 +459,51 @@ int ppf_rise_apply(const float* x, const void* nodes_u8, const int* shift, int N
                    int B, int Cc, int H, int W, float* out, ppf_stream_t stream);
 int ppf_rise_accumulate(const void* nodes_u8, const int* shift, const float* prob, int B, int N, int M, int s, int thr, int H, int W, int G, float* sal,
                         float* cell, ppf_stream_t stream);
+/* KernelSHAP cell attributions (csrc/shap.hip; Lundberg & Lee, 2017): Shapley values of d = s x s square players of an image for the
+ * value of a class, by the least-squares fit to N sampled coalitions under the constraint that the attributions add up to
+ * f(x) - f(baseline), with the paired sampling of Covert & Lee (2021).  Forwards only, as RISE; the forwards and ppf_class_prob are the
+ * caller's.  The reference has no such pass, and nobody has run this one on a trained checkpoint.  Additions of ABI 10: no existing
+ * entry point changed.  Coalitions, masked images and the Gram matrix are integer-exact; this is the contract the numpy referees
+ * (interpret.shap_*) keep bit for bit, and csrc/shap_plan.h states its index rules for a host program (tests/shap_plan_check.cpp).
+ *   sizes     image H x W with H == W; s players per side, 2 <= s <= 14, d = s^2 players in [4, 196]; s divides H and the player width
+ *             H / s is a multiple of 4 (a 16-byte vector never straddles a player); s divides side = sqrt(G), a player is r x r grid
+ *             cells, r = side / s.  N samples per image, N even, 2 <= N <= 2^30; 1 <= M <= 8 classes per image.
+ *             Player of pixel (y, x): (y / (H / s)) * s + x / (W / s); of grid cell (gy, gx): (gy / r) * s + gx / r.
+ *   draws     Philox4x32-10 with key = seed (64 bits) and counter = (k, 0x80000001 + j, image id low, image id high) for pair j = n >> 1
+ *             of image id: counter word 1 lies in [0x80000001, 0xC0000000], disjoint from every other draw of the library (the list is
+ *             under ppf_pixel_random).  Key of player q: word q % 4 of call k = q / 4, all 32 bits.  Size of coalition 2j: from call
+ *             k = 0xFFFFFFFF, u = w.x >> 8, size = 1 + #{t in [0, d - 3] : table[t] <= u}, so 1 <= size <= d - 1 whatever the table holds.
+ *   table     int32 [d - 1] on the DEVICE, computed once by the host: table[t] = round(2^24 * sum_{k <= t + 1} w_k / sum_k w_k) with
+ *             w_k = 1 / (k (d - k)), k = 1 .. d - 1, the Shapley kernel's distribution of sizes; table[d - 2] = 2^24.  The host side of
+ *             the binding refuses a table that is not non-decreasing or does not end at 2^24 (ops.shap_coalitions).
+ *   members   q is in coalition 2j iff #{r : (key_r, r) < (key_q, q) lexicographically} < size: a uniform subset of that size, by a
+ *             counting rank, no atomics.  Coalition 2j + 1 is the complement of coalition 2j.  A coalition depends on (seed, image id,
+ *             n, d) alone, not on the batch.
+ *   ppf_shap_coalitions  coal uint32 [B][N][Wd], Wd = ceil(d / 32): bit q % 32 of word q / 32 is the membership of player q; unused bits 0.
+ *   ppf_shap_apply       out fp32 [Nc][B][Cc][H][W] for samples n0 .. n0 + Nc - 1 (0 <= n0, n0 + Nc <= N): a pixel is x when its player's
+ *                        bit is set, else base = baseline fp32 [B][Cc][H][W] or, NULL, the constant baseline_const (as
+ *                        ppf_patch_perturb).  A select only: bit-exact.  x and the baseline are read once, all Nc copies written from
+ *                        registers with 16-byte accesses; the coalition words of the chunk are staged in LDS.  x, baseline, out 16-byte
+ *                        aligned.
+ *   ppf_shap_gram        from coal, val fp32 [N][B][M] and v0 fp32 [B][M]:  A int32 [B][d][d] = #{n : z_i and z_j}, the full symmetric
+ *                        matrix (popcounts of ANDed bit-columns, integer adds only);  bvec fp64 [B][M][d] = the sum over n ascending,
+ *                        over the samples with z_{n,i} = 1 only, of fsub((double)val, (double)v0): one rounded subtract and one rounded
+ *                        add per term, nothing contracted, started from +0.  Both bit-exact to a numpy loop.
+ *   ppf_shap_solve       per image in fp64: A = L L^T by Cholesky, x_m = A^-1 b_m and y = A^-1 1, delta_m = (double)v1 - (double)v0 (v1
+ *                        fp32 [B][M], the value of the whole image), phi_m = x_m - y * ((sum x_m - delta_m) / sum y): the least-squares
+ *                        fit under sum phi = delta.  One factorisation per image serves the M + 1 right-hand sides; fixed summation
+ *                        order, no atomics: repeats are bit-identical.  The factor lives in `scratch`
+ *                        (ppf_shap_solve_scratch_bytes(B, d) = B * d^2 * 8 bytes, 8-byte aligned, used by this launch only; 0 for sizes
+ *                        outside the limits).  Writes phi fp64 [B][M][d], cell fp32 [B][M][G] = (float)(phi[player of g] / r^2) and bad
+ *                        int32 [B].  A pivot that is <= 0 or NaN sets bad[b] = 1 and makes all M rows of that image NaN (else bad[b] =
+ *                        0); a row whose bvec or delta is not finite is all NaN and leaves the other rows alone.  G <= 1024. */
+int ppf_shap_coalitions(const void* image_id_i64, uint64_t seed, const int* table, int B, int N, int s, void* coal_u32, ppf_stream_t stream);
+int ppf_shap_apply(const float* x, const void* coal_u32, int N, int n0, int Nc, int s, const float* baseline, float baseline_const, int B, int Cc,
+                   int H, int W, float* out, ppf_stream_t stream);
+int ppf_shap_gram(const void* coal_u32, const float* val, const float* v0, int B, int N, int M, int s, int* A, double* bvec, ppf_stream_t stream);
+size_t ppf_shap_solve_scratch_bytes(int B, int d);
+int ppf_shap_solve(const int* A, const double* bvec, const float* v0, const float* v1, int B, int M, int s, int G, void* scratch, size_t scratch_bytes,
+                   double* phi, float* cell, int* bad, ppf_stream_t stream);
 /* Integrated gradients (csrc/ig.hip; Sundararajan et al., 2017): attribution = (x - baseline) * the gradient averaged along the straight
  * path from the baseline to x; the attributions of an image sum to f(x) - f(baseline).  The forwards and backwards along the path are the
  * caller's (interpret.input_gradient); these three streaming kernels are everything in between.  The reference has no such pass.

@@ -898,6 +898,7 @@ def explain(ppnet, x, classes=None, top_classes=1, topk=10, against=False, maps=
 # (device=False) are the referees.
 ORDER_MODES = ("evidence", "attention", "random")
 EXTRA_ORDERS = ("rise",)                # opt-in orders of faithfulness_curves / faithfulness: the black-box baseline (rise_saliency, below)
+GAME_ORDERS = ("shap",)                 # opt-in order: the cells ranked by their Shapley values (kernel_shap, below); cell resolution only
 CURVE_MODES = ("deletion", "insertion")
 
 _PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -1108,24 +1109,32 @@ def perturb_pixels(x, rank, counts, insertion=False, baseline=0.0, device=True):
     return np.where(keep[:, :, :, None], x[None, :, None], base[None, :, None]).astype(np.float32)
 
 
-def _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig):
-    """(score, the Rise or None, the IntegratedGradients or None) of an order at a resolution.  'pixel': score fp32 [B, M, H, W], the map
-    of pixel_scores.  'cell': the 'rise' and 'ig' orders give their cell score fp32 [B, M, G] (_rank_cell_scores ranks it); 'evidence',
-    'attention' and 'random' give None: ppf_cell_order scores and ranks those in one launch (cell_order_from_outputs)."""
+def _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig, shap=None):
+    """(score, the Rise or None, the IntegratedGradients or None, the Shap or None) of an order at a resolution.  'pixel': score fp32
+    [B, M, H, W], the map of pixel_scores.  'cell': the 'rise', 'ig' and 'shap' orders give their cell score fp32 [B, M, G]
+    (_rank_cell_scores ranks it); 'evidence', 'attention' and 'random' give None: ppf_cell_order scores and ranks those in one launch
+    (cell_order_from_outputs)."""
     from . import ops
     (B, _, H, W), M, G = x.shape, cls.shape[1], int(ppnet.num_patches)
     pixel = resolution == "pixel"
+    if order in GAME_ORDERS:            # the one place the faithfulness code runs the KernelSHAP pass, from the curve's own baseline
+        if pixel:
+            raise ValueError(f"faithfulness: the {order!r} order is defined at resolution='cell' only (its players are grid cells; a "
+                             "piecewise-constant pixel map is not provided)")
+        found = _shap_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
+                                   **{**SHAP_DEFAULTS, **(shap or {})})
+        return found.cell, None, None, found
     if order in EXTRA_ORDERS + GRADIENT_ORDERS:
         if order in EXTRA_ORDERS:       # the one place the faithfulness code runs the RISE pass, from the curve's own baseline ...
             found = _rise_from_classes(ppnet, x, cls, baseline=baseline, seed=seed, image_ids=image_ids, batch_size=batch_size, scratch_bytes=scratch_bytes,
                                        **{**RISE_DEFAULTS, **(rise or {})})
-            return (found.saliency.contiguous() if pixel else found.cell), found, None
+            return (found.saliency.contiguous() if pixel else found.cell), found, None, None
         _refuse_pending_gradients("faithfulness_curves", ppnet)                                      # ... and integrated gradients
         found = _ig_pass(ppnet, x, outs, "logit", None, cls, baseline=baseline, batch_size=batch_size, **{**IG_DEFAULTS, **(ig or {})})
         a = found.attribution
-        return (((a[:, :, 0] + a[:, :, 1]) + a[:, :, 2]).contiguous() if pixel else found.cell), None, found      # two rounded adds, in this order
+        return (((a[:, :, 0] + a[:, :, 1]) + a[:, :, 2]).contiguous() if pixel else found.cell), None, found, None      # two rounded adds, in this order
     if not pixel:
-        return None, None, None
+        return None, None, None, None
     side = int(round(G ** 0.5))
     if order in ORDER_MODES[:2] and (H != W or side * side != G):
         raise ValueError(f"pixel_scores: the {order} map is up-sampled from a square grid to a square image, got G={G} and {H} x {W}")
@@ -1136,13 +1145,13 @@ def _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_
         reserved = torch.zeros((B, G + 1), dtype=torch.bool, device=x.device)
         reserved.scatter_(1, torch.where((idx >= 0) & (idx < G), idx, torch.full_like(idx, G)), True)      # entries outside the grid: the spare column
         grid = torch.where(reserved[:, None, :G], cell, torch.zeros_like(cell))
-        return upsample_cubic_device(grid.reshape(B, M, side, side).contiguous(), H), None, None
+        return upsample_cubic_device(grid.reshape(B, M, side, side).contiguous(), H), None, None, None
     if order == "attention":
         up = upsample_cubic_device(outs["token_attn"].reshape(B, side, side).contiguous(), H)
-        return up[:, None].expand(B, M, H, W).contiguous(), None, None
+        return up[:, None].expand(B, M, H, W).contiguous(), None, None, None
     if order == "random":
         s = ops.pixel_random(_image_ids(image_ids, B, x.device), H * W, seed)
-        return s.reshape(B, 1, H, W).expand(B, M, H, W).contiguous(), None, None
+        return s.reshape(B, 1, H, W).expand(B, M, H, W).contiguous(), None, None, None
     raise ValueError(f"pixel_scores: order must be one of {ORDER_MODES + EXTRA_ORDERS + GRADIENT_ORDERS}, got {order!r}")
 
 
@@ -1184,12 +1193,13 @@ class Faithfulness(Record):
     """What faithfulness_curves returns, as device tensors (numpy arrays after cpu()): curves[mode] fp32 [B, M, S] = the probability of
     class classes[b, m] after counts[s] cells were removed ('deletion') or shown ('insertion'); counts int32 [S]; classes int32 [B, M];
     order, rank int32 and score fp32 [B, M, G] as ppf_cell_order wrote them.  grid_cells = G.  rise: the Rise the 'rise' order ranked by
-    (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order.
+    (its cell scores are `score`), None for every other order; ig: likewise the IntegratedGradients of the 'ig' order; shap: likewise the
+    Shap of the 'shap' order.
     resolution 'pixel': counts are pixels, grid_cells = H * W, rank int32 and score fp32 are [B, M, H * W] as ppf_pixel_order ranked them,
     and order is None (51 MB per class column at 224^2 that nobody reads)."""
     FIELDS = ("curves", "counts", "classes", "order", "rank", "score")
-    META = dict(grid_cells=int, rise=None, ig=None, resolution=str)
-    DEFAULTS = dict(rise=None, ig=None, resolution="cell")
+    META = dict(grid_cells=int, rise=None, ig=None, resolution=str, shap=None)
+    DEFAULTS = dict(rise=None, ig=None, resolution="cell", shap=None)
 
     def auc(self):
         """{mode: fp64 [B, M]}: the area under each curve over the removed / shown fraction counts / G (trapezoid, on the host)."""
@@ -1233,13 +1243,14 @@ def _class_probs(ppnet, imgs, cols, batch_size):
 
 
 def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, seed, image_ids, batch_size, scratch_bytes, rise=None, ig=None,
-                         resolution="cell"):
+                         resolution="cell", shap=None):
     from . import ops
     B, G = x.shape[0], int(ppnet.num_patches)
     M, S = cls.shape[1], counts.shape[0]
     w_l = ppnet.last_layer.weight.detach().contiguous()
     ordr, perturb = None, ops.patch_perturb
-    score, found, found_ig = _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig)
+    score, found, found_ig, found_shap = _order_scores(ppnet, x, outs, cls, order, resolution, baseline, seed, image_ids, batch_size, scratch_bytes,
+                                                       rise, ig, shap)
     if resolution == "pixel":
         # every order is a [B, M, H, W] map (pixel_scores); one ppf_pixel_order launch ranks the B * M rows, ppf_pixel_perturb takes
         # ppf_patch_perturb's place below.  The chunking, the forwards and ppf_class_prob are the cell path's.
@@ -1248,7 +1259,7 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
         rank = pixel_order_from_scores(score, cls)
     elif score is not None:
         # 'rise': the cells ranked by their mean RISE saliency; 'ig': by the integrated gradients of the class logit summed over each
-        # cell, along the path from the curve's own baseline
+        # cell, along the path from the curve's own baseline; 'shap': by the Shapley value of their player, shared among its cells
         ordr, rank, score = _rank_cell_scores(score, cls, G, w_l)
     else:
         ordr, rank, score = cell_order_from_outputs(outs["act_full"], outs["idx"], outs["token_attn"], w_l, 1.0 - float(ppnet.global_coe), cls, G,
@@ -1269,7 +1280,7 @@ def _curves_from_outputs(ppnet, x, outs, cls, counts, modes, order, baseline, se
                 imgs = imgs.reshape((n * B * M,) + tuple(x.shape[1:]))
                 prob[s0:s0 + n] = _class_probs(ppnet, imgs, [cls_flat[:n * B * M]], int(batch_size or B))[0].reshape(n, B, M)
             curves[mode] = prob.permute(1, 2, 0).contiguous()
-    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found, ig=found_ig, resolution=resolution)
+    return Faithfulness(curves, counts, cls, ordr, rank, score, G, rise=found, ig=found_ig, resolution=resolution, shap=found_shap)
 
 
 def _pick_classes(ppnet, outs, classes, top_classes, B):
@@ -1284,7 +1295,7 @@ def _pick_classes(ppnet, outs, classes, top_classes, B):
 
 @torch.no_grad()
 def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, modes=CURVE_MODES, order="evidence", baseline=0.0, seed=0, image_ids=None,
-                        batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None):
+                        batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None, shap=None):
     """Deletion / insertion curves of a batch x [B, 3, H, W] (CUDA): one eval forward, one ppf_cell_order launch, then per mode
     ppf_patch_perturb in chunks of steps, the model's forward over each chunk in sub-batches of `batch_size` images (default B; the
     images of a chunk are ordered step, sample, class) and one ppf_class_prob per chunk.  The chunk's images are the one large scratch
@@ -1294,7 +1305,9 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     by their RISE saliency for the class (rise_saliency with the same baseline, seed, image_ids, batch_size and scratch_bytes;
     rise = dict(masks=, cells=, p=) overrides RISE_DEFAULTS; the result carries the Rise), or 'ig': by the integrated gradients of the
     class logit summed over each cell (integrated_gradients along the path from the same baseline, in the same sample groups;
-    ig = dict(steps=, rule=) overrides IG_DEFAULTS; the result carries the IntegratedGradients).  baseline: what a removed pixel becomes, a
+    ig = dict(steps=, rule=) overrides IG_DEFAULTS; the result carries the IntegratedGradients), or 'shap': by the Shapley value of the
+    cell's player for the class (kernel_shap with the same baseline, seed, image_ids, batch_size and scratch_bytes;
+    shap = dict(samples=, cells=, value=) overrides SHAP_DEFAULTS; the result carries the Shap; cell resolution only).  baseline: what a removed pixel becomes, a
     number in normalised space (0 = the data-set mean colour), a tensor like x, or 'blur': gauss_blur(x) with blur = dict(sigma=, radius=)
     over BLUR_DEFAULTS, computed once and used wherever the baseline is (the rise and ig passes included).  resolution 'pixel': the
     metric as published -- the order's [B, M, H, W] map (pixel_scores) is ranked by one ppf_pixel_order launch, counts are pixels (default
@@ -1312,7 +1325,7 @@ def faithfulness_curves(ppnet, x, classes=None, top_classes=1, counts=None, mode
     cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
     counts = _device_counts(counts, G, x.device)
     return _curves_from_outputs(ppnet, x, outs, cls, counts, tuple(modes), order, baseline, seed, image_ids, batch_size, scratch_bytes, rise, ig,
-                                resolution)
+                                resolution, shap)
 
 
 def _device_counts(counts, G, device):
@@ -1324,9 +1337,9 @@ def _device_counts(counts, G, device):
 
 @torch.no_grad()
 def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=None, top_classes=1, against_label=False, baseline=0.0, seed=0,
-                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None):
+                 max_images=0, batch_size=None, scratch_bytes=1 << 30, rise=None, ig=None, resolution="cell", blur=None, shap=None):
     """The curves over a data set.  loader yields (x, labels) or (x, labels, ids); without ids an image's id is its running index.  Per
-    batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=), and 'ig', with ig = dict(steps=, rule=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
+    batch one eval forward serves every order (orders may name 'rise', with rise = dict(masks=, cells=, p=), 'ig', with ig = dict(steps=, rule=), and 'shap', with shap = dict(samples=, cells=, value=)); classes are the top `top_classes` of the logits, or with against_label the image's label.
     The per-image curves stay on the device and are read back once at the end.  Returns dict(images, counts, grid_cells, orders:
     {order: {mode: dict(curve = the mean curve [S], auc = the mean area)}}, per_image: {order: {mode: fp32 [N, M, S]}}, classes [N, M],
     image_ids [N]); rows whose class could not be picked (-1) are left out of the means.  resolution, baseline = 'blur' and blur: as in
@@ -1348,7 +1361,7 @@ def faithfulness(ppnet, loader, orders=ORDER_MODES, modes=CURVE_MODES, counts=No
             dev_counts = _device_counts(counts, G, x.device)
         for order in orders:
             f = _curves_from_outputs(ppnet, x, outs, cls, dev_counts, tuple(modes), order, baseline, seed, ids, batch_size, scratch_bytes, rise, ig,
-                                     resolution)
+                                     resolution, shap)
             for mode in modes:
                 kept.setdefault((order, mode), []).append(f.curves[mode])
         cls_kept.append(cls); ids_kept.append(ids)
@@ -1537,6 +1550,264 @@ def rise_saliency(ppnet, x, classes=None, top_classes=1, masks=512, cells=7, p=0
     outs = _eval_outputs(ppnet, x)
     cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
     return _rise_from_classes(ppnet, x, cls, masks, cells, p, baseline, seed, image_ids, batch_size, scratch_bytes)
+
+
+# ------------------------------------------------------------------------------------------------ KernelSHAP: Shapley values of grid cells
+# KernelSHAP (Lundberg & Lee, 2017) is the baseline a reader of the faithfulness table asks for after RISE and integrated gradients.  Its
+# players are d = cells x cells square blocks of grid cells, the resolution of the 'evidence' order; it needs forwards alone, as RISE;
+# and it is efficient by construction: the attributions add up to f(x) - f(baseline) exactly (to rounding), even across the jumps of the
+# token reservation, where the `delta` of integrated gradients does not fall with more steps.  N coalitions are drawn in complementary
+# pairs (Covert & Lee, 2021) with sizes from the Shapley kernel's distribution, so the weighted regression becomes a plain one: A = Z^T Z,
+# b = Z^T (v - v0), solved under sum phi = v1 - v0.  Coalitions, masked images and A are integer-exact (the contract is in
+# include/ppf_hip.h): ppf_shap_coalitions draws, ppf_shap_apply writes the masked images of a chunk of samples, the model's forward scores
+# them, ppf_shap_gram sums and ppf_shap_solve factors in fp64 (csrc/shap.hip).  The numpy forms below (device=False) are the referees.
+# The reference has no such pass, and nobody has run this one on a trained checkpoint.
+SHAP_DEFAULTS = dict(samples=512, cells=7, value="prob")
+SHAP_VALUES = ("prob", "logit")
+
+
+def _shap_sizes(cells, samples=None):
+    """(s, d, Wd) of the coalition contract: d = s^2 players in ceil(d / 32) words; samples, when given, even and in [2, 2^30]."""
+    s = int(cells)
+    if not 2 <= s <= 14:
+        raise ValueError(f"shap: cells={s} outside [2, 14]")
+    if samples is not None and (int(samples) % 2 or not 2 <= int(samples) <= 1 << 30):
+        raise ValueError(f"shap: samples={int(samples)} must be even and lie in [2, 2^30] (coalitions are drawn in complementary pairs)")
+    return s, s * s, (s * s + 31) // 32
+
+
+def shap_size_table(d):
+    """int32 [d - 1]: table[t] = round(2^24 * P(size <= t + 1)) under the Shapley kernel's distribution of coalition sizes,
+    P(size = k) ~ 1 / (k (d - k)) for k = 1 .. d - 1, in exact rational arithmetic (halves round up); non-decreasing, table[d - 2] = 2^24."""
+    from fractions import Fraction
+    d = int(d)
+    if not 4 <= d <= 196:
+        raise ValueError(f"shap_size_table: d={d} outside [4, 196]")
+    w = [Fraction(1, k * (d - k)) for k in range(1, d)]
+    total, run, table = sum(w), Fraction(0), []
+    for wk in w:
+        run += wk
+        table.append(int((run / total * (1 << 25) + 1) // 2))
+    return np.asarray(table, dtype=np.int32)
+
+
+def shap_members(coal, cells):
+    """bool [B, N, d]: the membership bits of coal [B, N, Wd] (uint32 words, or the int32 a device tensor holds them in), unpacked."""
+    s, d, Wd = _shap_sizes(cells)
+    w = _host(coal, np.int32).view(np.uint32)
+    return (((w[..., None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)).reshape(w.shape[:2] + (Wd * 32,))[..., :d]).astype(bool)
+
+
+def _shap_player_maps(size, cells, grid_cells=None):
+    """The player of every pixel [H, H], or of every grid cell [G] with r = side / cells."""
+    s, d, _ = _shap_sizes(cells)
+    if grid_cells is None:
+        H = int(size)
+        if H % s or (H // s) % 4:
+            raise ValueError(f"shap: cells={s} must divide H={H} into players whose width is a multiple of 4")
+        q = np.arange(H) // (H // s)
+        return q[:, None] * s + q[None, :]
+    G = int(grid_cells)
+    side = int(round(G ** 0.5))
+    if side * side != G or side % s or G > 1024:
+        raise ValueError(f"shap: cells={s} must divide the side of a square grid of at most 1024 cells, got G={G}")
+    q = np.arange(side) // (side // s)
+    return (q[:, None] * s + q[None, :]).reshape(G)
+
+
+def shap_coalitions_from_ids(image_ids, cells, samples, seed=0, device=True):
+    """coal [B, N, ceil(d / 32)]: bit q % 32 of word q / 32 says whether player q of d = cells^2 is in coalition n of image image_ids[b];
+    coalition 2j + 1 is the complement of coalition 2j, whose size follows shap_size_table(d) and whose members are a uniform subset, from
+    Philox draws keyed by (seed, image id, j): a function of (seed, image id, n, d) alone, not of the batch.  device=True: one
+    ppf_shap_coalitions launch, an int32 CUDA tensor holding the uint32 words (image_ids a CUDA tensor or anything torch.as_tensor
+    takes, then put on the current device); device=False: the numpy Philox, uint32."""
+    s, d, Wd = _shap_sizes(cells, samples)
+    N, table = int(samples), shap_size_table(d)
+    if device:
+        from . import ops
+        ids = torch.as_tensor(image_ids)
+        ids = ids.to(device=ids.device if ids.is_cuda else "cuda", dtype=torch.int64).contiguous()
+        return ops.shap_coalitions(ids, s, N, table, seed)
+    ids = _host(image_ids, np.int64).reshape(-1).astype(np.uint64)
+    B, P, Q, sd = ids.shape[0], N // 2, (d + 3) // 4, int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((B, P, Q + 1, 4), dtype=np.uint64)
+    ctr[..., 0] = np.concatenate([np.arange(Q), [0xFFFFFFFF]]).astype(np.uint64)                  # the call after the key words: the size
+    ctr[..., 1] = (np.uint64(0x80000001) + np.arange(P, dtype=np.uint64))[None, :, None]
+    ctr[..., 2], ctr[..., 3] = (ids & np.uint64(0xFFFFFFFF))[:, None, None], (ids >> np.uint64(32))[:, None, None]
+    w = philox4x32_10(ctr, np.array([sd & 0xFFFFFFFF, sd >> 32], dtype=np.uint64))                # [B, P, Q + 1, 4]
+    keys = w[:, :, :Q].reshape(B, P, Q * 4)[:, :, :d]
+    u = (w[:, :, Q, 0] >> np.uint32(8)).astype(np.int64)
+    size = 1 + (table[None, None, :d - 2].astype(np.int64) <= u[..., None]).sum(-1)                # [B, P], in [1, d - 1]
+    order = np.argsort(keys, axis=-1, kind="stable")                                              # (key, player) ascending
+    rank = np.empty_like(order)
+    np.put_along_axis(rank, order, np.broadcast_to(np.arange(d), order.shape), axis=-1)
+    even = rank < size[..., None]
+    z = np.stack([even, ~even], axis=2).reshape(B, N, d)
+    bits = np.zeros((B, N, Wd * 32), dtype=np.uint64)
+    bits[..., :d] = z
+    return (bits.reshape(B, N, Wd, 32) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+def shap_apply(x, coal, cells, n0=0, count=None, baseline=0.0, device=True, out=None):
+    """The masked images [Nc, B, Cc, H, W] of x [B, Cc, H, W] under coalitions n0 .. n0 + count - 1 (default: to the last): a pixel is x
+    when its player is in the coalition, else the baseline (a number or a tensor like x).  device=True: one ppf_shap_apply launch;
+    device=False: numpy."""
+    if device:
+        from . import ops
+        return ops.shap_apply(x, coal, cells, n0, count, baseline, out=out)
+    x = _host(x, np.float32)
+    if x.shape[2] != x.shape[3]:
+        raise ValueError(f"shap_apply: H={x.shape[2]} W={x.shape[3]}: square images only")
+    qmap, z = _shap_player_maps(x.shape[2], cells), shap_members(coal, cells)
+    n0, N = int(n0), z.shape[1]
+    Nc = N - n0 if count is None else int(count)
+    if n0 < 0 or Nc < 1 or n0 + Nc > N:
+        raise ValueError(f"shap_apply: samples {n0} .. {n0 + Nc - 1} outside [0, {N})")
+    keep = z[:, n0:n0 + Nc][:, :, qmap].transpose(1, 0, 2, 3)[:, :, None]                          # [Nc, B, 1, H, W]
+    base = np.broadcast_to(_host(baseline, np.float32), x.shape)
+    return np.where(keep, x[None], base[None]).astype(np.float32)
+
+
+def shap_gram(coal, val, v0, cells, device=True):
+    """(A int32 [B, d, d], bvec fp64 [B, M, d]) of the regression: A[b, i, j] = the number of samples that hold players i and j;
+    bvec[b, m, i] = the fp64 sum over n ascending, over the samples that hold player i only, of (double)val[n, b, m] - (double)v0[b, m],
+    from +0.  device=True: one ppf_shap_gram launch; device=False: numpy, sample by sample."""
+    if device:
+        from . import ops
+        return ops.shap_gram(coal, val, v0, cells)
+    z, val, v0 = shap_members(coal, cells), _host(val, np.float32), _host(v0, np.float32)
+    (B, N, d), M = z.shape, val.shape[2]
+    if val.shape != (N, B, M) or v0.shape != (B, M) or not 1 <= M <= 8:
+        raise ValueError(f"shap_gram: val must be [{N}, {B}, M] and v0 [{B}, M] with M in [1, 8], got {list(val.shape)} and {list(v0.shape)}")
+    zi = z.astype(np.int64)
+    A = np.einsum("bni,bnj->bij", zi, zi).astype(np.int32)
+    bvec, from_ = np.zeros((B, M, d), dtype=np.float64), v0.astype(np.float64)
+    with np.errstate(all="ignore"):
+        for n in range(N):                                                                        # ascending: the order is the contract
+            term = val[n].astype(np.float64) - from_                                              # [B, M]
+            bvec = np.where(z[:, n, None, :], bvec + term[:, :, None], bvec)
+    return A, bvec
+
+
+def shap_solve(A, bvec, v0, v1, cells, grid_cells, device=True):
+    """(phi fp64 [B, M, d], cell fp32 [B, M, G], bad int32 [B]): per image A = L L^T, x_m = A^-1 bvec_m, y = A^-1 1 and
+    phi_m = x_m - y (sum x_m - delta_m) / sum y with delta_m = (double)v1 - (double)v0, the least-squares attributions that add up to
+    delta_m; cell = (float)(phi[player of the cell] / r^2), a player's value shared among its r x r cells.  An image whose A is not positive
+    definite has bad = 1 and NaN rows; a row whose bvec or delta is not finite is NaN.  device=True: one ppf_shap_solve launch;
+    device=False: numpy's Cholesky, in fp64 too but not bit for bit (the device's error is held to a forward-error bound of it)."""
+    if device:
+        from . import ops
+        return ops.shap_solve(A, bvec, v0, v1, cells, grid_cells)
+    s, d, _ = _shap_sizes(cells)
+    cmap = _shap_player_maps(None, s, grid_cells)
+    A, bvec = _host(A, np.int32).astype(np.float64), _host(bvec, np.float64)
+    delta = _host(v1, np.float32).astype(np.float64) - _host(v0, np.float32).astype(np.float64)
+    (B, M, _), r = bvec.shape, int(round(int(grid_cells) ** 0.5)) // s
+    phi, bad = np.full((B, M, d), np.nan), np.zeros(B, dtype=np.int32)
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            try:
+                L = np.linalg.cholesky(A[b])
+            except np.linalg.LinAlgError:
+                bad[b] = 1
+                continue
+            y = np.linalg.solve(L.T, np.linalg.solve(L, np.ones(d)))
+            for m in range(M):
+                if not (np.isfinite(bvec[b, m]).all() and np.isfinite(delta[b, m])):
+                    continue
+                xm = np.linalg.solve(L.T, np.linalg.solve(L, bvec[b, m]))
+                phi[b, m] = xm - y * ((xm.sum() - delta[b, m]) / y.sum())
+        return phi, (phi[:, :, cmap] / float(r * r)).astype(np.float32), bad
+
+
+class Shap(Record):
+    """What kernel_shap returns, as device tensors (numpy arrays after cpu()): phi fp64 [B, M, d], the Shapley values of the d = cells^2
+    players; cell fp32 [B, M, G], a player's value shared equally among its grid cells; value fp32 [N, B, M], the value of every masked
+    image; value_base, value_full fp32 [B, M], the values of the all-baseline image and of x; gram int32 [B, d, d] and bvec fp64
+    [B, M, d], the regression's sums; bad int32 [B] (1: the image's system was singular, its rows are NaN); classes int32 [B, M]; coal
+    int32 [B, N, Wd], the coalition words.  cells, kind: the settings (kind: what `value` holds, 'prob' or 'logit')."""
+    FIELDS = ("phi", "cell", "value", "value_base", "value_full", "gram", "bvec", "bad", "classes", "coal")
+    META = dict(cells=int, kind=str)
+
+    def delta(self):
+        """sum phi - (value_full - value_base) [B, M] in fp64: the efficiency gap, rounding error alone."""
+        wide = (lambda t: t.astype(np.float64)) if self.on_host else (lambda t: t.double())
+        return self.phi.sum(-1) - (wide(self.value_full) - wide(self.value_base))
+
+
+def _shap_check(samples, cells, value, grid_cells):
+    s, d, _ = _shap_sizes(cells, samples)
+    if value not in SHAP_VALUES:
+        raise ValueError(f"kernel_shap: value must be one of {SHAP_VALUES}, got {value!r}")
+    if int(samples) < 4 * d:
+        raise ValueError(f"kernel_shap: samples={int(samples)} is below 4 * cells^2 = {4 * d}: the regression of {d} players is likely singular")
+    side = int(round(int(grid_cells) ** 0.5))
+    if side * side != int(grid_cells) or side % s:
+        raise ValueError(f"kernel_shap: cells={s} does not divide the grid side {side} (G={int(grid_cells)})")
+    return s
+
+
+def _shap_values(ppnet, imgs, cols, value, batch_size):
+    """The values fp32 [R] of the classes cols[j] int32 [R] of imgs [R, C, H, W], per column: 'prob' the class probability of the curves
+    (_class_probs), 'logit' the class logit (NaN for a class outside the model's).  The caller holds eval mode and no_grad."""
+    if value == "prob":
+        return _class_probs(ppnet, imgs, cols, batch_size)
+    logits = torch.cat([r.logits for r in forward_groups(ppnet, imgs, batch_size)]).float()
+    C, nan = logits.shape[1], torch.full((), float("nan"), dtype=torch.float32, device=logits.device)
+    return [torch.where((c >= 0) & (c < C), logits.gather(1, c.clamp(0, C - 1).long()[:, None])[:, 0], nan) for c in cols]
+
+
+def _shap_from_classes(ppnet, x, cls, samples, cells, value, baseline, seed, image_ids, batch_size, scratch_bytes):
+    from . import ops
+    B, G = x.shape[0], int(ppnet.num_patches)
+    M, N = cls.shape[1], int(samples)
+    s = _shap_check(N, cells, value, G)
+    coal = ops.shap_coalitions(_image_ids(image_ids, B, x.device), s, N, shap_size_table(s * s), seed)
+    # scratch: the masked images of one chunk of samples, samples_per_chunk * B images, never more than scratch_bytes (one sample at least)
+    chunk = _chunk_items(N, scratch_bytes, x.numel() * 4)
+    cols = [cls[:, m].reshape(1, B).expand(max(chunk, 2), B).reshape(-1).contiguous() for m in range(M)]
+    buf = torch.empty((chunk,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+    val = torch.empty((N, B, M), dtype=torch.float32, device=x.device)
+    ends = torch.empty((2, B, M), dtype=torch.float32, device=x.device)
+    bs = int(batch_size or B)
+    with ppnet.eval_mode():
+        for n0 in range(0, N, chunk):
+            n = min(chunk, N - n0)
+            imgs = ops.shap_apply(x, coal, s, n0, n, baseline, out=buf[:n]).reshape((n * B,) + tuple(x.shape[1:]))
+            # a coalition does not depend on the class: one image serves all M columns
+            for m, v in enumerate(_shap_values(ppnet, imgs, [c[:n * B] for c in cols], value, bs)):
+                val[n0:n0 + n, :, m] = v.reshape(n, B)
+        # the two ends of the game: x itself and the all-baseline image
+        blank = baseline if isinstance(baseline, torch.Tensor) else torch.full_like(x, float(baseline))
+        for m, v in enumerate(_shap_values(ppnet, torch.cat([x, blank.to(x.dtype)]), [c[:2 * B] for c in cols], value, bs)):
+            ends[:, :, m] = v.reshape(2, B)
+    v1, v0 = ends[0].contiguous(), ends[1].contiguous()
+    A, bvec = ops.shap_gram(coal, val, v0, s)
+    phi, cell, bad = ops.shap_solve(A, bvec, v0, v1, s, G)
+    return Shap(phi, cell, val, v0, v1, A, bvec, bad, cls, coal, s, value)
+
+
+@torch.no_grad()
+def kernel_shap(ppnet, x, classes=None, top_classes=1, samples=512, cells=7, value="prob", baseline=0.0, seed=0, image_ids=None, batch_size=None,
+                scratch_bytes=1 << 30):
+    """KernelSHAP attributions of a batch x [B, 3, H, W] (CUDA) for the classes of explain (None: the top `top_classes` of the logits): one
+    eval forward and the class pick, one ppf_shap_coalitions launch, then per chunk of samples ppf_shap_apply into the one scratch buffer
+    (samples-per-chunk = scratch_bytes // (B * image bytes), at least one) and the model's forward over the chunk in sub-batches of
+    `batch_size` images (default B; the images of a chunk are ordered sample, sample-of-the-batch); the forwards of x and of the
+    all-baseline image; one ppf_shap_gram and one ppf_shap_solve launch.  samples = N coalitions per image, even and at least 4 * cells^2
+    (at N = 2 d about half of the systems tried were singular, at 4 d none); cells = s players per side, which must divide the grid side;
+    value: 'prob', the class probability of the curves (ppf_class_prob), or 'logit', the class logit; baseline: what a pixel outside
+    the coalition becomes (a number in normalised space or a tensor like x); seed, image_ids [B] (None: 0 .. B-1) key the coalitions, so
+    an image's coalitions do not depend on its batch.  Nothing image-sized or d^2-sized passes through the host.  Returns a Shap (device
+    tensors; nothing is read back here)."""
+    _shap_check(samples, cells, value, ppnet.num_patches)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("kernel_shap needs a CUDA/HIP batch (no CPU fallback path; shap_coalitions_from_ids / shap_apply / shap_gram / shap_solve "
+                           "with device=False are the host referees)")
+    x = x.float().contiguous()
+    outs = _eval_outputs(ppnet, x)
+    cls = _pick_classes(ppnet, outs, classes, top_classes, x.shape[0])
+    return _shap_from_classes(ppnet, x, cls, samples, cells, value, baseline, seed, image_ids, batch_size, scratch_bytes)
 
 
 # ------------------------------------------------------------------------------------------------ spatial alignment: does a cell's activation depend on its pixels?

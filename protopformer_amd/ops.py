@@ -781,6 +781,105 @@ def rise_accumulate(nodes, shift, prob, size, cells, grid_cells, thr):
     return sal, cell
 
 
+# ---- KernelSHAP cell attributions (csrc/shap.hip): coalitions, masked images, Gram sums, the constrained least-squares solve
+def _shap_coal(who, coal, cells):
+    """(B, N) of coal int32 [B, N, ceil(cells^2 / 32)]: the uint32 words of ppf_shap_coalitions, held as int32 (the same bits)."""
+    Wd = (int(cells) ** 2 + 31) // 32
+    if not isinstance(coal, torch.Tensor) or coal.dim() != 3:
+        raise ValueError(f"{who}: coal must be an int32 CUDA tensor [B, N, {Wd}]")
+    B, N = coal.shape[:2]
+    _dev_tensor(who, "coal", coal, torch.int32, (B, N, Wd))
+    return B, N
+
+
+def shap_coalitions(image_ids, cells, samples, table, seed=0):
+    """coal int32 [B, N, ceil(d / 32)], the membership bits of `samples` coalitions per image (ppf_shap_coalitions, include/ppf_hip.h); one
+    launch.  image_ids int64 [B]; table: the size table, d - 1 integers on the host (interpret.shap_size_table), refused here when it is
+    not non-decreasing or does not end at 2^24."""
+    import numpy as np
+    who = "shap_coalitions"
+    if not isinstance(image_ids, torch.Tensor) or image_ids.dim() != 1:
+        raise ValueError(f"{who}: image_ids must be an int64 CUDA tensor [B]")
+    B, N, s = image_ids.shape[0], int(samples), int(cells)
+    _dev_tensor(who, "image_ids", image_ids, torch.int64, (B,))
+    d = s * s
+    t = np.asarray(table)
+    if t.dtype.kind not in "iu" or t.shape != (max(d - 1, 0),) or t.size == 0 or (np.diff(t.astype(np.int64)) < 0).any() or int(t[-1]) != 1 << 24:
+        raise ValueError(f"{who}: table must hold {d - 1} non-decreasing integers that end at 2^24")
+    table_d = torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(image_ids.device)
+    coal = torch.empty((B, max(N, 0), (d + 31) // 32), dtype=torch.int32, device=image_ids.device)
+    _lib.call("ppf_shap_coalitions", image_ids, int(seed) & 0xFFFFFFFFFFFFFFFF, table_d, B, N, s, coal)
+    return coal
+
+
+def shap_apply(x, coal, cells, n0=0, count=None, baseline=0.0, out=None):
+    """The masked images out fp32 [Nc, B, Cc, H, W] of x fp32 [B, Cc, H, W] under the coalitions n0 .. n0 + count - 1 (default: to the last)
+    of coal (ppf_shap_apply, include/ppf_hip.h); one launch.  baseline: a number, or an fp32 tensor like x."""
+    who = "shap_apply"
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"{who}: x must be an fp32 CUDA tensor [B, Cc, H, W]")
+    _dev_tensor(who, "x", x, torch.float32, x.shape)
+    B, Cc, H, W = x.shape
+    Bn, N = _shap_coal(who, coal, cells)
+    if Bn != B or coal.device != x.device:
+        raise ValueError(f"{who}: coal must be [{B}, N, Wd] on {x.device}, got {list(coal.shape)} on {coal.device}")
+    n0 = int(n0)
+    Nc = N - n0 if count is None else int(count)
+    base_t, base_c = None, 0.0
+    if isinstance(baseline, torch.Tensor):
+        base_t = _dev_tensor(who, "baseline", baseline, torch.float32, x.shape, x.device)
+    else:
+        base_c = float(baseline)
+    shape = (max(Nc, 0), B, Cc, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _dev_tensor(who, "out", out, torch.float32, shape, x.device)
+    _lib.call("ppf_shap_apply", x, coal, N, n0, Nc, int(cells), base_t, base_c, B, Cc, H, W, out)
+    return out
+
+
+def shap_gram(coal, val, v0, cells):
+    """(A int32 [B, d, d], bvec fp64 [B, M, d]) from coal, val fp32 [N, B, M] and v0 fp32 [B, M] (ppf_shap_gram, include/ppf_hip.h); one
+    launch, integer adds and an ascending fp64 sum."""
+    who = "shap_gram"
+    B, N = _shap_coal(who, coal, cells)
+    if not isinstance(val, torch.Tensor) or val.dim() != 3:
+        raise ValueError(f"{who}: val must be an fp32 CUDA tensor [N, B, M]")
+    M, d = val.shape[2], int(cells) ** 2
+    _dev_tensor(who, "val", val, torch.float32, (N, B, M), coal.device)
+    _dev_tensor(who, "v0", v0, torch.float32, (B, M), coal.device)
+    A = torch.empty((B, d, d), dtype=torch.int32, device=coal.device)
+    bvec = torch.empty((B, M, d), dtype=torch.float64, device=coal.device)
+    _lib.call("ppf_shap_gram", coal, val, v0, B, N, M, int(cells), A, bvec)
+    return A, bvec
+
+
+def shap_solve(A, bvec, v0, v1, cells, grid_cells):
+    """(phi fp64 [B, M, d], cell fp32 [B, M, G], bad int32 [B]) from the Gram matrix A int32 [B, d, d], bvec fp64 [B, M, d] and the values
+    v0, v1 fp32 [B, M] of the all-baseline and the whole image (ppf_shap_solve, include/ppf_hip.h); one launch, the factor in the stream's
+    workspace."""
+    who = "shap_solve"
+    s, G = int(cells), int(grid_cells)
+    d = s * s
+    if not isinstance(A, torch.Tensor) or A.dim() != 3:
+        raise ValueError(f"{who}: A must be an int32 CUDA tensor [B, {d}, {d}]")
+    B = A.shape[0]
+    _dev_tensor(who, "A", A, torch.int32, (B, d, d))
+    if not isinstance(bvec, torch.Tensor) or bvec.dim() != 3:
+        raise ValueError(f"{who}: bvec must be an fp64 CUDA tensor [{B}, M, {d}]")
+    M = bvec.shape[1]
+    _dev_tensor(who, "bvec", bvec, torch.float64, (B, M, d), A.device)
+    _dev_tensor(who, "v0", v0, torch.float32, (B, M), A.device)
+    _dev_tensor(who, "v1", v1, torch.float32, (B, M), A.device)
+    phi = torch.empty((B, M, d), dtype=torch.float64, device=A.device)
+    cell = torch.empty((B, M, max(G, 0)), dtype=torch.float32, device=A.device)
+    bad = torch.empty((B,), dtype=torch.int32, device=A.device)
+    ws = _workspace(A.device, max(_lib.lib().ppf_shap_solve_scratch_bytes(B, d), 16))
+    _lib.call("ppf_shap_solve", A, bvec, v0, v1, B, M, s, G, ws, ws.numel(), phi, cell, bad)
+    return phi, cell, bad
+
+
 # ---- "this looks like that, because" (csrc/because.hip): colour transform, bilateral filter, warp, and the score of a perturbed forward
 def _host_f32(who, name, a, n):
     """A host table as a contiguous fp32 numpy array of n entries: the C side takes its address."""
