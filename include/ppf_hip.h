@@ -192,9 +192,13 @@ int ppf_attn_bwd(const void* qkv, const void* out, const void* dout, void* dqkv,
  * covered (head_dim in {32,48,64}, heads in {2,4}, N <= 224, K and V images of all heads within the 160 KiB LDS), else 0.
  * ppf_th_fwd: a16 = bf16 proj_w(softmax(proj_l(scale q k^T))) [B][H][N][NPK], hm = its head mean [B][N][NP] (rollout input, cait:228),
  * rowmax / zinv [B][H][N] = softmax statistics of the mixed logits (saved for backward); out (optional) = the attention output A V,
- * bf16 [B*N][D] (cait:128).
+ * bf16 [B*N][D] (cait:128).  Paddings: N <= NP <= NPK <= 32 ceil(N / 32), NP % 4 == 0, NPK % 8 == 0 -- the kernel zeroes pad columns only up to
+ * the last 32-key trip it visits, so a wider a16 / hm is refused (PPF_ERR_SHAPE), not left partly unwritten.  Every pointer but out must
+ * be non-null (PPF_ERR_ARG).
  * ppf_th_bwd: ds16 = bf16 dS [B][H][N][NPK] from dout = dO [B*N][D]; partial (>= ppf_th_bwd_partial_floats floats) receives one row of
- * parameter-gradient sums per workgroup; ppf_th_param_reduce adds their fixed-order (bit-reproducible) totals to dww, dbw, dbl, dwl. */
+ * parameter-gradient sums per workgroup; N <= NPK <= 16 ceil(N / 16), NPK % 8 == 0 (pad columns are zeroed up to the last 16-key tile; a
+ * wider ds16 is refused); no pointer may be null (PPF_ERR_ARG).  ppf_th_param_reduce adds their fixed-order (bit-reproducible) totals to
+ * dww, dbw, dbl, dwl (none may be null). */
 int ppf_th_fused_supported(int H, int N, int D);
 int ppf_th_fwd(const void* qkv, const float* wl, const float* bl, const float* ww, const float* bw, void* a16, float* hm, float* rowmax,
                float* zinv, void* out, int B, int H, int N, int D, int NP, int NPK, ppf_stream_t stream);
@@ -204,11 +208,13 @@ int ppf_th_bwd(const void* qkv, const void* dout, const float* wl, const float* 
 int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, float* dbw, float* dbl, float* dwl, ppf_stream_t stream);
 /* the three per-head products behind ppf_th_bwd in one launch: dqkv [B*N][3D] bf16 <- dQ_h = scale dS_h K_h | dK_h = scale dS_h^T Q_h |
  * dV_h = A_h^T dO_h from ds16 / a16 [B][H][N][NPK], packed qkv and dout [B*N][D] (ppf_th_grads_supported: N <= 208, head_dim 32/48/64;
+ * any head count H >= 1 with D % H == 0 is accepted: one workgroup per (sample, head); NPK must be N rounded up to 8;
  * a shape it does not cover cannot be trained) */
 int ppf_th_grads_supported(int H, int N, int D);
 int ppf_th_grads(const void* qkv, const void* dout, const void* ds16, const void* a16, void* dqkv, int B, int H, int N, int D, int NPK,
                  ppf_stream_t stream);
-/* class attention: q [B][D] (cls rows, unscaled), k/v [B*N1][D] bf16; policy softmax WITHOUT the identity term (cait:58-59) */
+/* class attention: q [B][D] (cls rows, unscaled), k/v [B*N1][D] bf16; policy softmax WITHOUT the identity term (cait:58-59);
+ * 1 <= H <= 4, 1 <= N1 <= 256, head_dim even and <= 64 (else PPF_ERR_SHAPE); every pointer but policy must be non-null (PPF_ERR_ARG) */
 int ppf_class_attn_fwd(const void* q, const void* k, const void* v, const float* policy, float* attn, float* zinv, float* rowmean,
                        void* out, int B, int H, int N1, int D, ppf_stream_t stream);
 int ppf_class_attn_bwd(const void* q, const void* k, const void* v, const float* attn, const float* zinv, const void* dout, void* dq,

@@ -753,7 +753,10 @@ int ppf_th_fused_supported(int H, int N, int D) {
 int ppf_th_fwd(const void* qkv, const float* wl, const float* bl, const float* ww, const float* bw, void* a16, float* hm, float* rowmax, float* zinv,
                void* out, int B, int H, int N, int D, int NP, int NPK, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && ppf_th_fused_supported(H, N, D), PPF_ERR_SHAPE, "ppf_th_fwd: unsupported shape (B=%d H=%d N=%d D=%d)", B, H, N, D);
-    PPF_CHECK_ARG(NP % 4 == 0 && NPK % 8 == 0 && NPK >= NP && NP >= N && NPK <= 256, PPF_ERR_SHAPE, "ppf_th_fwd: bad padding");
+    // the kernel writes pad columns up to the last 32-key trip it visits: a wider a16 / hm would be left partly unwritten
+    PPF_CHECK_ARG(NP % 4 == 0 && NPK % 8 == 0 && NPK >= NP && NP >= N && NPK <= (N + 31) / 32 * 32, PPF_ERR_SHAPE,
+                  "ppf_th_fwd: bad padding (N=%d NP=%d NPK=%d): N <= NP <= NPK <= 32 ceil(N / 32), NP %% 4 == 0, NPK %% 8 == 0", N, NP, NPK);
+    PPF_CHECK_ARG(qkv && wl && bl && ww && bw && a16 && hm && rowmax && zinv, PPF_ERR_ARG, "ppf_th_fwd: null pointer");
     ThFusedParams p = ThFusedParams(); p.qkv = (const bf16_t*)qkv; p.wl = wl; p.bl = bl; p.ww = ww; p.bw = bw; p.a16 = (bf16_t*)a16; p.hm = hm;
     p.rowmax = rowmax; p.zinv = zinv; p.out = (bf16_t*)out; p.B = B; p.N = N; p.D = D; p.NP = NP; p.NPK = NPK; p.scale = 1.0f / sqrtf((float)(D / H));
     return dispatch_th(D / H, H, "ppf_th_fwd", [&](auto hd, auto hv) {
@@ -770,7 +773,10 @@ size_t ppf_th_bwd_partial_floats(int B, int H, int N) { return (size_t)B * th_gr
 int ppf_th_bwd(const void* qkv, const void* dout, const float* wl, const float* bl, const float* ww, const float* rowmax, const float* zinv, void* ds16,
                float* partial, int B, int H, int N, int D, int NPK, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && ppf_th_fused_supported(H, N, D), PPF_ERR_SHAPE, "ppf_th_bwd: unsupported shape (B=%d H=%d N=%d D=%d)", B, H, N, D);
-    PPF_CHECK_ARG(NPK % 8 == 0 && NPK >= N && NPK <= 256, PPF_ERR_SHAPE, "ppf_th_bwd: bad padding");
+    // the kernel writes pad columns up to the last 16-key tile it visits
+    PPF_CHECK_ARG(NPK % 8 == 0 && NPK >= N && NPK <= (N + 15) / 16 * 16, PPF_ERR_SHAPE,
+                  "ppf_th_bwd: bad padding (N=%d NPK=%d): N <= NPK <= 16 ceil(N / 16), NPK %% 8 == 0", N, NPK);
+    PPF_CHECK_ARG(qkv && dout && wl && bl && ww && rowmax && zinv && ds16 && partial, PPF_ERR_ARG, "ppf_th_bwd: null pointer");
     ThFusedParams p = ThFusedParams(); p.qkv = (const bf16_t*)qkv; p.dout = (const bf16_t*)dout; p.wl = wl; p.bl = bl; p.ww = ww; p.rowmax = (float*)rowmax;
     p.zinv = (float*)zinv; p.ds16 = (bf16_t*)ds16; p.partial = partial; p.B = B; p.N = N; p.D = D; p.NPK = NPK; p.scale = 1.0f / sqrtf((float)(D / H));
     return dispatch_th(D / H, H, "ppf_th_bwd", [&](auto hd, auto hv) {
@@ -805,6 +811,7 @@ int ppf_th_grads(const void* qkv, const void* dout, const void* ds16, const void
 
 int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, float* dbw, float* dbl, float* dwl, hipStream_t stream) {
     PPF_CHECK_ARG(B > 0 && (H == 2 || H == 4) && N > 0, PPF_ERR_SHAPE, "ppf_th_param_reduce: bad shape");
+    PPF_CHECK_ARG(partial && dww && dbw && dbl && dwl, PPF_ERR_ARG, "ppf_th_param_reduce: null pointer");
     const int PW = 2 * H * H + 2 * H;
     return ppf_launch<th_param_reduce_kernel>(dim3(PW), dim3(256), 0, stream, "ppf_th_param_reduce", partial, B * th_groups(N), PW, H, dww, dbw, dbl, dwl);
 }
@@ -813,7 +820,8 @@ int ppf_th_param_reduce(const float* partial, int B, int H, int N, float* dww, f
 // attn [B][H][N1], zinv [B][H], rowmean [B][N1] = mean over heads (the rollout's class-attention row).
 int ppf_class_attn_fwd(const void* q, const void* k, const void* v, const float* policy, float* attn, float* zinv, float* rowmean, void* out,
                        int B, int H, int N1, int D, hipStream_t stream) {
-    PPF_CHECK_ARG(B > 0 && H >= 1 && H <= 4 && N1 <= 256 && D % H == 0 && (D / H) <= 64 && (D / H) % 2 == 0, PPF_ERR_SHAPE, "ppf_class_attn_fwd: bad shape");
+    PPF_CHECK_ARG(B > 0 && H >= 1 && H <= 4 && N1 >= 1 && N1 <= 256 && D % H == 0 && (D / H) <= 64 && (D / H) % 2 == 0, PPF_ERR_SHAPE, "ppf_class_attn_fwd: bad shape");
+    PPF_CHECK_ARG(q && k && v && attn && zinv && rowmean && out, PPF_ERR_ARG, "ppf_class_attn_fwd: null pointer");
     CaParams p = CaParams(); p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.policy = policy; p.attn = attn; p.zinv = zinv;
     p.rowmean = rowmean; p.out = (bf16_t*)out; p.B = B; p.H = H; p.N1 = N1; p.D = D; p.scale = 1.0f / sqrtf((float)(D / H));
     return ppf_launch<class_attn_fwd_kernel>(dim3(B), dim3(256), 0, stream, "ppf_class_attn_fwd", p);
@@ -821,7 +829,8 @@ int ppf_class_attn_fwd(const void* q, const void* k, const void* v, const float*
 
 int ppf_class_attn_bwd(const void* q, const void* k, const void* v, const float* attn, const float* zinv, const void* dout, void* dq, void* dk,
                        void* dv, int B, int H, int N1, int D, hipStream_t stream) {
-    PPF_CHECK_ARG(B > 0 && H >= 1 && H <= 4 && N1 <= 256 && D % H == 0 && (D / H) <= 64 && (D / H) % 2 == 0, PPF_ERR_SHAPE, "ppf_class_attn_bwd: bad shape");
+    PPF_CHECK_ARG(B > 0 && H >= 1 && H <= 4 && N1 >= 1 && N1 <= 256 && D % H == 0 && (D / H) <= 64 && (D / H) % 2 == 0, PPF_ERR_SHAPE, "ppf_class_attn_bwd: bad shape");
+    PPF_CHECK_ARG(q && k && v && attn && zinv && dout && dq && dk && dv, PPF_ERR_ARG, "ppf_class_attn_bwd: null pointer");
     CaParams p = CaParams(); p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.attn = (float*)attn; p.zinv = (float*)zinv;
     p.dout = (const bf16_t*)dout; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.B = B; p.H = H; p.N1 = N1; p.D = D;
     p.scale = 1.0f / sqrtf((float)(D / H));
