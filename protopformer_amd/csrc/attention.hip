@@ -10,18 +10,17 @@
 //   ds_read_b64_tr_b16 (V / K / Q / dO read "transposed": contraction over keys or queries)
 // Kernels:
 //   attn_fwd      O = softmax_policy(Q K^T * scale) V, saves row max and 1/(sum+eps) per (b,h,q)
+//   attn_fwd16    the same forward pass and the head-mean map in one launch (head_dim 64, N <= 208; 16-query geometry)
 //   attn_headmean mean over heads of the probabilities -> (B, N, NP) fp32 (rollout input), recomputed from
 //                 the saved statistics (no B*H*N*N tensor ever exists)
 //   attn_bwd_stream / attn_bwd_onepass   dQ, dK, dV in one launch, every (query tile, key tile) pair visited once
+// The steps the kernels share (score tile, keep flags, the backward's dQ step, piece addressing, bf16 row pieces) are stated once, in front
+// of the kernels.  Where a kernel still writes such a step out, a comment there says what the shared form cost it.
 #include "ppf_common.h"
 #include "ppf_hip.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
-
-constexpr float SOFTMAX_EPS = 1e-6f;     // deit:29 eps
-constexpr float LOG2E = 1.44269504088896340736f;
 
 struct AttnParams {
     const bf16_t* qkv;     // [B*N][ld] : q | k | v at column offsets 0, D, 2D (+ h*HD)
@@ -63,7 +62,55 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& v, int o) {
     u32x4 u = {pack_bf16x2(v[o], v[o + 1]), pack_bf16x2(v[o + 2], v[o + 3]), pack_bf16x2(v[o + 4], v[o + 5]), pack_bf16x2(v[o + 6], v[o + 7])};
     return __builtin_bit_cast(bf16x8, u);
 }
-__device__ __forceinline__ int reg_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    u32x4 u = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
+    return __builtin_bit_cast(bf16x8, u);
+}
+// Four consecutive accumulator registers (group g of a 32x32 tile: rows / keys 8 g + 4 (lane >> 5) .. + 3 of this lane's column) as a float4,
+// and such a group as four bf16 (callers pass scaled values)
+__device__ __forceinline__ float4 group4(const f32x16& v, int g) { return make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]); }
+__device__ __forceinline__ float4 group4(const f32x4& v) { return make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void set_group4(f32x16& v, int g, float4 x) { v[4 * g] = x.x; v[4 * g + 1] = x.y; v[4 * g + 2] = x.z; v[4 * g + 3] = x.w; }
+__device__ __forceinline__ float4 mul4(float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
+__device__ __forceinline__ uint2 pack4(float4 v) { return make_uint2(pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)); }
+// ... into a swizzled tile of bf16 rows: this lane's row, the four values 8 c16 + 4 hh .. + 3 of it
+__device__ __forceinline__ void tile_put4(unsigned char* tile, int row, int c16, int hh, float4 v) {
+    *reinterpret_cast<uint2*>(tile + row_off(row, c16) + 8 * hh) = pack4(v);
+}
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = 0.f;
+    return z;
+}
+// 32 keys (rows row0 .. row0 + 31 of a K tile) x 32 queries (qf: the lane's query row, contraction-contiguous) of unscaled scores
+template <int KS>
+__device__ __forceinline__ f32x16 score_tile32(const unsigned char* tK, int row0, const bf16x8 (&qf)[KS], int lane) {
+    f32x16 s = zero16();
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, row0, ks, lane), qf[ks], s, 0, 0, 0);
+    return s;
+}
+// The frag_rows fragments of one row straight from global memory: 8 values at d = ks*16 + hh*8 of the row at `row`
+template <int KS>
+__device__ __forceinline__ void row_frags_global(bf16x8 (&f)[KS], const bf16_t* row, int hh) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) f[ks] = *reinterpret_cast<const bf16x8*>(row + ks * 16 + hh * 8);
+}
+// Keep flag of a key: the policy's (all ones without a policy), 0 for the padding past N
+__device__ __forceinline__ float keep_flag(const float* policy, int b, int N, int key) {
+    return (key < N) ? (policy ? policy[(size_t)b * N + key] : 1.0f) : 0.0f;
+}
+// "A masked query still attends to itself": qself = the lane's query, or -1 where the rule is off (CaiT class attention)
+__device__ __forceinline__ float keep_at(int key, int qself, float keep) { return (key == qself) ? 1.0f : keep; }
+// LDS-DMA piece addressing (a piece = 1 KiB = rows row0 .. row0 + 7 of an image of 128-byte rows): lane l carries row row0 + (l >> 3), LDS chunk
+// slot (l & 7) whose SOURCE chunk is slot ^ kswz(row).  Rows past N repeat the last valid row (finite).  Byte offset from the first element
+// of the tensor's row 0; ld = its row stride and col = the image's first column, both in bf16.
+__device__ __forceinline__ int dma_piece_offset(int row0, int N, int ld, int col, int lane) {
+    const int r = row0 + (lane >> 3);
+    return (min(r, N - 1) * ld + col) * 2 + (((lane & 7) ^ kswz(r)) << 4);
+}
 
 // Stage ROWS rows (HD bf16 each) from src (row stride ld) into a swizzled LDS tile.  Rows beyond nvalid are
 // zero-filled, or (CLAMP) replicate the last valid row so that padded keys produce finite scores that never
@@ -94,18 +141,6 @@ struct Stage {
         }
     }
 };
-template <int HD, bool CLAMP, int NTHR = 256>
-__device__ __forceinline__ void stage_rows(unsigned char* tile, const bf16_t* src, int ld, int row_begin, int rows, int nvalid, int tid) {
-    constexpr int CH = HD / 8;
-    for (int i = tid; i < rows * CH; i += NTHR) {
-        const int r = i / CH, c = i - r * CH;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        int gr = row_begin + r;
-        if (CLAMP) gr = min(gr, nvalid - 1);
-        if (gr < nvalid) v = *reinterpret_cast<const uint4*>(src + (size_t)gr * ld + c * 8);
-        *reinterpret_cast<uint4*>(tile + row_off(r, c)) = v;
-    }
-}
 
 // One workgroup per (batch, head): K/V are staged ONCE and shared by all query tiles (8 waves when N > 128: the kernels are
 // bound by the K/V/Q traffic and its latency, not by the MFMAs -- profiles/r1_step1_kernel_stats.txt).
@@ -131,9 +166,8 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, Geo<NT>::NW == 8 ? 4 : 2) void attn_
         Stage<HD, NT * 32, NTHR> sk, sv;           // every global load of the prologue in flight before the first LDS write
         sk.template load<true>(base + p.D, p.ld, 0, N, tid);
         sv.template load<false>(base + 2 * p.D, p.ld, 0, N, tid);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(base + (size_t)qc * p.ld + ks * 16 + hh * 8);
-        for (int i = tid; i < NT * 32; i += NTHR) pol[i] = (i < N) ? (p.policy ? p.policy[(size_t)b * N + i] : 1.0f) : 0.0f;
+        row_frags_global<KS>(qf, base + (size_t)qc * p.ld, hh);
+        for (int i = tid; i < NT * 32; i += NTHR) pol[i] = keep_flag(p.policy, b, N, i);
         sk.store(tK, tid);
         sv.store(tV, tid);
     }
@@ -146,30 +180,20 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, Geo<NT>::NW == 8 ? 4 : 2) void attn_
     float mraw = -INFINITY;                      // max of the unscaled scores (scale > 0)
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, t * 32, ks, lane), qf[ks], s, 0, 0, 0);
+        const f32x16 s = score_tile32<KS>(tK, t * 32, qf, lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) mraw = fmaxf(mraw, s[r]);
     }
     mraw = fmaxf(mraw, __shfl_xor(mraw, 32, 64));
     const float mx = mraw * p.scale;
-    const float c1 = p.scale * 1.44269504088896340736f, m1 = mraw * c1;     // exp(x*scale - mx) = exp2(x*c1 - m1)
+    const float c1 = p.scale * LOG2E, m1 = mraw * c1;     // exp(x*scale - mx) = exp2(x*c1 - m1)
     float sum = 0.f;
     f32x16 o[DT];
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    for (int dt = 0; dt < DT; ++dt) o[dt] = zero16();
 #pragma unroll 1
     for (int t = 0; t < NT; ++t) {
-        f32x16 s;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, t * 32, ks, lane), qf[ks], s, 0, 0, 0);
+        f32x16 s = score_tile32<KS>(tK, t * 32, qf, lane);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int key0 = t * 32 + 8 * g + 4 * hh;
@@ -177,8 +201,7 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, Geo<NT>::NW == 8 ? 4 : 2) void attn_
             const float keep[4] = {kp.x, kp.y, kp.z, kp.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float k = (key0 + i == qself) ? 1.0f : keep[i];
-                const float e = __builtin_amdgcn_exp2f(s[4 * g + i] * c1 - m1) * k;
+                const float e = __builtin_amdgcn_exp2f(s[4 * g + i] * c1 - m1) * keep_at(key0 + i, qself, keep[i]);
                 sum += e;
                 s[4 * g + i] = e + c;                 // unnormalised probability (+eps/N); padded keys hit zero V rows
             }
@@ -205,9 +228,7 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, Geo<NT>::NW == 8 ? 4 : 2) void attn_
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = dt * 32 + 8 * g + 4 * hh;
-                if (d < HD)
-                    *reinterpret_cast<uint2*>(orow + d) = make_uint2(pack_bf16x2(o[dt][4 * g] * zi, o[dt][4 * g + 1] * zi),
-                                                                     pack_bf16x2(o[dt][4 * g + 2] * zi, o[dt][4 * g + 3] * zi));
+                if (d < HD) *reinterpret_cast<uint2*>(orow + d) = pack4(mul4(group4(o[dt], g), zi));
             }
     }
 }
@@ -251,8 +272,6 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
     static_assert(HD == 64, "128-byte rows");
     constexpr int KS = HD / 32, DB = HD / 16, ROWS = NT16 * 16, BUF = Fwd16<HD, NT16>::BUF;
     constexpr int NPIECE = 2 * ROWS / 8, PPW = (NPIECE + F16_WAVES - 1) / F16_WAVES;      // 1 KiB pieces (8 rows) of K then V; pieces per wave
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void gbl_void;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds16[];
     float* pol = reinterpret_cast<float*>(lds16 + 2 * BUF);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, l15 = lane & 15;
@@ -272,14 +291,14 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
     const int qself = p.self_keep ? q : -1;
     const float c = p.eps_c, c1 = p.scale * LOG2E;
     // K / V of a head go global -> LDS by LDS-DMA (no staging registers, asynchronous): piece j = wave + 7 i covers rows 8 j' .. 8 j' + 7 of K
-    // (j < ROWS / 8) or V; lane l carries row (l >> 3), LDS chunk slot (l & 7) whose SOURCE chunk is slot ^ kswz(row).  Rows past N repeat
-    // the last valid row (finite; their probabilities are forced to zero below).  Two buffers: head h + 1 lands while head h is multiplied.
+    // (j < ROWS / 8) or V, addressed by dma_piece_offset (the probabilities of the keys past N are forced to zero below).  Two buffers: head
+    // h + 1 lands while head h is multiplied.
     int src_off[PPW], dst_off[PPW];
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
         const int j = min(wave + F16_WAVES * i, NPIECE - 1);
-        const int isv = j >= ROWS / 8 ? 1 : 0, r = (j - isv * (ROWS / 8)) * 8 + (lane >> 3);
-        src_off[i] = (min(r, N - 1) * p.ld + (1 + isv) * p.D) * 2 + (((lane & 7) ^ kswz(r)) << 4);
+        const int isv = j >= ROWS / 8 ? 1 : 0;
+        src_off[i] = dma_piece_offset((j - isv * (ROWS / 8)) * 8, N, p.ld, (1 + isv) * p.D, lane);
         dst_off[i] = j * 1024;
     }
     const unsigned char* gbase = reinterpret_cast<const unsigned char*>(p.qkv + (size_t)b * N * p.ld);
@@ -293,7 +312,9 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
                 lds_dma16_hidden(gbase + src_off[i] + h * HD * 2, lds_base + buf * BUF + __builtin_amdgcn_readfirstlane(dst_off[i]));
     };
     issue(0, 0);
-    for (int i = tid; i < ROWS; i += F16_NTHR) pol[i] = (i < N) ? (p.policy ? p.policy[(size_t)b * N + i] : 1.0f) : 0.0f;
+    for (int i = tid; i < ROWS; i += F16_NTHR) pol[i] = keep_flag(p.policy, b, N, i);
+    // the query row as the second operand of the 16x16x32 products: 8 values at d = 32 ks + 8 grp (written out here and for head h + 1
+    // below: as one lambda the two loads changed the head loop's code)
     bf16x8 qn[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qn[ks] = *reinterpret_cast<const bf16x8*>(p.qkv + ((size_t)b * N + qc) * p.ld + 32 * ks + 8 * grp);
@@ -363,6 +384,8 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
                 for (int i = 0; i < 4; ++i) {
                     const bool real = key0 + i < N;
                     float e = __builtin_amdgcn_exp2f(s[t][i] * c1 - m1);
+                    // (keep_at written out: through the function, by value or by reference, the POLICY instantiations read the keep flags with
+                    //  12 / 26 fewer LDS instructions and <64, 13, true, false> spills 128 bytes instead of 96)
                     if constexpr (POLICY) e *= (key0 + i == qself) ? 1.0f : keep[i];
                     else e = real ? e : 0.f;
                     sum += e;
@@ -402,10 +425,8 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
         for (int tp = 0; tp < (NT16 + 1) / 2; ++tp) {
             constexpr int LAST = NT16 - 1;
             const bool second = 2 * tp + 1 <= LAST;               // compile-time after unrolling
-            typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
             const f32x4 a = s[2 * tp], bq = second ? s[(2 * tp + 1 <= LAST) ? 2 * tp + 1 : LAST] : f32x4{0.f, 0.f, 0.f, 0.f};
-            const u32x4 u = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(bq[0], bq[1]), pack_bf16x2(bq[2], bq[3])};
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, u);
+            const bf16x8 pf = pack8(a, bq);
 #pragma unroll
             for (int db = 0; db < DB; ++db)
                 o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr16(tV, 32 * tp, 16 * db, lane, second), pf, o[db], 0, 0, 0);
@@ -414,7 +435,7 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
             bf16_t* orow = p.out + ((size_t)b * N + q) * p.D + h * HD;
 #pragma unroll
             for (int db = 0; db < DB; ++db)
-                *reinterpret_cast<uint2*>(orow + 16 * db + 4 * grp) = make_uint2(pack_bf16x2(o[db][0] * zi, o[db][1] * zi), pack_bf16x2(o[db][2] * zi, o[db][3] * zi));
+                *reinterpret_cast<uint2*>(orow + 16 * db + 4 * grp) = pack4(mul4(group4(o[db]), zi));
         }
     }
     if (p.headmean && active && q < N) {
@@ -423,7 +444,7 @@ __global__ __launch_bounds__(F16_NTHR, 1) void attn_fwd16_kernel(const AttnParam
 #pragma unroll
         for (int t = 0; t < NT16; ++t) {
             const int key0 = t * 16 + 4 * grp;
-            float4 v = make_float4(mean[t][0] * invH, mean[t][1] * invH, mean[t][2] * invH, mean[t][3] * invH);
+            float4 v = mul4(group4(mean[t]), invH);
             if constexpr (TAIL) {
                 const float cz = czsum * invH;
                 if (t < NT16 - 1) { v.x += cz; v.y += cz; v.z += cz; v.w += cz; }
@@ -450,15 +471,13 @@ __global__ __launch_bounds__(256, 2) void attn_headmean_kernel(const AttnParams 
     const float c = p.eps_c;
     for (int i = tid; i < KT * 32; i += 256) {
         const int key = key_begin + i;
-        pol[i] = (key < N) ? (p.policy ? p.policy[(size_t)b * N + key] : 1.0f) : 0.0f;
+        pol[i] = keep_flag(p.policy, b, N, key);
         cv[i] = (key < N) ? c : 0.0f;
     }
     const int qself = p.self_keep ? q : -1;
     f32x16 acc[KT];
 #pragma unroll
-    for (int t = 0; t < KT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    for (int t = 0; t < KT; ++t) acc[t] = zero16();
     Stage<HD, KT * 32, 256> sk;                     // next head's K tile travels in registers while this head is computed
     sk.template load<true>(p.qkv + (size_t)b * N * p.ld + p.D, p.ld, key_begin, N, tid);
     for (int h = 0; h < p.H; ++h) {
@@ -467,19 +486,14 @@ __global__ __launch_bounds__(256, 2) void attn_headmean_kernel(const AttnParams 
         sk.store(tK, tid);
         __syncthreads();
         bf16x8 qf[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(base + (size_t)qc * p.ld + ks * 16 + hh * 8);
+        row_frags_global<KS>(qf, base + (size_t)qc * p.ld, hh);
         if (h + 1 < p.H) sk.template load<true>(base + HD + p.D, p.ld, key_begin, N, tid);
         if (!active) continue;
         const size_t si = ((size_t)b * p.H + h) * N + qc;
         const float mx = p.rowmax[si], zi = p.zinv[si];
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
-            f32x16 s;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tK, t * 32, ks, lane), qf[ks], s, 0, 0, 0);
+            const f32x16 s = score_tile32<KS>(tK, t * 32, qf, lane);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int kl = t * 32 + 8 * g + 4 * hh;
@@ -488,8 +502,7 @@ __global__ __launch_bounds__(256, 2) void attn_headmean_kernel(const AttnParams 
                 const float keep[4] = {kp.x, kp.y, kp.z, kp.w}, cc[4] = {cq.x, cq.y, cq.z, cq.w};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float k = (key_begin + kl + i == qself) ? 1.0f : keep[i];
-                    acc[t][4 * g + i] += (__expf(s[4 * g + i] * p.scale - mx) * k + cc[i]) * zi;
+                    acc[t][4 * g + i] += (__expf(s[4 * g + i] * p.scale - mx) * keep_at(key_begin + kl + i, qself, keep[i]) + cc[i]) * zi;
                 }
             }
         }
@@ -502,10 +515,37 @@ __global__ __launch_bounds__(256, 2) void attn_headmean_kernel(const AttnParams 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int key = key_begin + t * 32 + 8 * g + 4 * hh;
-                if (key < p.NP)
-                    *reinterpret_cast<float4*>(row + key) = make_float4(acc[t][4 * g] * invH, acc[t][4 * g + 1] * invH, acc[t][4 * g + 2] * invH, acc[t][4 * g + 3] * invH);
+                if (key < p.NP) *reinterpret_cast<float4*>(row + key) = mul4(group4(acc[t], g), invH);
             }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ backward: the dQ step of a pair
+// Both backward kernels decompose the work into (query tile t, key tile w) pairs; wave w keeps its key tile's K^T fragments (ktr) in
+// registers, the dQ accumulators of the query tiles sit in LDS as [dt][g][lane][4] floats (qa = this lane's first group of one tile), and
+// `scr` is the wave's own 4 KiB tile holding dS as bf16 [key][query].
+// dQ^T[d][q] of the pair: K^T (registers) x dS^T (scratch, keys in the contraction slots, queries in the lanes), added to the query tile's
+// accumulator by plain read-modify-write.
+// (The other steps of a pair -- S and dO.V^T, the packed softmax + dS, the dK / dV products, delta -- are written out in each of the two
+//  kernels: as shared functions they compiled attn_bwd_stream_kernel to other code at the same 256 VGPRs and its launches at N = 197 took
+//  153.5-155.3 us against 147.8-150.0 us (profiles/attention_refactor_speed.txt).  What that kernel shares leaves its code unchanged.)
+template <int DT>
+__device__ __forceinline__ void pair_dq(float* qa, const bf16x8 (&ktr)[2][DT], const unsigned char* scr, int lane) {
+    f32x16 dq[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) set_group4(dq[dt], gq, *reinterpret_cast<const float4*>(qa + (dt * 4 + gq) * 256));
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+        const bf16x8 dst = frag_tr(scr, 16 * st, 0, lane);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[st][dt], dst, dq[dt], 0, 0, 0);
+    }
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) *reinterpret_cast<float4*>(qa + (dt * 4 + gq) * 256) = group4(dq[dt], gq);
 }
 
 // ------------------------------------------------------------------------------------------------ backward, one pass
@@ -516,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void attn_headmean_kernel(const AttnParams 
 // the key tiles reach a query tile is fixed (bit-identical from run to run, no atomics).  dS is needed in two layouts (keys in the
 // lanes for dK, queries in the lanes for dQ): it is written once, as bf16 [key][query], into a 4 KiB per-wave scratch tile and read
 // back transposed (ds_read_b64_tr_b16).  Per pair: 20 MFMA 32x32x16 (S, dP, dV, dK, dQ) and ONE softmax evaluation, against 28 and
-// two for the two-phase kernel above.  LDS: Q and dO images (2 x NT x 4 KiB), dQ accumulators (NT x 8 KiB), scratch, row statistics
+// two for the two-phase kernel this one replaced.  LDS: Q and dO images (2 x NT x 4 KiB), dQ accumulators (NT x 8 KiB), scratch, row statistics
 // = 147.5 KiB at NT = 7; K and V never enter LDS except for the one transposed copy of the wave's own K tile.
 template <int HD, int NT>
 struct OnePassLds {
@@ -564,7 +604,7 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, 2) void attn_bwd_onepass_kernel(cons
         for (int i = tid; i < NT * 32; i += NTHR) {
             const size_t si = ((size_t)b * p.H + h) * N + i;
             const float zi = i < N ? p.zinv[si] : 0.f;   // zero => padded queries contribute nothing
-            pol[i] = (i < N) ? (p.policy ? p.policy[(size_t)b * N + i] : 1.0f) : 0.0f;
+            pol[i] = keep_flag(p.policy, b, N, i);
             st_m[i] = i < N ? p.rowmax[si] * LOG2E : 0.f;
             st_z[i] = zi;
             st_cz[i] = p.eps_c * zi;                     // the eps / N term of the policy softmax, per query
@@ -607,17 +647,13 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, 2) void attn_bwd_onepass_kernel(cons
     const float keep_key = row < N ? pol[rc] : 0.f;
     f32x16 dk[DT], dv[DT];
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+    for (int dt = 0; dt < DT; ++dt) { dk[dt] = zero16(); dv[dt] = zero16(); }
 #pragma unroll 1
     for (int i = 0; i < NT; ++i) {
         if (active) {
             int t = wave + i;
             if (t >= NT) t -= NT;
-            f32x16 s, g;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; g[r] = 0.f; }
+            f32x16 s = zero16(), g = zero16();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(tQ, t * 32, ks, lane), kf[ks], s, 0, 0, 0);   // [q][key]
@@ -650,8 +686,7 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, 2) void attn_bwd_onepass_kernel(cons
                     g[r] = po.x; g[r + 1] = po.y;                                  // out[q][key]
                 }
                 // dS as bf16 [key][query] for the transposed read below: this lane's key row, queries 8 gg + 4 hh .. + 3
-                *reinterpret_cast<uint2*>(scr + row_off(l31, gg) + 8 * hh) =
-                    make_uint2(pack_bf16x2(s[4 * gg], s[4 * gg + 1]), pack_bf16x2(s[4 * gg + 2], s[4 * gg + 3]));
+                tile_put4(scr, l31, gg, hh, group4(s, gg));
             }
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
@@ -665,26 +700,7 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, 2) void attn_bwd_onepass_kernel(cons
             // dQ^T[d][q] of this pair: K^T (registers) x dS^T (scratch, keys in the contraction slots, queries in the lanes)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            float* qa = dqacc + t * DQT + lane * 4;
-            f32x16 dq[DT];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const float4 v = *reinterpret_cast<const float4*>(qa + (dt * 4 + gq) * 256);
-                    dq[dt][4 * gq] = v.x; dq[dt][4 * gq + 1] = v.y; dq[dt][4 * gq + 2] = v.z; dq[dt][4 * gq + 3] = v.w;
-                }
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                const bf16x8 dst = frag_tr(scr, 16 * st, 0, lane);
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[st][dt], dst, dq[dt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    *reinterpret_cast<float4*>(qa + (dt * 4 + gq) * 256) = make_float4(dq[dt][4 * gq], dq[dt][4 * gq + 1], dq[dt][4 * gq + 2], dq[dt][4 * gq + 3]);
+            pair_dq<DT>(dqacc + t * DQT + lane * 4, ktr, scr, lane);
         }
         __syncthreads();                           // the next step's owner of each query tile sees this step's sums
     }
@@ -699,13 +715,9 @@ __global__ __launch_bounds__(Geo<NT>::NTHR, 2) void attn_bwd_onepass_kernel(cons
             for (int g = 0; g < 4; ++g) {
                 const int c16 = dt * 4 + g;
                 if (c16 * 8 < HD) {
-                    const float4 q4 = *reinterpret_cast<const float4*>(qa + (dt * 4 + g) * 256);
-                    *reinterpret_cast<uint2*>(tDQ + row_off(row, c16) + 8 * hh) =
-                        make_uint2(pack_bf16x2(q4.x * p.scale, q4.y * p.scale), pack_bf16x2(q4.z * p.scale, q4.w * p.scale));
-                    *reinterpret_cast<uint2*>(tQ + row_off(row, c16) + 8 * hh) =
-                        make_uint2(pack_bf16x2(dk[dt][4 * g] * p.scale, dk[dt][4 * g + 1] * p.scale), pack_bf16x2(dk[dt][4 * g + 2] * p.scale, dk[dt][4 * g + 3] * p.scale));
-                    *reinterpret_cast<uint2*>(tO + row_off(row, c16) + 8 * hh) =
-                        make_uint2(pack_bf16x2(dv[dt][4 * g], dv[dt][4 * g + 1]), pack_bf16x2(dv[dt][4 * g + 2], dv[dt][4 * g + 3]));
+                    tile_put4(tDQ, row, c16, hh, mul4(*reinterpret_cast<const float4*>(qa + c16 * 256), p.scale));
+                    tile_put4(tQ, row, c16, hh, mul4(group4(dk[dt], g), p.scale));
+                    tile_put4(tO, row, c16, hh, group4(dv[dt], g));
                 }
             }
     }
@@ -754,8 +766,6 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
     constexpr int DT = (HD + 31) / 32, KS = HD / 16;
     constexpr int DQT = DT * 4 * 64 * 4;                        // floats of one query tile's dQ accumulator: [dt][g][lane][4]
     constexpr int PPW = 8;                                      // 1 KiB pieces per wave: 4 of the Q image, 4 of the dO image (4 NT each)
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void gbl_void;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     unsigned char* tQ = lds;
     unsigned char* tO = lds + TILE;                            // dO
@@ -784,15 +794,15 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
         const unsigned char* ob = reinterpret_cast<const unsigned char*>(p.dout + (size_t)b * N * p.D + h * HD);
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
-            const int j = wave + NT * (i & 3), r = j * 8 + (lane >> 3);
-            const int off = min(r, N - 1) * (i < 4 ? p.ld : p.D) * 2 + (((lane & 7) ^ kswz(r)) << 4);
+            const int j = wave + NT * (i & 3), off = dma_piece_offset(j * 8, N, i < 4 ? p.ld : p.D, 0, lane);
             // (hidden from the compiler's wait-count pass, see lds_dma16_hidden: with the builtin it put s_waitcnt vmcnt(0) between the issue of
             //  item i + 1's images and the stores of item i's results -- the overlap this kernel is built around never happened)
             lds_dma16_hidden((i < 4 ? qb : ob) + off, lds_base + (i < 4 ? 0 : TILE) + j * 1024);
         }
     };
     // rows of the wave's own tile, MFMA fragment layout (lane -> row l31, 8 values at d = 16 ks + 8 hh): K, V (key tile), O (query tile,
-    // for delta = rowsum(dO * O)) and the softmax statistics of the own query rows
+    // for delta = rowsum(dO * O)) and the softmax statistics of the own query rows.  (K and V written out: through row_frags_global, which
+    // serves the O rows below, this kernel comes out three instructions longer.)
     bf16x8 kf[KS], vf[KS];
     auto load_rows = [&](int item) {
         const int b = item / H, h = item - b * H;
@@ -811,11 +821,7 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
         // ---- own query rows: O (for delta = rowsum(dO * O)) and the softmax statistics; consumed behind the wait for the images
         // (prefetching them one item ahead costs 19 more live registers = spills: measured slower)
         bf16x8 ovf[KS];
-        {
-            const bf16_t* orow = p.out + ((size_t)b * N + rc) * p.D + h * HD + 8 * hh;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) ovf[ks] = *reinterpret_cast<const bf16x8*>(orow + 16 * ks);
-        }
+        row_frags_global<KS>(ovf, p.out + ((size_t)b * N + rc) * p.D + h * HD, hh);
         const size_t si = ((size_t)b * H + h) * N + rc;
         const float s_m = p.rowmax[si], s_z = p.zinv[si];
         const float s_pol = p.policy ? p.policy[(size_t)b * N + rc] : 1.0f;
@@ -863,12 +869,8 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
 
         f32x16 dk[DT], dv[DT];
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+        for (int dt = 0; dt < DT; ++dt) { dk[dt] = zero16(); dv[dt] = zero16(); }
         bf16x8 dsf[2], pf[2];                           // dS and P of the pair between its two halves (bf16: MFMA operands of P2)
-#pragma unroll
-        for (int st = 0; st < 2; ++st) { dsf[st] = kf[0]; pf[st] = kf[0]; }
 
         // P1 of step i: scores, dP, softmax, dS
         auto p1 = [&](int i) {
@@ -910,8 +912,7 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
                     g[r] = po.x; g[r + 1] = po.y;                                  // out[q][key]
                 }
                 // dS as bf16 [key][query] for the transposed read of P2: this lane's key row, queries 8 gg + 4 hh .. + 3
-                *reinterpret_cast<uint2*>(scr + row_off(l31, gg) + 8 * hh) =
-                    make_uint2(pack_bf16x2(s[4 * gg], s[4 * gg + 1]), pack_bf16x2(s[4 * gg + 2], s[4 * gg + 3]));
+                tile_put4(scr, l31, gg, hh, group4(s, gg));
             }
 #pragma unroll
             for (int st = 0; st < 2; ++st) { dsf[st] = pack8(s, 8 * st); pf[st] = pack8(g, 8 * st); }
@@ -928,26 +929,7 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
                     dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(tO, t * 32 + 16 * st, dt * 32, lane), pf[st], dv[dt], 0, 0, 0);
                 }
             // dQ^T[d][q] of this pair: K^T (registers) x dS^T (scratch, keys in the contraction slots, queries in the lanes)
-            float* qa = dqacc + t * DQT + lane * 4;
-            f32x16 dq[DT];
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const float4 v = *reinterpret_cast<const float4*>(qa + (dt * 4 + gq) * 256);
-                    dq[dt][4 * gq] = v.x; dq[dt][4 * gq + 1] = v.y; dq[dt][4 * gq + 2] = v.z; dq[dt][4 * gq + 3] = v.w;
-                }
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                const bf16x8 dst = frag_tr(scr, 16 * st, 0, lane);
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktr[st][dt], dst, dq[dt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq)
-                    *reinterpret_cast<float4*>(qa + (dt * 4 + gq) * 256) = make_float4(dq[dt][4 * gq], dq[dt][4 * gq + 1], dq[dt][4 * gq + 2], dq[dt][4 * gq + 3]);
+            pair_dq<DT>(dqacc + t * DQT + lane * 4, ktr, scr, lane);
         };
 #pragma unroll 1
         for (int i = 0; i < NT; ++i) {
@@ -967,11 +949,11 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
                 for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        float v0, v1, v2, v3;
-                        if (which == 0) { const float4 q4 = *reinterpret_cast<const float4*>(qa + (dt * 4 + g) * 256); v0 = q4.x * p.scale; v1 = q4.y * p.scale; v2 = q4.z * p.scale; v3 = q4.w * p.scale; }
-                        else if (which == 1) { v0 = dk[dt][4 * g] * p.scale; v1 = dk[dt][4 * g + 1] * p.scale; v2 = dk[dt][4 * g + 2] * p.scale; v3 = dk[dt][4 * g + 3] * p.scale; }
-                        else { v0 = dv[dt][4 * g]; v1 = dv[dt][4 * g + 1]; v2 = dv[dt][4 * g + 2]; v3 = dv[dt][4 * g + 3]; }
-                        *reinterpret_cast<uint2*>(scr + row_off(l31, dt * 4 + g) + 8 * hh) = make_uint2(pack_bf16x2(v0, v1), pack_bf16x2(v2, v3));
+                        float4 v;
+                        if (which == 0) v = mul4(*reinterpret_cast<const float4*>(qa + (dt * 4 + g) * 256), p.scale);
+                        else if (which == 1) v = mul4(group4(dk[dt], g), p.scale);
+                        else v = group4(dv[dt], g);
+                        tile_put4(scr, l31, dt * 4 + g, hh, v);
                     }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -988,22 +970,34 @@ __global__ __launch_bounds__(NT * 64, 2) void attn_bwd_stream_kernel(const AttnP
     }
 }
 
+template <int V> using Int = std::integral_constant<int, V>;
+// The head widths the kernels are instantiated for: rc = f(Int<hd>()); false (rc untouched) for any other width
+template <typename F>
+bool for_head_dim(int hd, int& rc, F&& f) {
+    if (hd == 64) rc = f(Int<64>());
+    else if (hd == 48) rc = f(Int<48>());
+    else if (hd == 32) rc = f(Int<32>());
+    else return false;
+    return true;
+}
+// f(Int<head_dim>(), Int<NT>()), NT = the smallest of 1, 2, 4, 7 key tiles of 32 that hold N tokens
 template <typename F>
 int dispatch(int hd, int N, const char* who, F&& f) {
     const int nt = (N + 31) / 32;
-#define PPF_HD_CASE(HDV)                                                         \
-    if (hd == HDV) {                                                             \
-        if (nt <= 1) return f(std::integral_constant<int, HDV>(), std::integral_constant<int, 1>()); \
-        if (nt <= 2) return f(std::integral_constant<int, HDV>(), std::integral_constant<int, 2>()); \
-        if (nt <= 4) return f(std::integral_constant<int, HDV>(), std::integral_constant<int, 4>()); \
-        if (nt <= 7) return f(std::integral_constant<int, HDV>(), std::integral_constant<int, 7>()); \
-    }
-    PPF_HD_CASE(64)
-    PPF_HD_CASE(48)
-    PPF_HD_CASE(32)
-#undef PPF_HD_CASE
+    int rc = PPF_ERR_SHAPE;
+    if (nt <= 7 && for_head_dim(hd, rc, [&](auto hdc) {
+            if (nt <= 1) return f(hdc, Int<1>());
+            if (nt <= 2) return f(hdc, Int<2>());
+            if (nt <= 4) return f(hdc, Int<4>());
+            return f(hdc, Int<7>());
+        }))
+        return rc;
     ppf_set_error("%s: unsupported head_dim=%d / tokens=%d (head_dim in {32,48,64}, tokens <= 224)", who, hd, N);
     return PPF_ERR_SHAPE;
+}
+int check_np(const char* who, int NP, int N) {
+    PPF_CHECK_ARG(NP >= N && NP % 4 == 0 && NP < N + 4, PPF_ERR_SHAPE, "%s: NP=%d must be N rounded up to a multiple of 4", who, NP);
+    return 0;
 }
 
 int fill(AttnParams& p, const void* qkv, int B, int H, int N, int D, const float* policy, float* rowmax, float* zinv, int self_keep, int eps_n, const char* who) {
@@ -1044,24 +1038,23 @@ int ppf_attn_fwd_hm(const void* qkv, void* out, const float* policy, float* rowm
     int rc = fill(p, qkv, B, H, N, D, policy, rowmax, zinv, self_keep, eps_n, "ppf_attn_fwd_hm");
     if (rc) return rc;
     PPF_CHECK_ARG(ppf_attn_fwd_hm_supported(H, N, D), PPF_ERR_SHAPE, "ppf_attn_fwd_hm: head_dim must be 64 and N <= 208 (H=%d N=%d D=%d)", H, N, D);
-    PPF_CHECK_ARG(headmean == nullptr || (NP >= N && NP % 4 == 0 && NP < N + 4), PPF_ERR_SHAPE, "ppf_attn_fwd_hm: NP=%d must be N rounded up to a multiple of 4", NP);
+    if (headmean != nullptr && (rc = check_np("ppf_attn_fwd_hm", NP, N))) return rc;
     p.out = (bf16_t*)out; p.headmean = headmean; p.NP = NP;
     PpfProbeScope probe(PPF_PROBE_ATTN_FWD, stream, 4.0 * B * H * (double)N * N * (D / H),
                         8.0 * B * N * (double)D + 8.0 * B * H * N + (headmean ? 4.0 * B * N * (double)NP : 0.0));
     const int nb = (N + 15) / 16;
     const dim3 grid((nb + F16_WAVES - 1) / F16_WAVES, B);
-    constexpr int lds6 = Fwd16<64, 6>::LDS, lds13 = Fwd16<64, 13>::LDS;
     const dim3 block(F16_NTHR);
-    const char* who = "ppf_attn_fwd_hm";
-    // round 6 (profiles/r6_attn_fwd_packed.txt): the packed softmax where only the last key tile is padded -- 65.8 -> 58.1 us stand-alone, +0.6 % of the step
-    if (N > 96) {
-        if (policy) return ppf_launch<attn_fwd16_kernel<64, 13, true, false>>(grid, block, lds13, stream, who, p);
-        if (N <= 192) return ppf_launch<attn_fwd16_kernel<64, 13, false, false>>(grid, block, lds13, stream, who, p);
-        return ppf_launch<attn_fwd16_kernel<64, 13, false, true>>(grid, block, lds13, stream, who, p);
-    }
-    if (policy) return ppf_launch<attn_fwd16_kernel<64, 6, true, false>>(grid, block, lds6, stream, who, p);
-    if (N > 80) return ppf_launch<attn_fwd16_kernel<64, 6, false, true>>(grid, block, lds6, stream, who, p);
-    return ppf_launch<attn_fwd16_kernel<64, 6, false, false>>(grid, block, lds6, stream, who, p);
+    // NT16 = 6 or 13 key tiles of 16; POLICY when one is given; else TAIL where only the last key tile is padded (N > 16 (NT16 - 1)) --
+    // round 6 (profiles/r6_attn_fwd_packed.txt): the packed softmax, 65.8 -> 58.1 us stand-alone, +0.6 % of the step
+    auto launch = [&](auto nt16c) {
+        constexpr int NT16 = decltype(nt16c)::value, lds = Fwd16<64, NT16>::LDS;
+        const char* who = "ppf_attn_fwd_hm";
+        if (policy) return ppf_launch<attn_fwd16_kernel<64, NT16, true, false>>(grid, block, lds, stream, who, p);
+        if (N > 16 * (NT16 - 1)) return ppf_launch<attn_fwd16_kernel<64, NT16, false, true>>(grid, block, lds, stream, who, p);
+        return ppf_launch<attn_fwd16_kernel<64, NT16, false, false>>(grid, block, lds, stream, who, p);
+    };
+    return N > 96 ? launch(Int<13>()) : launch(Int<6>());
 }
 
 // headmean[B][N][NP] = mean_h probabilities (NP = N rounded up to a multiple of 4; pad columns are written as 0).
@@ -1070,15 +1063,13 @@ int ppf_attn_headmean(const void* qkv, const float* policy, const float* rowmax,
     AttnParams p;
     int rc = fill(p, qkv, B, H, N, D, policy, (float*)rowmax, (float*)zinv, self_keep, eps_n, "ppf_attn_headmean");
     if (rc) return rc;
-    PPF_CHECK_ARG(NP >= N && NP % 4 == 0 && NP < N + 4, PPF_ERR_SHAPE, "ppf_attn_headmean: NP=%d must be N rounded up to a multiple of 4", NP);
+    if ((rc = check_np("ppf_attn_headmean", NP, N))) return rc;
     p.headmean = headmean; p.NP = NP;
-    const int hd = D / H;
     constexpr int KT = 4;
-    dim3 grid((N + 127) / 128, (N + KT * 32 - 1) / (KT * 32), B);
-    if (hd == 64) return ppf_launch<attn_headmean_kernel<64, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
-    if (hd == 48) return ppf_launch<attn_headmean_kernel<48, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
-    if (hd == 32) return ppf_launch<attn_headmean_kernel<32, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p);
-    ppf_set_error("ppf_attn_headmean: unsupported head_dim=%d", hd);
+    const dim3 grid((N + 127) / 128, (N + KT * 32 - 1) / (KT * 32), B);
+    if (for_head_dim(D / H, rc, [&](auto hd) { return ppf_launch<attn_headmean_kernel<decltype(hd)::value, KT>>(grid, dim3(256), 0, stream, "ppf_attn_headmean", p); }))
+        return rc;
+    ppf_set_error("ppf_attn_headmean: unsupported head_dim=%d", D / H);
     return PPF_ERR_SHAPE;
 }
 

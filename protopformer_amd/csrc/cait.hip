@@ -18,8 +18,6 @@
 
 namespace {
 
-constexpr float SOFTMAX_EPS = 1e-6f;
-
 // ------------------------------------------------------------------------------------------------ class attention
 struct CaParams {
     const bf16_t* q;        // [B][D]     (unscaled q projection of the cls row)
@@ -190,7 +188,6 @@ struct ThFusedParams {
     int B, N, D, NP, NPK;
     float scale;
 };
-constexpr float TH_LOG2E = 1.44269504088896340736f;
 constexpr int TH_WAVES = 7, TH_NTHR = TH_WAVES * 64;      // 7 x 16 = 112 queries per workgroup: N = 196 -> 2 workgroups per sample
 
 // [H][N][HD] bf16 image of one third (K or V) of the sample's packed qkv rows; global reads are row-contiguous
@@ -296,9 +293,9 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_fwd_kernel(const ThFusedParams 
             float mt = m[g];
 #pragma unroll
             for (int r = 0; r < 8; ++r) mt = fmaxf(mt, o[g][r]);
-            float acc = l[g] * __builtin_amdgcn_exp2f((m[g] - mt) * TH_LOG2E);
+            float acc = l[g] * __builtin_amdgcn_exp2f((m[g] - mt) * LOG2E);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) acc += __builtin_amdgcn_exp2f((o[g][r] - mt) * TH_LOG2E);
+            for (int r = 0; r < 8; ++r) acc += __builtin_amdgcn_exp2f((o[g][r] - mt) * LOG2E);
             l[g] = acc; m[g] = mt;
         }
     }
@@ -310,10 +307,10 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_fwd_kernel(const ThFusedParams 
         for (int sh = 16; sh <= 32; sh <<= 1) {
             const float mo = __shfl_xor(mm, sh, 64), lo = __shfl_xor(sum, sh, 64);
             const float mn = fmaxf(mm, mo);
-            sum = sum * __builtin_amdgcn_exp2f((mm - mn) * TH_LOG2E) + lo * __builtin_amdgcn_exp2f((mo - mn) * TH_LOG2E);
+            sum = sum * __builtin_amdgcn_exp2f((mm - mn) * LOG2E) + lo * __builtin_amdgcn_exp2f((mo - mn) * LOG2E);
             mm = mn;
         }
-        m2[g] = mm * TH_LOG2E; zi[g] = 1.0f / sum;
+        m2[g] = mm * LOG2E; zi[g] = 1.0f / sum;
         if (grp == 0 && q < N) {
             const size_t si = ((size_t)b * H + g) * N + q;
             p.rowmax[si] = mm; p.zinv[si] = zi[g];
@@ -355,7 +352,7 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_fwd_kernel(const ThFusedParams 
                     float a = blv[g];
 #pragma unroll
                     for (int h = 0; h < H; ++h) a += wl[g][h] * s[u][h][i];
-                    pr[g] = valid ? __builtin_amdgcn_exp2f(a * TH_LOG2E - m2[g]) * zi[g] : 0.f;
+                    pr[g] = valid ? __builtin_amdgcn_exp2f(a * LOG2E - m2[g]) * zi[g] : 0.f;
                 }
                 float mu = 0.f;
 #pragma unroll
@@ -431,7 +428,7 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_bwd_kernel(const ThFusedParams 
     for (int g = 0; g < H; ++g) {
         blv[g] = p.bl[g];
         const size_t si = ((size_t)b * H + g) * N + qc;
-        m2[g] = p.rowmax[si] * TH_LOG2E;
+        m2[g] = p.rowmax[si] * LOG2E;
         zi[g] = qvalid ? p.zinv[si] : 0.f;                                    // padded queries: P = 0
 #pragma unroll
         for (int h = 0; h < H; ++h) { wl[g][h] = p.wl[g * H + h]; ww[g][h] = p.ww[g * H + h]; }
@@ -470,7 +467,7 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_bwd_kernel(const ThFusedParams 
                         float a = blv[g];
 #pragma unroll
                         for (int h = 0; h < H; ++h) a += wl[g][h] * (s[u][h][i] * p.scale);
-                        pr[g] = valid ? __builtin_amdgcn_exp2f(a * TH_LOG2E - m2[g]) * zi[g] : 0.f;
+                        pr[g] = valid ? __builtin_amdgcn_exp2f(a * LOG2E - m2[g]) * zi[g] : 0.f;
                     }
 #pragma unroll
                     for (int h = 0; h < H; ++h) {
@@ -516,7 +513,7 @@ __global__ __launch_bounds__(TH_NTHR, 1) void th_bwd_kernel(const ThFusedParams 
                         float a = blv[g];
 #pragma unroll
                         for (int h = 0; h < H; ++h) a += wl[g][h] * sr[h];
-                        pr[g] = valid ? __builtin_amdgcn_exp2f(a * TH_LOG2E - m2[g]) * zi[g] : 0.f;
+                        pr[g] = valid ? __builtin_amdgcn_exp2f(a * LOG2E - m2[g]) * zi[g] : 0.f;
                         dav[g] = valid ? da[u][g][i] : 0.f;
                     }
 #pragma unroll

@@ -13,6 +13,9 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
+constexpr float SOFTMAX_EPS = 1e-6f;                                  // eps of the policy softmax (deit:29), attention.hip and cait.hip
+constexpr float LOG2E = 1.44269504088896340736f;                      // exp(x) = exp2(x * LOG2E)
+
 #define PPF_ERR_SHAPE (-1)
 #define PPF_ERR_ALIGN (-2)
 #define PPF_ERR_ARG (-3)

@@ -120,7 +120,7 @@ fail here, pass there:
   15. m2 of head 1 shifted by 1e-3 (P_1 scaled by 2**-0.001)            -> 88 tests: 63 fwd, 12 chains, 13 families (not the peaked ones, where P is
                                                                           0 or 1, and bl = +-80 at N = 196 / 100, where r_e carries 4 x 213 u)
 fail in both files, so they do not count as evidence for this one (failures here / there):
-   1. bw added at padded keys (`a = valid ? a : 0` removed)             84 / 5      2. m2 of head 1 taken from m without * TH_LOG2E        94 / 4
+   1. bw added at padded keys (`a = valid ? a : 0` removed)             84 / 5      2. m2 of head 1 taken from m without * LOG2E           94 / 4
    3. dot[h] without its second shuffle                                 90 / 4      4. dbl accumulating pr instead of dsp                  96 / 1
    5. th_grads scaling dV by scale                                      92 / 3      6. th_grads image rows past N filled with 1.0, not 0   76 / 4
    8. the head mean divided by H + 1                                    94 / 2     11. dot[h] multiplied by 1 + 2**-9                       96 / 1
