@@ -412,8 +412,9 @@ int ppf_class_prob(const float* logits, const int* cls, int R, int C, float* pro
  *                      0x80000000, image id low, image id high): a function of (seed, image id, pixel) alone.  Counter word 1 across the
  *                      library: 0 the random cell order, 1 + n < 2^31 the RISE masks, e/4 high (0 below 2^34 elements) the input noise of
  *                      ppf_add_gauss_noise, 0x80000000 ppf_warp_nodes, 0x80000001 + (n >> 1) in [0x80000001, 0xC0000000] the KernelSHAP
- *                      coalitions (ppf_shap_coalitions) -- so this draw is disjoint from the cell order, the RISE masks and the coalitions
- *                      but NOT from ppf_warp_nodes: pixel q and warp node q < (s + 1)^2 <= 289 of the same image under the same seed share
+ *                      coalitions (ppf_shap_coalitions), 0xC0000001 the PartsWorld scene and 0xC0000002 its pixel noise (ppf_synth_scene,
+ *                      ppf_synth_render; the rest of (0xC0000000, 0xFFFFFFFF] is free) -- so this draw is disjoint from the cell order,
+ *                      the RISE masks, the coalitions and PartsWorld but NOT from ppf_warp_nodes: pixel q and warp node q < (s + 1)^2 <= 289 of the same image under the same seed share
  *                      a Philox block (this draw reads word .x, the node's dy).  The two never meet in one computation (a pixel order and
  *                      a shape perturbation of 'because'); a caller who needs them independent gives them different seeds.
  *   ppf_pixel_perturb  ppf_patch_perturb's contract with rank int32 [B][M][n], n = H * W, in place of the cell's rank: out fp32
@@ -871,6 +872,53 @@ int ppf_aug_apply(const void* in_u8, const double* plan_dev, int slot, const voi
 int ppf_aug_sharpness(const void* in_u8, const double* plan_dev, int slot, int B, int H, int W, void* out_u8, ppf_stream_t stream);
 int ppf_aug_affine(const void* in_u8, const double* plan_dev, int slot, int B, int H, int W, int fill_r, int fill_g, int fill_b,
                    void* out_u8, ppf_stream_t stream);
+/* PartsWorld (csrc/synth.hip; the shared arithmetic is csrc/synth_plan.h, checked on the host by tests/synth_plan_check.cpp): a data set
+ * the library renders itself, with classes defined by parts and, per image, the object's box, every part's place and the class table that
+ * says which parts tell two classes apart -- annotations true by construction (the idea of FunnyBirds, Hesse et al., ICCV 2023).  The
+ * reference has no such pass.  Additions of ABI 10: no existing entry point changed.  Integers only, so the numpy referees
+ * (data.partsworld_*) and the kernels agree bit for bit.
+ *   spec      C classes in [2, 1024], K parts per object in [1, 8], D distractors in [0, 8], frame H in [32, 1024], W in [32, 1024] and a
+ *             multiple of 16, g background cells per side in [1, 8], noise amplitude in [0, 32], seed (64 bits).  Both entry points take
+ *             all of them and refuse, before any device call and by name, K, D, C, C > A^K, H, W, W % 16, g, noise, B < 1 and an out or
+ *             partmap that is not 16-byte aligned: PPF_ERR_SHAPE every one of them; a null pointer is PPF_ERR_ARG.
+ *   ids       image ids int64 [B], >= 0.  label = id % C.  (data.PartsWorld: train ids 0 .. n_train - 1, test ids test_id_base + i.)
+ *   classes   A = 24 attributes = shape * 6 + colour; shapes disk, square, diamond, ring; colours red (220, 40, 40), green (40, 180, 60),
+ *             blue (50, 80, 220), yellow (235, 210, 40), magenta (200, 60, 200), cyan (40, 200, 210).  class_parts[c][k] = digit k of c in
+ *             base A: a function of the spec alone, and two classes below A^K differ in a digit; hence C <= A^K.
+ *   draws     Philox4x32-10, key = seed, counter = (item, 0xC0000001, id low, id high); u = word >> 8 is a 24-bit draw and
+ *             range(u, n) = (u * n) >> 24 in [0, n).  Items: 0 the object (x: half-size, y: centre x, z: centre y, w: the part forced
+ *             visible); 1 + k part k (x: visible, y: jitter x, z: jitter y); 9 + 2d distractor d (x: on, y: attribute, z: radius) and
+ *             10 + 2d (x: centre x, y: centre y); 32 + e / 4, word e % 4: channel e % 3 of background node e / 3.
+ *   object    m = min(H, W); hs = 5m/16 + range(u, 13m/32 - 5m/16 + 1); ox = hs + range(u, W - 2 hs), oy likewise with H: the body is the
+ *             square |x - ox| <= hs, |y - oy| <= hs, colour (112, 112, 112); box = (ox - hs, oy - hs, ox + hs + 1, oy + hs + 1), upper
+ *             edges exclusive, inside the frame because 2 hs + 1 <= m.
+ *   parts     pitch p = (2 hs + 1) / 3, jitter j = (p - 1) / 8, radius r = (p - 1) / 2 - j >= 3.  Part k sits on cell (0, 2, 6, 8, 1, 3, 5,
+ *             7)[k] of the 3 x 3 grid of pitch p around (ox, oy) (row-major, the centre cell is left to the body): cx = ox + (cell % 3 - 1)
+ *             * p + range(u, 2j + 1) - j, cy likewise with cell / 3.  Since 2 (r + j) <= p - 1 a part stays in its cell: the parts of one
+ *             object are disjoint and inside the box by construction.  visible = (u < 3 * 2^22) or k == range(u of item 0 w, K): at
+ *             least one part is visible.  attribute = class_parts[label][k].
+ *   others    distractor d: on = u < 2^23, attribute = range(u, 24), r = m/16 + range(u, m/8 - m/16 + 1), cx = r + range(u, W - 2r),
+ *             cy = r + range(u, H - 2r): inside the frame, possibly under the object.  Node channel = 64 + range(u, 128).
+ *   shapes    with dx, dy the offsets from the centre and d2 = dx^2 + dy^2: disk d2 <= r^2; square max(|dx|, |dy|) <= r; diamond
+ *             |dx| + |dy| <= r; ring d2 <= r^2 and not (r^2 / 16 < d2 < r^2 / 4), taken as 16 d2 > r^2 and 4 d2 < r^2: an annulus with
+ *             a centre dot, so every shape contains its centre and lies inside max(|dx|, |dy|) <= r.
+ *   scene     int32 [B][PPF_SYNTH_WORDS]: word 0 the label, 1 .. 4 the box, 5 + 5k .. part k as (visible, cx, cy, r, attribute), 45 + 5d
+ *             .. distractor d as (on, cx, cy, r, attribute), 85 + q node q = i * (g + 1) + j as r | g << 8 | b << 16; the rest zero.
+ *             The table is the annotation.
+ *   pixels    painter's order.  1. background: ch = ceil(H / g), cw = ceil(W / g), i = y / ch, ry = y % ch, j and rx likewise; per
+ *             channel floor(((ch-ry) * ((cw-rx) * n[i][j] + rx * n[i][j+1]) + ry * ((cw-rx) * n[i+1][j] + rx * n[i+1][j+1])) / (ch * cw)).
+ *             2. the distractors that are on, in index order.  3. the body.  4. the visible parts in index order.  Then, when noise > 0,
+ *             per pixel q = y * W + x one Philox call with counter (q, 0xC0000002, id low, id high): channel c gets
+ *             + range(word c >> 8, 2 noise + 1) - noise and is clamped to [0, 255].  A frame depends on (spec, id) alone.
+ *   ppf_synth_scene   scene of ids; one lane per image.
+ *   ppf_synth_render  out uint8 [B][H][W][3] from the scene table (the ids are read for the noise only); partmap uint8 [B][H][W] or NULL:
+ *                     the code of the topmost primitive, 0 background, 1 distractor, 2 body, 3 + k part k.  The caller's buffers hold
+ *                     B * H * W * 3 and B * H * W bytes from the pointers on; nothing else is written.  A lane owns 16 pixels of a row
+ *                     and writes them as three 16-byte stores (the partmap as one); the image's scene row is staged in LDS. */
+#define PPF_SYNTH_WORDS 168
+int ppf_synth_scene(int* scene, const void* ids_i64, int B, int C, int K, int D, int H, int W, int g, int noise, uint64_t seed, ppf_stream_t stream);
+int ppf_synth_render(void* out_u8, void* partmap_u8, const int* scene, const void* ids_i64, int B, int H, int W, int C, int K, int D, int g,
+                     int noise, uint64_t seed, ppf_stream_t stream);
 /* Mixup / CutMix of the device batch (timm 0.5.4 Mixup, tools/engine_proto.py:47-48, main.py:325-335).  The per-sample parameter
  * table is int32 [B][PPF_MIX_WORDS]: kind (0 untouched, 1 blend, 2 box paste), the box rows [yl, yh) and columns [xl, xh), and two
  * fp32 weights stored as their bits.  Sample i is mixed with sample j = B-1-i as it was before the call:

@@ -130,7 +130,10 @@ class PrototypeBank:
 
 # ------------------------------------------------------------------------------------------------ the report
 def image_index(ds):
-    """{image id: (file path, label)} of a data.Cub2011 (its own ids) or of StanfordCars / Dogs (position in the data set)."""
+    """{image id: (file path, label)} of a data.Cub2011 (its own ids) or of StanfordCars / Dogs (position in the data set); a
+    data.PartsWorld has no files: its entries read 'partsworld:<id>'."""
+    if hasattr(ds, "original") and hasattr(ds, "spec"):
+        return {int(i): (f"partsworld:{int(i)}", int(t)) for i, t in zip(ds.ids, ds.labels)}
     if hasattr(ds, "data") and hasattr(ds, "base_folder"):
         return {int(i): (os.path.join(ds.root, ds.base_folder, fp), int(t) - 1) for i, fp, t in ds.data}
     if hasattr(ds, "_samples"):
@@ -172,8 +175,9 @@ def write_bank(out_dir, result, index, ppc, side, patch_size):
     return npz, js
 
 
-def write_gallery(out_dir, result, index, view_transform, side, patch_size, branch="local"):
-    """proto_<p>/rank<r>.jpg: the view-transformed image of every entry with its patch rectangle drawn.  Returns the written paths."""
+def write_gallery(out_dir, result, index, view_transform, side, patch_size, branch="local", original=None):
+    """proto_<p>/rank<r>.jpg: the view-transformed image of every entry with its patch rectangle drawn.  original: image id -> uint8 HWC
+    frame of a data set without files (data.PartsWorld.original); None: the file the index names.  Returns the written paths."""
     from PIL import Image
 
     from .data import default_loader
@@ -181,8 +185,8 @@ def write_gallery(out_dir, result, index, view_transform, side, patch_size, bran
     r, written = result[branch], []
     for p in range(r["values"].shape[0]):
         for k in range(int(r["filled"][p])):
-            path = index[int(r["image_ids"][p, k])][0]
-            view = np.asarray(view_transform(default_loader(path)))
+            iid = int(r["image_ids"][p, k])
+            view = np.asarray(view_transform(Image.fromarray(original(iid)) if original is not None else default_loader(index[iid][0])))
             gp = int(r["grid_pos"][p, k])
             if gp >= 0:
                 x0, y0, x1, y1 = patch_box(gp, side, patch_size)
@@ -224,7 +228,7 @@ def main(args, model=None):
     npz, js = write_bank(args.output_dir, result, index, bank.ppc, bank.side, patch)
     print(f"prototype bank over {len(ds)} {args.split} images: {npz} {js}", flush=True)
     if args.gallery:
-        written = write_gallery(args.output_dir, result, index, ds.transform, bank.side, patch)
+        written = write_gallery(args.output_dir, result, index, ds.transform, bank.side, patch, original=getattr(ds, "original", None))
         print(f"gallery: {len(written)} images under {args.output_dir}", flush=True)
     if args.project:
         n = bank.project_(model)

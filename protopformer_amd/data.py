@@ -380,7 +380,10 @@ def build_dataset(is_train, args, transform=None):
         return StanfordCars(args.data_path, split="train" if is_train else "test", transform=transform), 196
     if args.data_set == "Dogs":
         return Dogs(root=os.path.join(args.data_path, "stanford_dogs"), train=is_train, cropped=False, transform=transform), 120
-    raise NotImplementedError(f"data_set {args.data_set!r}: only CUB2011U / Car / Dogs (scripts/train_{{cub,car,dog}}.sh) are on the path")
+    if args.data_set == "PartsWorld":                    # rendered, not read: the spec is the whole data set
+        spec = partsworld_spec_from_args(args)
+        return PartsWorld(spec, train=is_train, transform=transform), spec.classes
+    raise NotImplementedError(f"data_set {args.data_set!r}: only CUB2011U / Car / Dogs (scripts/train_{{cub,car,dog}}.sh) and PartsWorld are on the path")
 
 
 # ------------------------------------------------------------------------------------------------ GPU finisher + loader
@@ -471,12 +474,19 @@ def device_data_enabled(args):
 class DeviceDataset:
     """The decoded originals of a Cub2011 / StanfordCars / Dogs on the device: one pass with ToUint8HWC as the only transform (CPU workers
     decode, nothing is decoded again), then one flat uint8 buffer of HWC frames, an int64 offset table, an int32 (h, w) table, the labels
-    and, for a data set with return_id, the image ids.  Every rank holds the whole set; samplers keep working on the indices."""
+    and, for a data set with return_id, the image ids.  Every rank holds the whole set; samplers keep working on the indices.
+    A PartsWorld is rendered straight into the flat buffer by ppf_synth_scene + ppf_synth_render, in runs of at most 256 frames: no
+    worker, no decode, no upload; `rendered` says which of the two happened."""
 
     def __init__(self, dataset, device, num_workers=0, max_bytes=64 << 30):
         import copy
         import time
         t0 = time.perf_counter()
+        self.rendered = isinstance(dataset, PartsWorld)
+        if self.rendered:
+            self._render(dataset, device, max_bytes)
+            self.decode_seconds = time.perf_counter() - t0
+            return
         ds = copy.copy(dataset)
         ds.transform = ToUint8HWC()
         with_ids = bool(getattr(ds, "return_id", False))
@@ -512,6 +522,31 @@ class DeviceDataset:
         self.ids = torch.from_numpy(self.ids_host).to(self.device) if with_ids else None
         self.dataset = dataset
         self.decode_seconds = time.perf_counter() - t0
+
+    def _render(self, dataset, device, max_bytes):
+        from . import ops
+        spec, n = dataset.spec, len(dataset)
+        frame = spec.height * spec.width * 3
+        if n * frame > max_bytes:
+            raise RuntimeError(f"DeviceDataset: the {n} rendered frames need {n * frame} bytes, max_bytes is {max_bytes}; there is no fallback: raise "
+                               "max_bytes or use the CPU loader")
+        self.device = torch.device(device)
+        self.sizes_host = np.tile(np.array([[spec.height, spec.width]], dtype=np.int32), (n, 1))
+        self.offsets_host = np.arange(n, dtype=np.int64) * frame
+        self.flat = torch.empty(n * frame, dtype=torch.uint8, device=self.device)
+        self.ids_host = dataset.ids.copy()
+        ids = torch.from_numpy(self.ids_host).to(self.device)
+        for k in range(0, n, 256):                             # rendered in runs of 256 frames; the frame size is a multiple of 16 bytes
+            run = ids[k:k + 256]
+            ops.synth_render(spec, ops.synth_scene(spec, run), run, out=self.flat[k * frame:(k + len(run)) * frame])
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.sizes = torch.from_numpy(self.sizes_host).to(self.device)
+        self.labels_host = dataset.labels.copy()
+        self.labels = torch.from_numpy(self.labels_host).to(self.device)
+        if not getattr(dataset, "return_id", False):
+            self.ids_host, ids = None, None
+        self.ids = ids
+        self.dataset = dataset
 
     def __len__(self):
         return len(self.labels_host)
@@ -955,6 +990,308 @@ def randaugment_apply(frames, plan, fill, device=False):
             _lib.call("ppf_aug_affine", cur, plan_dev, s, B, H, W, fill[0], fill[1], fill[2], nxt)
         cur, nxt = nxt, (cur if cur is not frames else None)
     return cur
+
+
+# ------------------------------------------------------------------------------------------------ PartsWorld
+# A data set the project renders itself: classes are rows of part attributes, and every image knows its object's box, its parts' places
+# and the class table (the idea of FunnyBirds, Hesse et al., ICCV 2023).  The contract is written out in include/ppf_hip.h and the shared
+# arithmetic in csrc/synth_plan.h, whose constants are mirrored here; the functions below are the numpy referees (device=False) of
+# ppf_synth_scene / ppf_synth_render, which equal them bit for bit.  Integers only.
+SYNTH_WORDS = 168                                     # PPF_SYNTH_WORDS of the header
+SYNTH_SHAPES, SYNTH_COLOURS, SYNTH_ATTRS = ("disk", "square", "diamond", "ring"), 6, 24
+SYNTH_PALETTE = np.array([(220, 40, 40), (40, 180, 60), (50, 80, 220), (235, 210, 40), (200, 60, 200), (40, 200, 210)], dtype=np.uint8)
+SYNTH_BODY = np.array((112, 112, 112), dtype=np.uint8)
+SYNTH_BOX, SYNTH_PART0, SYNTH_DIST0, SYNTH_NODE0, SYNTH_PRIM_WORDS = 1, 5, 45, 85, 5          # (on, cx, cy, r, attribute) per primitive
+SYNTH_STREAM_SCENE, SYNTH_STREAM_NOISE = 0xC0000001, 0xC0000002
+SYNTH_ITEM_PART0, SYNTH_ITEM_DIST0, SYNTH_ITEM_NODE0 = 1, 9, 32
+SYNTH_SLOT_CELLS = (0, 2, 6, 8, 1, 3, 5, 7)
+_SPEC_FIELDS = ("classes", "parts", "distractors", "height", "width", "n_train", "n_test", "test_id_base", "seed", "noise", "grid")
+
+
+class PartsWorldSpec:
+    """The settings of a PartsWorld, nothing else: C classes of K parts, D distractors, the frame, the split sizes, the id of the first
+    test image, the seed, the pixel-noise amplitude and the background's cells per side.  Round-trips through JSON."""
+
+    def __init__(self, classes=20, parts=4, distractors=3, height=256, width=256, n_train=4096, n_test=1024, test_id_base=1 << 32, seed=0,
+                 noise=8, grid=4):
+        for k in _SPEC_FIELDS:
+            v = locals()[k]
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"PartsWorldSpec: {k}={v!r} is not an integer")
+            setattr(self, k, int(v))
+        self.validate()
+
+    def validate(self):
+        """Refuses by name what ppf_synth_scene / ppf_synth_render refuse, and what only the data set sees."""
+        C, K = self.classes, self.parts
+        if not 1 <= K <= 8:
+            raise ValueError(f"PartsWorldSpec: parts K={K} outside [1, 8]")
+        if not 0 <= self.distractors <= 8:
+            raise ValueError(f"PartsWorldSpec: distractors D={self.distractors} outside [0, 8]")
+        if not 2 <= C <= 1024:
+            raise ValueError(f"PartsWorldSpec: classes C={C} outside [2, 1024]")
+        if C > SYNTH_ATTRS ** K:
+            raise ValueError(f"PartsWorldSpec: classes C={C} exceed A^K = {SYNTH_ATTRS ** K} rows of K={K} attributes (C > A^K)")
+        if not 32 <= self.height <= 1024:
+            raise ValueError(f"PartsWorldSpec: height H={self.height} outside [32, 1024]")
+        if not 32 <= self.width <= 1024 or self.width % 16:
+            raise ValueError(f"PartsWorldSpec: width W={self.width} outside [32, 1024] or not a multiple of 16")
+        if not 1 <= self.grid <= 8:
+            raise ValueError(f"PartsWorldSpec: grid g={self.grid} outside [1, 8]")
+        if not 0 <= self.noise <= 32:
+            raise ValueError(f"PartsWorldSpec: noise={self.noise} amplitude outside [0, 32]")
+        if self.n_train < 1 or self.n_test < 1 or not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"PartsWorldSpec: n_train={self.n_train}, n_test={self.n_test} must be >= 1 and seed={self.seed} in [0, 2^64)")
+        if self.test_id_base < self.n_train or self.test_id_base + self.n_test > 1 << 62:
+            raise ValueError(f"PartsWorldSpec: test_id_base={self.test_id_base} must leave the train ids 0 .. {self.n_train - 1} alone and stay below 2^62")
+
+    def to_dict(self):
+        return {k: getattr(self, k) for k in _SPEC_FIELDS}
+
+    def to_json(self):
+        import json
+        return json.dumps(self.to_dict())
+
+    @classmethod
+    def from_dict(cls, d):
+        unknown = sorted(set(d) - set(_SPEC_FIELDS))
+        if unknown:
+            raise ValueError(f"PartsWorldSpec: unknown settings {unknown}")
+        return cls(**d)
+
+    @classmethod
+    def from_json(cls, text):
+        import json
+        return cls.from_dict(json.loads(text))
+
+    def __eq__(self, other):
+        return isinstance(other, PartsWorldSpec) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return "PartsWorldSpec(" + ", ".join(f"{k}={getattr(self, k)}" for k in _SPEC_FIELDS) + ")"
+
+
+def partsworld_class_table(spec):
+    """class_parts int32 [C][K]: part k of class c is digit k of c in base A = 24 -- a function of the spec alone, rows pairwise distinct
+    because C <= A^K (PartsWorldSpec.validate refuses anything else)."""
+    spec.validate()
+    c = np.arange(spec.classes, dtype=np.int64)[:, None]
+    return ((c // SYNTH_ATTRS ** np.arange(spec.parts, dtype=np.int64)[None, :]) % SYNTH_ATTRS).astype(np.int32)
+
+
+def _synth_ids(ids):
+    ids = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids, dtype=np.int64).reshape(-1)
+    if (ids < 0).any():
+        raise ValueError("PartsWorld: image ids are >= 0")
+    return ids
+
+
+def _synth_draw(spec, ids, item, stream):
+    """uint64 [..., 4]: the four 24-bit draws of Philox counter (item, stream, id low, id high) under the spec's seed."""
+    from .interpret import philox4x32_10
+    ids = ids.astype(np.uint64)
+    item = np.broadcast_to(np.asarray(item, dtype=np.uint64), ids.shape)
+    ctr = np.stack([item, np.full(ids.shape, stream, dtype=np.uint64), ids & np.uint64(0xFFFFFFFF), ids >> np.uint64(32)], axis=-1)
+    key = np.array([spec.seed & 0xFFFFFFFF, spec.seed >> 32], dtype=np.uint64)
+    return (philox4x32_10(ctr, key) >> np.uint32(8)).astype(np.uint64)
+
+
+def _synth_range(u, n):
+    return ((u * np.asarray(n, dtype=np.int64).astype(np.uint64)) >> np.uint64(24)).astype(np.int64)
+
+
+def _device_ids(ids):
+    if isinstance(ids, torch.Tensor) and ids.is_cuda:
+        return ids
+    return torch.from_numpy(_synth_ids(ids)).cuda()
+
+
+def partsworld_scene_from_ids(spec, ids, device=False):
+    """The scene table int32 [B][SYNTH_WORDS] of image ids (include/ppf_hip.h): label, box, parts, distractors, background nodes -- a pure
+    function of (spec, id), and the annotation.  device=False: the numpy referee; device=True: ppf_synth_scene (a CUDA tensor comes back;
+    no fallback)."""
+    spec.validate()
+    if device:
+        from . import ops
+        return ops.synth_scene(spec, _device_ids(ids))
+    ids = _synth_ids(ids)
+    B, H, W, K = len(ids), spec.height, spec.width, spec.parts
+    scene = np.zeros((B, SYNTH_WORDS), dtype=np.int64)
+    label = (ids % spec.classes).astype(np.int64)
+    scene[:, 0] = label
+    m = min(H, W)
+    wo = _synth_draw(spec, ids, 0, SYNTH_STREAM_SCENE)
+    hs_min, hs_max = 5 * m // 16, 13 * m // 32
+    hs = hs_min + _synth_range(wo[:, 0], hs_max - hs_min + 1)
+    ox, oy = hs + _synth_range(wo[:, 1], W - 2 * hs), hs + _synth_range(wo[:, 2], H - 2 * hs)
+    scene[:, SYNTH_BOX:SYNTH_BOX + 4] = np.stack([ox - hs, oy - hs, ox + hs + 1, oy + hs + 1], axis=1)
+    forced = _synth_range(wo[:, 3], K)
+    p = (2 * hs + 1) // 3
+    j = (p - 1) // 8
+    r = (p - 1) // 2 - j
+    table = partsworld_class_table(spec)
+    for k in range(K):
+        w = _synth_draw(spec, ids, SYNTH_ITEM_PART0 + k, SYNTH_STREAM_SCENE)
+        cell, at = SYNTH_SLOT_CELLS[k], SYNTH_PART0 + SYNTH_PRIM_WORDS * k
+        scene[:, at] = (w[:, 0] < (3 << 22)) | (forced == k)
+        scene[:, at + 1] = ox + (cell % 3 - 1) * p + _synth_range(w[:, 1], 2 * j + 1) - j
+        scene[:, at + 2] = oy + (cell // 3 - 1) * p + _synth_range(w[:, 2], 2 * j + 1) - j
+        scene[:, at + 3] = r
+        scene[:, at + 4] = table[label, k]
+    for d in range(spec.distractors):
+        w0 = _synth_draw(spec, ids, SYNTH_ITEM_DIST0 + 2 * d, SYNTH_STREAM_SCENE)
+        w1 = _synth_draw(spec, ids, SYNTH_ITEM_DIST0 + 2 * d + 1, SYNTH_STREAM_SCENE)
+        at = SYNTH_DIST0 + SYNTH_PRIM_WORDS * d
+        rd = m // 16 + _synth_range(w0[:, 2], m // 8 - m // 16 + 1)
+        scene[:, at] = w0[:, 0] < (1 << 23)
+        scene[:, at + 1] = rd + _synth_range(w1[:, 0], W - 2 * rd)
+        scene[:, at + 2] = rd + _synth_range(w1[:, 1], H - 2 * rd)
+        scene[:, at + 3] = rd
+        scene[:, at + 4] = _synth_range(w0[:, 1], SYNTH_ATTRS)
+    draws = 3 * (spec.grid + 1) ** 2
+    for c4 in range(-(-draws // 4)):
+        w = _synth_draw(spec, ids, SYNTH_ITEM_NODE0 + c4, SYNTH_STREAM_SCENE)
+        for i in range(4):
+            e = 4 * c4 + i
+            if e < draws:
+                scene[:, SYNTH_NODE0 + e // 3] |= (64 + _synth_range(w[:, i], 128)) << (8 * (e % 3))
+    return scene.astype(np.int32)
+
+
+def _synth_inside(shape, dx, dy, r):
+    ax, ay = np.abs(dx), np.abs(dy)
+    d2, r2 = ax * ax + ay * ay, r * r
+    box = (ax <= r) & (ay <= r)
+    if shape == 0:
+        return box & (d2 <= r2)
+    if shape == 1:
+        return box
+    if shape == 2:
+        return box & (ax + ay <= r)
+    return box & (d2 <= r2) & ~((16 * d2 > r2) & (4 * d2 < r2))
+
+
+def _synth_render_np(spec, row, img_id):
+    """(frame uint8 [H][W][3], partmap uint8 [H][W]) of one scene row."""
+    H, W, g = spec.height, spec.width, spec.grid
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.int64), np.arange(W, dtype=np.int64), indexing="ij")
+    row = row.astype(np.int64)
+    L, ch, cw = g + 1, -(-H // g), -(-W // g)
+    i, ry, j, rx = ys // ch, ys % ch, xs // cw, xs % cw
+    nodes = row[SYNTH_NODE0:SYNTH_NODE0 + L * L].reshape(L, L)
+    frame = np.empty((H, W, 3), dtype=np.int64)
+    for c in range(3):
+        n = (nodes >> (8 * c)) & 255
+        frame[..., c] = ((ch - ry) * ((cw - rx) * n[i, j] + rx * n[i, j + 1]) + ry * ((cw - rx) * n[i + 1, j] + rx * n[i + 1, j + 1])) // (ch * cw)
+    top = np.zeros((H, W), dtype=np.uint8)
+
+    def paint(at, code):
+        on, cx, cy, r, attr = (int(v) for v in row[at:at + SYNTH_PRIM_WORDS])
+        if on:
+            a = attr % SYNTH_ATTRS
+            inside = _synth_inside(a // SYNTH_COLOURS, xs - cx, ys - cy, r)
+            frame[inside] = SYNTH_PALETTE[a % SYNTH_COLOURS]
+            top[inside] = code
+    for d in range(spec.distractors):
+        paint(SYNTH_DIST0 + SYNTH_PRIM_WORDS * d, 1)
+    x0, y0, x1, y1 = (int(v) for v in row[SYNTH_BOX:SYNTH_BOX + 4])
+    body = (xs >= x0) & (xs < x1) & (ys >= y0) & (ys < y1)
+    frame[body] = SYNTH_BODY
+    top[body] = 2
+    for k in range(spec.parts):
+        paint(SYNTH_PART0 + SYNTH_PRIM_WORDS * k, 3 + k)
+    if spec.noise > 0:
+        w = _synth_draw(spec, np.full(H * W, img_id, dtype=np.int64), np.arange(H * W, dtype=np.uint64), SYNTH_STREAM_NOISE)
+        frame = np.clip(frame + (_synth_range(w[:, :3], 2 * spec.noise + 1) - spec.noise).reshape(H, W, 3), 0, 255)
+    return frame.astype(np.uint8), top
+
+
+def partsworld_render(spec, scene, ids, device=False, partmap=False):
+    """uint8 [B][H][W][3] frames of a scene table (the ids carry the pixel noise), and with partmap also uint8 [B][H][W], the code of the
+    topmost primitive: 0 background, 1 distractor, 2 body, 3 + k part k.  device=False: the numpy referee; device=True: ppf_synth_render
+    (scene a CUDA int32 tensor or a host table; CUDA tensors come back; no fallback)."""
+    spec.validate()
+    if device:
+        from . import ops
+        ids = _device_ids(ids)
+        if not isinstance(scene, torch.Tensor):
+            scene = torch.from_numpy(np.ascontiguousarray(scene, dtype=np.int32)).to(ids.device)
+        return ops.synth_render(spec, scene, ids, partmap=bool(partmap))
+    ids = _synth_ids(ids)
+    scene = np.asarray(scene.cpu() if isinstance(scene, torch.Tensor) else scene, dtype=np.int32).reshape(len(ids), SYNTH_WORDS)
+    frames = np.empty((len(ids), spec.height, spec.width, 3), dtype=np.uint8)
+    maps = np.empty((len(ids), spec.height, spec.width), dtype=np.uint8)
+    for b, img_id in enumerate(ids):
+        frames[b], maps[b] = _synth_render_np(spec, scene[b], int(img_id))
+    return (frames, maps) if partmap else frames
+
+
+class PartsWorldAnnotation:
+    """What interpret.CubParts offers its callers, from the scene table: id_to_bbox {id: (x0, y0, x1, y1)}, id_to_part_loc {id: [[part id
+    from 1, x, y] of the visible parts]}, part_names {'1': ...}; and image_sizes {id: (W, H)}, class_parts int32 [C][K], n_parts = K, the
+    ids and the scene table itself."""
+
+    def __init__(self, spec, ids, scene):
+        K = spec.parts
+        self.spec, self.ids, self.scene, self.n_parts, self.class_parts = spec, ids, scene, K, partsworld_class_table(spec)
+        self.part_names = {str(k + 1): f"part {k + 1}" for k in range(K)}
+        self.id_to_bbox, self.id_to_part_loc, self.image_sizes = {}, {}, {}
+        for i, row in zip(ids.tolist(), scene.tolist()):
+            self.id_to_bbox[i] = tuple(row[SYNTH_BOX:SYNTH_BOX + 4])
+            parts = (row[SYNTH_PART0 + SYNTH_PRIM_WORDS * k:SYNTH_PART0 + SYNTH_PRIM_WORDS * (k + 1)] for k in range(K))
+            self.id_to_part_loc[i] = [[k + 1, p[1], p[2]] for k, p in enumerate(parts) if p[0]]
+            self.image_sizes[i] = (spec.width, spec.height)
+
+
+class PartsWorld:
+    """A map-style data set like Cub2011 over a PartsWorldSpec: train images have ids 0 .. n_train - 1, test images test_id_base .. ;
+    label = id % C.  __getitem__ renders the frame with the numpy referee and hands it over as a PIL image, so the CPU loaders work as for
+    a file-backed set; DeviceDataset renders the whole set on the device instead.  original(id) and image_size(id) stand in for files."""
+
+    def __init__(self, spec=None, train=True, transform=None, return_id=False):
+        self.spec = spec if spec is not None else PartsWorldSpec()
+        self.spec.validate()
+        self.train, self.transform, self.return_id = bool(train), transform, return_id
+        n, base = (self.spec.n_train, 0) if self.train else (self.spec.n_test, self.spec.test_id_base)
+        self.ids = base + np.arange(n, dtype=np.int64)
+        self.labels = (self.ids % self.spec.classes).astype(np.int64)
+        self._annotation = None
+
+    def __len__(self):
+        return len(self.ids)
+
+    def original(self, img_id):
+        """uint8 [H][W][3]: the frame of image id, as DeviceDataset holds it."""
+        ids = np.array([int(img_id)], dtype=np.int64)
+        return partsworld_render(self.spec, partsworld_scene_from_ids(self.spec, ids), ids)[0]
+
+    def image_size(self, img_id):
+        return (self.spec.width, self.spec.height)
+
+    def __getitem__(self, idx):
+        img_id = int(self.ids[idx])
+        img = Image.fromarray(self.original(img_id))
+        if self.transform is not None:
+            img = self.transform(img)
+        return (img, int(self.labels[idx]), img_id) if self.return_id else (img, int(self.labels[idx]))
+
+    def annotation(self):
+        if self._annotation is None:
+            self._annotation = PartsWorldAnnotation(self.spec, self.ids, partsworld_scene_from_ids(self.spec, self.ids))
+        return self._annotation
+
+
+def partsworld_spec_from_args(args):
+    """args.partsworld when a Python caller set it (a PartsWorldSpec or its dict); else the settings file --data_path names, when that is
+    an existing .json file; else the defaults."""
+    spec = getattr(args, "partsworld", None)
+    if spec is not None:
+        return spec if isinstance(spec, PartsWorldSpec) else PartsWorldSpec.from_dict(dict(spec))
+    path = getattr(args, "data_path", None)
+    if path and str(path).endswith(".json") and os.path.isfile(path):
+        with open(path) as f:
+            return PartsWorldSpec.from_json(f.read())
+    return PartsWorldSpec()
 
 
 # ------------------------------------------------------------------------------------------------ tools/preprocess.py

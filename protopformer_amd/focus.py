@@ -15,7 +15,7 @@ them, so the boxes map linearly (interpret.scaled_boxes); PPF_DEVICE_DATA is hon
 
 writes OUT/focus.json: counts, settings, and overall, per class and (with --protos own) per prototype the measures of
 interpret.focus_summary; with --per-image also OUT/focus.npz, the rows.  For CUB the boxes are bounding_boxes.txt's
-(interpret.CubParts.id_to_bbox); for any other set --boxes names a JSON {image id: [x0, y0, x1, y1]} in pixels of the original files,
+(interpret.CubParts.id_to_bbox), for PartsWorld the rendered objects' own (data.PartsWorld.annotation()); for any other set --boxes names a JSON {image id: [x0, y0, x1, y1]} in pixels of the original files,
 the image id being the image's index in the split's file order.  Nothing GPU-related is imported with the module: the parser works
 anywhere."""
 import json
@@ -68,7 +68,8 @@ def cub_boxes(data_path):
 def summarize(result, args):
     """The JSON record: counts, settings and the measures (keys as strings, NaN as null)."""
     from .tooling import json_clean
-    settings = dict(result.get("settings", {}), split=args.split, data_set=args.data_set, boxes=args.boxes or "bounding_boxes.txt")
+    settings = dict(result.get("settings", {}), split=args.split, data_set=args.data_set,
+                    boxes=args.boxes or ("annotation" if args.data_set == "PartsWorld" else "bounding_boxes.txt"))
     return json_clean(dict(images=int(result["images"]), rows=int(result["rows"]), settings=settings, overall=result["overall"],
                            per_class=dict(sorted(result["per_class"].items())),
                            per_prototype=None if result.get("per_prototype") is None else dict(sorted(result["per_prototype"].items()))))
@@ -81,14 +82,17 @@ def main(args, model=None):
     from .interpret import foreground_focus
     from .tooling import tool_setup, write_json
     model, loader, ds, _ = tool_setup(args, "focus", model, square=True)       # the square view, resident on the device where PPF_DEVICE_DATA says so
+    rendered = args.data_set == "PartsWorld"                    # no files: boxes and sizes are the data set's own annotation
     if args.boxes:
         boxes = read_boxes(args.boxes)
     elif args.data_set == "CUB2011U":
         boxes = cub_boxes(args.data_path)
+    elif rendered:
+        boxes = dict(ds.annotation().id_to_bbox)
     else:
         raise ValueError(f"focus: --boxes FILE.json is needed for data_set {args.data_set!r} (only CUB's annotation is read here)")
-    sizes = {}
-    for i, path in image_files(ds).items():
+    sizes = dict(ds.annotation().image_sizes) if rendered else {}
+    for i, path in ({} if rendered else image_files(ds)).items():
         with Image.open(path) as im:
             sizes[i] = im.size                                  # (width, height) of the original file
     model.eval()

@@ -34,7 +34,8 @@ def get_args_parser():
     a("--batch_size", type=int)
     a("--check_test", type=str2bool, default=False)
     # model
-    a("--data_set", default="CUB2011U", type=str)
+    a("--data_set", default="CUB2011U", type=str, help="CUB2011U (200 classes, 15 parts, read under --data_path), or PartsWorld: the classes, "
+      "parts and annotations of the rendered set (data.PartsWorld); --data_path may then name a settings .json")
     a("--base_architecture", type=str, default="vgg16")
     a("--input_size", default=224, type=int, help="images input size")
     a("--prototype_shape", nargs="+", type=int, default=[2000, 64, 1, 1])
@@ -84,13 +85,18 @@ def main(args, model=None):
     from .tooling import load_for_eval, model_from_args
     device = torch.device("cuda")
     nb_classes, n_parts, half_size, part_thresh = 200, 15, 36, 0.8
+    rendered = args.data_set == "PartsWorld"                  # classes, parts and sizes are the spec's; nothing is read from disk
+    view = D.build_view_transform(args, square=True)          # the reference's Resize((size, size)); GpuFinisher normalises
+    if rendered:
+        ds = D.PartsWorld(D.partsworld_spec_from_args(args), train=False, transform=view, return_id=True)
+        nb_classes, n_parts = ds.spec.classes, ds.spec.parts
     if model is None:
-        model = model_from_args(args, nb_classes, img_size=args.input_size, pretrained=True)
+        model = model_from_args(args, nb_classes, img_size=args.input_size, pretrained=not rendered)
     load_for_eval(model, args, device)
     model.eval()
-    root, meta = cub_dirs(args.data_path)
-    view = D.build_view_transform(args, square=True)          # the reference's Resize((size, size)); GpuFinisher normalises
-    ds = D.Cub2011(root, train=False, transform=view, return_id=True)
+    if not rendered:
+        root, meta = cub_dirs(args.data_path)
+        ds = D.Cub2011(root, train=False, transform=view, return_id=True)
     if D.device_data_enabled(args):                     # the same square bilinear view produced on the device from resident originals
         loader = D.DeviceAugLoader(D.DeviceDataset(ds, device, num_workers=10), args.batch_size, D.GpuFinisher(re_prob=0.0), False, args, square=True)
     else:
@@ -98,9 +104,9 @@ def main(args, model=None):
     if args.check_test:
         acc = E.evaluate_epoch(loader, model, device)
         print(f"test accuracy: {acc['acc1']:.2f}%", flush=True)
-    parts = CubParts(meta)
-    sizes = {}
-    for img_id, fp, _ in ds.data:
+    parts = ds.annotation() if rendered else CubParts(meta)
+    sizes = dict(parts.image_sizes) if rendered else {}
+    for img_id, fp, _ in ([] if rendered else ds.data):
         with Image.open(os.path.join(ds.root, ds.base_folder, fp)) as im:
             sizes[int(img_id)] = im.size                       # (width, height) of the original file
     scores = interpretability_scores(model, loader, parts, sizes, num_classes=nb_classes, part_thresh=part_thresh, half_size=half_size,

@@ -1345,6 +1345,56 @@ def mixup_target(label, table_dev, num_classes, off_value, on_value):
     return t
 
 
+SYNTH_WORDS = _lib.DEFINES["PPF_SYNTH_WORDS"]                                                     # read from include/ppf_hip.h
+
+
+def _synth_words(spec):
+    """(C, K, D, H, W, g, noise, seed) of a data.PartsWorldSpec as the entry points take them."""
+    return (int(spec.classes), int(spec.parts), int(spec.distractors), int(spec.height), int(spec.width), int(spec.grid), int(spec.noise),
+            int(spec.seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def synth_scene(spec, ids):
+    """The scene table int32 [B, SYNTH_WORDS] of image ids int64 [B] under a data.PartsWorldSpec (ppf_synth_scene, include/ppf_hip.h);
+    one launch."""
+    who = "synth_scene"
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+        raise ValueError(f"{who}: ids must be an int64 CUDA tensor [B]")
+    B = ids.shape[0]
+    _dev_tensor(who, "ids", ids, torch.int64, (B,))
+    C, K, D, H, W, g, noise, seed = _synth_words(spec)
+    scene = torch.empty((B, SYNTH_WORDS), dtype=torch.int32, device=ids.device)
+    _lib.call("ppf_synth_scene", scene, ids, B, C, K, D, H, W, g, noise, seed)
+    return scene
+
+
+def synth_render(spec, scene, ids, out=None, partmap=False):
+    """The frames uint8 [B, H, W, 3] of a scene table (ppf_synth_render, include/ppf_hip.h); one launch.  out: a contiguous uint8 CUDA
+    tensor of B * H * W * 3 elements to render into (a slice of a DeviceDataset's flat buffer), any shape; None: a new [B, H, W, 3].
+    partmap: True for a new uint8 [B, H, W], or a tensor of B * H * W elements.  Returns out, or (out, partmap)."""
+    who = "synth_render"
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+        raise ValueError(f"{who}: ids must be an int64 CUDA tensor [B]")
+    B = ids.shape[0]
+    _dev_tensor(who, "ids", ids, torch.int64, (B,))
+    _dev_tensor(who, "scene", scene, torch.int32, (B, SYNTH_WORDS), ids.device)
+    C, K, D, H, W, g, noise, seed = _synth_words(spec)
+
+    def buffer(name, t, shape):
+        n = 1
+        for s in shape:
+            n *= s
+        if t is None:
+            return torch.empty(shape, dtype=torch.uint8, device=ids.device)
+        if not isinstance(t, torch.Tensor) or t.dim() < 1:
+            raise ValueError(f"{who}: {name} must be a uint8 CUDA tensor of {n} elements")
+        return _dev_tensor(who, name, t, torch.uint8, t.shape if t.numel() == n else shape, ids.device)
+    out = buffer("out", out, (B, H, W, 3))
+    pm = None if partmap is False or partmap is None else buffer("partmap", None if partmap is True else partmap, (B, H, W))
+    _lib.call("ppf_synth_render", out, pm, scene, ids, B, H, W, C, K, D, g, noise, seed)
+    return out if pm is None else (out, pm)
+
+
 def sgemm(a, b, out, M, N, K, sam, sak, sbn, sbk, alpha=1.0, beta=0.0):
     ws = _workspace(out.device, 16 * M * N * 4)
     _lib.call("ppf_sgemm", a, b, out, M, N, K, sam, sak, sbn, sbk, out.shape[-1], float(alpha), float(beta), ws, ws.numel() // 4)

@@ -124,7 +124,7 @@ def get_args_parser():
     a("--mixup-mode", type=str, default="batch")
     a("--finetune", default="", help="names the run in the reference's scripts; nothing is loaded from it")
     # data, run
-    a("--data_set", type=str, default="CIFAR100", choices=["CUB2011U", "Car", "Dogs"])
+    a("--data_set", type=str, default="CIFAR100", choices=["CUB2011U", "Car", "Dogs", "PartsWorld"])
     a("--inat-category", type=str, default="name",
       choices=["kingdom", "phylum", "class", "order", "supercategory", "family", "genus", "name"], help="unused")
     a("--output_dir", default="output_kd/test/", help="where logs and checkpoints go; empty: nothing is saved")
