@@ -919,6 +919,46 @@ int ppf_aug_affine(const void* in_u8, const double* plan_dev, int slot, int B, i
 int ppf_synth_scene(int* scene, const void* ids_i64, int B, int C, int K, int D, int H, int W, int g, int noise, uint64_t seed, ppf_stream_t stream);
 int ppf_synth_render(void* out_u8, void* partmap_u8, const int* scene, const void* ids_i64, int B, int H, int W, int C, int K, int D, int g,
                      int noise, uint64_t seed, ppf_stream_t stream);
+/* Part interventions on PartsWorld (csrc/synth.hip, csrc/partcheck.hip; interpret.part_interventions / part_attribution / part_agreement):
+ * the scene table is the render's input, so a row edited and rendered again under the same id is the same image without part k, without
+ * the distractors, or with another class's part -- the noise is keyed by (id, pixel), so only the edited pixels differ (the protocol of
+ * FunnyBirds, Hesse et al., ICCV 2023).  The reference has no such pass.  Additions of ABI 10: no existing entry point changed.
+ *   ppf_synth_edit  scene int32 [B][PPF_SYNTH_WORDS] as ppf_synth_scene writes it; edits int32 [B][E][2] = (op, arg) per image and edit;
+ *                   out int32 [B][E][PPF_SYNTH_WORDS] the edited rows, changed int32 [B][E].  One launch, integers only; the rule is
+ *                   csrc/synth_plan.h's synth_edit_valid / synth_edit_word (checked on the host by tests/synth_edit_check.cpp), and the
+ *                   numpy referee data.partsworld_edit(device=False) agrees bit for bit.  Ops:
+ *                     0 COPY             the row as it is;
+ *                     1 PARTS_OFF        arg a bit mask over the parts: visible := 0 for every part k with bit k set;
+ *                     2 DISTRACTORS_OFF  arg a bit mask over the distractors: on := 0 for the masked ones;
+ *                     3 BACKGROUND       arg = r | g << 8 | b << 16: every one of the (g + 1)^2 nodes takes this colour (a flat background);
+ *                     4 PART_ATTR        arg = k | attr << 8: part k's attribute becomes attr in [0, 24).
+ *                   changed = 1 when the edit alters a word of a primitive that is on before or after the edit, or alters a node; else 0
+ *                   (hiding an invisible part, recolouring an invisible part, an attribute set to its own value).  An edit is invalid
+ *                   when its op is unknown, a mask bit is at or above K (or D), k >= K, attr >= 24, or a colour is above 0xFFFFFF (a
+ *                   negative arg is invalid for every op but COPY): the row is copied unchanged and changed = -1 -- the table lives on
+ *                   the device, so it cannot be refused on the host; ops.synth_edit raises on any -1 after its one read.  An edit list
+ *                   is applied to the SAME row, edit by edit; a chain (the counterfactual: PART_ATTR for every part that differs from
+ *                   another class's row) is a sequence of calls with the previous out as scene, made by the Python wrapper
+ *                   (interpret.part_interventions).  Refused by name: B < 1, E < 1, B * E beyond the grid, K, D, g (PPF_ERR_SHAPE), a null
+ *                   pointer (PPF_ERR_ARG).  C is taken for the spec's sake and checked like ppf_synth_scene's.
+ *   view rule       the square view of S x S pixels of an H x W frame (data.partsworld_view: the bilinear (S, S) resize the eval loaders
+ *                   make) takes the primitive code of view pixel (y, x) from frame pixel (PPF_VIEW_SRC(y, H, S), PPF_VIEW_SRC(x, W, S)):
+ *                   ((2 i + 1) * n) / (2 S) in integers, nearest by pixel centre, always inside the frame.
+ *   ppf_part_mass   score fp32 [R][S][S] (the [B, M, S, S] maps of interpret.pixel_scores; row r belongs to image r / rows_per_img),
+ *                   partmap uint8 [R / rows_per_img][H][W] with codes 0 .. 2 + K.  Per row r and code c in [0, 3 + K):
+ *                   pos[r][c] = sum max(s, 0) and neg[r][c] = sum max(-s, 0) in fp64 over the view pixels whose code (view rule) is c,
+ *                   count[r][c] int32 the number of those pixels.  A non-finite score adds 0 to both sums (its pixel is still counted
+ *                   under its code); a code above 2 + K is added and counted nowhere; nonfinite[r] int32 (or NULL) counts the pixels
+ *                   that are either.  One workgroup per row; lane partials, wave reduction by shuffles, the waves combined in wave
+ *                   order: no floating-point atomics, bit-identical from run to run.  Every term is exact in fp64, so any order is
+ *                   within n * 2^-53 * sum |s| of the exact sum of a bin of n terms.  16-byte score loads when S % 4 == 0 and score is
+ *                   16-byte aligned, single elements otherwise.  Refused by name (PPF_ERR_SHAPE): K outside [1, 8], S < 1, H < 1, W < 1,
+ *                   rows_per_img < 1, R < 1, R % rows_per_img != 0, S * S > 2^31 - 1, H * W > 2^31 - 1; a null pointer other than
+ *                   nonfinite is PPF_ERR_ARG.  The numpy referee is interpret.part_mass(device=False). */
+#define PPF_VIEW_SRC(i, n, S) ((int)(((2 * (int64_t)(i) + 1) * (int64_t)(n)) / (2 * (int64_t)(S))))
+int ppf_synth_edit(int* out, int* changed, const int* scene, const int* edits, int B, int E, int C, int K, int D, int g, ppf_stream_t stream);
+int ppf_part_mass(const float* score, const void* partmap_u8, int R, int rows_per_img, int S, int H, int W, int K, double* pos, double* neg,
+                  int* count, int* nonfinite, ppf_stream_t stream);
 /* Mixup / CutMix of the device batch (timm 0.5.4 Mixup, tools/engine_proto.py:47-48, main.py:325-335).  The per-sample parameter
  * table is int32 [B][PPF_MIX_WORDS]: kind (0 untouched, 1 blend, 2 box paste), the box rows [yl, yh) and columns [xl, xh), and two
  * fp32 weights stored as their bits.  Sample i is mixed with sample j = B-1-i as it was before the call:

@@ -8,6 +8,7 @@
 //     test reads workgroup-uniform words and the primitive loops have the trip counts of the launch (D, K), not of the lane.  A lane owns
 //     16 consecutive pixels of a row: 48 bytes written as three 16-byte stores (byte stores made the table and colour passes of
 //     device_data.hip 3.5 x a copy), the partmap as one 16-byte store.  Painter's order: background, distractors, body, parts, then noise.
+//   * synth_edit_kernel: the interventions.  One workgroup per (image, edit), one lane per word of the row; the rule is synth_plan.h's.
 #include <limits.h>
 
 #include "ppf_common.h"
@@ -166,6 +167,26 @@ __global__ __launch_bounds__(NT_SYNTH) void synth_render_kernel(uint4* __restric
     }
 }
 
+// grid: B * E workgroups of NT_SYNTH threads, one per (image, edit); lane w < SYNTH_WORDS owns word w of the edited row.  The row is staged
+// in LDS because the rule reads the primitive's on-word next to the word it edits.  Latency-bound and not tuned.
+__global__ __launch_bounds__(NT_SYNTH) void synth_edit_kernel(int* __restrict__ out, int* __restrict__ changed, const int* __restrict__ scene,
+                                                              const int* __restrict__ edits, int E, int K, int D, int g) {
+    __shared__ int sc[SYNTH_WORDS];
+    const int be = blockIdx.x, b = be / E, w = threadIdx.x;
+    if (w < SYNTH_WORDS) sc[w] = scene[(size_t)b * SYNTH_WORDS + w];
+    const int op = edits[2 * (size_t)be], arg = edits[2 * (size_t)be + 1];
+    __syncthreads();
+    const bool valid = synth_edit_valid(op, arg, K, D);
+    int differs = 0;
+    if (w < SYNTH_WORDS) {
+        const int v = valid ? synth_edit_word(sc, w, op, arg, K, D, g) : sc[w];
+        out[(size_t)be * SYNTH_WORDS + w] = v;
+        differs = v != sc[w] && synth_edit_live(sc, w, op, arg, K, D, g);
+    }
+    const int any = __syncthreads_or(differs);
+    if (w == 0) changed[be] = valid ? (any ? 1 : 0) : -1;
+}
+
 // The spec words both entry points take, refused by name before any device call.
 int synth_check(const char* who, int B, int C, int K, int D, int H, int W, int g, int noise) {
     PPF_CHECK_ARG(B >= 1, PPF_ERR_SHAPE, "%s: B=%d (>= 1)", who, B);
@@ -205,6 +226,14 @@ int ppf_synth_render(void* out_u8, void* partmap_u8, const int* scene, const voi
     PPF_CHECK_ARG((long long)B * blocks_per_img <= INT_MAX, PPF_ERR_SHAPE, "ppf_synth_render: B=%d x H=%d x W=%d exceeds the grid", B, H, W);
     return ppf_launch<synth_render_kernel>(dim3((unsigned)(B * blocks_per_img)), dim3(NT_SYNTH), 0, stream, "ppf_synth_render", (uint4*)out_u8,
                                            (uint4*)partmap_u8, scene, (const long long*)ids_i64, H, W, K, D, g, noise, seed, blocks_per_img);
+}
+
+int ppf_synth_edit(int* out, int* changed, const int* scene, const int* edits, int B, int E, int C, int K, int D, int g, hipStream_t stream) {
+    if (int rc = synth_check("ppf_synth_edit", B, C, K, D, SYNTH_MIN_SIDE, SYNTH_MIN_SIDE, g, 0)) return rc;   // the frame and the noise are not an edit's business
+    PPF_CHECK_ARG(E >= 1, PPF_ERR_SHAPE, "ppf_synth_edit: E=%d edits per image (>= 1)", E);
+    PPF_CHECK_ARG((long long)B * E <= INT_MAX / SYNTH_WORDS, PPF_ERR_SHAPE, "ppf_synth_edit: B=%d x E=%d rows exceed the grid", B, E);
+    PPF_CHECK_ARG(out && changed && scene && edits, PPF_ERR_ARG, "ppf_synth_edit: null pointer (out, changed, scene, edits)");
+    return ppf_launch<synth_edit_kernel>(dim3((unsigned)(B * E)), dim3(NT_SYNTH), 0, stream, "ppf_synth_edit", out, changed, scene, edits, E, K, D, g);
 }
 
 }  // extern "C"

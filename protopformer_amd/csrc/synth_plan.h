@@ -139,3 +139,41 @@ PPF_HD int synth_spec_fault(int C, int K, int D, int H, int W, int g, int noise)
     if (noise < 0 || noise > SYNTH_MAX_NOISE) return 9;
     return 0;
 }
+
+// ---- scene edits (ppf_synth_edit): one edit (op, arg) applied to a scene row.  synth_edit_valid says whether the edit is one; for a valid
+// edit synth_edit_word gives word w of the edited row from the row itself, so a lane per word needs nothing else; synth_edit_live says
+// whether a difference in word w counts as a change: a node always, a word of a primitive when the primitive is on before or after the
+// edit, nothing else (label and box never differ).  An invalid edit copies the row and reports -1.
+constexpr int SYNTH_EDIT_COPY = 0, SYNTH_EDIT_PARTS_OFF = 1, SYNTH_EDIT_DISTRACTORS_OFF = 2, SYNTH_EDIT_BACKGROUND = 3, SYNTH_EDIT_PART_ATTR = 4;
+constexpr int SYNTH_EDIT_OPS = 5;
+PPF_HD bool synth_edit_valid(int op, int arg, int K, int D) {
+    const uint32_t a = (uint32_t)arg;                                         // a negative arg has bit 31 set: above every mask and colour
+    switch (op) {
+        case SYNTH_EDIT_COPY: return true;
+        case SYNTH_EDIT_PARTS_OFF: return (a >> K) == 0;                      // K <= 8: the shift is defined
+        case SYNTH_EDIT_DISTRACTORS_OFF: return (a >> D) == 0;
+        case SYNTH_EDIT_BACKGROUND: return a <= 0xFFFFFFu;
+        case SYNTH_EDIT_PART_ATTR: return (a & 255u) < (uint32_t)K && (a >> 8) < (uint32_t)SYNTH_ATTRS;
+        default: return false;
+    }
+}
+PPF_HD int synth_edit_word(const int* row, int w, int op, int arg, int K, int D, int g) {
+    const int v = row[w];
+    if (w >= SYNTH_PART0 && w < SYNTH_DIST0) {
+        const int k = (w - SYNTH_PART0) / SYNTH_PRIM_WORDS, f = (w - SYNTH_PART0) - k * SYNTH_PRIM_WORDS;
+        if (op == SYNTH_EDIT_PARTS_OFF && f == SYNTH_ON && k < K && ((arg >> k) & 1)) return 0;
+        if (op == SYNTH_EDIT_PART_ATTR && f == SYNTH_ATTR && k == (arg & 255)) return arg >> 8;
+    } else if (w >= SYNTH_DIST0 && w < SYNTH_NODE0) {
+        const int d = (w - SYNTH_DIST0) / SYNTH_PRIM_WORDS, f = (w - SYNTH_DIST0) - d * SYNTH_PRIM_WORDS;
+        if (op == SYNTH_EDIT_DISTRACTORS_OFF && f == SYNTH_ON && d < D && ((arg >> d) & 1)) return 0;
+    } else if (w >= SYNTH_NODE0 && w < SYNTH_NODE0 + (g + 1) * (g + 1)) {
+        if (op == SYNTH_EDIT_BACKGROUND) return arg;
+    }
+    return v;
+}
+PPF_HD bool synth_edit_live(const int* row, int w, int op, int arg, int K, int D, int g) {
+    if (w >= SYNTH_NODE0) return w < SYNTH_NODE0 + (g + 1) * (g + 1);
+    if (w < SYNTH_PART0) return false;
+    const int on = w - (w - SYNTH_PART0) % SYNTH_PRIM_WORDS + SYNTH_ON;       // SYNTH_DIST0 - SYNTH_PART0 is a multiple of the primitive's words
+    return row[on] != 0 || synth_edit_word(row, on, op, arg, K, D, g) != 0;
+}

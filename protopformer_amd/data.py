@@ -1226,6 +1226,98 @@ def partsworld_render(spec, scene, ids, device=False, partmap=False):
     return (frames, maps) if partmap else frames
 
 
+EDIT_COPY, EDIT_PARTS_OFF, EDIT_DISTRACTORS_OFF, EDIT_BACKGROUND, EDIT_PART_ATTR = range(5)     # the ops of ppf_synth_edit (include/ppf_hip.h)
+
+
+def _edit_valid(op, arg, K, Dn):
+    a = arg & 0xFFFFFFFF                                 # as the rule reads it: a negative arg is above every mask and colour
+    if op == EDIT_COPY:
+        return True
+    if op == EDIT_PARTS_OFF:
+        return a >> K == 0
+    if op == EDIT_DISTRACTORS_OFF:
+        return a >> Dn == 0
+    if op == EDIT_BACKGROUND:
+        return a <= 0xFFFFFF
+    if op == EDIT_PART_ATTR:
+        return (a & 255) < K and (a >> 8) < SYNTH_ATTRS
+    return False
+
+
+def partsworld_edit(spec, scene, edits, device=False, check=True):
+    """(out int32 [B][E][SYNTH_WORDS], changed int32 [B][E]) of a scene table int32 [B][SYNTH_WORDS] and edits int32 [B][E][2] = (op, arg):
+    every edit applied to the image's own row (include/ppf_hip.h, ppf_synth_edit).  changed: 1 when the edit alters a word of a primitive
+    that is on before or after it, or a node; 0 when it alters nothing that is drawn; -1 for an invalid edit, whose row is copied.
+    device=False: the numpy referee (it reports -1 and does not raise); device=True: ops.synth_edit (CUDA tensors come back; with check
+    it raises on any -1 after its one read; no fallback)."""
+    spec.validate()
+    if device:
+        from . import ops
+        dev = scene.device if isinstance(scene, torch.Tensor) and scene.is_cuda else torch.device("cuda")
+        to_dev = lambda t: t if isinstance(t, torch.Tensor) and t.is_cuda else torch.from_numpy(np.ascontiguousarray(t, dtype=np.int32)).to(dev)
+        return ops.synth_edit(spec, to_dev(scene), to_dev(edits), check=check)
+    host = lambda t: np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, dtype=np.int32)
+    scene, edits = host(scene), host(edits)
+    B = scene.shape[0]
+    if scene.shape != (B, SYNTH_WORDS) or edits.ndim != 3 or edits.shape[0] != B or edits.shape[1] < 1 or edits.shape[2] != 2:
+        raise ValueError(f"partsworld_edit: scene must be [B, {SYNTH_WORDS}] and edits [B, E >= 1, 2], got {scene.shape} and {edits.shape}")
+    K, Dn, nodes = spec.parts, spec.distractors, (spec.grid + 1) ** 2
+    E = edits.shape[1]
+    out = np.repeat(scene[:, None, :], E, axis=1).copy()
+    changed = np.zeros((B, E), dtype=np.int32)
+    for b in range(B):
+        for e in range(E):
+            op, arg = int(edits[b, e, 0]), int(edits[b, e, 1])
+            if not _edit_valid(op, arg, K, Dn):
+                changed[b, e] = -1
+                continue
+            row = out[b, e]
+            if op in (EDIT_PARTS_OFF, EDIT_DISTRACTORS_OFF):
+                base = SYNTH_PART0 if op == EDIT_PARTS_OFF else SYNTH_DIST0
+                for k in range(K if op == EDIT_PARTS_OFF else Dn):
+                    if arg >> k & 1:
+                        changed[b, e] |= int(row[base + SYNTH_PRIM_WORDS * k] != 0)       # switching off what is off changes nothing
+                        row[base + SYNTH_PRIM_WORDS * k] = 0
+            elif op == EDIT_BACKGROUND:
+                changed[b, e] = int((row[SYNTH_NODE0:SYNTH_NODE0 + nodes] != arg).any())
+                row[SYNTH_NODE0:SYNTH_NODE0 + nodes] = arg
+            elif op == EDIT_PART_ATTR:
+                at = SYNTH_PART0 + SYNTH_PRIM_WORDS * (arg & 255)
+                changed[b, e] = int(row[at] != 0 and row[at + 4] != arg >> 8)
+                row[at + 4] = arg >> 8
+    return out, changed
+
+
+def partsworld_view_src(i, n, size):
+    """PPF_VIEW_SRC of include/ppf_hip.h: the frame coordinate in [0, n) a view coordinate i in [0, size) takes its primitive code from,
+    ((2 i + 1) n) // (2 size) -- nearest by pixel centre.  Integers (numpy int64 for arrays)."""
+    return ((2 * np.asarray(i, dtype=np.int64) + 1) * int(n)) // (2 * int(size))
+
+
+def partsworld_view_partmap(partmap, size):
+    """uint8 [B][size][size]: the partmap [B][H][W] as the square view of `size` sees it (the view rule)."""
+    pm = np.asarray(partmap.cpu() if isinstance(partmap, torch.Tensor) else partmap, dtype=np.uint8)
+    i = np.arange(size)
+    return pm[:, partsworld_view_src(i, pm.shape[1], size)[:, None], partsworld_view_src(i, pm.shape[2], size)[None, :]]
+
+
+def partsworld_view(spec, frames_u8, size, finisher, workspace=None):
+    """The model's square view fp32 [N, 3, size, size] of rendered frames uint8 [N][H][W][3] on the device: resize_plan over the frames'
+    offsets, resize_crop(device=True, filter=Image.BILINEAR), then the GpuFinisher -- the calls DeviceAugLoader(square=True) makes, so the
+    view of an unedited frame is bit-equal to what that loader yields for the image.  No new kernel.  workspace: a uint8 CUDA scratch
+    tensor to reuse (resize_workspace_bytes says how large; a larger one is made when it is too small)."""
+    H, W = spec.height, spec.width
+    if not (isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
+            and frames_u8.dim() == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3)):
+        raise RuntimeError(f"partsworld_view needs a contiguous uint8 CUDA tensor [N, {H}, {W}, 3] (no CPU fallback path)")
+    if getattr(finisher, "re_prob", 0.0) > 0:
+        raise ValueError("partsworld_view: the finisher must not erase (GpuFinisher(re_prob=0.0)): this is the eval view")
+    N, S = frames_u8.shape[0], int(size)
+    plan = resize_plan(np.arange(N, dtype=np.int64) * (H * W * 3), np.tile(np.array([[H, W]], dtype=np.int32), (N, 1)), [(0, 0, W, H)] * N,
+                       [(S, S)] * N, [(0, 0)] * N, [0] * N)
+    return finisher(resize_crop(frames_u8.reshape(-1), plan, S, S, device=True, workspace=workspace, filter=Image.BILINEAR))
+
+
 class PartsWorldAnnotation:
     """What interpret.CubParts offers its callers, from the scene table: id_to_bbox {id: (x0, y0, x1, y1)}, id_to_part_loc {id: [[part id
     from 1, x, y] of the visible parts]}, part_names {'1': ...}; and image_sizes {id: (W, H)}, class_parts int32 [C][K], n_parts = K, the

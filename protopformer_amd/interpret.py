@@ -6,6 +6,7 @@ CPU-side post-processing restated on numpy / PIL.  OpenCV is not installed in th
 reference uses are written out from their documented definitions (unpinned against cv2 itself, tested for their properties):
 `resize_cubic` = cv2.resize(..., interpolation=INTER_CUBIC) (Keys kernel a = -0.75, half-pixel centres, replicated border),
 `colormap_jet` = cv2.applyColorMap(..., COLORMAP_JET) (BGR), `draw_rect` = cv2.rectangle outline."""
+import math
 import os
 
 import numpy as np
@@ -3039,6 +3040,327 @@ def foreground_focus(ppnet, loader, boxes, image_sizes, protos="own", protos_per
     rows = read_rows(keep, "foreground_focus")                                                             # the one read
     out = focus_summary(rows, meta.img_size, meta.patch, per_prototype=protos == "own")
     out["settings"] = dict(protos=protos, protos_per_image=int(protos_per_image), percentile=percentile, img_size=meta.img_size, patch=meta.patch)
+    if per_image:
+        out["per_image"] = rows
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ part interventions on PartsWorld
+# Every faithfulness number above removes content by painting over it.  On PartsWorld the scene table is the render's input: a row edited
+# (ppf_synth_edit) and rendered again under the same id is the same image without part k, without the distractors or with another class's
+# part, noise included -- so what a part is worth to the model can be measured exactly, and an explanation held to it (the protocol of
+# FunnyBirds, Hesse et al., ICCV 2023).  ppf_part_mass says how much of a score map lies on each primitive, through the view rule of
+# include/ppf_hip.h.  The numpy forms (device=False) are the referees.  The reference has no such pass.
+PART_ORDERS = ("evidence", "attention", "random", "rise", "ig")
+PART_VALUES = ("prob", "logit")
+EDIT_COUNTERFACTUAL = 5             # in Interventions.edits only: the chain of PART_ATTR edits towards class `arg`; ppf_synth_edit never sees it
+
+
+def part_mass(score, partmap, rows_per_img, K, device=True):
+    """(pos fp64 [R, 3 + K], neg fp64 [R, 3 + K], count int32 [R, 3 + K], nonfinite int32 [R]) of score fp32 [R, S, S] (or [B, M, S, S]
+    with rows_per_img = M) and partmap uint8 [R / rows_per_img, H, W]: the sums of max(s, 0) and max(-s, 0) over the view pixels of each
+    primitive code (0 background, 1 distractor, 2 body, 3 + k part k; the view rule of include/ppf_hip.h), the pixels per code, and the
+    pixels that are non-finite (they add 0 and stay counted under their code) or carry a code above 2 + K (counted nowhere else).
+    device=True: one ppf_part_mass launch on CUDA tensors (no fallback); device=False: the numpy referee, its sums exactly rounded (math.fsum)."""
+    if device:
+        from . import ops
+        return ops.part_mass(score.reshape((-1,) + tuple(score.shape[-2:])), partmap, rows_per_img, K)
+    from .data import partsworld_view_partmap
+    s = np.asarray(score.cpu() if isinstance(score, torch.Tensor) else score, dtype=np.float32)
+    s = s.reshape((-1,) + s.shape[-2:])
+    R, S, nb = s.shape[0], s.shape[-1], 3 + int(K)
+    if s.shape[-2] != S or rows_per_img < 1 or R % rows_per_img:
+        raise ValueError(f"part_mass: score must be [R, S, S] with R a multiple of rows_per_img={rows_per_img}, got {s.shape}")
+    codes = partsworld_view_partmap(partmap, S)
+    pos, neg = np.zeros((R, nb), dtype=np.float64), np.zeros((R, nb), dtype=np.float64)
+    count, bad = np.zeros((R, nb), dtype=np.int32), np.zeros(R, dtype=np.int32)
+    for r in range(R):
+        code, fin = codes[r // rows_per_img], np.isfinite(s[r])
+        bad[r] = int((~fin | (code >= nb)).sum())
+        v = np.where(fin, s[r], np.float32(0)).astype(np.float64)
+        for c in range(nb):
+            sel = code == c
+            count[r, c] = int(sel.sum())
+            pos[r, c], neg[r, c] = math.fsum(np.maximum(v[sel], 0.0).tolist()), math.fsum(np.maximum(-v[sel], 0.0).tolist())     # exactly rounded
+    return pos, neg, count, bad
+
+
+class Interventions(Record):
+    """What part_interventions returns, as device tensors (numpy arrays after cpu()): edits int32 [B, E, 2] = (op, arg) as ppf_synth_edit
+    takes them (the counterfactual column reads (EDIT_COUNTERFACTUAL, target class)); changed int32 [B, E]; value fp32 [B, E, M], the
+    probability or the logit of class classes[b, m] on the image of edit e; classes int32 [B, M]; scene int32 [B, SYNTH_WORDS], the unedited
+    table; pred int32 [B, E], the arg-max class on the image of edit e."""
+    FIELDS = ("edits", "changed", "value", "classes", "scene", "pred")
+    META = dict(kind=str)
+
+
+def standard_edits(spec):
+    """The edit list of part_interventions as host rows [(op, arg)], E - 1 = K + 4 of them; the counterfactual follows as the last column.
+    COPY, PARTS_OFF 1 << k for every k, PARTS_OFF of all, DISTRACTORS_OFF of all, BACKGROUND (128, 128, 128)."""
+    from . import data as D
+    K = spec.parts
+    return ([(D.EDIT_COPY, 0)] + [(D.EDIT_PARTS_OFF, 1 << k) for k in range(K)] + [(D.EDIT_PARTS_OFF, (1 << K) - 1)]
+            + [(D.EDIT_DISTRACTORS_OFF, (1 << spec.distractors) - 1), (D.EDIT_BACKGROUND, 128 | 128 << 8 | 128 << 16)])
+
+
+def _counterfactual_rows(spec, scene, ids):
+    """(rows int32 [B, SYNTH_WORDS], changed int32 [B], target int32 [B]): every image's row turned into the row of class (label + 1) % C
+    with the same geometry: PART_ATTR for every part k with the other class's attribute, one ppf_synth_edit call per k on the previous
+    call's rows (where the two classes agree the edit changes nothing).  The chain lives here, not in the kernel."""
+    from . import data as D
+    from . import ops
+    C, K = spec.classes, spec.parts
+    table = torch.from_numpy(D.partsworld_class_table(spec)).to(scene.device)
+    target = ((ids % C + 1) % C).to(torch.int64)
+    rows, changed = scene, torch.zeros(scene.shape[0], dtype=torch.int32, device=scene.device)
+    for k in range(K):
+        arg = (table[target, k].to(torch.int32) << 8) | k
+        edit = torch.stack([torch.full_like(arg, D.EDIT_PART_ATTR), arg], dim=1)[:, None, :].contiguous()
+        out, ch = ops.synth_edit(spec, rows, edit, check=False)
+        rows, changed = out[:, 0].contiguous(), torch.maximum(changed, ch[:, 0])
+    return rows, changed, target.to(torch.int32)
+
+
+@torch.no_grad()
+def part_interventions(ppnet, spec, ids, classes=None, top_classes=1, value="prob", edits=None, batch_size=None, scratch_bytes=1 << 30):
+    """What every edit of the scene is worth to the model, for PartsWorld images ids int64 [B]: ppf_synth_scene, ppf_synth_edit, then
+    ppf_synth_render of the B * E edited rows under ids.repeat_interleave(E) in chunks into one scratch buffer of at most scratch_bytes
+    (one frame at least), data.partsworld_view, the model's forward in groups of batch_size images (default B) and ppf_class_prob (value
+    'prob') or the logit column ('logit').  Nothing image-sized passes through the host; ppnet.precise is honoured.
+    edits None: the standard list, E = K + 5 -- standard_edits(spec), then the counterfactual (the image of class (label + 1) % C with
+    the same geometry and noise, _counterfactual_rows); else int32 [B, E, 2] of ppf_synth_edit's ops (an invalid one raises after the
+    one read of `changed`).  classes: as in explain; None: the top `top_classes` of the unedited image's logits (_pick_classes).
+    Returns an Interventions of device tensors; .cpu() is one host read."""
+    from . import data as D
+    from . import ops
+    if value not in PART_VALUES:
+        raise ValueError(f"part_interventions: value must be one of {PART_VALUES}, got {value!r}")
+    ids = D._device_ids(ids).contiguous()
+    B, H, W, S = ids.shape[0], spec.height, spec.width, int(ppnet.img_size)
+    scene = ops.synth_scene(spec, ids)
+    if edits is None:
+        std = torch.tensor(standard_edits(spec), dtype=torch.int32, device=ids.device)[None].expand(B, -1, -1).contiguous()
+        rows, changed = ops.synth_edit(spec, scene, std, check=False)
+        cf_rows, cf_changed, target = _counterfactual_rows(spec, scene, ids)
+        rows, changed = torch.cat([rows, cf_rows[:, None]], dim=1), torch.cat([changed, cf_changed[:, None]], dim=1)
+        edits = torch.cat([std, torch.stack([torch.full_like(target, EDIT_COUNTERFACTUAL), target], dim=1)[:, None]], dim=1)
+    else:
+        edits = edits if isinstance(edits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(edits, dtype=np.int32))
+        edits = edits.to(device=ids.device, dtype=torch.int32).contiguous()
+        rows, changed = ops.synth_edit(spec, scene, edits, check=True)
+    E = rows.shape[1]
+    rows, ids_rep = rows.reshape(B * E, -1).contiguous(), ids.repeat_interleave(E)
+    finisher, frame = D.GpuFinisher(re_prob=0.0), H * W * 3
+    chunk = _chunk_items(B * E, scratch_bytes, frame)
+    buf, ws = torch.empty(chunk * frame, dtype=torch.uint8, device=ids.device), None
+    Cn = ppnet.last_layer.weight.shape[0]
+    logits = torch.empty((B * E, Cn), dtype=torch.float32, device=ids.device)
+    with ppnet.eval_mode():
+        if classes is None:                               # the predicted class of the unedited image
+            x0 = []
+            for s0 in range(0, B, chunk):
+                n = min(chunk, B - s0)
+                f = ops.synth_render(spec, scene[s0:s0 + n], ids[s0:s0 + n].contiguous(), out=buf[:n * frame])
+                x0.append(D.partsworld_view(spec, f.view(n, H, W, 3), S, finisher))
+            cls = _pick_classes(ppnet, _eval_outputs(ppnet, torch.cat(x0)), None, top_classes, B)
+            del x0
+        else:
+            cls = _explain_classes(classes, B, Cn, ids.device)
+        for s0 in range(0, B * E, chunk):
+            n = min(chunk, B * E - s0)
+            f = ops.synth_render(spec, rows[s0:s0 + n], ids_rep[s0:s0 + n].contiguous(), out=buf[:n * frame])
+            x = D.partsworld_view(spec, f.view(n, H, W, 3), S, finisher)
+            logits[s0:s0 + n] = torch.cat([r.logits for r in forward_groups(ppnet, x, int(batch_size or B))])
+    M = cls.shape[1]
+    cols = cls[:, None, :].expand(B, E, M).reshape(B * E, M)
+    if value == "prob":
+        val = torch.stack([ops.class_prob(logits, cols[:, m].contiguous()) for m in range(M)], dim=1)
+    else:
+        val = torch.where(cols >= 0, logits.gather(1, cols.clamp(min=0).long()), torch.full((), float("nan"), device=ids.device))
+    return Interventions(edits, changed, val.reshape(B, E, M).contiguous(), cls, scene, logits.argmax(1).to(torch.int32).reshape(B, E), kind=value)
+
+
+def _attribution_mass(ppnet, x, outs, partmap, K, cls, order, ids, **order_kwargs):
+    if order not in PART_ORDERS:
+        raise ValueError(f"part_attribution: order must be one of {PART_ORDERS}, got {order!r}"
+                         + (" (the 'shap' players are grid cells: no pixel map is provided, as pixel_scores says)" if order in GAME_ORDERS else ""))
+    score = pixel_scores(ppnet, x, outs, cls, order, image_ids=ids, **order_kwargs)
+    return part_mass(score.contiguous(), partmap, cls.shape[1], K, device=True)
+
+
+@torch.no_grad()
+def part_attribution(ppnet, x, ids, spec, cls, order, **order_kwargs):
+    """(pos, neg fp64 [B * M, 3 + K], count int32 [B * M, 3 + K], nonfinite int32 [B * M]): the mass of the order's pixel map
+    (pixel_scores: 'evidence', 'attention', 'random', 'rise' or 'ig'; 'shap' is refused by name) for the classes cls int32 [B, M] on every
+    primitive of the PartsWorld images ids, x [B, 3, S, S] being their square view.  One eval forward, pixel_scores, one
+    ppf_synth_render(partmap=True) of the ids, one ppf_part_mass.  order_kwargs: baseline, seed, batch_size, scratch_bytes, rise, ig."""
+    from . import data as D
+    from . import ops
+    if order not in PART_ORDERS:
+        _attribution_mass(ppnet, x, None, None, spec.parts, cls, order, None)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4:
+        raise RuntimeError("part_attribution needs a CUDA/HIP batch [B, 3, S, S] (no CPU fallback path; part_mass(device=False) is the host referee)")
+    x, ids = x.float().contiguous(), D._device_ids(ids).contiguous()
+    _, partmap = ops.synth_render(spec, ops.synth_scene(spec, ids), ids, partmap=True)
+    return _attribution_mass(ppnet, x, _eval_outputs(ppnet, x), partmap, spec.parts, cls, order, ids, **order_kwargs)
+
+
+def _avg_ranks(v):
+    """fp64 ranks 1 .. n of v, equal values sharing the mean of their ranks."""
+    v = np.asarray(v, dtype=np.float64)
+    order = np.argsort(v, kind="stable")
+    ranks, sv = np.empty(v.size, dtype=np.float64), v[order]
+    i = 0
+    while i < v.size:
+        j = i
+        while j + 1 < v.size and sv[j + 1] == sv[i]:
+            j += 1
+        ranks[order[i:j + 1]] = (i + j) / 2.0 + 1.0
+        i = j + 1
+    return ranks
+
+
+def spearman(a, b):
+    """Spearman's rho of two vectors (Pearson of the average ranks, fp64); None when there are fewer than two entries or either is constant."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if a.size < 2 or a.size != b.size or (a == a[0]).all() or (b == b[0]).all():
+        return None
+    ra, rb = _avg_ranks(a) - (a.size + 1) / 2.0, _avg_ranks(b) - (b.size + 1) / 2.0
+    return float(_ordered_sum(ra * rb) / np.sqrt(_ordered_sum(ra * ra) * _ordered_sum(rb * rb)))
+
+
+def _descending(key, live):
+    """The live indices by descending key, equal keys by smaller index."""
+    idx = np.flatnonzero(live)
+    return idx[np.argsort(-np.asarray(key, dtype=np.float64)[idx], kind="stable")]
+
+
+def _deletion_area(v0, values, V):
+    """Trapezoid over j / V of the V + 1 values (the unedited one, then after j = 1 .. V parts were hidden), fp64."""
+    c = np.concatenate([[float(v0)], np.asarray(values, dtype=np.float64)[:V]])
+    return float(((c[1:] + c[:-1]) * 0.5).sum() / V)
+
+
+def part_agreement_from_rows(rows):
+    """The report of part_agreement from all rows, on the host (numpy, fp64, image-id order: the result does not depend on the order the
+    rows arrive in).  rows: image_ids [N], labels [N], value fp [N, E], pred [N, E] and changed [N, E] of the standard edit list (E = K + 5:
+    COPY, part k off, all parts off, distractors off, flat background, counterfactual), visible [N, K], class_parts [C, K], view S, and
+    orders {order: dict(pos, neg fp64 [N, 3 + K], count [N, 3 + K], nonfinite [N], deleted fp [N, K])} with deleted[:, j] the value after
+    the j + 1 parts of largest mass were hidden; oracle, reverse [N, K] the same for descending and ascending importance.
+    model: importance[k] = the mean of v - v(part k off) over the images where that edit changed the image (importance_images[k] of
+    them) next to discriminative_parts (the columns of class_parts that are not constant); parts_share = (v - v(all parts off)) / v;
+    distractor_effect, background_effect = |v - v(edit)| and how often the arg-max class changes under each; counterfactual_follows =
+    the share predicted as (label + 1) % C on the counterfactual among the images predicted as their label whose counterfactual differs.
+    per_order: single_deletion = the mean Spearman rho between the signed part mass pos - neg and the importance over an image's visible
+    parts (images where it is undefined are counted, not hidden); top_part_match; mass_share of the positive mass on parts, body,
+    distractors and background next to area_share = count / S^2; part_deletion = the mean areas of the order, the oracle and its reverse
+    and normalised = (A_reverse - A_order) / (A_reverse - A_oracle), None when the denominator is 0."""
+    ids = np.asarray(rows["image_ids"]).reshape(-1)
+    at = np.argsort(ids, kind="stable")
+    take = lambda v: np.asarray(v)[at]
+    value, pred, changed = take(rows["value"]).astype(np.float64), take(rows["pred"]).astype(np.int64), take(rows["changed"]).astype(np.int64)
+    labels, visible = take(rows["labels"]).astype(np.int64), take(rows["visible"]) != 0
+    table, S = np.asarray(rows["class_parts"]), int(rows["view"])
+    N, K, C = ids.size, visible.shape[1], table.shape[0]
+    if value.shape != (N, K + 5):
+        raise ValueError(f"part_agreement_from_rows: value must be [N, K + 5] = [{N}, {K + 5}] (the standard edit list), got {value.shape}")
+    v0, a_all, a_dist, a_bg, a_cf = value[:, 0], K + 1, K + 2, K + 3, K + 4
+    imp = v0[:, None] - value[:, 1:K + 1]                                     # [N, K]
+    live = visible & (changed[:, 1:K + 1] == 1)
+    mean = lambda v: _ordered_mean(v)[0]
+    eligible = (pred[:, 0] == labels) & (changed[:, a_cf] == 1)
+    model = dict(importance=[mean(imp[live[:, k], k]) for k in range(K)], importance_images=[int(live[:, k].sum()) for k in range(K)],
+                 discriminative_parts=[int(k) for k in range(K) if (table[:, k] != table[0, k]).any()],
+                 parts_share=_ratio_mean(v0 - value[:, a_all], v0)[0],
+                 distractor_effect=mean(np.abs(v0 - value[:, a_dist])), background_effect=mean(np.abs(v0 - value[:, a_bg])),
+                 distractor_changes_prediction=mean(pred[:, a_dist] != pred[:, 0]), background_changes_prediction=mean(pred[:, a_bg] != pred[:, 0]),
+                 accuracy=mean(pred[:, 0] == labels), counterfactual_images=int(eligible.sum()),
+                 counterfactual_follows=mean(pred[eligible, a_cf] == (labels[eligible] + 1) % C))
+    nvis = live.sum(1)
+    areas = lambda dv: np.array([_deletion_area(v0[i], dv[i], nvis[i]) for i in range(N) if nvis[i] > 0], dtype=np.float64)
+    a_oracle, a_reverse = mean(areas(take(rows["oracle"]))), mean(areas(take(rows["reverse"])))
+    per_order = {}
+    for order, f in rows["orders"].items():
+        pos, neg, cnt = take(f["pos"]).astype(np.float64), take(f["neg"]).astype(np.float64), take(f["count"]).astype(np.float64)
+        signed = pos[:, 3:] - neg[:, 3:]
+        rho, undefined, match = [], 0, []
+        for i in range(N):
+            k = np.flatnonzero(live[i])
+            r = spearman(signed[i, k], imp[i, k])
+            undefined += r is None
+            rho += [] if r is None else [r]
+            if k.size:
+                match.append(_descending(signed[i], live[i])[0] == _descending(imp[i], live[i])[0])
+        total = pos.sum(1)
+        groups = dict(parts=pos[:, 3:].sum(1), body=pos[:, 2], distractors=pos[:, 1], background=pos[:, 0])
+        area = dict(parts=cnt[:, 3:].sum(1), body=cnt[:, 2], distractors=cnt[:, 1], background=cnt[:, 0])
+        a_order = mean(areas(take(f["deleted"])))
+        den = None if a_oracle is None or a_reverse is None else a_reverse - a_oracle
+        per_order[order] = dict(
+            single_deletion=mean(rho), defined=len(rho), undefined=int(undefined), top_part_match=mean(match),
+            mass_share={g: _ratio_mean(v, total)[0] for g, v in groups.items()}, zero_mass_images=int((total <= 0).sum()),
+            area_share={g: mean(v / float(S * S)) for g, v in area.items()}, distractor_mass=_ratio_mean(groups["distractors"], total)[0],
+            distractor_effect=model["distractor_effect"], nonfinite_images=int((take(f["nonfinite"]) > 0).sum()),
+            part_deletion=dict(order=a_order, oracle=a_oracle, reverse=a_reverse, normalised=None if not den else (a_reverse - a_order) / den))
+    return dict(images=int(N), parts=int(K), model=model, per_order=per_order)
+
+
+def _cumulative_masks(key, live):
+    """int32 [B, K] PARTS_OFF masks: entry j hides the j + 1 live parts of largest key (equal keys: the smaller k); the parts that are not
+    live follow (hiding them changes nothing), so entry V - 1 and every later one hide all V live parts."""
+    k = torch.where(live, key.double(), torch.full((), float("-inf"), dtype=torch.float64, device=key.device))
+    order = torch.sort(k, dim=1, descending=True, stable=True)[1]
+    return torch.cumsum(torch.ones_like(order) << order, dim=1).to(torch.int32)        # distinct bits: the sum is the union
+
+
+@torch.no_grad()
+def part_agreement(ppnet, loader, spec, orders=("evidence", "attention", "random"), value="prob", against_label=False, max_images=0, per_image=False,
+                   pass_images=16, rise=None, ig=None, seed=0, batch_size=None, scratch_bytes=1 << 30):
+    """Explanations against the truth over a PartsWorld split.  loader yields (x, labels, ids) in the square view; the images are
+    regrouped into passes of pass_images (tooling.regroup), so the result does not depend on the loader's batch size.  Per pass: one eval
+    forward and the class pick (the predicted class, or the label with against_label), part_interventions with the standard list, one
+    partmap render, per order one pixel_scores + ppf_part_mass, then one more part_interventions over the cumulative PARTS_OFF masks of
+    every order, the oracle (descending importance) and its reverse.  The rows stay on the device and are read once at the end;
+    part_agreement_from_rows holds the arithmetic.  Returns its dict plus settings and, with per_image, per_image = the rows."""
+    from . import data as D
+    from . import ops
+    orders = tuple(orders)
+    for order in orders:
+        if order not in PART_ORDERS:
+            _attribution_mass(ppnet, None, None, None, spec.parts, None, order, None)
+    K, keep = spec.parts, []
+    for x, y, ids in regroup(batches_with_ids(loader, max_images), int(pass_images)):
+        x = (x if x.is_cuda else x.cuda()).float().contiguous()
+        ids, y = ids.to(x.device).contiguous(), torch.as_tensor(y).to(x.device, torch.int64)
+        B = x.shape[0]
+        outs = _eval_outputs(ppnet, x)
+        cls = _pick_classes(ppnet, outs, y if against_label else None, 1, B)
+        iv = part_interventions(ppnet, spec, ids, classes=cls, value=value, batch_size=batch_size, scratch_bytes=scratch_bytes)
+        _, partmap = ops.synth_render(spec, iv.scene, ids, partmap=True)
+        val = iv.value[:, :, 0]
+        live = iv.changed[:, 1:K + 1] == 1
+        imp = val[:, :1] - val[:, 1:K + 1]
+        row = dict(image_ids=ids, labels=y, classes=cls[:, 0], value=val, pred=iv.pred, changed=iv.changed,
+                   visible=iv.scene[:, D.SYNTH_PART0:D.SYNTH_PART0 + D.SYNTH_PRIM_WORDS * K:D.SYNTH_PRIM_WORDS].contiguous())
+        masks = [_cumulative_masks(imp, live), _cumulative_masks(-imp, live)]
+        for order in orders:
+            pos, neg, cnt, bad = _attribution_mass(ppnet, x, outs, partmap, K, cls, order, ids, seed=seed, batch_size=batch_size,
+                                                   scratch_bytes=scratch_bytes, rise=rise, ig=ig)
+            row.update({f"{order}.pos": pos, f"{order}.neg": neg, f"{order}.count": cnt, f"{order}.nonfinite": bad})
+            masks.append(_cumulative_masks(pos[:, 3:] - neg[:, 3:], live))
+        m = torch.cat(masks, dim=1)                                           # [B, (2 + orders) * K]
+        dele = part_interventions(ppnet, spec, ids, classes=cls, value=value, batch_size=batch_size, scratch_bytes=scratch_bytes,
+                                  edits=torch.stack([torch.full_like(m, D.EDIT_PARTS_OFF), m], dim=2)).value[:, :, 0]
+        row.update(oracle=dele[:, :K], reverse=dele[:, K:2 * K], **{f"{o}.deleted": dele[:, (2 + j) * K:(3 + j) * K] for j, o in enumerate(orders)})
+        keep.append(row)
+    flat = read_rows(keep, "part_agreement")                                  # the one read
+    rows = {k: v for k, v in flat.items() if "." not in k}
+    rows.update(orders={o: {k: flat[f"{o}.{k}"] for k in ("pos", "neg", "count", "nonfinite", "deleted")} for o in orders},
+                class_parts=D.partsworld_class_table(spec), view=int(ppnet.img_size))
+    out = part_agreement_from_rows(rows)
+    out["settings"] = dict(orders=list(orders), value=value, against_label=bool(against_label), pass_images=int(pass_images), seed=int(seed),
+                           rise={**RISE_DEFAULTS, **(rise or {})} if "rise" in orders else None, ig={**IG_DEFAULTS, **(ig or {})} if "ig" in orders else None,
+                           img_size=int(ppnet.img_size))
     if per_image:
         out["per_image"] = rows
     return out

@@ -1395,6 +1395,58 @@ def synth_render(spec, scene, ids, out=None, partmap=False):
     return out if pm is None else (out, pm)
 
 
+def synth_edit(spec, scene, edits, out=None, check=True):
+    """(out int32 [B, E, SYNTH_WORDS], changed int32 [B, E]) of a scene table int32 [B, SYNTH_WORDS] and edits int32 [B, E, 2] = (op, arg)
+    (ppf_synth_edit, include/ppf_hip.h); one launch.  out: an int32 CUDA tensor of B * E * SYNTH_WORDS elements to write into, or None.
+    check: read `changed` back (the one read) and raise on any -1, naming the first invalid edit; False: no read, the -1 stays in
+    `changed` for the caller.  A chain of edits is a sequence of calls with out[:, e] as the next scene."""
+    who = "synth_edit"
+    if not isinstance(scene, torch.Tensor) or scene.dim() != 2 or not isinstance(edits, torch.Tensor) or edits.dim() != 3:
+        raise ValueError(f"{who}: scene must be an int32 CUDA tensor [B, {SYNTH_WORDS}] and edits one of [B, E, 2]")
+    B, E = scene.shape[0], edits.shape[1]
+    _dev_tensor(who, "scene", scene, torch.int32, (B, SYNTH_WORDS))
+    _dev_tensor(who, "edits", edits, torch.int32, (B, E, 2), scene.device)
+    C, K, D, _, _, g, _, _ = _synth_words(spec)
+    if out is None:
+        out = torch.empty((B, E, SYNTH_WORDS), dtype=torch.int32, device=scene.device)
+    elif not isinstance(out, torch.Tensor) or out.numel() != B * E * SYNTH_WORDS:
+        raise ValueError(f"{who}: out must be an int32 CUDA tensor of {B * E * SYNTH_WORDS} elements")
+    else:
+        _dev_tensor(who, "out", out, torch.int32, out.shape, scene.device)
+    changed = torch.empty((B, E), dtype=torch.int32, device=scene.device)
+    _lib.call("ppf_synth_edit", out, changed, scene, edits, B, E, C, K, D, g)
+    if check:
+        bad = (changed.cpu() < 0).nonzero()
+        if len(bad):
+            b, e = (int(v) for v in bad[0])
+            raise ValueError(f"{who}: {len(bad)} invalid edits, the first is edit {e} of image {b}: (op, arg) = {tuple(edits[b, e].tolist())} "
+                             f"with K={K} parts and D={D} distractors (unknown op, a mask bit or k out of range, attr >= 24, or a colour above 0xFFFFFF)")
+    return out.view(B, E, SYNTH_WORDS), changed
+
+
+def part_mass(score, partmap, rows_per_img, K, want_nonfinite=True):
+    """(pos fp64 [R, 3 + K], neg fp64 [R, 3 + K], count int32 [R, 3 + K], nonfinite int32 [R] or None) of score fp32 [R, S, S] and
+    partmap uint8 [R / rows_per_img, H, W] (ppf_part_mass, include/ppf_hip.h): the positive and the negative mass of every row on
+    each primitive code, seen through the view rule; one launch, fixed order."""
+    who = "part_mass"
+    if not isinstance(score, torch.Tensor) or score.dim() != 3 or score.shape[1] != score.shape[2]:
+        raise ValueError(f"{who}: score must be an fp32 CUDA tensor [R, S, S]")
+    if not isinstance(partmap, torch.Tensor) or partmap.dim() != 3:
+        raise ValueError(f"{who}: partmap must be a uint8 CUDA tensor [R / rows_per_img, H, W]")
+    R, S = int(score.shape[0]), int(score.shape[1])
+    rows_per_img, K = int(rows_per_img), int(K)
+    _dev_tensor(who, "score", score, torch.float32, score.shape)
+    nb = max(3 + K, 1)
+    pos = torch.empty((R, nb), dtype=torch.float64, device=score.device)
+    neg = torch.empty_like(pos)
+    count = torch.empty((R, nb), dtype=torch.int32, device=score.device)
+    bad = torch.empty(R, dtype=torch.int32, device=score.device) if want_nonfinite else None
+    if rows_per_img >= 1 and R % rows_per_img == 0:                        # anything else is the library's to refuse by name
+        _dev_tensor(who, "partmap", partmap, torch.uint8, (R // rows_per_img,) + tuple(partmap.shape[1:]), score.device)
+    _lib.call("ppf_part_mass", score, partmap, R, rows_per_img, S, int(partmap.shape[1]), int(partmap.shape[2]), K, pos, neg, count, bad)
+    return pos, neg, count, bad
+
+
 def sgemm(a, b, out, M, N, K, sam, sak, sbn, sbk, alpha=1.0, beta=0.0):
     ws = _workspace(out.device, 16 * M * N * 4)
     _lib.call("ppf_sgemm", a, b, out, M, N, K, sam, sak, sbn, sbk, out.shape[-1], float(alpha), float(beta), ws, ws.numel() // 4)
